@@ -2,6 +2,8 @@
 """Headline benchmark: WaveNet-vocoder TRAINING throughput (audio samples / s, whole job) on MI355X.
 
     python bench.py --gpus N --steps K --warmup W           (N>1: launched by torch.distributed.run)
+    python bench.py --gpus N --steps K --warmup W --full    (the headline plus every extra measurement below)
+    python bench.py ... --dump-outputs DIR                  (also write what the last timed step computed as DIR/<name>.npy)
 
 One "step" = the full training step of the reference (wavenet_vocoder/train.py:303) on one batch per GPU:
 pack weights -> forward (upsample net, 24 gated residual layers, head) -> masked MoL loss -> backward ->
@@ -14,12 +16,19 @@ shape; --workload c2_4stack gives paper_hparams.py's 4-stack variant), R=256 G=5
 MoL, raw 16-bit scalar input, 80-mel local conditioning through the '2D' upsample net [5,5,11] (hop 275),
 dropout 0.05, batch 8 x 11 000 samples per GPU, bf16 MFMA operands with fp32 accumulation.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0: metric, value, unit, higher_is_better, dtype, ms_per_step (one timed step) and the
+configuration.  A plain run does only that: set up, warm up, time the K steps, print.  With --full the line also carries
   roofline     -- the dominant kernel (gate GEMM `wn_gemm_lds_kernel<2,2,4,2,32,3,EPI_GATE,1>`, one launch per
                   layer and step) timed live with HIP events on its launch stream inside the timed region;
   cpu_baseline -- the oracle (CPU restatement of the reference arithmetic, torch-CPU fp32 on all host
-                  cores) running the same training step on a bounded sample of the same workload.
-A short autoregressive-synthesis measurement (RTF at 22.05 kHz) is appended under "synthesis".
+                  cores) running the same training step on a bounded sample of the same workload;
+and the untimed extras after the timed region (sustained blocks, feeder-fed steps, device timeline, host enqueue cost,
+exclusive-kernel view, other workloads in child processes, the per-rank exchange and N = 1 reference under N ranks).
+A short autoregressive-synthesis measurement (RTF at 22.05 kHz) is appended under "synthesis" (--full only).
+
+--dump-outputs DIR writes, after the timed steps, what the last timed step handed its caller -- the loss and the flat
+parameter, gradient, Adam moment and EMA vectors -- as float32 DIR/<name>.npy; vectors longer than DUMP_SAMPLE keep a
+fixed, seeded sample of positions.  Inputs and weights are seeded, so the same arguments give the same inputs every run.
 """
 import argparse
 import json
@@ -106,6 +115,21 @@ def synthetic_batch(hp, B, T, seed, device):
     y = wav.view(B, T, 1).contiguous().to(device)
     lengths = torch.full((B,), T, dtype=torch.int32, device=device)
     return x, c.to(device), y, lengths, wav, c
+
+
+DUMP_SAMPLE = 1 << 20       # elements kept of a longer vector by --dump-outputs (4 MB in float32; six vectors stay well under 64 MB)
+
+
+def dump_outputs(out_dir, arrays, seed=5339):
+    """--dump-outputs: each tensor flattened to float32 as out_dir/<name>.npy.  A vector longer than DUMP_SAMPLE keeps the positions of a
+    seeded draw without replacement, sorted: the same positions for the same length in every run, so two builds compare element for element."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().reshape(-1).float().cpu().numpy()
+        if a.size > DUMP_SAMPLE:
+            a = a[np.sort(np.random.default_rng(seed).choice(a.size, DUMP_SAMPLE, replace=False))]
+        np.save(os.path.join(out_dir, name + '.npy'), np.ascontiguousarray(a, dtype=np.float32))
+    _log('outputs of the last timed step written to %s (%s)' % (out_dir, ', '.join(sorted(arrays))))
 
 
 def _log(msg):
@@ -702,7 +726,16 @@ def main():
                     'a single-GPU rehearsal of what torch.distributed.run --nproc-per-node N executes')
     ap.add_argument('--dry-run', action='store_true', help='launch / rendezvous rehearsal without a GPU: the same self-launch, the same bucketed exchange walk over gloo '
                     'with a stand-in engine; prints a line marked dry_run with value null (never a measurement)')
+    ap.add_argument('--full', action='store_true', help='also run every measurement beyond the headline: live roofline of the dominant kernel, sustained blocks, '
+                    'feeder, device timeline, host enqueue, exclusive-kernel view, synthesis, other workloads, CPU baselines, per-rank exchange / N = 1 '
+                    'reference (the --no-* switches and --sustained trim a --full run; without --full none of these run)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='after the timed steps, write what the last timed step computed (loss, parameters, '
+                    'gradients, Adam moments, EMA; float32, seeded sample of long vectors) as DIR/<name>.npy')
     args = ap.parse_args()
+    if not args.full:
+        # a plain run is the headline alone: set up, warm up, the timed steps, the optional output dump, the result line
+        args.no_cpu_baseline = args.no_synth = args.no_other_workloads = args.no_feeder = args.no_exclusive = True
+        args.sustained = 0
 
     # `python bench.py --gpus N` with no launcher around it starts the N ranks itself (one process per GPU, the environment
     # torch.distributed.run would set); under a launcher (WORLD_SIZE / RANK present) this process IS one of the ranks.
@@ -740,7 +773,7 @@ def main():
         os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
         os.environ.setdefault('MASTER_PORT', '29533')
         from wavenet_vocoder import launch as _launch
-        if world > 1 and os.environ.get('WN_BENCH_RCCL_DEBUG', '1') != '0':
+        if world > 1 and args.full and os.environ.get('WN_BENCH_RCCL_DEBUG', '1') != '0':
             # the first multi-GPU run explains itself: RCCL's own account of the topology it built goes to side files (one per process),
             # an excerpt into the JSON line (collective.rccl_topology)
             rccl_dir = os.environ.get('WN_BENCH_RCCL_DEBUG_DIR') or os.path.join(ROOT, 'bench_rccl_debug_n%d' % world)
@@ -822,7 +855,8 @@ def main():
     if use_dist:
         dist.barrier()
     torch.cuda.synchronize()
-    eng.profile(True)
+    if args.full:
+        eng.profile(True)         # live roofline of the dominant kernel: event pairs + in-kernel stamps around every timed gate launch
     t0 = time.time()
     for i in range(args.steps):
         one_step(args.warmup + i)
@@ -832,11 +866,14 @@ def main():
     torch.cuda.synchronize()
     dt = time.time() - t0
     _log('timed region done: %.1f ms/step' % (dt / args.steps * 1e3))
-    prof_ms, prof_n = eng.profile_result()
-    kern_ms, kern_n = eng.profile_kernel_result()
-    kern_mhz, kern_mhz_n = eng.profile_kernel_clock()        # mean shader clock inside the timed gate launches (in-kernel cycle counter / wall clock)
-    rows_launch = eng.profile_rows_per_launch()
-    eng.profile(False)
+    if args.full:
+        prof_ms, prof_n = eng.profile_result()
+        kern_ms, kern_n = eng.profile_kernel_result()
+        kern_mhz, kern_mhz_n = eng.profile_kernel_clock()        # mean shader clock inside the timed gate launches (in-kernel cycle counter / wall clock)
+        rows_launch = eng.profile_rows_per_launch()
+        eng.profile(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'loss': loss, 'params': flat, 'grads': grads, 'adam_m': m, 'adam_v': v, 'ema': ema})
     # ---- sustained view (>= 20 warm-up, >= 100 timed steps, median of 3): the contract's timed region above may be a
     # fraction of a second (power and clocks have not settled); this block is NOT the headline `value`, it is reported next to it
     sustained = None
@@ -877,13 +914,14 @@ def main():
     # enough to change which stream runs ahead) -- forward / backward chain / weight-gradient tail and how long two launches overlap
     device_timeline = None
     try:
-        sys.path.insert(0, os.path.join(ROOT, 'tools'))
-        import devtrace
-        torch.cuda.synchronize()
-        eng.trace_arm(6)                              # the 6th step from here: the host is ahead of the device again by then
-        for _i in range(9):
-            one_step(args.warmup + args.steps + _i)
-        device_timeline = devtrace.summarise(eng.trace_read())
+        if args.full:
+            sys.path.insert(0, os.path.join(ROOT, 'tools'))
+            import devtrace
+            torch.cuda.synchronize()
+            eng.trace_arm(6)                              # the 6th step from here: the host is ahead of the device again by then
+            for _i in range(9):
+                one_step(args.warmup + args.steps + _i)
+            device_timeline = devtrace.summarise(eng.trace_read())
         if device_timeline:
             device_timeline['what'] = ('one un-profiled step of the same loop, {first workgroup start, last workgroup end} stamps of every tile-engine / grouped '
                                        'weight-gradient launch on the 100 MHz wall clock (wn_trace_arm / wn_trace_read, tools/devtrace.py)')
@@ -921,7 +959,7 @@ def main():
     # untimed extra under the multi-rank code path: 10 more steps with the exchange instrumented (device events per bucket and at the
     # join), every rank's figures gathered on rank 0
     per_rank = None
-    if use_dist:
+    if use_dist and args.full:
         from wavenet_vocoder.parallel import ExchangeTimer
         xt = ExchangeTimer()
         torch.cuda.synchronize(); dist.barrier()
@@ -948,7 +986,7 @@ def main():
     # barrier), i.e. this box's own N = 1 figure next to the N-rank one.  The driver computes scaling from its own N = 1 run; this is
     # the builder-side cross-check that both numbers come from one process on one box.
     n1_reference = None
-    if use_dist and world > 1:
+    if use_dist and world > 1 and args.full:
         torch.cuda.synchronize(); dist.barrier()
         if rank == 0:
             for i in range(2):
@@ -967,21 +1005,6 @@ def main():
         samples = world * B * T * args.steps
         value = samples / dt
         mac = mac_per_sample(hp)
-        # dominant kernel: gate GEMM.  Algorithmic flops per launch = 2 * G * (3R + C) * B*T  (SURVEY 8d per-sample x units/launch)
-        R, G, C = hp.residual_channels, hp.gate_channels, hp.cin_channels
-        rows_launch = rows_launch or B * T       # the layer chain runs per half-batch on two streams
-        flops_launch = 2.0 * G * (3 * R + C) * rows_launch
-        # two clocks on the same launches: the kernel's OWN duration from in-kernel stamps (first workgroup start .. last workgroup end;
-        # what rocprofv3's kernel trace reports, profiles/*kernel_stats.csv) and the HIP-event bracket on the launch stream, which also
-        # counts the wait for CU slots behind the other half-batch's kernels.  `achieved` / `frac` use the kernel's own duration.
-        avg_ev_s = (prof_ms / max(prof_n, 1)) * 1e-3
-        avg_s = (kern_ms / max(kern_n, 1)) * 1e-3 if kern_n else avg_ev_s
-        achieved = flops_launch / avg_s / 1e12 if (kern_n or prof_n) else None
-        achieved_ev = flops_launch / avg_ev_s / 1e12 if prof_n else None
-        peak = 2500.0
-        traffic = load_traffic(args.workload, B, T)
-        unprof = sustained['ms_per_step'] if sustained else None
-        ex_avg = (exk_ms / max(exk_n, 1)) if exk_n else (excl_ms / max(excl_n, 1))
         res = {
             'metric': 'wavenet_train_audio_samples_per_sec', 'value': value, 'unit': 'audio_samples/s',
             'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': dt / args.steps * 1e3,
@@ -996,47 +1019,66 @@ def main():
             'samples_per_sec_per_gpu': value / world,
             'train_tflops_algorithmic': 6.0 * mac * value / 1e12,
             'final_loss': final_loss,
-            'roofline': {'bound': 'mfma', 'kernel': 'wn_gemm_lds_kernel<2,2,4,2,32,3,EPI_GATE,1,3> (dilated conv + cond GEMM + gate, fwd)',
-                         'achieved': achieved, 'peak': peak, 'unit': 'TFLOP/s', 'frac': (achieved / peak) if achieved else None,
-                         # power as a bound: the step draws ~1.35 kW and the shader clock sits well under the 2400 MHz the 2.5 PFLOP/s peak assumes.  sclk_in_kernel_mhz =
-                         # workgroup 0 of every timed launch reads the shader-cycle counter over the 100 MHz wall clock; peak_at_clock = peak x sclk / 2400
-                         'sclk_in_kernel_mhz': kern_mhz or None, 'peak_at_clock': (peak * kern_mhz / 2400.0) if kern_mhz else None,
-                         'frac_of_peak_at_clock': (achieved / (peak * kern_mhz / 2400.0)) if (achieved and kern_mhz) else None,
-                         'frac_incl_queue_wait': (achieved_ev / peak) if achieved_ev else None,
-                         'timing': 'achieved / frac: in-kernel start..end stamps of every timed launch (the kernel duration rocprofv3 reports); '
-                                   'frac_incl_queue_wait: HIP events around the same launches on their stream (adds the wait behind the other stream)',
-                         'traffic': (traffic['gate_bytes_per_launch'] * rows_launch / (B * T / 2.0)) if (traffic and traffic.get('gate_bytes_per_launch')) else None,
-                         'traffic_source': (traffic['source'] + ': 2 x FETCH_SIZE + WRITE_SIZE per gate launch of a half batch') if traffic else None,
-                         'launches_timed': int(kern_n or prof_n), 'avg_launch_ms': avg_s * 1e3 if (kern_n or prof_n) else None,
-                         'avg_launch_ms_event_bracket': avg_ev_s * 1e3 if prof_n else None,
-                         'alg_flops_per_launch': flops_launch, 'alg_bytes_per_launch': float(rows_launch) * (2 * R + 2 * C + 2 * G),
-                         'rows_per_launch': rows_launch,
-                         'profiling_cost': {'what': 'the timed region records 2 events per gate launch and the kernel stamps its start / end; the sustained blocks '
-                                                    'below run the same steps without either', 'ms_per_step_profiled': dt / args.steps * 1e3, 'ms_per_step_unprofiled': unprof},
-                         'note': 'each launch covers one half-batch and shares the GPU with the HBM-bound out-conv launches of the other half-batch on a second stream'},
-            'roofline_exclusive': {'what': 'same kernel, whole batch on one stream (no concurrent kernels), 2 untimed steps after the timed region; in-kernel stamps',
-                                   'avg_launch_ms': ex_avg, 'avg_launch_ms_event_bracket': excl_ms / max(excl_n, 1), 'rows_per_launch': excl_rows,
-                                   'sclk_in_kernel_mhz': exk_mhz or None, 'peak_at_clock': (peak * exk_mhz / 2400.0) if exk_mhz else None,
-                                   'achieved': (2.0 * G * (3 * R + C) * excl_rows / (ex_avg * 1e-3) / 1e12) if excl_n else None,
-                                   'frac': (2.0 * G * (3 * R + C) * excl_rows / (ex_avg * 1e-3) / 1e12 / peak) if excl_n else None},
-            # whole-step view asked for by the north star: SURVEY 8d algorithmic HBM bytes per audio sample (bf16) x samples/s vs 8 TB/s
-            'hbm_roofline_whole_step': {'alg_bytes_per_sample': alg_bytes_per_sample(hp), 'achieved_GBps': alg_bytes_per_sample(hp) * value / world / 1e9,
-                                        'peak_GBps': 8000.0, 'frac': alg_bytes_per_sample(hp) * value / world / 8e12,
-                                        'alg_bytes_per_step': alg_bytes_per_sample(hp) * B * T,
-                                        'traffic_per_step': traffic['bytes_per_step'] if traffic else None,
-                                        'traffic_fetch_x2_per_step': traffic['fetch_x2_bytes_per_step'] if traffic else None,
-                                        'traffic_write_per_step': traffic['write_bytes_per_step'] if traffic else None,
-                                        'traffic_source': (traffic['source'] + ': sum over ALL kernels of 2 x FETCH_SIZE + WRITE_SIZE per step') if traffic else None},
-            'mfma_whole_step_frac': 6.0 * mac * value / world / 1e12 / peak,
-            'sustained': sustained, 'with_feeder': with_feeder, 'host_enqueue': host_enqueue, 'device_timeline': device_timeline,
             'grad_buckets': [list(b) for b in eng.grad_buckets()], 'force_dist': bool(args.force_dist),
-            'collective': collective, 'per_rank': per_rank, 'n1_reference': n1_reference,
-            'scaling_vs_n1': (value / n1_reference['value']) if n1_reference else None,      # speed-up factor over this box's own 1-rank run
+            'collective': collective,
             'emulated_allreduce': ({'gbps': args.emulate_allreduce_gbps, 'bytes': int(eng.n_params) * 4,
                                     'serial_ms': int(eng.n_params) * 4 / (args.emulate_allreduce_gbps * 1e9) * 1e3,
                                     'what': 'single-GPU model: each gradient bucket occupies the communication stream for bytes / bandwidth once its event fired'}
                                    if args.emulate_allreduce_gbps > 0 else None),
         }
+        if args.full:
+            # dominant kernel: gate GEMM.  Algorithmic flops per launch = 2 * G * (3R + C) * B*T  (SURVEY 8d per-sample x units/launch)
+            R, G, C = hp.residual_channels, hp.gate_channels, hp.cin_channels
+            rows_launch = rows_launch or B * T       # the layer chain runs per half-batch on two streams
+            flops_launch = 2.0 * G * (3 * R + C) * rows_launch
+            # two clocks on the same launches: the kernel's OWN duration from in-kernel stamps (first workgroup start .. last workgroup end;
+            # what rocprofv3's kernel trace reports, profiles/*kernel_stats.csv) and the HIP-event bracket on the launch stream, which also
+            # counts the wait for CU slots behind the other half-batch's kernels.  `achieved` / `frac` use the kernel's own duration.
+            avg_ev_s = (prof_ms / max(prof_n, 1)) * 1e-3
+            avg_s = (kern_ms / max(kern_n, 1)) * 1e-3 if kern_n else avg_ev_s
+            achieved = flops_launch / avg_s / 1e12 if (kern_n or prof_n) else None
+            achieved_ev = flops_launch / avg_ev_s / 1e12 if prof_n else None
+            peak = 2500.0
+            traffic = load_traffic(args.workload, B, T)
+            unprof = sustained['ms_per_step'] if sustained else None
+            ex_avg = (exk_ms / max(exk_n, 1)) if exk_n else (excl_ms / max(excl_n, 1))
+            res.update({
+                'roofline': {'bound': 'mfma', 'kernel': 'wn_gemm_lds_kernel<2,2,4,2,32,3,EPI_GATE,1,3> (dilated conv + cond GEMM + gate, fwd)',
+                             'achieved': achieved, 'peak': peak, 'unit': 'TFLOP/s', 'frac': (achieved / peak) if achieved else None,
+                             # power as a bound: the step draws ~1.35 kW and the shader clock sits well under the 2400 MHz the 2.5 PFLOP/s peak assumes.  sclk_in_kernel_mhz =
+                             # workgroup 0 of every timed launch reads the shader-cycle counter over the 100 MHz wall clock; peak_at_clock = peak x sclk / 2400
+                             'sclk_in_kernel_mhz': kern_mhz or None, 'peak_at_clock': (peak * kern_mhz / 2400.0) if kern_mhz else None,
+                             'frac_of_peak_at_clock': (achieved / (peak * kern_mhz / 2400.0)) if (achieved and kern_mhz) else None,
+                             'frac_incl_queue_wait': (achieved_ev / peak) if achieved_ev else None,
+                             'timing': 'achieved / frac: in-kernel start..end stamps of every timed launch (the kernel duration rocprofv3 reports); '
+                                       'frac_incl_queue_wait: HIP events around the same launches on their stream (adds the wait behind the other stream)',
+                             'traffic': (traffic['gate_bytes_per_launch'] * rows_launch / (B * T / 2.0)) if (traffic and traffic.get('gate_bytes_per_launch')) else None,
+                             'traffic_source': (traffic['source'] + ': 2 x FETCH_SIZE + WRITE_SIZE per gate launch of a half batch') if traffic else None,
+                             'launches_timed': int(kern_n or prof_n), 'avg_launch_ms': avg_s * 1e3 if (kern_n or prof_n) else None,
+                             'avg_launch_ms_event_bracket': avg_ev_s * 1e3 if prof_n else None,
+                             'alg_flops_per_launch': flops_launch, 'alg_bytes_per_launch': float(rows_launch) * (2 * R + 2 * C + 2 * G),
+                             'rows_per_launch': rows_launch,
+                             'profiling_cost': {'what': 'the timed region records 2 events per gate launch and the kernel stamps its start / end; the sustained blocks '
+                                                        'below run the same steps without either', 'ms_per_step_profiled': dt / args.steps * 1e3, 'ms_per_step_unprofiled': unprof},
+                             'note': 'each launch covers one half-batch and shares the GPU with the HBM-bound out-conv launches of the other half-batch on a second stream'},
+                'roofline_exclusive': {'what': 'same kernel, whole batch on one stream (no concurrent kernels), 2 untimed steps after the timed region; in-kernel stamps',
+                                       'avg_launch_ms': ex_avg, 'avg_launch_ms_event_bracket': excl_ms / max(excl_n, 1), 'rows_per_launch': excl_rows,
+                                       'sclk_in_kernel_mhz': exk_mhz or None, 'peak_at_clock': (peak * exk_mhz / 2400.0) if exk_mhz else None,
+                                       'achieved': (2.0 * G * (3 * R + C) * excl_rows / (ex_avg * 1e-3) / 1e12) if excl_n else None,
+                                       'frac': (2.0 * G * (3 * R + C) * excl_rows / (ex_avg * 1e-3) / 1e12 / peak) if excl_n else None},
+                # whole-step view asked for by the north star: SURVEY 8d algorithmic HBM bytes per audio sample (bf16) x samples/s vs 8 TB/s
+                'hbm_roofline_whole_step': {'alg_bytes_per_sample': alg_bytes_per_sample(hp), 'achieved_GBps': alg_bytes_per_sample(hp) * value / world / 1e9,
+                                            'peak_GBps': 8000.0, 'frac': alg_bytes_per_sample(hp) * value / world / 8e12,
+                                            'alg_bytes_per_step': alg_bytes_per_sample(hp) * B * T,
+                                            'traffic_per_step': traffic['bytes_per_step'] if traffic else None,
+                                            'traffic_fetch_x2_per_step': traffic['fetch_x2_bytes_per_step'] if traffic else None,
+                                            'traffic_write_per_step': traffic['write_bytes_per_step'] if traffic else None,
+                                            'traffic_source': (traffic['source'] + ': sum over ALL kernels of 2 x FETCH_SIZE + WRITE_SIZE per step') if traffic else None},
+                'mfma_whole_step_frac': 6.0 * mac * value / world / 1e12 / peak,
+                'sustained': sustained, 'with_feeder': with_feeder, 'host_enqueue': host_enqueue, 'device_timeline': device_timeline,
+                'per_rank': per_rank, 'n1_reference': n1_reference,
+                'scaling_vs_n1': (value / n1_reference['value']) if n1_reference else None,      # speed-up factor over this box's own 1-rank run
+            })
         if not args.no_synth and world == 1:      # replicas-only path: measured on one GPU, not while the other ranks wait
             _log('synthesis measurement ...')
             try:
@@ -1072,7 +1114,8 @@ def main():
                     res['cpu_baseline_synthesis'] = {'value': None, 'sample': 'failed: ' + str(e)[:200]}
         else:
             res['cpu_baseline'] = None
-        res['synthesis_summary'] = synthesis_summary(res)      # LAST key on purpose
+        if args.full:
+            res['synthesis_summary'] = synthesis_summary(res)      # LAST key on purpose
         sys.stdout.flush()
         os.write(result_fd, (json.dumps(res) + '\n').encode())
     if use_dist:

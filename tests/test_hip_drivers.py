@@ -135,3 +135,35 @@ def test_feeder_prefetch_keeps_batches_and_errors_in_order(tmp_path):
             c.request_stop()
         counts.append(n)
     assert counts[0] == counts[1] and counts[0] < 300, counts
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_its_outputs(tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR` (a small batch of the C2 model): ONE result line with the headline keys and none
+    of the --full extras, and the last timed step's loss / parameters / gradients / Adam moments / EMA as float32 .npy under 64 MB in all.
+    Two runs with the same arguments see the same inputs: their dumps agree (to the ordering of float atomics)."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    lines, dumps = [], []
+    for run in ('a', 'b'):
+        out = str(tmp_path / run)
+        r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--batch', '2', '--time', '2200',
+                            '--dump-outputs', out], capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-3000:]
+        rows = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(rows) == 1, r.stdout
+        lines.append(json.loads(rows[0]))
+        names = sorted(os.listdir(out))
+        assert names == ['adam_m.npy', 'adam_v.npy', 'ema.npy', 'grads.npy', 'loss.npy', 'params.npy'], names
+        assert sum(os.path.getsize(os.path.join(out, n)) for n in names) <= 64 * 2 ** 20
+        dumps.append({n[:-4]: np.load(os.path.join(out, n)) for n in names})
+    for d in lines:
+        assert d['metric'] == 'wavenet_train_audio_samples_per_sec' and d['unit'] == 'audio_samples/s' and d['higher_is_better'] is True
+        assert d['dtype'] == 'bf16' and d['steps'] == 3 and d['warmup'] == 1 and d['ms_per_step'] > 0
+        assert abs(d['value'] - 2 * 2200 / (d['ms_per_step'] * 1e-3)) <= 1e-6 * d['value']
+        assert not {'roofline', 'sustained', 'synthesis', 'cpu_baseline_synthesis', 'other_workloads', 'device_timeline'} & set(d)
+    for k, a in dumps[0].items():
+        b = dumps[1][k]
+        assert a.dtype == np.float32 and a.shape == b.shape and np.isfinite(a).all(), k
+        assert np.linalg.norm(a.astype(np.float64) - b) <= 1e-4 * max(np.linalg.norm(b.astype(np.float64)), 1e-30), k
+    assert dumps[0]['loss'].shape == (1,) and abs(float(dumps[0]['loss'][0]) - lines[0]['final_loss']) <= 1e-6 * max(1.0, abs(lines[0]['final_loss']))

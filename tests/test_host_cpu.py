@@ -957,6 +957,26 @@ def test_bench_traffic_constants_come_from_the_committed_pmc_summary():
     assert bench.load_traffic('c2', 4, 11000) is None and bench.load_traffic('c5_stress', 8, 12000) is None
 
 
+def test_bench_dump_outputs_writes_float32_and_a_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: every array lands as float32 <name>.npy; a short vector whole, a long one as the same seeded, sorted
+    sample of positions in every run (so two builds compare element for element), and six vectors of the C2 size stay under 64 MB."""
+    sys.path.insert(0, ROOT)
+    import bench
+    n_long = bench.DUMP_SAMPLE * 3 + 17
+    arrays = {'loss': torch.tensor([1.25]), 'short': torch.arange(10, dtype=torch.float64), 'long': torch.arange(n_long, dtype=torch.float32)}
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    assert sorted(os.listdir(tmp_path / 'a')) == ['long.npy', 'loss.npy', 'short.npy']
+    a = {k: np.load(str(tmp_path / 'a' / (k + '.npy'))) for k in arrays}
+    b = {k: np.load(str(tmp_path / 'b' / (k + '.npy'))) for k in arrays}
+    assert all(v.dtype == np.float32 and v.ndim == 1 for v in a.values())
+    assert a['loss'].tolist() == [1.25] and a['short'].tolist() == list(range(10))
+    pos = a['long']                                   # values == positions: the sample is sorted, distinct, in range
+    assert pos.size == bench.DUMP_SAMPLE and np.all(np.diff(pos) > 0) and pos[0] >= 0 and pos[-1] < n_long
+    assert np.array_equal(a['long'], b['long'])
+    assert 6 * bench.DUMP_SAMPLE * 4 + 4 < 64 * 2 ** 20
+
+
 def test_device_timeline_summary_of_in_kernel_stamps(tmp_path):
     """tools/devtrace.py (what bench.py's `device_timeline` block and the WN_DEVTRACE file view are made of): phases and overlap of a
     hand-made two-stream step -- forward until the first backward launch, backward chain until the last d x, tail until the last weight

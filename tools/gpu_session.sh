@@ -5,9 +5,9 @@
 #   tests        full `pytest -m gpu` suite, verbose (-s keeps the measured distances), junit-free log
 #   tests:<expr> only the tests matching -k <expr>
 #   smoke        __graft_entry__.smoke()
-#   bench        default-flag bench line (what the driver runs) -> bench.json
+#   bench        the bench line with every extra measurement (--full) -> bench.json
 #   forcedist    short bench through the one-rank RCCL path (process group, bucketed ReduceOp.AVG exchange, barriers) -> bench_forcedist.json
-#   benchq       short bench (no synth / cpu baseline / other workloads) -> benchq.json
+#   benchq       short bench (--full, but no synth / cpu baseline / other workloads) -> benchq.json
 #   ab:<name>=<ENV=V>[,<ENV=V>]   one A/B arm of the short bench (appends to ab.txt); `ab:base=` for the baseline
 #   kt           rocprofv3 kernel trace + stats of the bench step (live, two streams) -> kernel_stats.csv, timeline.txt
 #   roctx        WN_ROCTX=1: rocTX ranges of the C-ABI entry points in a rocprofv3 marker + kernel trace -> roctx_marker_stats.csv
@@ -26,14 +26,15 @@ OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
 export WN_PARITY_REPORT_DIR=$OUT
-BQ="--no-cpu-baseline --no-synth --no-exclusive --no-other-workloads --sustained 0"
+# every bench call below reads more than the headline (roofline, per-rank figures, ...): --full, trimmed by the --no-* switches
+BQ="--full --no-cpu-baseline --no-synth --no-exclusive --no-other-workloads --sustained 0"
 for st in "$@"; do
   cd $R
   case $st in
     tests) ( timeout 1500 python -m pytest tests -m gpu -q -s --maxfail=8 2>&1; echo "rc=$?" ) > $OUT/pytest_gpu_verbose.log; grep -E "passed|failed|error|rc=" $OUT/pytest_gpu_verbose.log | tail -5 ;;
     tests:*) ( timeout 1200 python -m pytest tests -m gpu -q -s --maxfail=8 -k "${st#tests:}" 2>&1; echo "rc=$?" ) > $OUT/pytest_gpu_k.log; grep -E "passed|failed|error|rc=" $OUT/pytest_gpu_k.log | tail -5 ;;
     smoke) ( timeout 300 python __graft_entry__.py smoke 2>&1 | tail -3 ) > $OUT/smoke.log; cat $OUT/smoke.log ;;
-    bench) timeout 900 python bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "rc=$?" >> $OUT/bench.err; cut -c1-400 $OUT/bench.json; tail -3 $OUT/bench.err ;;
+    bench) timeout 900 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "rc=$?" >> $OUT/bench.err; cut -c1-400 $OUT/bench.json; tail -3 $OUT/bench.err ;;
     forcedist) GPU_MAX_HW_QUEUES=8 timeout 300 python bench.py --force-dist --steps 40 --warmup 8 $BQ > $OUT/bench_forcedist.json 2> $OUT/bench_forcedist.err; cut -c1-300 $OUT/bench_forcedist.json; grep -i "process group" $OUT/bench_forcedist.err | tail -2 ;;
     benchq) timeout 300 python bench.py --steps 40 --warmup 8 $BQ > $OUT/benchq.json 2> $OUT/benchq.err; cut -c1-300 $OUT/benchq.json ;;
     ab:*) spec=${st#ab:}; name=${spec%%=*}; envs=$(echo "${spec#*=}" | tr ',' ' ')
