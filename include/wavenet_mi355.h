@@ -233,6 +233,36 @@ int wn_synth_last_instances(const wn_ctx* ctx);
  * instead of one matvec per stream), 0 otherwise.  Environment: WN_PIPE_BATCHPRE=0 keeps the per-stream form (A/B switch). */
 int wn_synth_last_batched(const wn_ctx* ctx);
 
+/* ---- streaming synthesis: the same generation as ONE wn_synthesize, cut into pushes of mel frames as they arrive ------------
+ * The reference's loop is a streaming computation (zero queues, wavenet.py:815-816; silence input, :433-445; step t reads only its
+ * own conditioning frame and the queues, :821-886): a stream continues the ring queues, the time index, the fed-back sample and the
+ * device noise counter across pushes, and the samples it returns are bit-identical to one wn_synthesize over the concatenated frames
+ * (same B, seed, steps_per_graph, noise / teacher forcing).  One open stream per context, B <= 32 utterances in lockstep.
+ *
+ * Mel frames of context the upsample net needs on each side of a frame (host only: no context, no GPU): 0 / 0 for 'NearestNeighbor',
+ * '2D' and '1D' (time kernel == stride); 'SubPixel': ceil(h / hop) on both sides with h = sum_i prod_{k >= i} s_k samples (layer i's 3-tap
+ * time kernel reaches one of its input samples); 'Resize': ceil(h / hop) with h = sum_i p_i * prod_{k > i} s_k samples, p_i = (s_i - 1) / 2
+ * on the left, s_i - 1 - p_i on the right (the s-tap SAME kernels). */
+int wn_synth_stream_lookahead(const wn_config* cfg, int32_t* frames_left, int32_t* frames_right);
+/* Open a stream of B utterances at t = 0.  The path is chosen as wn_synthesize(steps_per_graph) would for B and kept for the life of the
+ * stream (the fp32 launch-per-layer path for compute_dtype = WN_COMPUTE_F32).  seed: the device noise of wn_synthesize(noise = NULL, seed) over the
+ * whole utterance.  Global conditioning: what wn_set_global_condition set, captured here.  Ends any stream already open on the context.
+ * Allocates only what a wn_synthesize of B streams would (nothing on inference-only contexts). */
+int wn_synth_stream_begin(wn_ctx* ctx, int32_t B, uint64_t seed, int32_t steps_per_graph, void* stream);
+/* Append Tn >= 0 frames, c = float [B, cin, Tn], and generate every frame whose conditioning is now complete: frames [done, pushed -
+ * frames_right), with final = 1 [done, pushed).  That is n = frames * hop samples: out_samples [B, n] (float or int32 as wn_synthesize),
+ * optional out_raw [B, O, n], optional noise [n, B, noise_per_step] (NULL: the device stream of `seed`, continued), optional
+ * test_inputs [B, n].  *n_out (host) = n, known at enqueue time (no synchronisation).  n may be 0.  Asynchronous and ordered like
+ * wn_synthesize; never allocates.  WN_E_SHAPE if n > max_time or B x (window frames) x hop exceeds max_batch x max_time (window =
+ * frames_left of context + the frames not yet generated).  After final = 1 the stream is closed.  WN_E_STATE: no stream open, or the
+ * stream was ended by wn_synthesize / wn_pack_weights / wn_set_global_condition / wn_synth_pipe_dtype, or poisoned: a pipeline run of
+ * this stream that wn_synth_check (or the next push) reported failed.  wn_train_fwd / wn_train_bwd between pushes do not disturb it.
+ * wn_get_upsampled_features afterwards returns the features of the span this push generated. */
+int wn_synth_stream_push(wn_ctx* ctx, const float* c, int32_t Tn, int32_t final, const float* noise, const void* test_inputs,
+                         void* out_samples, float* out_raw, int32_t* n_out, void* stream);
+/* Abandon the open stream (no device work; what was pushed and not generated is dropped).  A later push returns WN_E_STATE. */
+int wn_synth_stream_end(wn_ctx* ctx);
+
 /* Stand-alone samplers on [B,O,T] parameters (train-time log path, wavenet.py:302-325). */
 int wn_sample(wn_ctx* ctx, const float* y_hat, int32_t B, int32_t T, const float* noise /*[T,B,nps]*/,
               void* out /* float [B,T] or int32 [B,T] */, void* stream);

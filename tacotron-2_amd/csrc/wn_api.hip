@@ -1,6 +1,7 @@
 // Host side of the C ABI: context, parameter table, workspace, dispatch.
 #include "wn_common.h"
 #include <math.h>
+#include <algorithm>
 
 std::string g_create_err;
 
@@ -179,6 +180,8 @@ static int alloc_workspace(wn_ctx* c) {
     return WN_OK;
 }
 
+static int stream_alloc(wn_ctx* c);
+
 extern "C" int wn_create(const wn_config* cfg, wn_ctx** out) {
     wn_ctx* z = nullptr;
     if (!cfg || !out) WN_FAIL(z, WN_E_ARG, "wn_create: null argument");
@@ -263,6 +266,7 @@ extern "C" int wn_create(const wn_config* cfg, wn_ctx** out) {
             c->pipe_cap = pb;
             rc = c->cfg.compute_dtype == WN_COMPUTE_F32 ? wn_synth_f32_reserve(c, c->maxB) : pb > 0 ? wn_pipe_reserve(c, pb, c->maxT) : wn_synth_reserve(c);
         }
+        if (rc == WN_OK) rc = stream_alloc(c);      // the streaming state too: wn_synth_stream_* never allocate here
     }
     if (rc != WN_OK) { g_create_err = c->err; wn_destroy(c); return rc; }
     *out = c;
@@ -274,6 +278,9 @@ extern "C" void wn_destroy(wn_ctx* c) {
     wn_synth_free(c);
     wn_synth_f32_free(c);
     wn_pipe_free(c);
+    for (float* q : c->strm.pend) if (q) hipFree(q);
+    if (c->strm.gbias) hipFree(c->strm.gbias);
+    if (c->strm.carry) hipFree(c->strm.carry);
     wn_f32_free(c);
     auto fr = [](PackedW& w) { if (w.dev) hipFree(w.dev); if (w.dev_segs) hipFree(w.dev_segs); w.dev = nullptr; w.dev_segs = nullptr; };
     for (auto& p : c->packs) { fr(p.w1); fr(p.wo); fr(p.ws); fr(p.w2T); fr(p.w1T); }
@@ -358,6 +365,7 @@ struct WnRange {
 extern "C" int wn_pack_weights(wn_ctx* c, const float* params, void* stream) {
     if (!c || !params) return WN_E_ARG;
     WnRange range("wn_pack_weights");
+    c->strm.open = false;                              // (ends an open stream: its pipeline slices / bias are of the old weights)
     return wn_launch_pack(c, params, (hipStream_t)stream);
 }
 
@@ -375,6 +383,7 @@ extern "C" int wn_set_global_condition(wn_ctx* c, const void* g, int32_t B, void
     if (!c || !g) return WN_E_ARG;
     if (c->gin <= 0) WN_FAIL(c, WN_E_STATE, "wn_set_global_condition: the model has no global conditioning (gin_channels <= 0)");
     if (B <= 0 || B > c->maxB) WN_FAIL(c, WN_E_SHAPE, "batch %d outside (0, max_batch=%d]", B, c->maxB);
+    c->strm.open = false;
     if (c->cfg.use_speaker_embedding) WN_HIP(c, hipMemcpyAsync(c->gids, g, (size_t)B * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     else WN_HIP(c, hipMemcpyAsync(c->gvec, g, (size_t)B * c->gin * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     c->gB = B; c->have_g = true;
@@ -402,7 +411,7 @@ extern "C" int wn_train_fwd(wn_ctx* c, const void* x, const float* cc, const voi
     // x and c are needed again by wn_train_bwd: keep ctx-owned copies (caller pointers are borrowed for this call only)
     WN_HIP(c, hipMemcpyAsync(c->XIN, x, (size_t)B * T * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     WN_HIP(c, hipMemcpyAsync(c->CIN, cc, (size_t)B * c->C * Tc * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    c->fx = c->XIN; c->fc = c->CIN; c->fy = y; c->flen = lengths; c->fB = B; c->fT = T; c->fTc = Tc; c->fseed = seed;
+    c->fx = c->XIN; c->fc = c->CIN; c->fy = y; c->flen = lengths; c->fB = B; c->fT = T; c->fTc = Tc; c->fseed = seed; c->fup_pitch = 0;
     c->have_fwd = false; c->have_bwd = false;
     rc = wn_fwd_impl(c, (hipStream_t)stream, loss_out, y_hat_out);
     if (rc == WN_OK) c->have_fwd = true;
@@ -426,7 +435,10 @@ extern "C" int wn_optim_step(wn_ctx* c, float* p, const float* g, float* m, floa
 extern "C" int wn_get_upsampled_features(wn_ctx* c, float* out, void* stream) {
     if (!c || !out) return WN_E_ARG;
     if (c->fB <= 0) WN_FAIL(c, WN_E_STATE, "no forward/synthesis has run yet");
-    WN_HIP(c, hipMemcpyAsync(out, c->CUP[c->cup_final_idx], (size_t)c->fB * c->C * c->fT * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    if (c->fup_pitch > 0)      // after a stream push: the span's columns of the upsampled window
+        WN_HIP(c, hipMemcpy2DAsync(out, (size_t)c->fT * 4, c->CUP[c->cup_final_idx] + c->fup_off, (size_t)c->fup_pitch * 4, (size_t)c->fT * 4, (size_t)c->fB * c->C,
+                                   hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    else WN_HIP(c, hipMemcpyAsync(out, c->CUP[c->cup_final_idx], (size_t)c->fB * c->C * c->fT * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return WN_OK;
 }
 
@@ -437,6 +449,7 @@ extern "C" int wn_synthesize(wn_ctx* c, const float* cc, int32_t B, int32_t Tc, 
     if (!c->packed) WN_FAIL(c, WN_E_STATE, "wn_pack_weights must be called before wn_synthesize");
     if (B <= 0 || B > 32) WN_FAIL(c, WN_E_SHAPE, "synthesis batch %d outside (0, 32]", B);
     if (Tc <= 0) WN_FAIL(c, WN_E_SHAPE, "Tc must be positive");
+    c->strm.open = false; c->fup_pitch = 0;            // (ends an open stream: its queues are overwritten)
     int rc = wn_pipe_check(c, false);                  // a hand-off timeout of the previous pipeline run surfaces here at the latest
     if (rc) return rc;
     if (!noise) {                                      // device Philox stream keyed by `seed` (header)
@@ -456,7 +469,7 @@ extern "C" int wn_synth_check(wn_ctx* c) { if (!c) return WN_E_ARG; return wn_pi
 extern "C" int wn_synth_last_path(const wn_ctx* c) { return c ? c->synth_path : WN_E_ARG; }
 extern "C" int wn_synth_last_instances(const wn_ctx* c) { return c ? c->synth_instances : WN_E_ARG; }
 extern "C" int wn_synth_last_batched(const wn_ctx* c) { return c ? (c->synth_path == 2 ? c->synth_batchpre : 0) : WN_E_ARG; }
-extern "C" int wn_synth_pipe_dtype(wn_ctx* c, int32_t half) { if (!c) return WN_E_ARG; c->pipe_f16 = half != 0; return WN_OK; }
+extern "C" int wn_synth_pipe_dtype(wn_ctx* c, int32_t half) { if (!c) return WN_E_ARG; c->pipe_f16 = half != 0; c->strm.open = false; return WN_OK; }
 extern "C" int wn_synth_last_config(const wn_ctx* c, int32_t* out, int32_t cap) {
     if (!c || !out || cap < 0) return WN_E_ARG;
     int32_t v[WN_SYNTH_CFG_N] = {c->synth_path, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -551,3 +564,142 @@ extern "C" int wn_test_dropout_mask(uint64_t seed, int32_t layer, float p, int64
     return WN_OK;
 }
 
+
+// ---- streaming synthesis ------------------------------------------------------------------------------------------------------
+extern "C" int wn_synth_stream_lookahead(const wn_config* cfg, int32_t* frames_left, int32_t* frames_right) {
+    if (!cfg || !frames_left || !frames_right || cfg->n_upsample < 0 || cfg->n_upsample > WN_MAX_UPSAMPLE) return WN_E_ARG;
+    int64_t hop = 1;
+    for (int i = 0; i < cfg->n_upsample; ++i) { if (cfg->upsample_scales[i] <= 0) return WN_E_ARG; hop *= cfg->upsample_scales[i]; }
+    int32_t l = 0, r = 0;
+    if (cfg->upsample_type == WN_UP_SUBPIXEL) {
+        // modules.py:578-640: every layer convolves its INPUT with a 3-tap time kernel (SAME) before the shuffle: one input sample of layer i on
+        // each side = prod(scales[i:]) samples at the final rate.  [5, 5, 11]: 275 + 55 + 11 = 341 samples = 2 frames; [11, 25]: 2 frames
+        int64_t h = 0, later = 1;
+        for (int i = cfg->n_upsample - 1; i >= 0; --i) { later *= cfg->upsample_scales[i]; h += later; }
+        l = r = (int32_t)((h + hop - 1) / hop);
+    } else if (cfg->upsample_type == WN_UP_RESIZE) {
+        // modules.py:657-695: nearest resize x s, then an s-tap time kernel (SAME: p = (s-1)/2 before, s-1-p after) at the OUTPUT rate of the layer;
+        // p samples of layer i are p * prod(later scales) samples at the final rate.  sum_i < hop / 2: at most one frame on each side
+        int64_t hl = 0, hr = 0, later = 1;
+        for (int i = cfg->n_upsample - 1; i >= 0; --i) {
+            const int s = cfg->upsample_scales[i], p = (s - 1) / 2;
+            hl += (int64_t)p * later; hr += (int64_t)(s - 1 - p) * later; later *= s;
+        }
+        l = (int32_t)((hl + hop - 1) / hop); r = (int32_t)((hr + hop - 1) / hop);
+    } else if (cfg->upsample_type != WN_UP_NEAREST && cfg->upsample_type != WN_UP_2D && cfg->upsample_type != WN_UP_1D) return WN_E_ARG;
+    *frames_left = l; *frames_right = r;
+    return WN_OK;
+}
+
+// pending mel frames of the stream: [B][C][w] taken from the previous window (columns drop .. drop + keep) and the pushed frames [B][C][Tn]
+__global__ void wn_stream_window_kernel(const float* __restrict__ prev, int64_t prev_cols, int64_t drop, int64_t keep, const float* __restrict__ cnew, int Tn,
+                                        float* __restrict__ win, int64_t w, int64_t rows) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rows * w) return;
+    const int64_t row = i / w, col = i - row * w;
+    win[i] = col < keep ? prev[row * prev_cols + drop + col] : cnew[row * Tn + (col - keep)];
+}
+
+// stream state buffers, sized for (max_batch, max_time): the window of pending frames never holds more than max_batch x max_time / hop
+// frame columns (push checks it), the bias [L][B][G], the carried inputs
+static int stream_alloc(wn_ctx* c) {
+    auto& S = c->strm;
+    if (!S.pend[0]) {
+        S.pend_cap = (int64_t)c->C * (c->NT / c->hop + 1);
+        for (float*& q : S.pend) WN_HIP(c, hipMalloc((void**)&q, (size_t)S.pend_cap * 4));
+    }
+    if (!S.carry) WN_HIP(c, hipMalloc((void**)&S.carry, 32 * 4));
+    if (c->gin > 0 && !S.gbias) WN_HIP(c, hipMalloc((void**)&S.gbias, (size_t)c->L * c->maxB * c->G * 4));
+    return WN_OK;
+}
+
+extern "C" int wn_synth_stream_begin(wn_ctx* c, int32_t B, uint64_t seed, int32_t steps_per_graph, void* stream) {
+    if (!c) return WN_E_ARG;
+    WnRange range("wn_synth_stream_begin");
+    auto& S = c->strm;
+    S.open = false;
+    if (!c->packed) WN_FAIL(c, WN_E_STATE, "wn_pack_weights must be called before wn_synth_stream_begin");
+    if (B <= 0 || B > 32 || B > c->maxB) WN_FAIL(c, WN_E_SHAPE, "stream batch %d outside (0, min(32, max_batch = %d)]", B, c->maxB);
+    if (c->gin > 0 && (!c->have_g || c->gB != B))
+        WN_FAIL(c, WN_E_STATE, "global conditioning is enabled: call wn_set_global_condition with this batch (B=%d) first [wavenet.py:766-777]", B);
+    int rc = wn_pipe_check(c, false);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    // the path of wn_synthesize(steps_per_graph) for B (wn_synth_impl), kept for the life of the stream
+    const int path = c->cfg.compute_dtype == WN_COMPUTE_F32 ? 3 : wn_synth_takes_pipe(c, B, steps_per_graph) ? 2 : 1;
+    if ((rc = wn_noise_reserve(c, B, c->maxT))) return rc;
+    if ((rc = path == 3 ? wn_synth_f32_reserve(c, B) : path == 2 ? wn_pipe_reserve(c, B, c->maxT) : wn_synth_reserve(c))) return rc;
+    if ((rc = stream_alloc(c))) return rc;
+    if (c->gin > 0) {      // the stream's own copy: a training step between pushes rewrites c->gbias
+        if ((rc = wn_gbias_fwd(c, B, st))) return rc;
+        WN_HIP(c, hipMemcpyAsync(S.gbias, c->gbias, (size_t)c->L * B * c->G * 4, hipMemcpyDeviceToDevice, st));
+    }
+    wn_synth_stream_lookahead(&c->cfg, &S.left, &S.right);
+    S.B = B; S.seed = seed; S.spg = steps_per_graph; S.path = path;
+    S.pushed = S.done = S.pend_first = 0; S.cur = 0; S.poisoned = false;
+    S.open = true;
+    return WN_OK;
+}
+
+extern "C" int wn_synth_stream_push(wn_ctx* c, const float* cc, int32_t Tn, int32_t final, const float* noise, const void* test_inputs,
+                                    void* out_samples, float* out_raw, int32_t* n_out, void* stream) {
+    if (!c) return WN_E_ARG;
+    WnRange range("wn_synth_stream_push");
+    auto& S = c->strm;
+    if (!S.open) WN_FAIL(c, WN_E_STATE, "wn_synth_stream_push: no open stream (never begun, closed by a final push, or ended by wn_synthesize / "
+                                       "wn_pack_weights / wn_set_global_condition / wn_synth_pipe_dtype)");
+    if (S.poisoned) WN_FAIL(c, WN_E_STATE, "wn_synth_stream_push: a pipeline run of this stream failed (wn_synth_check); begin a new stream");
+    if (Tn < 0 || (Tn > 0 && !cc) || !n_out) WN_FAIL(c, WN_E_ARG, "wn_synth_stream_push: bad frames (Tn = %d) or null n_out", Tn);
+    int rc = wn_pipe_check(c, false);                  // a failed earlier push surfaces here at the latest (and poisons the stream)
+    if (rc) return rc;
+    const int B = S.B, hop = c->hop;
+    const int64_t pushed = S.pushed + Tn;
+    const int64_t gen_end = final ? pushed : std::max(S.done, pushed - S.right);
+    const int64_t n = (gen_end - S.done) * hop;
+    const int64_t wstart = std::max<int64_t>(0, S.done - S.left), w = pushed - wstart;
+    if (n > c->maxT) WN_FAIL(c, WN_E_SHAPE, "wn_synth_stream_push: %lld samples in one push exceed max_time = %d", (long long)n, c->maxT);
+    if ((int64_t)B * w * hop > c->NT)
+        WN_FAIL(c, WN_E_SHAPE, "wn_synth_stream_push: a window of %lld frames (%d of left context + the frames not yet generated) x %d streams exceeds the workspace", (long long)w, S.left, B);
+    if (S.done * hop + n > INT32_MAX) WN_FAIL(c, WN_E_SHAPE, "wn_synth_stream_push: utterance longer than 2^31 samples");
+    if (n > 0 && !out_samples) WN_FAIL(c, WN_E_ARG, "wn_synth_stream_push: null out_samples");
+    hipStream_t st = (hipStream_t)stream;
+    // pending frames [wstart, pushed): the part of the previous window still needed + the new frames, into the other buffer (the stream's
+    // state advances only once everything below is enqueued; a failure after the first enqueue poisons the stream)
+    float* win = S.pend[S.cur ^ 1];
+    S.poisoned = true;
+    if (w > 0) {
+        const int64_t rows = (int64_t)B * c->C;
+        hipLaunchKernelGGL(wn_stream_window_kernel, dim3(cdiv(rows * w, 256)), dim3(256), 0, st, S.pend[S.cur], S.pushed - S.pend_first, wstart - S.pend_first,
+                           S.pushed - wstart, cc, Tn, win, w, rows);
+        WN_LAUNCH_CHECK(c);
+    }
+    if (n > 0) {
+        const int T = (int)n;
+        // the window's upsampled conditioning (wavenet.py:781-803); rows of the frames generated here are exact: the lookahead keeps every row an
+        // artificial window edge touches out of the span (and a window edge at frame 0 / the final frame is the utterance's own edge)
+        if ((rc = wn_upsample_fwd(c, nullptr, win, B, (int)w, st))) return rc;
+        const int nps = wn_noise_per_step(c);
+        if (!noise) {      // the device stream of `seed` over the whole utterance, continued: elements [t0 B nps, (t0 + n) B nps)
+            if ((rc = wn_fill_noise_span(c, c->noise_buf, S.done * hop * B * nps, (int64_t)T * B * nps, S.seed, st))) return rc;
+            noise = c->noise_buf;
+        }
+        WnSpan sp;
+        sp.t0 = (int)(S.done * hop); sp.Tcb = (int)(w * hop); sp.cbt_off = (int)((S.done - wstart) * hop); sp.carry = S.carry; sp.gbias = S.gbias;
+        rc = S.path == 2 ? wn_pipe_span(c, B, T, sp, noise, test_inputs, out_samples, out_raw, st)
+           : S.path == 3 ? wn_synth_f32_span(c, B, T, sp, noise, test_inputs, out_samples, out_raw, S.spg, st)
+                         : wn_synth_span(c, B, T, sp, noise, test_inputs, out_samples, out_raw, S.spg, st);
+        if (rc) return rc;
+        c->fB = B; c->fT = T; c->fTc = (int)(gen_end - S.done); c->fup_off = sp.cbt_off; c->fup_pitch = sp.Tcb;
+    }
+    S.poisoned = false;
+    S.cur ^= 1; S.pend_first = wstart; S.pushed = pushed; S.done = gen_end;
+    *n_out = (int32_t)n;
+    if (final) S.open = false;
+    return WN_OK;
+}
+
+extern "C" int wn_synth_stream_end(wn_ctx* c) {
+    if (!c) return WN_E_ARG;
+    c->strm.open = false;
+    return WN_OK;
+}

@@ -201,7 +201,22 @@ struct wn_ctx {
     void* f32 = nullptr;                  // fp32-forward state (wn_f32.hip), allocated on the first forward of a cfg.compute_dtype = WN_COMPUTE_F32 context
     bool fwd_was_f32 = false;
     float* dy32_next = nullptr;           // the next wn_loss_run also writes d y_hat in fp32 here ([rows][ldDY]; fp32 training mode)
+    // streaming synthesis (wn_synth_stream_*): frames pushed so far, frames generated, the pending window [pend_first, pushed) of mel frames
+    // ([B][C][pushed - pend_first], ping-pong), the stream's own global-conditioning bias and the pipeline's carried next input per stream
+    struct {
+        bool open = false, poisoned = false; int path = 0;          // path: 1 launch-per-layer, 2 pipeline, 3 fp32 launch-per-layer
+        int B = 0, spg = 0, left = 0, right = 0; uint64_t seed = 0;
+        int64_t pushed = 0, done = 0, pend_first = 0; int cur = 0;
+        float* pend[2] = {nullptr, nullptr}; int64_t pend_cap = 0;      // floats per buffer
+        float* gbias = nullptr;                                        // [L][B][G] (gin > 0)
+        int32_t* carry = nullptr;                                      // [32] fed-back sample bits / class id of every stream (pipeline)
+    } strm;
+    int64_t fup_off = 0, fup_pitch = 0;   // wn_get_upsampled_features after a push: the span's columns [fup_off, fup_off + fT) of rows of fup_pitch
 };
+
+// one push of a stream as the synthesis paths see it: absolute first sample t0, span length T, conditioning rows cbt[b][cbt_off + t] of a
+// window of Tcb rows per stream, the stream's carry / bias; t0 == 0 starts from silence and zero queues exactly as wn_synthesize does
+struct WnSpan { int t0, Tcb, cbt_off; int32_t* carry; const float* gbias; };
 
 extern std::string g_create_err;
 
@@ -221,6 +236,15 @@ int wn_bwd_impl(wn_ctx* ctx, float* grads, hipStream_t st);
 int wn_optim_impl(wn_ctx* ctx, float* p, const float* g, float* m, float* v, float* ema, float lr, int64_t step, hipStream_t st);
 int wn_synth_impl(wn_ctx* ctx, const float* c, int B, int Tc, const float* noise, uint64_t seed,
                   const void* test_inputs, void* out_samples, float* out_raw, int steps_per_graph, hipStream_t st);
+// one push of an open stream (conditioning already upsampled into cbt): T samples on the path the stream was opened with
+int wn_synth_span(wn_ctx* ctx, int B, int T, const WnSpan& sp, const float* noise, const void* test_inputs, void* out_samples, float* out_raw,
+                  int steps_per_graph, hipStream_t st);
+bool wn_synth_takes_pipe(const wn_ctx* ctx, int B, int steps_per_graph);      // wn_synthesize's path choice (bf16 modes)
+int wn_synth_f32_span(wn_ctx* ctx, int B, int T, const WnSpan& sp, const float* noise, const void* test_inputs, void* out_samples, float* out_raw,
+                      int steps_per_graph, hipStream_t st);
+int wn_pipe_span(wn_ctx* ctx, int B, int T, const WnSpan& sp, const float* noise, const void* test_inputs, void* out_samples, float* out_raw,
+                 hipStream_t st);
+int wn_fill_noise_span(wn_ctx* ctx, float* noise, int64_t first, int64_t n, uint64_t seed, hipStream_t st);   // elements [first, first + n) of the flat stream
 void wn_synth_free(wn_ctx* ctx);
 void wn_synth_f32_free(wn_ctx* ctx);
 int wn_synth_f32_reserve(wn_ctx* ctx, int B);

@@ -362,12 +362,10 @@ __host__ __device__ inline void wn_philox4x32_10(uint32_t c0, uint32_t c1, uint3
 }
 // 24 random bits -> (0, 1) open at both ends, then clamped to the reference's range [1e-5, 1 - 1e-5] (mixture.py:91,104)
 __host__ __device__ inline float wn_u01(uint32_t w) { return ((float)(w >> 8) + 0.5f) * (1.0f / 16777216.0f); }
-__global__ void wn_noise_kernel(float* __restrict__ out, int64_t n, uint32_t k0, uint32_t k1, int gaussian) {
-    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g * 4 >= n) return;
+// the four elements 4g .. 4g+3 of the stream (one Philox group; Box-Muller pairs stay inside it)
+__device__ __forceinline__ void wn_noise_group(int64_t g, uint32_t k0, uint32_t k1, int gaussian, float v[4]) {
     uint32_t w[4];
     wn_philox4x32_10((uint32_t)g, (uint32_t)(g >> 32), k0, k1, w);
-    float v[4];
     if (gaussian) {                                   // Box-Muller on the word pairs (w0, w1) and (w2, w3)
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
@@ -378,6 +376,12 @@ __global__ void wn_noise_kernel(float* __restrict__ out, int64_t n, uint32_t k0,
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] = fminf(fmaxf(wn_u01(w[j]), 1e-5f), 1.0f - 1e-5f);     // exact ops only (no rounding: any compiler, and the numpy mirror, give the same bits)
     }
+}
+__global__ void wn_noise_kernel(float* __restrict__ out, int64_t n, uint32_t k0, uint32_t k1, int gaussian) {
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g * 4 >= n) return;
+    float v[4];
+    wn_noise_group(g, k0, k1, gaussian, v);
     if (g * 4 + 3 < n) *reinterpret_cast<float4*>(out + g * 4) = make_float4(v[0], v[1], v[2], v[3]);
     else for (int j = 0; j < 4 && g * 4 + j < n; ++j) out[g * 4 + j] = v[j];
 }
@@ -386,6 +390,24 @@ int wn_fill_noise_impl(wn_ctx* c, float* noise, int B, int T, uint64_t seed, hip
     if ((reinterpret_cast<uintptr_t>(noise) & 15) != 0) WN_FAIL(c, WN_E_ARG, "noise buffer must be 16-byte aligned");
     const int gaussian = (c->cfg.input_type != WN_INPUT_MULAW_QUANTIZE && c->O == 2) ? 1 : 0;
     hipLaunchKernelGGL(wn_noise_kernel, dim3(cdiv((n + 3) / 4, 256)), dim3(256), 0, st, noise, n, (uint32_t)seed, (uint32_t)(seed >> 32), gaussian);
+    WN_LAUNCH_CHECK(c);
+    return WN_OK;
+}
+
+// elements [first, first + n) of the same stream into out[0 .. n): a streaming push starting at sample t0 starts at element t0 * B * nps, not
+// necessarily on a group boundary -- thread i evaluates group first / 4 + i whole (the same code as above) and keeps the elements in range
+__global__ void wn_noise_span_kernel(float* __restrict__ out, int64_t first, int64_t n, uint32_t k0, uint32_t k1, int gaussian) {
+    const int64_t g = first / 4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g * 4 >= first + n) return;
+    float v[4];
+    wn_noise_group(g, k0, k1, gaussian, v);
+    for (int j = 0; j < 4; ++j) { const int64_t e = g * 4 + j; if (e >= first && e < first + n) out[e - first] = v[j]; }
+}
+int wn_fill_noise_span(wn_ctx* c, float* noise, int64_t first, int64_t n, uint64_t seed, hipStream_t st) {
+    if (n <= 0) return WN_OK;
+    const int gaussian = (c->cfg.input_type != WN_INPUT_MULAW_QUANTIZE && c->O == 2) ? 1 : 0;
+    const int64_t groups = (first + n + 3) / 4 - first / 4;
+    hipLaunchKernelGGL(wn_noise_span_kernel, dim3(cdiv(groups, 256)), dim3(256), 0, st, noise, first, n, (uint32_t)seed, (uint32_t)(seed >> 32), gaussian);
     WN_LAUNCH_CHECK(c);
     return WN_OK;
 }

@@ -20,11 +20,11 @@ struct Synth {
     float* skip_acc = nullptr;     // [32][S]
     bf16_t* h2 = nullptr;          // [32][S]
     float* yraw = nullptr;         // [32][OP]
-    int32_t* t_dev = nullptr;
+    int32_t* t_dev = nullptr;      // [0] absolute time index of the next step, [1] first sample of the running span (0 for wn_synthesize; a stream push: its t0)
     hipStream_t priv = nullptr;    // capture / replay happens on a ctx-owned stream (the caller's may be the legacy
     hipEvent_t ev0 = nullptr, ev1 = nullptr;   // NULL stream, which cannot be captured); ordered by events
     bf16_t** ring_tab = nullptr;   // device table of ring pointers
-    hipGraphExec_t gexec = nullptr; int g_steps = 0; int g_B = 0; const void* g_key[5] = {0, 0, 0, 0, 0}; int g_T = 0;
+    hipGraphExec_t gexec = nullptr; int g_steps = 0; int g_B = 0; const void* g_key[6] = {0, 0, 0, 0, 0, 0}; int g_T = 0, g_Tcb = 0;
 };
 
 __device__ __forceinline__ f32x16_t zero16() { f32x16_t z; for (int i = 0; i < 16; ++i) z[i] = 0.0f; return z; }
@@ -44,12 +44,12 @@ __device__ __forceinline__ float acc_at(const float* red, int wave_stride, int n
 // ---- stage A: z = [W_dil | W_cin] [x(t-2d); x(t-d); x(t); c_t] + b  -> tanh * sigmoid -> u    (modules.py:273-303, 494-510)
 template <int NW>
 __global__ __launch_bounds__(NW * 64) void wn_synth_gate(const bf16_t* __restrict__ Apk, int ksteps, const bf16_t* __restrict__ ring, int mask,
-                                                     int d, int R, const bf16_t* __restrict__ cbt, int C, int T, int B,
+                                                     int d, int R, const bf16_t* __restrict__ cbt, int C, int Tcb, int B,
                                                      const float* __restrict__ bias, int bias_bstride, int GH, bf16_t* __restrict__ ucur,
                                                      const int32_t* __restrict__ t_dev, int kil) {
     __shared__ float red[NW * 2 * 64 * 16];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int t = *t_dev;
+    const int t = t_dev[0], tl = t - t_dev[1];      // absolute (queues) / span-local (conditioning rows cbt[n][tl], Tcb per stream)
     const int n = lane & 31, h = lane >> 5;
     const int blk = blockIdx.x;
     f32x16_t acc0 = zero16(), acc1 = zero16();
@@ -72,7 +72,7 @@ __global__ __launch_bounds__(NW * 64) void wn_synth_gate(const bf16_t* __restric
                         const int tau = t - (2 - j) * d;
                         if (tau >= 0) bv[i] = *reinterpret_cast<const uint4*>(ring + ((size_t)(tau & mask) * 32 + n) * R + r);
                     } else {
-                        bv[i] = *reinterpret_cast<const uint4*>(cbt + ((size_t)n * T + t) * C + (k0 - 3 * R));
+                        bv[i] = *reinterpret_cast<const uint4*>(cbt + ((size_t)n * Tcb + tl) * C + (k0 - 3 * R));
                     }
                 }
                 a0[i] = *reinterpret_cast<const uint4*>(A0 + (size_t)ks * 512);
@@ -224,16 +224,16 @@ __global__ __launch_bounds__(256) void wn_synth_sample(const float* __restrict__
     __shared__ float nxt_f[32];
     __shared__ int nxt_i[32];
     const int tid = threadIdx.x;
-    const int t = *t_dev;
+    const int t = t_dev[0], tl = t - t_dev[1];      // ring slots by the absolute index; noise, teacher forcing and outputs [.., T] by the span's
     if (tid < B) {
         const int n = tid;
         const float* p = yraw + (size_t)n * OP;
-        const float* nz = noise + ((size_t)t * B + n) * nps;
+        const float* nz = noise + ((size_t)tl * B + n) * nps;
         if (mode == 2) {
             float best = -INFINITY; int bi = 0;
             for (int q = 0; q < O; ++q) { const float v = p[q] - logf(-logf(nz[q])); if (v > best) { best = v; bi = q; } }
-            ((int32_t*)out_samples)[(size_t)n * T + t] = bi;
-            nxt_i[n] = test_inputs ? ((const int32_t*)test_inputs)[(size_t)n * T + t] : bi;
+            ((int32_t*)out_samples)[(size_t)n * T + tl] = bi;
+            nxt_i[n] = test_inputs ? ((const int32_t*)test_inputs)[(size_t)n * T + tl] : bi;
         } else {
             float x;
             if (mode == 0) {
@@ -247,11 +247,11 @@ __global__ __launch_bounds__(256) void wn_synth_sample(const float* __restrict__
                 x = p[0] + expf(fmaxf(p[1], lsmin)) * nz[0];
             }
             x = fminf(fmaxf(x, -1.0f), 1.0f);
-            ((float*)out_samples)[(size_t)n * T + t] = x;
-            nxt_f[n] = test_inputs ? ((const float*)test_inputs)[(size_t)n * T + t] : x;
+            ((float*)out_samples)[(size_t)n * T + tl] = x;
+            nxt_f[n] = test_inputs ? ((const float*)test_inputs)[(size_t)n * T + tl] : x;
         }
     }
-    if (out_raw) for (int o = tid; o < B * O; o += 256) { const int n = o / O, oc = o - n * O; out_raw[((size_t)n * O + oc) * T + t] = yraw[(size_t)n * OP + oc]; }
+    if (out_raw) for (int o = tid; o < B * O; o += 256) { const int n = o / O, oc = o - n * O; out_raw[((size_t)n * O + oc) * T + tl] = yraw[(size_t)n * OP + oc]; }
     __syncthreads();
     // input convolution for step t+1 into ring 0
     for (int o = tid; o < B * R; o += 256) {
@@ -271,7 +271,7 @@ __global__ void wn_synth_init(const float* __restrict__ Wf, const float* __restr
         const float v = (mode == 2) ? Wf[(size_t)start_id * R + r] + bf_[r] : bf_[r];      // x = 0 for raw / mulaw
         ring0[((size_t)n) * R + r] = f2bf(v);
     }
-    if (threadIdx.x == 0) *t_dev = 0;
+    if (threadIdx.x == 0) { t_dev[0] = 0; t_dev[1] = 0; }
 }
 
 void wn_synth_free(wn_ctx* c) {
@@ -285,14 +285,15 @@ void wn_synth_free(wn_ctx* c) {
     delete s; c->synth = nullptr;
 }
 
-static int enqueue_step(wn_ctx* c, Synth* s, const float* noise, const void* test_inputs, void* out_samples, float* out_raw, hipStream_t st) {
+static int enqueue_step(wn_ctx* c, Synth* s, const bf16_t* cbt, int Tcb, const float* gbias, const float* noise, const void* test_inputs, void* out_samples,
+                        float* out_raw, hipStream_t st) {
     const int L = c->L, R = c->R, GH = c->GH, S = c->S, C = c->C, B = s->B, T = s->T;
     for (int l = 0; l < L; ++l) {
         // waves per block by the K of the launch: every wave should get its k-steps in ONE pass of <= WN_SYN_MAXK loads
         const int ksg = c->packs[l].w1.K >> 4, kso = GH >> 4;
-        const float* gbias_l = c->gin > 0 ? c->gbias + (size_t)l * B * c->G : c->b1sum + (size_t)l * c->G;
+        const float* gbias_l = c->gin > 0 ? gbias + (size_t)l * B * c->G : c->b1sum + (size_t)l * c->G;
 #define WN_LAUNCH_GATE(NW_) hipLaunchKernelGGL(wn_synth_gate<NW_>, dim3(GH / 32), dim3(NW_ * 64), 0, st, c->packs[l].w1.dev, ksg, s->ring[l], s->mask[l], \
-                           c->dil[l], R, c->cbt, C, T, B, gbias_l, c->gin > 0 ? c->G : 0, GH, s->ucur, s->t_dev, c->packs[l].w1.kil)
+                           c->dil[l], R, cbt, C, Tcb, B, gbias_l, c->gin > 0 ? c->G : 0, GH, s->ucur, s->t_dev, c->packs[l].w1.kil)
         if (ksg > 4 * WN_SYN_MAXK) WN_LAUNCH_GATE(8); else WN_LAUNCH_GATE(4);      // (16 waves = 1024 threads cap the kernel at 128 VGPRs: the up-front loads spill)
 #undef WN_LAUNCH_GATE
         const bool top = (l == L - 1);
@@ -312,6 +313,33 @@ static int enqueue_step(wn_ctx* c, Synth* s, const float* noise, const void* tes
     return WN_OK;
 }
 
+// T steps from the current t_dev: graphs of steps_per_graph steps (reused while the pointers and sizes match), then single steps
+static int synth_steps(wn_ctx* c, Synth* s, const bf16_t* cbt, int Tcb, const float* gbias, const float* noise, const void* test_inputs, void* out_samples,
+                       float* out_raw, int steps_per_graph, hipStream_t st) {
+    const int T = s->T, B = s->B;
+    int rc, done = 0;
+    if (steps_per_graph > 1 && T >= steps_per_graph) {
+        const void* key[6] = {noise, test_inputs, out_samples, out_raw, cbt, gbias};
+        const bool reuse = s->gexec && s->g_steps == steps_per_graph && s->g_B == B && s->g_T == T && s->g_Tcb == Tcb && memcmp(key, s->g_key, sizeof key) == 0;
+        if (!reuse) {
+            if (s->gexec) { hipGraphExecDestroy(s->gexec); s->gexec = nullptr; }
+            hipGraph_t graph;
+            WN_HIP(c, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+            for (int i = 0; i < steps_per_graph; ++i) {
+                rc = enqueue_step(c, s, cbt, Tcb, gbias, noise, test_inputs, out_samples, out_raw, st);
+                if (rc) { hipStreamEndCapture(st, &graph); return rc; }
+            }
+            WN_HIP(c, hipStreamEndCapture(st, &graph));
+            WN_HIP(c, hipGraphInstantiate(&s->gexec, graph, nullptr, nullptr, 0));
+            hipGraphDestroy(graph);
+            s->g_steps = steps_per_graph; s->g_B = B; s->g_T = T; s->g_Tcb = Tcb; memcpy(s->g_key, key, sizeof key);
+        }
+        for (; done + steps_per_graph <= T; done += steps_per_graph) WN_HIP(c, hipGraphLaunch(s->gexec, st));
+    }
+    for (; done < T; ++done) { rc = enqueue_step(c, s, cbt, Tcb, gbias, noise, test_inputs, out_samples, out_raw, st); if (rc) return rc; }
+    return WN_OK;
+}
+
 // state of the launch-per-layer path: ring queues for up to 32 streams, per-step scratch, the capture stream (sizes do not depend
 // on the utterance length).  wn_create calls this on inference-only contexts; training contexts get here on first use.
 int wn_synth_reserve(wn_ctx* c) {
@@ -328,11 +356,22 @@ int wn_synth_reserve(wn_ctx* c) {
         WN_HIP(c, hipMalloc((void**)&s->skip_acc, 32 * c->S * 4));
         WN_HIP(c, hipMalloc((void**)&s->h2, 32 * c->S * 2));
         WN_HIP(c, hipMalloc((void**)&s->yraw, 32 * c->OP * 4));
-        WN_HIP(c, hipMalloc((void**)&s->t_dev, 4));
+        WN_HIP(c, hipMalloc((void**)&s->t_dev, 8));
         WN_HIP(c, hipStreamCreateWithFlags(&s->priv, hipStreamNonBlocking));
         WN_HIP(c, hipEventCreateWithFlags(&s->ev0, hipEventDisableTiming));
         WN_HIP(c, hipEventCreateWithFlags(&s->ev1, hipEventDisableTiming));
     return WN_OK;
+}
+
+// The bf16 path of wn_synthesize(steps_per_graph) for B streams (a stream keeps the answer of its begin: the same path gives the same bits).
+// steps_per_graph <= 0 selects the persistent dataflow pipeline (wn_synth_pipe.hip) when the model fits it; WN_SYNTH_MODE=graph|pipe overrides.
+// (an inference-only context never grows its pre-sized pipeline: a batch beyond pipe_cap takes the launch-per-layer path, as
+// wn_synth_pipe_eligible tells the caller -- ADVICE round 5: this dispatch used to ignore pipe_cap and fail in wn_pipe_reserve)
+bool wn_synth_takes_pipe(const wn_ctx* c, int B, int steps_per_graph) {
+    const char* m = getenv("WN_SYNTH_MODE");
+    const bool want_pipe = m ? (strcmp(m, "pipe") == 0) : (steps_per_graph <= 0);
+    const bool over_cap = c->inference && c->pipe_cap > 0 && B > c->pipe_cap;
+    return want_pipe && !over_cap && wn_pipe_eligible(c, B);
 }
 
 int wn_synth_impl(wn_ctx* c, const float* cin, int B, int Tc, const float* noise, uint64_t, const void* test_inputs,
@@ -343,16 +382,8 @@ int wn_synth_impl(wn_ctx* c, const float* cin, int B, int Tc, const float* noise
         WN_FAIL(c, WN_E_STATE, "global conditioning is enabled: call wn_set_global_condition with this batch (B=%d) first [wavenet.py:766-777]", B);
     // the reference's own arithmetic (fp32 weights, queues, accumulation): its own launch-per-layer path, never the bf16 pipeline
     if (c->cfg.compute_dtype == WN_COMPUTE_F32) return wn_synth_f32_impl(c, cin, B, Tc, noise, test_inputs, out_samples, out_raw, steps_per_graph, caller_st);
-    {   // steps_per_graph <= 0 selects the persistent dataflow pipeline (wn_synth_pipe.hip) when the model fits it;
-        // WN_SYNTH_MODE=graph|pipe overrides
-        const char* m = getenv("WN_SYNTH_MODE");
-        const bool want_pipe = m ? (strcmp(m, "pipe") == 0) : (steps_per_graph <= 0);
-        // (an inference-only context never grows its pre-sized pipeline: a batch beyond pipe_cap takes the launch-per-layer path, as
-        // wn_synth_pipe_eligible tells the caller -- ADVICE round 5: this dispatch used to ignore pipe_cap and fail in wn_pipe_reserve)
-        const bool over_cap = c->inference && c->pipe_cap > 0 && B > c->pipe_cap;
-        if (want_pipe && !over_cap && wn_pipe_eligible(c, B)) return wn_pipe_synthesize(c, cin, B, Tc, noise, test_inputs, out_samples, out_raw, caller_st);
-        if (steps_per_graph <= 0) steps_per_graph = 32;
-    }
+    if (wn_synth_takes_pipe(c, B, steps_per_graph)) return wn_pipe_synthesize(c, cin, B, Tc, noise, test_inputs, out_samples, out_raw, caller_st);
+    if (steps_per_graph <= 0) steps_per_graph = 32;
     int rc0 = wn_synth_reserve(c);
     if (rc0) return rc0;
     const int L = c->L, R = c->R;
@@ -374,26 +405,35 @@ int wn_synth_impl(wn_ctx* c, const float* cin, int B, int Tc, const float* noise
                        s->ring[0], B, s->t_dev);
     WN_LAUNCH_CHECK(c);
 
-    int done = 0;
-    if (steps_per_graph > 1 && T >= steps_per_graph) {
-        const void* key[5] = {noise, test_inputs, out_samples, out_raw, cin};
-        const bool reuse = s->gexec && s->g_steps == steps_per_graph && s->g_B == B && s->g_T == T && memcmp(key, s->g_key, sizeof key) == 0;
-        if (!reuse) {
-            if (s->gexec) { hipGraphExecDestroy(s->gexec); s->gexec = nullptr; }
-            hipGraph_t graph;
-            WN_HIP(c, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-            for (int i = 0; i < steps_per_graph; ++i) {
-                rc = enqueue_step(c, s, noise, test_inputs, out_samples, out_raw, st);
-                if (rc) { hipStreamEndCapture(st, &graph); return rc; }
-            }
-            WN_HIP(c, hipStreamEndCapture(st, &graph));
-            WN_HIP(c, hipGraphInstantiate(&s->gexec, graph, nullptr, nullptr, 0));
-            hipGraphDestroy(graph);
-            s->g_steps = steps_per_graph; s->g_B = B; s->g_T = T; memcpy(s->g_key, key, sizeof key);
-        }
-        for (; done + steps_per_graph <= T; done += steps_per_graph) WN_HIP(c, hipGraphLaunch(s->gexec, st));
-    }
-    for (; done < T; ++done) { rc = enqueue_step(c, s, noise, test_inputs, out_samples, out_raw, st); if (rc) return rc; }
+    if ((rc = synth_steps(c, s, c->cbt, T, c->gbias, noise, test_inputs, out_samples, out_raw, steps_per_graph, st))) return rc;
+    WN_HIP(c, hipEventRecord(s->ev1, st));
+    WN_HIP(c, hipStreamWaitEvent(caller_st, s->ev1, 0));
+    return WN_OK;
+}
+
+// One push of an open stream on this path: the queues, the time index and ring 0's next input are those the previous push left (its last step
+// wrote ring0[(t + 1) & mask0]); only the first push (t0 = 0) zeroes the queues and starts from silence.  The span's first sample goes to t_dev[1]
+// in device memory, so captured graphs stay valid whatever t0 is.  The conditioning rows are cbt[b][sp.cbt_off + t] of a window of sp.Tcb.
+int wn_synth_span(wn_ctx* c, int B, int T, const WnSpan& sp, const float* noise, const void* test_inputs, void* out_samples, float* out_raw,
+                  int steps_per_graph, hipStream_t caller_st) {
+    int rc = wn_synth_reserve(c);
+    if (rc) return rc;
+    const int L = c->L, R = c->R;
+    Synth* s = c->synth;
+    c->synth_path = 1;
+    if (steps_per_graph <= 0) steps_per_graph = 32;
+    hipStream_t st = s->priv;
+    WN_HIP(c, hipEventRecord(s->ev0, caller_st));
+    WN_HIP(c, hipStreamWaitEvent(st, s->ev0, 0));
+    s->B = B; s->T = T;
+    if (sp.t0 == 0) {
+        for (int l = 0; l < L; ++l) WN_HIP(c, hipMemsetAsync(s->ring[l], 0, (size_t)(s->mask[l] + 1) * 32 * R * 2, st));
+        const int mode = c->cfg.input_type == WN_INPUT_MULAW_QUANTIZE ? 2 : (c->O == 2 ? 1 : 0);
+        hipLaunchKernelGGL(wn_synth_init, dim3(1), dim3(256), 0, st, c->params_dev + c->first.dil_k, c->params_dev + c->first.dil_b, R, mode, 127,
+                           s->ring[0], B, s->t_dev);
+        WN_LAUNCH_CHECK(c);
+    } else WN_HIP(c, hipMemsetD32Async((hipDeviceptr_t)(s->t_dev + 1), sp.t0, 1, st));
+    if ((rc = synth_steps(c, s, c->cbt + (size_t)sp.cbt_off * c->C, sp.Tcb, sp.gbias, noise, test_inputs, out_samples, out_raw, steps_per_graph, st))) return rc;
     WN_HIP(c, hipEventRecord(s->ev1, st));
     WN_HIP(c, hipStreamWaitEvent(caller_st, s->ev1, 0));
     return WN_OK;

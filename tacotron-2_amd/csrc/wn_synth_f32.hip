@@ -18,9 +18,9 @@ struct SynthF32 {
     int capB = 0;                                   // streams the rings are sized for
     std::vector<float*> ring; std::vector<int> mask;
     float *ucur = nullptr, *skip_acc = nullptr, *h2 = nullptr, *yraw = nullptr;
-    int32_t* t_dev = nullptr;
+    int32_t* t_dev = nullptr;                       // [0] absolute time index of the next step, [1] first sample of the running span (a stream push's t0)
     hipStream_t priv = nullptr; hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipGraphExec_t gexec = nullptr; int g_steps = 0, g_B = 0, g_T = 0; const void* g_key[5] = {0, 0, 0, 0, 0};
+    hipGraphExec_t gexec = nullptr; int g_steps = 0, g_B = 0, g_T = 0, g_Tcb = 0; const void* g_key[6] = {0, 0, 0, 0, 0, 0};
 };
 
 // ---- the shared core: K split over the 4 waves, one output column per lane, F32S_NS streams per workgroup.
@@ -76,11 +76,11 @@ static inline size_t f32s_lds_bytes(int K, int ncol) { return 4 * (size_t)std::m
 // ---- z = [W_dil ; W_cin]^T [x(t-2d); x(t-d); x(t); c_t] + b -> u = tanh(a) * sigmoid(b)     (modules.py:273-303, 494-510)
 __global__ __launch_bounds__(256) void wn_f32s_gate(const float* __restrict__ Wd, const float* __restrict__ Wc, int R, int C, int G, int GH,
                                                     const float* __restrict__ ring, int mask, int d, int SB,
-                                                    const float* __restrict__ cup, int T, int B,
+                                                    const float* __restrict__ cup, int Tcb, int B,
                                                     const float* __restrict__ bias, int bias_bstride, float* __restrict__ ucur,
                                                     const int32_t* __restrict__ t_dev) {
     extern __shared__ float smem[];
-    const int lane = threadIdx.x & 63, t = *t_dev, g = blockIdx.x * 64 + lane, n0 = blockIdx.y * F32S_NS, K = 3 * R + C;
+    const int lane = threadIdx.x & 63, t = t_dev[0], tl = t - t_dev[1], g = blockIdx.x * 64 + lane, n0 = blockIdx.y * F32S_NS, K = 3 * R + C;
     const int gc = min(g, GH - 1);
     f32s_matvec<2>(smem, K,
         [&](int k, int s) -> float {
@@ -90,7 +90,7 @@ __global__ __launch_bounds__(256) void wn_f32s_gate(const float* __restrict__ Wd
                 const int j = k / R, i = k - j * R, tau = t - (2 - j) * d;            // kernel index 0 <-> x[t - 2d], 2 <-> x[t]
                 return tau >= 0 ? ring[((size_t)(tau & mask) * SB + n) * R + i] : 0.0f;
             }
-            return cup[((size_t)n * C + (k - 3 * R)) * T + t];
+            return cup[((size_t)n * C + (k - 3 * R)) * Tcb + tl];          // conditioning: this span's columns of the upsampled window
         },
         [&](int k, int c) -> float { const float* W = k < 3 * R ? Wd + (size_t)k * G : Wc + (size_t)(k - 3 * R) * G; return W[c * GH + gc]; },
         [&](int s, const float* v) {
@@ -162,16 +162,16 @@ __global__ __launch_bounds__(256) void wn_f32s_sample(const float* __restrict__ 
     __shared__ float nxt_f[32];
     __shared__ int nxt_i[32];
     const int tid = threadIdx.x;
-    const int t = *t_dev;
+    const int t = t_dev[0], tl = t - t_dev[1];      // ring slots: absolute; noise, teacher forcing, outputs: span-local
     if (tid < B) {
         const int n = tid;
         const float* p = yraw + (size_t)n * OP;
-        const float* nz = noise + ((size_t)t * B + n) * nps;
+        const float* nz = noise + ((size_t)tl * B + n) * nps;
         if (mode == 2) {
             float best = -INFINITY; int bi = 0;
             for (int q = 0; q < O; ++q) { const float v = p[q] - logf(-logf(nz[q])); if (v > best) { best = v; bi = q; } }
-            ((int32_t*)out_samples)[(size_t)n * T + t] = bi;
-            nxt_i[n] = test_inputs ? ((const int32_t*)test_inputs)[(size_t)n * T + t] : bi;
+            ((int32_t*)out_samples)[(size_t)n * T + tl] = bi;
+            nxt_i[n] = test_inputs ? ((const int32_t*)test_inputs)[(size_t)n * T + tl] : bi;
         } else {
             float x;
             if (mode == 0) {
@@ -185,11 +185,11 @@ __global__ __launch_bounds__(256) void wn_f32s_sample(const float* __restrict__ 
                 x = p[0] + expf(fmaxf(p[1], lsmin)) * nz[0];
             }
             x = fminf(fmaxf(x, -1.0f), 1.0f);
-            ((float*)out_samples)[(size_t)n * T + t] = x;
-            nxt_f[n] = test_inputs ? ((const float*)test_inputs)[(size_t)n * T + t] : x;
+            ((float*)out_samples)[(size_t)n * T + tl] = x;
+            nxt_f[n] = test_inputs ? ((const float*)test_inputs)[(size_t)n * T + tl] : x;
         }
     }
-    if (out_raw) for (int o = tid; o < B * O; o += 256) { const int n = o / O, oc = o - n * O; out_raw[((size_t)n * O + oc) * T + t] = yraw[(size_t)n * OP + oc]; }
+    if (out_raw) for (int o = tid; o < B * O; o += 256) { const int n = o / O, oc = o - n * O; out_raw[((size_t)n * O + oc) * T + tl] = yraw[(size_t)n * OP + oc]; }
     __syncthreads();
     for (int o = tid; o < B * R; o += 256) {          // input convolution of step t + 1 into queue 0
         const int n = o / R, r = o - n * R;
@@ -205,7 +205,7 @@ __global__ void wn_f32s_init(const float* __restrict__ Wf, const float* __restri
         const int n = o / R, r = o - n * R;
         ring0[(size_t)n * R + r] = (mode == 2) ? Wf[(size_t)start_id * R + r] + bf_[r] : bf_[r];      // x = 0 for raw / mulaw
     }
-    if (threadIdx.x == 0) *t_dev = 0;
+    if (threadIdx.x == 0) { t_dev[0] = 0; t_dev[1] = 0; }
 }
 
 void wn_synth_f32_free(wn_ctx* c) {
@@ -247,22 +247,22 @@ int wn_synth_f32_reserve(wn_ctx* c, int B) {
         WN_HIP(c, hipMalloc((void**)&s->yraw, (size_t)B * c->OP * 4));
         s->capB = B;
     }
-    if (!s->t_dev) WN_HIP(c, hipMalloc((void**)&s->t_dev, 4));
+    if (!s->t_dev) WN_HIP(c, hipMalloc((void**)&s->t_dev, 8));
     if (!s->priv) WN_HIP(c, hipStreamCreateWithFlags(&s->priv, hipStreamNonBlocking));
     if (!s->ev0) WN_HIP(c, hipEventCreateWithFlags(&s->ev0, hipEventDisableTiming));
     if (!s->ev1) WN_HIP(c, hipEventCreateWithFlags(&s->ev1, hipEventDisableTiming));
     return WN_OK;
 }
 
-static int f32s_enqueue_step(wn_ctx* c, SynthF32* s, int B, int T, const float* noise, const void* test_inputs, void* out_samples, float* out_raw, hipStream_t st) {
+static int f32s_enqueue_step(wn_ctx* c, SynthF32* s, int B, int T, const float* cup, int Tcb, const float* gbias, const float* noise, const void* test_inputs,
+                             void* out_samples, float* out_raw, hipStream_t st) {
     const int L = c->L, R = c->R, G = c->G, GH = c->GH, S = c->S, C = c->C, SB = s->capB;
     const float* P = c->params_dev;
-    const float* cup = c->CUP[c->cup_final_idx];
     const int ny = cdiv(B, F32S_NS);
     for (int l = 0; l < L; ++l) {
         hipLaunchKernelGGL(wn_f32s_gate, dim3(cdiv(GH, 64), ny), dim3(256), f32s_lds_bytes(3 * R + C, 2), st, P + c->lay[l].dil_k, P + c->lay[l].cin_k, R, C, G, GH,
-                           s->ring[l], s->mask[l], c->dil[l], SB, cup, T, B,
-                           c->gin > 0 ? c->gbias + (size_t)l * B * G : c->b1sum + (size_t)l * G, c->gin > 0 ? G : 0, s->ucur, s->t_dev);
+                           s->ring[l], s->mask[l], c->dil[l], SB, cup, Tcb, B,
+                           c->gin > 0 ? gbias + (size_t)l * B * G : c->b1sum + (size_t)l * G, c->gin > 0 ? G : 0, s->ucur, s->t_dev);
         const bool top = (l == L - 1);
         hipLaunchKernelGGL(wn_f32s_out, dim3(cdiv(R, 64) + cdiv(S, 64), ny), dim3(256), f32s_lds_bytes(GH, 1), st, P + c->lay[l].out_k, P + c->lay[l].skip_k, R, S, GH,
                            s->ucur, P + c->lay[l].out_b, c->res_scale, s->ring[l], s->mask[l], top ? nullptr : s->ring[l + 1], top ? 0 : s->mask[l + 1], SB,
@@ -280,12 +280,11 @@ static int f32s_enqueue_step(wn_ctx* c, SynthF32* s, int B, int T, const float* 
     return WN_OK;
 }
 
-int wn_synth_f32_impl(wn_ctx* c, const float* cin, int B, int Tc, const float* noise, const void* test_inputs,
-                      void* out_samples, float* out_raw, int steps_per_graph, hipStream_t caller_st) {
-    const int T = Tc * c->hop;
-    if ((int64_t)B * T > c->NT) WN_FAIL(c, WN_E_SHAPE, "synthesis B*T = %d*%d exceeds the workspace (max_batch*max_time = %lld)", B, T, (long long)c->NT);
-    if (c->gin > 0 && (!c->have_g || c->gB != B))
-        WN_FAIL(c, WN_E_STATE, "global conditioning is enabled: call wn_set_global_condition with this batch (B=%d) first [wavenet.py:766-777]", B);
+// sp == nullptr: wn_synthesize (upsample the whole utterance here, zero queues, silence input); else one push of a stream whose conditioning
+// window the caller upsampled (CUP final level [B][C][sp->Tcb], this span from column sp->cbt_off): the queues, the time index and queue 0's next
+// input are those the previous push left; only its first push (t0 = 0) zeroes the queues and starts from silence
+static int f32_run(wn_ctx* c, const float* cin, int B, int T, int Tc, const WnSpan* sp, const float* noise, const void* test_inputs,
+                   void* out_samples, float* out_raw, int steps_per_graph, hipStream_t caller_st) {
     if (3 * c->R + c->C > 2000) WN_FAIL(c, WN_E_SHAPE, "fp32 synthesis: 3 * residual_channels + cin_channels = %d input taps exceed the 64 KB LDS image of 8 streams", 3 * c->R + c->C);
     int rc = wn_synth_f32_reserve(c, B);
     if (rc) return rc;
@@ -295,35 +294,56 @@ int wn_synth_f32_impl(wn_ctx* c, const float* cin, int B, int Tc, const float* n
     hipStream_t st = s->priv;                          // ctx-owned stream (the caller's may be the legacy NULL stream, which cannot be captured)
     WN_HIP(c, hipEventRecord(s->ev0, caller_st));
     WN_HIP(c, hipStreamWaitEvent(st, s->ev0, 0));
-    c->fB = B; c->fT = T; c->fTc = Tc;
-    if ((rc = wn_upsample_fwd(c, nullptr, cin, B, Tc, st))) return rc;      // fp32 [B][C][T] (wavenet.py:781-803)
-    if ((rc = wn_gbias_fwd(c, B, st))) return rc;
+    const float* cup = c->CUP[c->cup_final_idx];
+    const float* gbias = c->gbias;
+    int Tcb = T;
+    if (!sp) {
+        c->fB = B; c->fT = T; c->fTc = Tc;
+        if ((rc = wn_upsample_fwd(c, nullptr, cin, B, Tc, st))) return rc;      // fp32 [B][C][T] (wavenet.py:781-803)
+        if ((rc = wn_gbias_fwd(c, B, st))) return rc;
+    } else { cup += sp->cbt_off; Tcb = sp->Tcb; gbias = sp->gbias; }
     const int R = c->R;
-    for (int l = 0; l < c->L; ++l) WN_HIP(c, hipMemsetAsync(s->ring[l], 0, (size_t)(s->mask[l] + 1) * s->capB * R * 4, st));      // zero queues (wavenet.py:815-816)
-    const int mode = c->cfg.input_type == WN_INPUT_MULAW_QUANTIZE ? 2 : (c->O == 2 ? 1 : 0);
-    hipLaunchKernelGGL(wn_f32s_init, dim3(1), dim3(256), 0, st, c->params_dev + c->first.dil_k, c->params_dev + c->first.dil_b, R, mode, 127, s->ring[0], B, s->t_dev);
-    WN_LAUNCH_CHECK(c);
+    if (!sp || sp->t0 == 0) {
+        for (int l = 0; l < c->L; ++l) WN_HIP(c, hipMemsetAsync(s->ring[l], 0, (size_t)(s->mask[l] + 1) * s->capB * R * 4, st));      // zero queues (wavenet.py:815-816)
+        const int mode = c->cfg.input_type == WN_INPUT_MULAW_QUANTIZE ? 2 : (c->O == 2 ? 1 : 0);
+        hipLaunchKernelGGL(wn_f32s_init, dim3(1), dim3(256), 0, st, c->params_dev + c->first.dil_k, c->params_dev + c->first.dil_b, R, mode, 127, s->ring[0], B, s->t_dev);
+        WN_LAUNCH_CHECK(c);
+    } else WN_HIP(c, hipMemsetD32Async((hipDeviceptr_t)(s->t_dev + 1), sp->t0, 1, st));
     int done = 0;
     if (steps_per_graph > 1 && T >= steps_per_graph) {
-        const void* key[5] = {noise, test_inputs, out_samples, out_raw, cin};
-        const bool reuse = s->gexec && s->g_steps == steps_per_graph && s->g_B == B && s->g_T == T && memcmp(key, s->g_key, sizeof key) == 0;
+        const void* key[6] = {noise, test_inputs, out_samples, out_raw, cup, gbias};
+        const bool reuse = s->gexec && s->g_steps == steps_per_graph && s->g_B == B && s->g_T == T && s->g_Tcb == Tcb && memcmp(key, s->g_key, sizeof key) == 0;
         if (!reuse) {
             if (s->gexec) { hipGraphExecDestroy(s->gexec); s->gexec = nullptr; }
             hipGraph_t graph;
             WN_HIP(c, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
             for (int i = 0; i < steps_per_graph; ++i) {
-                rc = f32s_enqueue_step(c, s, B, T, noise, test_inputs, out_samples, out_raw, st);
+                rc = f32s_enqueue_step(c, s, B, T, cup, Tcb, gbias, noise, test_inputs, out_samples, out_raw, st);
                 if (rc) { hipStreamEndCapture(st, &graph); return rc; }
             }
             WN_HIP(c, hipStreamEndCapture(st, &graph));
             WN_HIP(c, hipGraphInstantiate(&s->gexec, graph, nullptr, nullptr, 0));
             hipGraphDestroy(graph);
-            s->g_steps = steps_per_graph; s->g_B = B; s->g_T = T; memcpy(s->g_key, key, sizeof key);
+            s->g_steps = steps_per_graph; s->g_B = B; s->g_T = T; s->g_Tcb = Tcb; memcpy(s->g_key, key, sizeof key);
         }
         for (; done + steps_per_graph <= T; done += steps_per_graph) WN_HIP(c, hipGraphLaunch(s->gexec, st));
     }
-    for (; done < T; ++done) { rc = f32s_enqueue_step(c, s, B, T, noise, test_inputs, out_samples, out_raw, st); if (rc) return rc; }
+    for (; done < T; ++done) { rc = f32s_enqueue_step(c, s, B, T, cup, Tcb, gbias, noise, test_inputs, out_samples, out_raw, st); if (rc) return rc; }
     WN_HIP(c, hipEventRecord(s->ev1, st));
     WN_HIP(c, hipStreamWaitEvent(caller_st, s->ev1, 0));
     return WN_OK;
+}
+
+int wn_synth_f32_impl(wn_ctx* c, const float* cin, int B, int Tc, const float* noise, const void* test_inputs,
+                      void* out_samples, float* out_raw, int steps_per_graph, hipStream_t caller_st) {
+    const int T = Tc * c->hop;
+    if ((int64_t)B * T > c->NT) WN_FAIL(c, WN_E_SHAPE, "synthesis B*T = %d*%d exceeds the workspace (max_batch*max_time = %lld)", B, T, (long long)c->NT);
+    if (c->gin > 0 && (!c->have_g || c->gB != B))
+        WN_FAIL(c, WN_E_STATE, "global conditioning is enabled: call wn_set_global_condition with this batch (B=%d) first [wavenet.py:766-777]", B);
+    return f32_run(c, cin, B, T, Tc, nullptr, noise, test_inputs, out_samples, out_raw, steps_per_graph, caller_st);
+}
+
+int wn_synth_f32_span(wn_ctx* c, int B, int T, const WnSpan& sp, const float* noise, const void* test_inputs, void* out_samples, float* out_raw,
+                      int steps_per_graph, hipStream_t st) {
+    return f32_run(c, nullptr, B, T, 0, &sp, noise, test_inputs, out_samples, out_raw, steps_per_graph, st);
 }

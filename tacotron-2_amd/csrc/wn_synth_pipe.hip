@@ -64,6 +64,10 @@ struct PipeArgs {
     unsigned long long* trace; int32_t trace_t0, trace_n;     // optional timestamps (WN_PIPE_TRACE=1): [trace_n][2*(L+2)] of s_memrealtime
     unsigned long long* svc; int32_t svc_l, svc_s;            // optional (WN_PIPE_SVC_TRACE=1): [trace_n][16] stamps of ONE layer CU's iteration for one stream (where its service time goes)
     int64_t ring_off[32]; int64_t cin_b_off[32]; int32_t ring_mask[32]; int32_t dil[32];
+    // streaming (wn_synth_stream_push): t0 = absolute index of this run's first sample -- ring slots and tap validity use t0 + t, everything else
+    // (conditioning rows, noise, teacher forcing, outputs, mailbox tags) is run-local; Tcb = conditioning rows per stream in cbt (== T for
+    // wn_synthesize); carry [B]: the head leaves every stream's next input there (float bits / class id) and a run with t0 > 0 starts from it
+    int32_t t0, Tcb; int32_t* carry;
 };
 
 // ---- granule I/O: 16 bytes, one write-through store / one L1-bypassing load ------------------------------------------
@@ -224,7 +228,8 @@ __global__ __launch_bounds__(PIPE_THREADS) void wn_synth_pipe_kernel(const PipeA
     u32x4* const XM_ = a.XM + moff * PIPE_XG; u32x4* const XML_ = a.XML + moff * PIPE_XG;
     u32x4* const SM_ = a.SM + moff * PIPE_SG; u32x4* const SML_ = a.SML + moff * PIPE_SG;
     bf16_t* const ring_ = a.ring + (MULTI ? a.ring_unit * s0 : 0);                       // a.ring_off[l] is per STREAM: x B for this instance's layer offset
-    const bf16_t* const cbt_ = a.cbt + (MULTI ? (int64_t)s0 * T * C : 0);
+    const int Tcb = a.Tcb, t0 = a.t0;
+    const bf16_t* const cbt_ = a.cbt + (MULTI ? (int64_t)s0 * Tcb * C : 0);
     const char* const ti_ = a.test_inputs ? (const char*)a.test_inputs + (MULTI ? (int64_t)s0 * T * 4 : 0) : nullptr;
     char* const outs_ = (char*)a.out_samples + (MULTI ? (int64_t)s0 * T * 4 : 0);
     float* const outr_ = a.out_raw ? a.out_raw + (MULTI ? (int64_t)s0 * a.O * T : 0) : nullptr;
@@ -312,7 +317,7 @@ __global__ __launch_bounds__(PIPE_THREADS) void wn_synth_pipe_kernel(const PipeA
                     const int tau = tn - d;
                     if (tau >= 0) v = tap1_is_cur ? *reinterpret_cast<const uint4*>(xcur_b + (k - R))
                                                   : __builtin_bit_cast(uint4, ld_g16(reinterpret_cast<const u32x4*>(ringb + (int64_t)(tau & mask) * R + (k - R))));
-                } else v = cvt8_bf16<H>(*reinterpret_cast<const uint4*>(cbt_ + ((int64_t)s * T + tn) * C + (k - 2 * R)));
+                } else v = cvt8_bf16<H>(*reinterpret_cast<const uint4*>(cbt_ + ((int64_t)s * Tcb + tn) * C + (k - 2 * R)));
                 *reinterpret_cast<uint4*>(vec + k) = v;
             }
             lds_barrier();
@@ -324,7 +329,7 @@ __global__ __launch_bounds__(PIPE_THREADS) void wn_synth_pipe_kernel(const PipeA
             if (tid < 64) zpast[s * PIPE_ZS + tid] = zpart[tid] + zpart[64 + tid] + zpart[128 + tid] + zpart[192 + tid] + (a.gbias ? gb : zb[tid]);
             lds_barrier();
         };
-        for (int s = 0; s < B; ++s) precompute(s, 0, false);
+        if (t0 == 0) for (int s = 0; s < B; ++s) precompute(s, 0, false);      // (a resumed run pre-multiplies its first sample as a mid-run one: below)
         // Inside the sample loop the pre-multiplication is split (round 4): its ring reads -- rows written >= d samples ago, HBM latency
         // once the streams' queues exceed L2 -- are REQUESTED by wave 3 right after this CU published its x partial and CONSUMED after the
         // skip chain, so their latency lies under the skip matvec and the wait for the previous layer's running sum instead of in front of
@@ -337,9 +342,10 @@ __global__ __launch_bounds__(PIPE_THREADS) void wn_synth_pipe_kernel(const PipeA
             // wave-uniform parts as scalars, per-lane parts as 32-bit byte offsets (a ring of one stream is <= 8192 rows x R x 2 B; the conditioning of a
             // run is B x T x C x 2 B < 4 GB): a per-lane 64-bit multiply per candidate address cost this wave 0.35 us per stream
             const char* ringb = (const char*)(ring_ + a.ring_off[l] * B + ((int64_t)(j * B + s) * (mask + 1)) * R);
-            const uint32_t row0 = (uint32_t)__builtin_amdgcn_readfirstlane(((tn - 2 * d) & mask) * R * 2), row1 = (uint32_t)__builtin_amdgcn_readfirstlane(((tn - d) & mask) * R * 2);
-            const char* cb = (const char*)cbt_ + (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((s * T + tn) * C) * 2;
-            const bool ok0 = tn - 2 * d >= 0, ok1 = tn - d >= 0 && !tap1_is_cur;
+            const int ta = t0 + tn;                                          // queues: absolute time; conditioning: this run's rows
+            const uint32_t row0 = (uint32_t)__builtin_amdgcn_readfirstlane(((ta - 2 * d) & mask) * R * 2), row1 = (uint32_t)__builtin_amdgcn_readfirstlane(((ta - d) & mask) * R * 2);
+            const char* cb = (const char*)cbt_ + (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((s * Tcb + tn) * C) * 2;
+            const bool ok0 = ta - 2 * d >= 0, ok1 = ta - d >= 0 && !tap1_is_cur;
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
                 const int i = lane + 64 * q, k = i * 8;
@@ -363,7 +369,7 @@ __global__ __launch_bounds__(PIPE_THREADS) void wn_synth_pipe_kernel(const PipeA
                     const int i = lane + 64 * q, k = i * 8;
                     if (i < KR) {
                         uint4 v = __builtin_bit_cast(uint4, q ? pf1 : pf0);
-                        if (k >= R && tap1_is_cur && tn - d >= 0) v = *reinterpret_cast<const uint4*>(xcur_b + (k - R));
+                        if (k >= R && tap1_is_cur && t0 + tn - d >= 0) v = *reinterpret_cast<const uint4*>(xcur_b + (k - R));
                         *reinterpret_cast<uint4*>(vec + k) = v;
                     } else if (i < KP) *reinterpret_cast<uint4*>(vec + k) = cvt8_bf16<H>(__builtin_bit_cast(uint4, q ? pf1 : pf0));      // the conditioning chunks
                 }
@@ -423,7 +429,7 @@ __global__ __launch_bounds__(PIPE_THREADS) void wn_synth_pipe_kernel(const PipeA
                 const int i = lane + 64 * q, k = i * 8;
                 if (i < KR) {
                     uint4 v = __builtin_bit_cast(uint4, q ? pf1 : pf0);
-                    if (k >= R && tap1_is_cur && tn - d >= 0) v = *reinterpret_cast<const uint4*>(xcur_b + (k - R));
+                    if (k >= R && tap1_is_cur && t0 + tn - d >= 0) v = *reinterpret_cast<const uint4*>(xcur_b + (k - R));
                     *reinterpret_cast<uint4*>(vb + k * 2) = v;
                 } else if (i < KP) *reinterpret_cast<uint4*>(vb + k * 2) = cvt8_bf16<H>(__builtin_bit_cast(uint4, q ? pf1 : pf0));
             }
@@ -524,6 +530,13 @@ __global__ __launch_bounds__(PIPE_THREADS) void wn_synth_pipe_kernel(const PipeA
                 skp_valid = true;
             }
         };
+        // A resumed run (t0 > 0): the first sample's pre-multiplication in the form every later one takes -- batched, or pre_issue / pre_finish -- so
+        // that the samples are bit-identical to one run over the whole utterance (the prologue form above differs in the last bits).  Both past taps
+        // come from the ring: the previous run's last iteration stored x(t0 - 1) there, the very bits a mid-run d = 1 layer reads from xcur_b.
+        if (t0 > 0) {
+            for (int s = 0; s < B; ++s) { pre_issue(s, 0, false); if (BP) pre_stash(s, 0, false); else pre_finish(s, 0, false); }
+            if (BP) pre_batch(0);
+        }
         for (int t = 0; t < T; ++t) {
             const uint32_t want = (uint32_t)(t + 1);
             for (int s = 0; s < B; ++s) {
@@ -717,7 +730,7 @@ __global__ __launch_bounds__(PIPE_THREADS) void wn_synth_pipe_kernel(const PipeA
                     bf16_t* ringb = ring_ + a.ring_off[l] * B + ((int64_t)(j * B + s) * (mask + 1)) * R;
                     {   // (R / 8 <= 48 chunks: the first lanes of wave 0; the other waves issue the same store disabled)
                         const bool en = tid < R / 8;
-                        st_buf16(poll_rsrc(ringb + (int64_t)(t & mask) * R, R * 2), en ? tid * 16 : -1, __builtin_bit_cast(u32x4, *reinterpret_cast<const uint4*>(xcur_b + (en ? tid * 8 : 0))));
+                        st_buf16(poll_rsrc(ringb + (int64_t)((t0 + t) & mask) * R, R * 2), en ? tid * 16 : -1, __builtin_bit_cast(u32x4, *reinterpret_cast<const uint4*>(xcur_b + (en ? tid * 8 : 0))));
                     }
                     PIPE_SVC(9);
                     if constexpr (H) {      // half has 5 exponent bits: a residual stream beyond 65504 became inf in the hand-off -- report it, do not synthesise garbage
@@ -797,9 +810,17 @@ __global__ __launch_bounds__(PIPE_THREADS) void wn_synth_pipe_kernel(const PipeA
             }
             lds_barrier();
         };
-        if (tid == 0) { nxt_f[0] = 0.0f; nxt_i[0] = a.start_id; }
-        lds_barrier();
-        for (int s = j; s < B; s += NH) publish_input(s, 0);          // head j of NH: the streams s = j (mod NH)
+        if (t0 == 0) {
+            if (tid == 0) { nxt_f[0] = 0.0f; nxt_i[0] = a.start_id; }
+            lds_barrier();
+            for (int s = j; s < B; s += NH) publish_input(s, 0);          // head j of NH: the streams s = j (mod NH)
+        } else {
+            for (int s = j; s < B; s += NH) {                             // a resumed run: the inputs the previous run left (publish_input ends on a barrier)
+                if (tid == 0) { const int32_t v = a.carry[s0 + s]; nxt_f[0] = __int_as_float(v); nxt_i[0] = v; }
+                lds_barrier();
+                publish_input(s, 0);
+            }
+        }
 
         for (int t = 0; t < T; ++t) {
             const uint32_t want = (uint32_t)(t + 1);
@@ -918,6 +939,7 @@ __global__ __launch_bounds__(PIPE_THREADS) void wn_synth_pipe_kernel(const PipeA
                 }
                 if (outr_) for (int o = tid; o < O; o += PIPE_THREADS) outr_[((int64_t)s * O + o) * T + t] = yraw[o];
                 lds_barrier();
+                if (a.carry && t + 1 == T && tid == 0) a.carry[s0 + s] = mode == 2 ? nxt_i[0] : __float_as_int(nxt_f[0]);      // the next run's first input
                 if (trace_on && s == 0 && tid == 0 && t >= a.trace_t0 && t < a.trace_t0 + a.trace_n) a.trace[(size_t)(t - a.trace_t0) * 2 * (a.L + 2) + 2 * L + 2] = wall_clock64();
                 if (t + 1 < T) publish_input(s, t + 1);
                 if (trace_on && s == 0 && tid == 0 && t >= a.trace_t0 && t < a.trace_t0 + a.trace_n) a.trace[(size_t)(t - a.trace_t0) * 2 * (a.L + 2) + 2 * L + 3] = wall_clock64();
@@ -937,6 +959,7 @@ struct Pipe {
     int32_t* abort_dev = nullptr;       // [0] flag of the running launch, [1] sticky OR of every run since the last wn_pipe_check, +256 B: XCC table
     int32_t* abort_host = nullptr;      // pinned: the abort flag of the last run lands here asynchronously (read by wn_pipe_check)
     bool pending = false;               // a run has been enqueued whose flag has not been inspected yet
+    bool pending_stream = false;        // ... and it was a push of the open stream: a raised flag poisons the stream
     int test_aborts = 0;
     int layer_lds = 0, head_lds = 0;
     bool f16 = false;                   // 16-bit storage type of weights / hand-offs / queues: IEEE half instead of bf16 (wn_ctx::pipe_f16 at the run)
@@ -1191,6 +1214,7 @@ int wn_pipe_check(wn_ctx* c, bool wait) {
     const int32_t flag = *p->abort_host;
     if (flag != 0) {
         *p->abort_host = 0;
+        if (p->pending_stream && c->strm.open) c->strm.poisoned = true;      // every later push of this stream: WN_E_STATE until the next begin
         (void)hipMemsetAsync(p->abort_dev + 1, 0, 4, p->priv);      // reported: the next runs start clean (ordered before them on the pipeline's stream)
         if (flag >= 400 && flag < 400 + 64)
             WN_FAIL(c, WN_E_HIP, "synthesis pipeline (fp16 storage): the residual stream of layer %d left the half-precision range (|x| > 65504); "
@@ -1200,10 +1224,11 @@ int wn_pipe_check(wn_ctx* c, bool wait) {
     return WN_OK;
 }
 
-int wn_pipe_synthesize(wn_ctx* c, const float* cin, int B, int Tc, const float* noise, const void* test_inputs,
-                       void* out_samples, float* out_raw, hipStream_t caller_st) {
-    const int T = Tc * c->hop, L = c->L, R = c->R;
-    if ((int64_t)B * T > c->NT) WN_FAIL(c, WN_E_SHAPE, "synthesis B*T = %d*%d exceeds the workspace (max_batch*max_time = %lld)", B, T, (long long)c->NT);
+// sp == nullptr: wn_synthesize (upsample the conditioning of the whole utterance here); else one push of a stream, whose conditioning window the caller
+// upsampled into cbt: no weight re-slice after the first push (wn_pack_weights / wn_synth_pipe_dtype end a stream, so the images cannot be stale)
+static int pipe_run(wn_ctx* c, const float* cin, int B, int T, int Tc, const WnSpan* sp, const float* noise, const void* test_inputs,
+                    void* out_samples, float* out_raw, hipStream_t caller_st) {
+    const int L = c->L, R = c->R;
     int rc;
     if ((rc = wn_pipe_reserve(c, B, T))) return rc;
     Pipe* p = (Pipe*)c->pipe;
@@ -1218,7 +1243,7 @@ int wn_pipe_synthesize(wn_ctx* c, const float* cin, int B, int Tc, const float* 
     a.nps = wn_noise_per_step(c); a.lsmin = a.mode == 1 ? c->cfg.log_scale_min_gauss : c->cfg.log_scale_min; a.start_id = 127; a.spx = p->spx;
     a.slices = p->slices; a.layer_slice_bytes = p->layer_slice_bytes; a.head_slice_off = p->head_slice_off;
     // ---- slice images from the current parameters (cheap: 27 MB)
-    {
+    if (!sp || sp->t0 == 0) {
         hipLaunchKernelGGL(wn_pipe_slice_kernel, dim3(p->nblocks), dim3(256), 0, st, c->params_dev, p->slices, p->jobs_dev, p->job_block0_dev, p->njobs, c->GH, p->f16 ? 1 : 0);
         WN_LAUNCH_CHECK(c);
         for (int l = 0; l < L; ++l) a.cin_b_off[l] = c->lay[l].cin_b;
@@ -1241,10 +1266,16 @@ int wn_pipe_synthesize(wn_ctx* c, const float* cin, int B, int Tc, const float* 
     WN_HIP(c, hipMemsetAsync(p->abort_dev + 64, 0, 4096, st));            // XCC table
     a.XM = p->XM; a.SM = p->SM; a.XML = p->XML; a.SML = p->SML; a.ring = p->ring; a.abort_flag = p->abort_dev; a.xcc_tab = p->abort_dev + 64;
     // ---- conditioning for the whole utterance (wavenet.py:781-803): cbt [B*T][C] bf16
-    c->fB = B; c->fT = T; c->fTc = Tc;
-    if ((rc = wn_upsample_fwd(c, nullptr, cin, B, Tc, st))) return rc;
-    if (c->gin > 0) { if ((rc = wn_gbias_fwd(c, B, st))) return rc; a.gbias = c->gbias; }      // wavenet.py:766-777
-    a.cbt = c->cbt; a.noise = noise; a.test_inputs = test_inputs; a.out_samples = out_samples; a.out_raw = out_raw;
+    if (!sp) {
+        c->fB = B; c->fT = T; c->fTc = Tc;
+        if ((rc = wn_upsample_fwd(c, nullptr, cin, B, Tc, st))) return rc;
+        if (c->gin > 0) { if ((rc = wn_gbias_fwd(c, B, st))) return rc; a.gbias = c->gbias; }      // wavenet.py:766-777
+        a.cbt = c->cbt; a.t0 = 0; a.Tcb = T; a.carry = nullptr;
+    } else {
+        a.cbt = c->cbt + (int64_t)sp->cbt_off * c->C; a.t0 = sp->t0; a.Tcb = sp->Tcb; a.carry = sp->carry;
+        if (c->gin > 0) a.gbias = sp->gbias;
+    }
+    a.noise = noise; a.test_inputs = test_inputs; a.out_samples = out_samples; a.out_raw = out_raw;
     a.win_global = c->params_dev + c->first.dil_k; a.bin_global = c->params_dev + c->first.dil_b;
     unsigned long long* trace_dev = nullptr; const int trace_n = 32;
 #ifdef WN_PIPE_SVC_BUILD
@@ -1343,5 +1374,17 @@ int wn_pipe_synthesize(wn_ctx* c, const float* cin, int B, int Tc, const float* 
     }
     WN_HIP(c, hipEventRecord(p->ev1, st));
     WN_HIP(c, hipStreamWaitEvent(caller_st, p->ev1, 0));
+    p->pending_stream = sp != nullptr;
     return WN_OK;
+}
+
+int wn_pipe_synthesize(wn_ctx* c, const float* cin, int B, int Tc, const float* noise, const void* test_inputs,
+                       void* out_samples, float* out_raw, hipStream_t caller_st) {
+    const int T = Tc * c->hop;
+    if ((int64_t)B * T > c->NT) WN_FAIL(c, WN_E_SHAPE, "synthesis B*T = %d*%d exceeds the workspace (max_batch*max_time = %lld)", B, T, (long long)c->NT);
+    return pipe_run(c, cin, B, T, Tc, nullptr, noise, test_inputs, out_samples, out_raw, caller_st);
+}
+
+int wn_pipe_span(wn_ctx* c, int B, int T, const WnSpan& sp, const float* noise, const void* test_inputs, void* out_samples, float* out_raw, hipStream_t st) {
+    return pipe_run(c, nullptr, B, T, 0, &sp, noise, test_inputs, out_samples, out_raw, st);
 }

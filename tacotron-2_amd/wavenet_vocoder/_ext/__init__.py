@@ -104,6 +104,10 @@ def load_library():
         'wn_synth_last_config': (ctypes.c_int, [vp, ctypes.POINTER(i32), i32]),
         'wn_synth_last_batched': (ctypes.c_int, [vp]),
         'wn_synth_pipe_eligible': (ctypes.c_int, [vp, i32]),
+        'wn_synth_stream_lookahead': (ctypes.c_int, [ctypes.POINTER(WnConfig), ctypes.POINTER(i32), ctypes.POINTER(i32)]),
+        'wn_synth_stream_begin': (ctypes.c_int, [vp, i32, u64, i32, vp]),
+        'wn_synth_stream_push': (ctypes.c_int, [vp, vp, i32, i32, vp, vp, vp, vp, ctypes.POINTER(i32), vp]),
+        'wn_synth_stream_end': (ctypes.c_int, [vp]),
         'wn_sample': (ctypes.c_int, [vp, vp, i32, i32, vp, vp, vp]),
         'wn_mulaw': (ctypes.c_int, [vp, vp, i64, vp]),
         'wn_inv_mulaw': (ctypes.c_int, [vp, vp, i64, vp]),
@@ -325,6 +329,38 @@ class Engine:
         self._ok(self.lib.wn_synthesize(self.h, _ptr(c), B, Tc, _ptr(noise), ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), _ptr(test_inputs),
                                         _ptr(out_samples), _ptr(out_raw), int(steps_per_graph), _stream()))
 
+    # ---- streaming synthesis (wn_synth_stream_*): the samples of one synthesize() over the concatenated frames, push by push
+    def stream_lookahead(self):
+        """(frames_left, frames_right) of mel context the upsample net needs around a frame: a push generates the frames
+        [done, pushed - frames_right) (all of them with final=True)."""
+        return stream_lookahead(self.cfg)
+
+    def stream_begin(self, B, seed=0, steps_per_graph=0):
+        """Open a stream of B utterances at t = 0 (path as synthesize(steps_per_graph) would take for B; global conditioning as set)."""
+        self._stream_B = None
+        self._ok(self.lib.wn_synth_stream_begin(self.h, int(B), ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), int(steps_per_graph), _stream()))
+        self._stream_B = int(B)
+
+    def stream_end(self):
+        """Abandon the open stream (a later stream_push raises WN_E_STATE)."""
+        self._stream_B = None
+        self._ok(self.lib.wn_synth_stream_end(self.h))
+
+    def stream_push(self, c, out_samples, out_raw=None, noise=None, test_inputs=None, final=False):
+        """Append c [B, cin, Tn] (None: no frames) and enqueue every sample whose conditioning is complete into out_samples [B, >= n]
+        (contiguous [B, n] view expected), out_raw [B, O, n]; returns n (known without synchronising)."""
+        import torch
+        Tn = 0 if c is None else int(c.shape[-1])
+        B = getattr(self, '_stream_B', None)
+        if c is not None:
+            _check(c, torch.float32, 'c')
+            if B is not None and tuple(c.shape) != (B, self.cfg.cin_channels, Tn):
+                raise ValueError('stream_push: c must be [B=%d, cin=%d, Tn] (got %s)' % (B, self.cfg.cin_channels, tuple(c.shape)))
+        n = ctypes.c_int32(0)
+        self._ok(self.lib.wn_synth_stream_push(self.h, _ptr(c), Tn, 1 if final else 0, _ptr(noise), _ptr(test_inputs), _ptr(out_samples),
+                                               _ptr(out_raw), ctypes.byref(n), _stream()))
+        return int(n.value)
+
     def fill_noise(self, noise, B, T, seed):
         """The device noise stream of synthesize(noise=None, seed): float32 [T, B, noise_per_step]."""
         import torch
@@ -413,6 +449,16 @@ class Engine:
     def sample(self, y_hat, noise, out):
         B, T = int(y_hat.shape[0]), int(y_hat.shape[-1])
         self._ok(self.lib.wn_sample(self.h, _ptr(y_hat), B, T, _ptr(noise), _ptr(out), _stream()))
+
+
+def stream_lookahead(cfg):
+    """wn_synth_stream_lookahead on a WnConfig (host only: no context, no GPU)."""
+    lib = load_library()
+    left, right = ctypes.c_int32(), ctypes.c_int32()
+    rc = lib.wn_synth_stream_lookahead(ctypes.byref(cfg), ctypes.byref(left), ctypes.byref(right))
+    if rc != 0:
+        raise WnError(rc, 'wn_synth_stream_lookahead: bad configuration')
+    return int(left.value), int(right.value)
 
 
 def learning_rate(schedule, init_lr, step, decay_rate=0.5, decay_steps=200000, warmup=4000.0):

@@ -27,6 +27,63 @@ def dropout_seed(random_seed, global_step, rank=0):
     return (int(random_seed) * 1000003 + int(global_step) + int(rank) * 0x9E3779B97F4A7C15) & 0xFFFFFFFFFFFFFFFF
 
 
+def stream_schedule(done, pushed, right, final):
+    """Frames a stream push generates (wn_synth_stream_push): [done, pushed - right) once `right` frames of context follow them, all the
+    pending frames [done, pushed) with final=True.  Returns (first, end)."""
+    return done, (pushed if final else max(done, pushed - right))
+
+
+class SynthesisStream(object):
+    """Generation of B utterances chunk by chunk as their mel frames arrive (WaveNet.stream): the samples are bit-identical to one
+    WaveNet.incremental-style run over the concatenated frames with the same seed.  push() returns the samples whose conditioning is now
+    complete, as a device tensor [B, n] (asynchronous: nothing waits for the GPU)."""
+
+    def __init__(self, model, batch, g=None, seed=0, steps_per_graph=0):
+        self.model, self.B = model, int(batch)
+        self.lookahead = model.engine.stream_lookahead()
+        self.done = self.pushed = 0
+        self.hop = model.engine.hop
+        model._ensure_packed()
+        if model.global_conditioning_enabled():
+            model._set_global(g, self.B)
+        model.engine.stream_begin(self.B, seed=seed, steps_per_graph=steps_per_graph)
+        self.closed = False
+
+    def push(self, c_frames=None, final=False, noise=None, test_inputs=None, return_raw=False):
+        """c_frames [B, cin, Tn] (None or Tn = 0: no new frames); noise [n, B, noise_per_step] / test_inputs [B, n] of the span this push
+        generates (its length follows from stream_schedule and the lookahead)."""
+        if self.closed:
+            raise RuntimeError('SynthesisStream: the stream is closed')
+        m = self.model
+        cc = None
+        if c_frames is not None and int(c_frames.shape[-1]) > 0:
+            if c_frames.dim() != 3 or c_frames.shape[0] != self.B or c_frames.shape[1] != m._hparams.cin_channels:
+                raise ValueError('SynthesisStream.push: c_frames must be [B=%d, cin=%d, Tn] (got %s)' % (self.B, m._hparams.cin_channels, tuple(c_frames.shape)))
+            cc = c_frames.to(m.device, torch.float32).contiguous()
+        Tn = 0 if cc is None else int(cc.shape[-1])
+        first, end = stream_schedule(self.done, self.pushed + Tn, self.lookahead[1], final)
+        n = (end - first) * self.hop
+        out = torch.empty(self.B, max(n, 1), device=m.device, dtype=torch.float32 if m.scalar_input else torch.int32)
+        raw = torch.empty(self.B, m._hparams.out_channels, max(n, 1), device=m.device) if return_raw else None
+        ti = None
+        if test_inputs is not None:
+            ti = (test_inputs.float() if m.scalar_input else test_inputs.to(torch.int32)).to(m.device).contiguous()
+        got = m.engine.stream_push(cc, out, raw, None if noise is None else noise.to(m.device).contiguous(), ti, final=final)
+        assert got == n
+        self.pushed += Tn
+        self.done = end
+        if final:
+            self.closed = True
+        out = out[:, :n]
+        return (out, raw[:, :, :n]) if return_raw else out
+
+    def close(self):
+        """Abandon the stream (frames pushed and not yet generated are dropped)."""
+        if not self.closed:
+            self.model.engine.stream_end()
+        self.closed = True
+
+
 class WaveNet(object):
     def __init__(self, hparams, init=False):
         self._hparams = hparams
@@ -148,7 +205,8 @@ class WaveNet(object):
             raise ValueError('Expected 3 dimension shape [batch_size(1), time_length, {}] for local condition features but found {}'.format(
                 hp.cin_channels, tuple(c.shape)))
         cT = c.transpose(1, 2).contiguous()
-        out = self.incremental(None, c=cT, g=g, time_length=None, test_inputs=test_inputs, check=True)
+        out = self.incremental(None, c=cT, g=g, time_length=None, test_inputs=test_inputs, check=True,
+                               chunk_frames=int(getattr(self._hparams, 'mi355_synthesis_chunk_frames', 0)))
         if is_mulaw_quantize(hp.input_type):
             y_hat = util.inv_mulaw_quantize(out)
         elif is_mulaw(hp.input_type):
@@ -244,12 +302,14 @@ class WaveNet(object):
         return torch.softmax(y_hat, dim=1) if softmax else y_hat
 
     def incremental(self, initial_input, c=None, g=None, time_length=100, test_inputs=None, softmax=True, quantize=True,
-                    log_scale_min=-7.0, log_scale_min_gauss=-7.0, noise=None, return_raw=False, check=False):
+                    log_scale_min=-7.0, log_scale_min_gauss=-7.0, noise=None, return_raw=False, check=False, chunk_frames=0):
         """Fast-WaveNet generation with ring-buffer queues: c [B,cin,Tc] -> samples [B,T] (wavenet.py:724-911).
         ``initial_input`` is accepted for signature parity; generation always starts from the reference's silence
         frame (wavenet.py:433-445).  ``noise`` [T,B,noise_per_step] may be supplied for reproducible draws.
         ``check``: wait for the generation and verify it; if the persistent pipeline gave up on a hand-off (a workgroup was not
-        resident -- the reference's loop cannot fail this way) the batch is re-run ONCE on the launch-per-layer graph path."""
+        resident -- the reference's loop cannot fail this way) the batch is re-run ONCE on the launch-per-layer graph path.
+        ``chunk_frames`` > 0: every group goes through a stream (wn_synth_stream_push) fed this many mel frames at a time -- the same samples,
+        bit for bit (same seed and stream grouping), as the one call per group of chunk_frames = 0."""
         hp = self._hparams
         B, Tc = int(c.shape[0]), int(c.shape[-1])
         hop = audio.get_hop_size(hp)
@@ -278,6 +338,31 @@ class WaveNet(object):
                 raise ValueError('global conditioning is enabled (gin_channels > 0) but no g was given')
             gt = torch.as_tensor(g, device=self.device).reshape(B, -1)
 
+        def run_stream(b0, b1, nz, spg_, sd):
+            # one group through a stream: chunk_frames mel frames per push (the samples of a push land in contiguous scratch, then in place)
+            nb = b1 - b0
+            right = self.engine.stream_lookahead()[1]
+            self.engine.stream_begin(nb, seed=sd, steps_per_graph=spg_)
+            done = pushed = 0
+            for f0 in range(0, Tc, int(chunk_frames)):
+                f1 = min(Tc, f0 + int(chunk_frames))
+                final = f1 == Tc
+                first, end = stream_schedule(done, f1, right, final)
+                t0, n = first * hop, (end - first) * hop
+                o = torch.empty(nb, max(n, 1), device=dev, dtype=out.dtype)
+                r = None if raw is None else torch.empty(nb, hp.out_channels, max(n, 1), device=dev)
+                got = self.engine.stream_push(cc[b0:b1, :, f0:f1].contiguous(), o, r, None if nz is None else nz[t0:t0 + n].contiguous(),
+                                              None if ti is None else ti[b0:b1, t0:t0 + n].contiguous(), final=final)
+                assert got == n
+                if n > 0:
+                    out[b0:b1, t0:t0 + n] = o[:, :n]
+                    if raw is not None:
+                        raw[b0:b1, :, t0:t0 + n] = r[:, :, :n]
+                    fe = torch.empty(nb, hp.cin_channels, n, device=dev)
+                    self.engine.upsampled_features(fe)
+                    feats[b0:b1, :, t0:t0 + n] = fe
+                done, pushed = end, f1
+
         def run(spg_):
             # The persistent pipeline pipelines the streams of a run through its layer ring: 10 streams at the wall time of one (34 - 37 us
             # per sample: real time at 22.05 kHz), every further stream + 3.6 us per sample (profiles/r5u_pipe_batch_scaling.txt) -- one run
@@ -298,6 +383,9 @@ class WaveNet(object):
                 nz = None if noise is None else noise[:, b0:b1].contiguous()
                 if gt is not None:
                     self._set_global(gt[b0:b1], b1 - b0)                                # wavenet.py:766-777
+                if chunk_frames > 0:
+                    run_stream(b0, b1, nz, spg_, seed * 64 + b0 // group)
+                    continue
                 self.engine.synthesize(cc[b0:b1].contiguous(), nz, out[b0:b1], None if raw is None else raw[b0:b1], None if ti is None else ti[b0:b1].contiguous(),
                                        steps_per_graph=spg_, seed=seed * 64 + b0 // group)
                 self.engine.upsampled_features(feats[b0:b1])
@@ -334,6 +422,18 @@ class WaveNet(object):
             log('WaveNet synthesis path: {} ({} streams per run)'.format(self.engine.synth_path, group))
         self.upsampled_local_features = feats
         return (out, raw) if return_raw else out
+
+    def stream(self, batch, g=None, seed=None, steps_per_graph=None):
+        """Open a SynthesisStream of `batch` utterances (<= 32, the model's engine must have been built for them).  seed None: derived as
+        incremental() derives it."""
+        hp = self._hparams
+        if self.engine is None:
+            self.build(batch, audio.get_hop_size(hp) * 64, inference_only=True)
+        if seed is None:
+            self._synth_calls = getattr(self, '_synth_calls', 0) + 1
+            seed = ((int(hp.wavenet_random_seed) << 20) + self._synth_calls) * 64
+        spg = int(getattr(hp, 'mi355_steps_per_graph', 0)) if steps_per_graph is None else int(steps_per_graph)
+        return SynthesisStream(self, batch, g=g, seed=seed, steps_per_graph=spg)
 
     # ------------------------------------------------------------------ checkpoint state
     def state_dict(self):
