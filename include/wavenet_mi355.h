@@ -286,7 +286,9 @@ const char* wn_dominant_kernel_name(void);
  * ================================================================================================ */
 #ifndef WN_NO_TEST_HOOKS
 /* copy an internal activation buffer of the last step to `out` as fp32 ("X","U","TS","DZ","R1","H2","DY","DSKIP","DPRE1","GX0",
- * "GX1","cbt" are bf16 [rows][channels]; "YHAT","DC","CUP" fp32). */
+ * "GX1","cbt" are bf16 [rows][channels]; "YHAT","DC","CUP" fp32).  "GX" with layer 0 ... L is d L / d h_layer as the backward chain
+ * keeps it (layer L: the zero-filled top), "XD" with layer 0 ... L-1 the dropout-applied conv input (the same buffer as "X" when
+ * dropout is 0); a layer outside these ranges is WN_E_ARG. */
 int wn_debug_copy(wn_ctx* ctx, const char* name, int32_t layer, float* out, int64_t n, void* stream);
 /* live HIP-event timing of the dominant training kernel (the gate GEMM, one launch per layer and step), recorded on the launch
  * stream between wn_profile(ctx,1) and wn_profile_result -- which SYNCHRONISES on the recorded events (bench only). */

@@ -338,10 +338,11 @@ def _conv1x1(x, K, b):
     return y if b is None else y + b[None, :, None]
 
 
-def glu_layer(P, params, cfg: OracleConfig, l, h, cu, mask, q, gvec=None):
+def glu_layer(P, params, cfg: OracleConfig, l, h, cu, mask, q, gvec=None, aux=None):
     """One ResidualConv1DGLU.step (modules.py:471-521) of layer l on its input h [B,R,T]: returns (next layer input, skip
     contribution, gate output u).  P = kernels as the contraction sees them (bf16-rounded when emulating), params = fp32 biases,
-    mask = {0,1} dropout mask [B,R,T] or None, q = rounding applied where the HIP path stores bf16 (identity for the fp32 oracle)."""
+    mask = {0,1} dropout mask [B,R,T] or None, q = rounding applied where the HIP path stores bf16 (identity for the fp32 oracle).
+    aux: optional dict; the gate pre-activation z [B,G,T] of this layer is appended to aux['z'] (observation only)."""
     k = cfg.kernel_size
     d = cfg.dilations()[l]
     keep = 1.0 - cfg.wavenet_dropout
@@ -360,6 +361,8 @@ def glu_layer(P, params, cfg: OracleConfig, l, h, cu, mask, q, gvec=None):
         zg = gvec @ params[p + 'residual_block_gin_conv/kernel'][0]
         bg = params.get(p + 'residual_block_gin_conv/bias')
         z = z + (zg if bg is None else zg + bg)[:, :, None]
+    if aux is not None:
+        aux.setdefault('z', []).append(z)
     a, b = z.chunk(2, dim=1)                                                 # modules.py:494
     u = q(torch.tanh(a) * torch.sigmoid(b))                                  # modules.py:510
     s = _conv1x1(u, P[p + 'residual_block_skip_conv/kernel'], params.get(p + 'residual_block_skip_conv/bias'))
@@ -402,7 +405,7 @@ def step(params, cfg: OracleConfig, x, c, dropout_masks=None, emulate_bf16=False
     aux['u'] = []
     for l, d in enumerate(cfg.dilations()):
         aux['layer_in'].append(h)
-        h, s, u = glu_layer(P, params, cfg, l, h, cu, None if dropout_masks is None else dropout_masks[l], q, gvec)
+        h, s, u = glu_layer(P, params, cfg, l, h, cu, None if dropout_masks is None else dropout_masks[l], q, gvec, aux if return_aux else None)
         aux['u'].append(u)
         if skips is None:                                                    # wavenet.py:706-715
             skips = s

@@ -540,6 +540,11 @@ extern "C" int wn_debug_copy(wn_ctx* c, const char* name, int32_t layer, float* 
     else if (s == "DZ") b = c->DZ + (size_t)layer * NT * c->G;
     else if (s == "GX0") b = c->GX0;
     else if (s == "GX1") b = c->GX1;
+    else if (s == "GX" || s == "XD") {      // d L / d h_layer (layer L: the zero-filled top) / the dropout-applied conv input (aliases X when dropout is 0)
+        const int hi = s == "GX" ? c->L : c->L - 1;
+        if (layer < 0 || layer > hi) WN_FAIL(c, WN_E_ARG, "wn_debug_copy('%s'): layer %d outside [0, %d]", name, layer, hi);
+        b = (s == "GX" ? c->GXall : c->XD) + (size_t)layer * NT * c->R;
+    }
     else if (s == "YHAT") f = c->YHAT;
     else if (s == "DC") f = c->DC;
     else if (s == "CUP") f = c->CUP[layer];

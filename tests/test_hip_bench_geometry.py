@@ -271,6 +271,31 @@ def test_c5_width_full_depth():
     _assert_case(r)
 
 
+def _default_hparams_model():
+    """hparams.py's own model, flags as the file has them: 20 layers / 2 stacks (dilations 1 .. 512), R = S = 128, G = 256, Gaussian head,
+    SubPixel [11, 25], legacy + residual_legacy, dropout 0.05 -- the tile configuration of the 128-channel LDS-DMA kernel, which the small-shape
+    suite runs at 6 layers x 400 samples only."""
+    cfg = oracle_cfg(make_hp())
+    assert (cfg.layers, cfg.stacks, cfg.residual_channels, cfg.gate_channels, cfg.skip_out_channels, cfg.out_channels) == (20, 2, 128, 256, 128, 2)
+    assert cfg.upsample_type == 'SubPixel' and list(cfg.upsample_scales) == [11, 25] and cfg.legacy and cfg.residual_legacy
+    return {}
+
+
+def test_default_hparams_model_b2_ragged():
+    """hparams.py's own model at B = 2 x 11 000 with a ragged second utterance (one utterance per stream): layer-local X / U at
+    d = 1, 256, 512 of both stacks, y_hat, every gradient tensor -- the tolerances of the C2 cases, unchanged."""
+    r = _case(_default_hparams_model(), 2, 11000, [11000, 9377], [0, 8, 9, 10, 18, 19], report='hparams_b2')
+    _assert_case(r)
+    r['eng'].close()
+
+
+def test_default_hparams_model_b8():
+    """The same model at the benched batch, B = 8 x 11 000 (688 tiles, 4 utterances per stream)."""
+    r = _case(_default_hparams_model(), 8, 11000, [11000] * 8, [0, 8, 9, 10, 18, 19], report='hparams_b8')
+    _assert_case(r)
+    r['eng'].close()
+
+
 def test_gradient_buckets_are_final_when_their_event_fires():
     """wn_bwd_num_buckets / _bucket_range / _wait_bucket (data-parallel overlap): the table is disjoint and covers the whole flat
     buffer; a side stream that waits for bucket i only and snapshots its range sees exactly the bytes the finished backward leaves

@@ -1,0 +1,345 @@
+"""Launch-local parity of the backward chain against the float64 references of tests/launch_ref.py (pytest -m gpu).
+
+Every other GPU test of the backward compares final weight-gradient tensors (sums over all B x T rows) with autograd as a rel-L2 per
+tensor (1.4e-2 and wider): a fault confined to a few rows of d z or d h -- a tap that reads the next utterance at an utterance end, a
+skipped tail tile, a keep-mask off by one element, a wrong b0 offset of the second stream -- is averaged away before anything is
+compared.  Here one ordinary training step runs through the engine, and then EVERY buffer a launch wrote is compared with the
+reference of that launch applied to the device's OWN inputs of that launch, element by element, every element, no exclusions:
+
+    |dev - ref| <= 2^-8 |ref| + K 2^-23 A + E          (terms derived in launch_ref.py, launch by launch; nothing is fitted)
+
+and exactly 0 where reference and operands are 0 (rows past a ragged length, GX[L], the masked half of EPI_MASK_STORE).  XD[l] is
+bit-exact.  DY: 2^-8 |ref| + 8 x the max-abs distance between the float32 and the float64 evaluation of the same oracle gradient on the
+same YHAT (measured on the CPU inside the test).
+
+Weight-gradient tensors are sums over all rows, where a worst-case bound is useless.  Their tolerance is a yardstick measured on the
+reference, in the test, per tensor: the same contraction of the same downloaded buffers in float32 with one running accumulator over
+128-row blocks in row order, against float64 (floored at 2^-24, the final rounding of any float32 result: WGRAD_YARD_FLOOR below).  The
+device gets 8 x that rel-L2 (different summation tree, float atomics between splits) and never more than 1e-5 (a condition, not a measurement: one wrong row in 22 000, all rows agreeing in sign, is 4.5e-5).  A
+tensor whose reference is all zeros (the top layer's W_out) must be exact zeros.  The upsample-net gradients: float64 backward of
+O.upsample from the device's DC, yardstick = the float32 backward.
+
+Per launch kind and layer the test prints the largest err / bound, the rel-L2 and where the worst element is (the small sweep engines:
+per launch kind, with the worst layer; WN_LAUNCH_LOCAL_DETAIL=1 prints every layer there too); on failure it names
+launch, layer, utterance, t, channel, tile index (row // 128) and whether the row is within 2 d of an utterance end.  For GX[l] the
+last 2 d rows of every utterance and the first 2 d rows of the next one are their own group ('GX edge'), and the tap gradients must be
+closer to the reference than HALF of what a read across the utterance start would add ('taps leak'), so a leak across b shows by name.
+The printed ratios are records, not thresholds."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import launch_ref as LR
+from hip_util import download_grads, dropout_mask_rows, make_hp, oracle_cfg, synth_batch, upload_params
+from oracle import wavenet_oracle as O
+from test_hip_bench_geometry import C5, PAPER
+from test_hip_parity import _run_fwd
+from test_hip_round6 import GEOMETRIES
+
+pytestmark = pytest.mark.gpu
+
+WGRAD_FACTOR = 8.0
+WGRAD_CAP = 1e-5
+# The yardstick of a tensor with one or a few elements is ONE draw of a rounding error, not a scale: it can be arbitrarily close to 0, and it is
+# exactly 0 when every float32 partial sum happens to be representable (measured on MI355X: 8.2e-9 .. 9.6e-9 for the one-element biases of the
+# 2D upsample net, 0 for the out-conv bias of layer 5 of softmax_c1 at B = 1 x 112 -- where the unchanged kernels are at 7.8e-8 .. 1.6e-7 and
+# 8.0e-9, i.e. one to three float32 ulps).  Every float32 result, the device's and the yardstick's own, carries the final rounding to float32:
+# half an ulp, 2^-24 relative.  A yardstick below that is luck, so the yardstick is floored at the precision of the output format (DESIGN
+# section 5).  The factor and the cap stay: the tolerance is never below 4.8e-7 and never above 1e-5.
+WGRAD_YARD_FLOOR = 2.0 ** -24
+
+
+class Report:
+    """Collects the comparisons of one engine and prints them compactly:
+        kind err/bound rel-L2 @utterance:t:channel[e]      element-wise launches (e: the worst element is within 2d of an utterance end)
+        tensor rel-L2/yardstick                            weight gradients (device against float64 / the float32 yardstick; dil = causal conv,
+                                                           fin = final_convolution, in = input_convolution, up = upsample net, k / b = kernel / bias)
+    detail=True: one line per layer and group (the benched geometries; every case with WN_LAUNCH_LOCAL_DETAIL=1); otherwise one line per
+    engine with the worst layer of every launch kind (the 54 small sweep engines).  A failure always lists every offending launch, layer,
+    utterance, t, channel and tile."""
+
+    def __init__(self, tag, B, T, detail):
+        self.tag, self.B, self.T = tag, B, T
+        self.detail = detail or os.environ.get('WN_LAUNCH_LOCAL_DETAIL') == '1'
+        self.fail = []
+        self.worst = {}          # kind -> (largest err / bound (weight gradients: rel-L2 / tolerance) over layers, layer, text)
+        self.pending = []
+
+    def _note(self, kind, l, ratio, text):
+        self.pending.append(text)
+        if kind not in self.worst or ratio >= self.worst[kind][0]:
+            self.worst[kind] = (ratio, l, text)
+
+    def flush(self, label):
+        if self.detail and self.pending:
+            print('[%s] %-8s %s' % (self.tag, label, ' | '.join(self.pending)))
+        self.pending = []
+
+    def elementwise(self, kind, l, dev, ref, bound, d=0, group=None):
+        """dev / ref / bound [B, T, ch]: every element, bound 0 means exact.  group ([B, T, 1] of {0, 1}): report / assert on those rows only."""
+        err = (dev - ref).abs()
+        ratio = torch.where(bound > 0, err / torch.where(bound > 0, bound, torch.ones_like(bound)),
+                            torch.where(err > 0, torch.full_like(err, float('inf')), torch.zeros_like(err)))
+        if group is not None:
+            ratio = torch.where(group > 0, ratio, torch.zeros_like(ratio))
+        worst = float(ratio.max())
+        idx = int(ratio.argmax())
+        b, rem = divmod(idx, ratio.shape[1] * ratio.shape[2])
+        t, ch = divmod(rem, ratio.shape[2])
+        nref = float(ref.norm())
+        rel = float((dev - ref).norm()) / nref if nref > 0 else float((dev - ref).norm())
+        nbad = int((ratio > 1.0).sum())
+        near = d > 0 and (t >= self.T - 2 * d or t < 2 * d)
+        self._note(kind, l, worst, '%s %.3f %.1e @%d:%d:%d%s' % (kind, worst, rel, b, t, ch, 'e' if near else ''))
+        if nbad:
+            self.fail.append('[%s] %s layer %d: err/bound %.3f, rel-L2 %.2e, %d of %d elements over the bound; worst at utterance %d t %d channel %d (row %d, tile %d%s): '
+                             'dev %.6g ref %.6g bound %.3g' % (self.tag, kind, l, worst, rel, nbad, ratio.numel(), b, t, ch, b * self.T + t, (b * self.T + t) // 128,
+                                                               ', within 2d of an utterance end' if near else '', float(dev[b, t, ch]), float(ref[b, t, ch]), float(bound[b, t, ch])))
+
+    def exact(self, kind, l, dev, ref):
+        nbad = int((dev != ref).sum())
+        self._note(kind, l, float(nbad), '%s %s' % (kind, 'bit-exact' if nbad == 0 else '%d differ' % nbad))
+        if nbad:
+            idx = int((dev != ref).flatten().to(torch.int8).argmax())
+            row, ch = divmod(idx, dev.shape[-1])
+            self.fail.append('[%s] %s layer %d: %d elements differ, first at utterance %d t %d channel %d (tile %d): dev %.6g ref %.6g' % (
+                self.tag, kind, l, nbad, row // self.T, row % self.T, ch, row // 128, float(dev.flatten()[idx]), float(ref.flatten()[idx])))
+
+    def tensor(self, name, l, dev, ref, yard):
+        """One weight-gradient tensor: rel-L2 of the device against float64, tolerance from the float32 yardstick of the same contraction."""
+        dev, ref = dev.double().reshape(-1), ref.double().reshape(-1)
+        short = '/'.join(p.replace('residual_block_', '').replace('local_conditioning_upsampling', 'up').replace('final_convolution', 'fin').replace('input_convolution', 'in')
+                         .replace('causal_conv', 'dil').replace('_conv', '').replace('kernel', 'k').replace('bias', 'b') for p in name.split('/')[-2:])
+        nref = float(ref.norm())
+        if nref == 0.0:
+            nz = int((dev != 0).sum())
+            self._note(short + ' (zero reference)', l, float(nz), '%s zeros' % short if nz == 0 else '%s %d NONZERO' % (short, nz))
+            if nz:
+                self.fail.append('[%s] wgrad %s: reference is all zeros, device has %d nonzero elements (max %.3e)' % (self.tag, name, nz, float(dev.abs().max())))
+            return
+        rel = float((dev - ref).norm()) / nref
+        tol = min(WGRAD_FACTOR * max(yard, WGRAD_YARD_FLOOR), WGRAD_CAP)
+        self._note('wgrad', l, rel / tol, '%s %.1e/%.1e' % (short, rel, yard))
+        if rel > tol:
+            self.fail.append('[%s] wgrad %s: rel-L2 %.3e > tolerance %.3e (8 x max(yardstick %.3e, 2^-24), cap 1e-5)' % (self.tag, name, rel, tol, yard))
+
+    def finish(self):
+        # the worst layer of every launch kind ("wgrad": the tensor closest to its tolerance, as rel-L2 / tolerance)
+        print('[%s] worst    %s' % (self.tag, ' | '.join('%s (L%d%s)' % (v[2], v[1], ', %.2f of tolerance' % v[0] if k == 'wgrad' else '') for k, v in sorted(self.worst.items()))))
+        assert not self.fail, '\n'.join(self.fail[:40])
+
+
+def _edge_group(B, T, d):
+    """1 on the last 2d rows of every utterance and the first 2d rows of the next one."""
+    g = torch.zeros(B, T, 1, dtype=torch.float64)
+    n = min(2 * d, T)
+    g[:, T - n:] = 1.0
+    g[1:, :n] = 1.0
+    return g
+
+
+def check_step(tag, eng, cfg, params, B, T, lengths, seed, x_in, y_or, c_in, grads_flat, g=None, chain_layers=None, wgrad_layers=None, wgrads=True, detail=False):
+    """The device's buffers after one train_fwd + train_bwd against launch_ref, one layer resident at a time."""
+    L, R, G, S, C = cfg.layers, cfg.residual_channels, cfg.gate_channels, cfg.skip_out_channels, cfg.cin_channels
+    GH, Oc = G // 2, cfg.out_channels
+    ldDY = (Oc + 15) // 16 * 16
+    n = B * T
+    chain_layers = set(range(L)) if chain_layers is None else set(chain_layers)
+    wgrad_layers = (set(range(L)) if wgrad_layers is None else set(wgrad_layers)) if wgrads else set()
+    W = LR.Weights(params, cfg, rounded=True)
+    rep = Report(tag, B, T, detail)
+    p = float(cfg.wavenet_dropout)
+    g_dev = download_grads(eng, grads_flat) if wgrads else {}
+
+    def dl(name, l, ch):
+        return eng.debug_copy(name, l, n, ch).cpu().double().view(B, T, ch)
+
+    def mask(l):
+        return torch.from_numpy(dropout_mask_rows(seed, l, 0, n, R, p)).double().view(B, T, R) if p > 0 else None
+
+    def tensors(label, l, refs, flush=True):
+        for k, (r, y) in refs.items():
+            if k in g_dev:
+                rep.tensor(k, l, g_dev[k], r, y)
+        if flush:
+            rep.flush(label)
+
+    # ---- loss: DY from the device's own YHAT
+    yhat = eng.debug_copy('YHAT', 0, B * Oc, T).cpu().view(B, Oc, T)
+    DY = dl('DY', 0, ldDY)
+    if ldDY > Oc:
+        assert float(DY[..., Oc:].abs().max()) == 0.0, 'DY padding columns must be 0'
+    dy64 = LR.ref_dy(cfg, yhat, y_or, lengths, torch.float64)
+    dy32 = LR.ref_dy(cfg, yhat, y_or, lengths, torch.float32).double()
+    e32 = float((dy32 - dy64).abs().max())
+    scored = (torch.arange(T)[None, :] < (torch.as_tensor(lengths)[:, None] - 1)).double()[..., None]      # prediction t is scored against sample t + 1 < length
+    assert float((dy64 * (1 - scored)).abs().max()) == 0.0
+    rep.elementwise('DY', 0, DY[..., :Oc], dy64, LR.BF * dy64.abs() + 8.0 * e32 * scored)      # (rows that are not scored: exactly 0)
+    del dy64, dy32, yhat
+    # ---- head
+    H2, R1, DPRE1, DSKIP = dl('H2', 0, S), dl('R1', 0, S), dl('DPRE1', 0, S), dl('DSKIP', 0, S)
+    rep.elementwise('DPRE1', 0, DPRE1, *LR.ref_dpre1(W, DY, H2, True))
+    rep.elementwise('DSKIP', 0, DSKIP, *LR.ref_dskip(W, DPRE1, R1, True))
+    rep.flush('head')
+    if wgrads:
+        tensors('head wg', 0, LR.ref_wgrads_head(W, R1, H2, DPRE1, DY, True))
+    del H2, R1, DPRE1, DY
+    cbt = dl('cbt', 0, C) if wgrad_layers else None
+    # ---- the chain, top to bottom; one layer's buffers resident at a time
+    GX_up = dl('GX', L, R)
+    assert float(GX_up.abs().max()) == 0.0, 'GX[L] (the dead residual branch of the top layer) must be zero-filled'
+    dc = None
+    want_dc = cfg.upsample_type != 'NearestNeighbor'
+    colsums, colsums32 = [], []
+    for l in range(L - 1, -1, -1):
+        d = W.dil[l]
+        DZ = dl('DZ', l, G)
+        if want_dc:
+            dc = LR.ref_dc_accumulate(W, l, DZ, dc, True)
+        if g is not None:
+            colsums.insert(0, DZ.sum(1))
+            a32, z32 = torch.zeros(B, G), DZ.float()
+            for r0 in range(0, T, 128):
+                a32 += z32[:, r0:r0 + 128].sum(1)
+            colsums32.insert(0, a32)
+            del z32
+        GX = dl('GX', l, R)
+        if l in chain_layers or l in wgrad_layers:
+            TS, U = dl('TS', l, GH), dl('U', l, GH)
+        if l in chain_layers:
+            rep.elementwise('DZ', l, DZ, *LR.ref_dz(W, l, GX_up, DSKIP, TS, U, True))
+            m = mask(l)
+            ref, bound = LR.ref_gx(W, l, DZ, m, GX_up if l < L - 1 else None, True)
+            rep.elementwise('GX', l, GX, ref, bound, d)
+            rep.elementwise('GX edge', l, GX, ref, bound, d, group=_edge_group(B, T, d))
+            del ref, bound
+            X = dl('X', l, R)
+            rep.exact('XD', l, dl('XD', l, R), LR.ref_xd(W, X, m))
+            if l == 0:
+                rep.elementwise('X0', 0, X, *LR.ref_x0(W, x_in, True, w_ulps=8 if cfg.wavenet_weight_normalization else 0))
+            if l < L - 1:
+                rep.elementwise('X_next', l, dl('X', l + 1, R), *LR.ref_x_next(W, l, U, X, True))
+            del X, m
+            rep.flush('L%02d d=%d' % (l, d))
+        if l in wgrad_layers:
+            XD = dl('XD', l, R)
+            refs = LR.ref_wgrads_layer(W, l, XD, cbt, DZ, U, DSKIP, GX_up, True)
+            tensors('L%02d wg' % l, l, refs, flush=False)
+            if B > 1:      # a tap that read across the utterance start would add `leak`: the device must be far closer to the reference than that
+                k = 'ResidualConv1DGLU_%d/residual_block_causal_conv/kernel' % l
+                leak = float(LR.taps_leak(W, l, XD, DZ).norm())
+                err = float((g_dev[k].double() - refs[k][0]).norm())
+                rep._note('taps leak', l, err / leak if leak > 0 else 0.0, 'taps leak %.1e/%.1e' % (err, leak))      # |dev - ref| / |what a read across the utterance start adds|
+                if leak > 0 and not err < 0.5 * leak:
+                    rep.fail.append('[%s] taps leak layer %d (d = %d): |dev - ref| = %.3e is not below half of what reading across the utterance start adds (%.3e)' % (tag, l, d, err, leak))
+            rep.flush('L%02d wg' % l)
+            del XD, refs
+        GX_up = GX
+    if want_dc:
+        DC = eng.debug_copy('DC', 0, B * C, T).cpu().double().view(B, C, T).permute(0, 2, 1)
+        rep.elementwise('DC', 0, DC, dc[0], LR.dc_bound(W, dc, G))
+        rep.flush('d c')
+    if wgrads:
+        tensors('input wg', 0, LR.ref_wgrads_input(W, x_in, GX_up, True))
+        if g is not None:
+            ids = g.long() if cfg.use_speaker_embedding else None
+            gvec = params['gc_embedding'][ids] if ids is not None else g
+            r64 = LR.ref_wgrads_gin(params, cfg, gvec, ids, colsums, torch.float64)
+            r32 = LR.ref_wgrads_gin(params, cfg, gvec, ids, colsums32, torch.float32)      # yardstick: float32 column sums (128-row blocks in row order) through the float32 contraction
+            tensors('gin wg', 0, {k: (r64[k], float((r32[k].double() - r64[k]).norm()) / max(float(r64[k].norm()), 1e-300)) for k in r64})
+        if want_dc:      # upsample net: float64 backward of O.upsample from the device's DC; yardstick = the float32 backward
+            up = {}
+            for dt in (torch.float64, torch.float32):
+                leaf = {k: v.to(dt).clone().requires_grad_(True) for k, v in params.items() if k.startswith('local_conditioning')}
+                out = O.upsample(leaf, cfg, c_in.to(dt))
+                out.backward(DC.permute(0, 2, 1).to(dt))
+                up[dt] = {k: v.grad.double() for k, v in leaf.items()}
+            tensors('up wg', 0, {k: (r, float((up[torch.float32][k] - r).norm()) / max(float(r.norm()), 1e-300)) for k, r in up[torch.float64].items()})
+    rep.finish()
+    return rep
+
+
+# ------------------------------------------------------------------------------------------------------------------ small configurations
+SMALL_CONFIGS = ['paper_width_drop', 'wide', 'mol_2d', 'gauss_subpixel', 'mol_2d_legacy_drop', 'mol_gin_embed', 'mol_nobias', 'softmax_c1', 'mol_weightnorm']
+
+
+@pytest.mark.parametrize('name', SMALL_CONFIGS)
+def test_launch_local_geometry_sweep(name):
+    """The six batch / time geometries of the tile-boundary sweep x one configuration, all layers, every launch."""
+    for B, T, lengths in GEOMETRIES:
+        r = _run_fwd(name, B=B, T=T, lengths=lengths)
+        cfg, eng = r['cfg'], r['eng']
+        assert r['T'] == T
+        grads = torch.empty(eng.n_params, device='cuda')
+        eng.train_bwd(grads)
+        torch.cuda.synchronize()
+        quant = cfg.input_type == 'mulaw-quantize'
+        x_in = r['y_or'] if quant else r['x_or'].view(B, T)
+        try:
+            check_step('%s B=%d T=%d' % (name, B, T), eng, cfg, r['params'], B, T, lengths, r['seed'], x_in, r['y_or'], r['c'], grads, g=r['g'],
+                       wgrads=not cfg.wavenet_weight_normalization)      # (v / g gradients stay with the end-to-end test)
+        finally:
+            eng.close()
+
+
+# ------------------------------------------------------------------------------------------------------------------ benched geometries
+def _big(tag, hp, B, T, lengths, chain_layers=None, wgrad_layers=None, grad_buckets=None, batch_parts=0, seed=1234, expect_8p=None, detail=True):
+    from wavenet_vocoder import _ext
+    cfg = oracle_cfg(hp)
+    assert T % cfg.hop == 0
+    eng = _ext.Engine(hp, B, T, grad_buckets=grad_buckets)
+    try:
+        if expect_8p is not None:
+            assert eng.lib.wn_test_gemm8p_mask(eng.h) == expect_8p
+        params = O.init_params(cfg, seed=5339, bias_scale=0.05)
+        gen = torch.Generator().manual_seed(7)
+        for k in params:
+            if k.startswith('local_conditioning') and k.endswith('kernel'):
+                params[k] = params[k] + 0.02 * torch.randn(params[k].shape, generator=gen)
+        eng.pack_weights(upload_params(eng, params))
+        if batch_parts:
+            eng.set_batch_parts(batch_parts)
+        wav, c = synth_batch(cfg, B, T, seed=3)
+        loss = torch.zeros(1, device='cuda')
+        eng.train_fwd(wav.view(B, 1, T).contiguous().cuda(), c.cuda(), wav.view(B, T, 1).contiguous().cuda(), torch.tensor(lengths, dtype=torch.int32).cuda(), seed, loss)
+        grads = torch.empty(eng.n_params, device='cuda')
+        eng.train_bwd(grads)
+        torch.cuda.synchronize()
+        assert np.isfinite(float(loss.item()))
+        return check_step(tag, eng, cfg, params, B, T, lengths, seed, wav, wav.view(B, T, 1), c, grads, chain_layers=chain_layers, wgrad_layers=wgrad_layers, detail=detail)
+    finally:
+        eng.close()
+
+
+def test_launch_local_c2_b2_two_streams():
+    """C2 at B = 2 x 11 000, lengths [11000, 9377], grad_buckets = 3: dilations to 2048, the 11000 % 128 tail tile, one utterance per stream."""
+    _big('c2_b2', make_hp(**PAPER), 2, 11000, [11000, 9377], grad_buckets=3)
+
+
+def test_launch_local_c2_b2_single_stream():
+    _big('c2_b2_parts1', make_hp(**PAPER), 2, 11000, [11000, 9377], grad_buckets=3, batch_parts=1, detail=False)      # (same launches as above, other stream order)
+
+
+def test_launch_local_c2_b2_on_the_8phase_kernel(monkeypatch):
+    monkeypatch.setenv('WN_GEMM8P', '3')
+    _big('c2_b2_gemm8p', make_hp(**PAPER), 2, 11000, [11000, 9377], grad_buckets=3, expect_8p=3, detail=False)
+
+
+def test_launch_local_c2_b8_bench_batch():
+    """The bench batch: chain at layers {0, 10, 11, 12, 23}, weight gradients of all layers."""
+    _big('c2_b8', make_hp(**PAPER), 8, 11000, [11000] * 8, chain_layers=[0, 10, 11, 12, 23])
+
+
+def test_launch_local_default_hparams_model_b8():
+    """hparams.py's own model (20 layers / 2 stacks, R = S = 128, G = 256, Gaussian, SubPixel [11, 25], flags as the file has them)."""
+    import hparams as H
+    hp = H._build()
+    cfg = oracle_cfg(hp)
+    assert (cfg.layers, cfg.stacks, cfg.residual_channels, cfg.gate_channels, cfg.out_channels, cfg.upsample_type) == (20, 2, 128, 256, 2, 'SubPixel')
+    _big('hparams_b8', hp, 8, 11000, [11000] * 8)
+
+
+def test_launch_local_c5_width_full_depth():
+    _big('c5_b2', make_hp(**C5), 2, 12000, [12000, 12000], chain_layers=[0, 9, 10, 29], wgrad_layers=[0, 9, 10, 29])
