@@ -237,7 +237,7 @@ int wn_synth_last_batched(const wn_ctx* ctx);
  * The reference's loop is a streaming computation (zero queues, wavenet.py:815-816; silence input, :433-445; step t reads only its
  * own conditioning frame and the queues, :821-886): a stream continues the ring queues, the time index, the fed-back sample and the
  * device noise counter across pushes, and the samples it returns are bit-identical to one wn_synthesize over the concatenated frames
- * (same B, seed, steps_per_graph, noise / teacher forcing).  One open stream per context, B <= 32 utterances in lockstep.
+ * (same B, seed, steps_per_graph, noise / teacher forcing).  One open stream per context, B <= 32 utterances in lockstep (independent utterances: the slot sessions below).
  *
  * Mel frames of context the upsample net needs on each side of a frame (host only: no context, no GPU): 0 / 0 for 'NearestNeighbor',
  * '2D' and '1D' (time kernel == stride); 'SubPixel': ceil(h / hop) on both sides with h = sum_i prod_{k >= i} s_k samples (layer i's 3-tap
@@ -262,6 +262,38 @@ int wn_synth_stream_push(wn_ctx* ctx, const float* c, int32_t Tn, int32_t final,
                          void* out_samples, float* out_raw, int32_t* n_out, void* stream);
 /* Abandon the open stream (no device work; what was pushed and not generated is dropped).  A later push returns WN_E_STATE. */
 int wn_synth_stream_end(wn_ctx* ctx);
+
+/* ---- synthesis slots: utterances join and leave a running batch (continuous batching for the vocoder) -----------------------
+ * A session is B slots (B <= 32, B <= max_batch) served by ONE path / pipeline configuration -- the one wn_synthesize(steps_per_graph) would take
+ * for B -- for the life of the session.  Every slot is idle or carries one utterance with its own t = 0, seed, global condition and mel frames;
+ * utterances are opened, fed, finished and replaced independently.  A slot's out_samples / out_raw depend only on the session's B and configuration,
+ * the slot index and the slot's own frames, noise, teacher forcing and condition -- not on how the frames were cut into pushes, when the slot was
+ * opened, what the other slots do or what occupied it before -- and are bit-identical to ONE wn_synthesize of the same B and steps_per_graph with the
+ * utterance's frames in batch row = slot index and, for device noise, column b of the [T, B, nps] noise = wn_fill_noise(B = 1, T, seed_b).
+ * Frames -> samples follow wn_synth_stream_lookahead per slot: a slot generates its frames [done, pushed - frames_right), all of them with final.
+ * A push runs max_b n_out[b] steps; slots with nothing (more) to generate take part as dummy steps that write nothing (no queue row, no output
+ * element, no abort).  Reopening a slot clears nothing: a tap before the utterance's own t = 0 is invalid per slot.
+ * Errors: WN_E_STATE for a call without a session, open of a live slot, frames for an idle slot, a session ended by wn_synthesize / wn_pack_weights /
+ * wn_synth_pipe_dtype / wn_synth_stream_begin, or poisoned by a failed pipeline run (reported by wn_synth_check or the next push); WN_E_SHAPE when a
+ * push would generate more than max_time samples for a slot or a slot's window exceeds the workspace (a rejected push leaves every slot as it was);
+ * WN_E_UNSUPPORTED from wn_synth_slots_begin on compute_dtype = WN_COMPUTE_F32 (the fp32 validation mode has no slot sessions).  A session and a
+ * stream exclude one another on a context; wn_train_fwd / wn_train_bwd between pushes do not disturb a session; wn_set_global_condition is not
+ * used (the condition is per slot).  Inference-only contexts never allocate in these calls. */
+int wn_synth_slots_begin(wn_ctx* ctx, int32_t B, int32_t steps_per_graph, void* stream);
+/* The slot becomes live at its own t = 0 with the next push.  g: this utterance's global condition on the device -- one int32 speaker id
+ * (use_speaker_embedding) or float [gin_channels]; NULL iff gin_channels <= 0.  seed: the slot's device noise (noise = NULL pushes). */
+int wn_synth_slot_open(wn_ctx* ctx, int32_t slot, uint64_t seed, const void* g, void* stream);
+/* c float [B, cin, Tn] (rows of idle slots ignored); frames[b] in [0, Tn] (host): the leading frames of row b appended to slot b; final_[b] != 0
+ * (host): slot b's utterance ends with these frames and the slot is idle afterwards.  n_out[b] (host) = samples generated for slot b, known at
+ * enqueue time.  out_samples [B, out_pitch] (float / int32 as wn_synthesize), optional out_raw [B, O, out_pitch], optional test_inputs
+ * [B, out_pitch], out_pitch >= max_b n_out[b]; elements beyond n_out[b] of a row keep the caller's bytes.  noise [max_b n_out[b], B, nps] indexed by
+ * the push-local step (rows of slots that do not generate are ignored) or NULL.  Asynchronous, ordered like wn_synthesize, never synchronises.
+ * wn_get_upsampled_features afterwards returns [B, cin, max_b n_out[b]]: row b = the conditioning slot b's n_out[b] steps read. */
+int wn_synth_slots_push(wn_ctx* ctx, const float* c, int32_t Tn, const int32_t* frames, const int32_t* final_, const float* noise,
+                        const void* test_inputs, void* out_samples, float* out_raw, int32_t out_pitch, int32_t* n_out, void* stream);
+int wn_synth_slot_abandon(wn_ctx* ctx, int32_t slot);              /* drop a live utterance (host only, no device work); the slot is idle */
+int wn_synth_slot_frames_done(const wn_ctx* ctx, int32_t slot);    /* frames generated so far, -1 idle; WN_E_ARG / WN_E_STATE */
+int wn_synth_slots_end(wn_ctx* ctx);
 
 /* Stand-alone samplers on [B,O,T] parameters (train-time log path, wavenet.py:302-325). */
 int wn_sample(wn_ctx* ctx, const float* y_hat, int32_t B, int32_t T, const float* noise /*[T,B,nps]*/,

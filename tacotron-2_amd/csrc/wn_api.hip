@@ -181,6 +181,8 @@ static int alloc_workspace(wn_ctx* c) {
 }
 
 static int stream_alloc(wn_ctx* c);
+static int slots_alloc(wn_ctx* c);
+static void slots_free(wn_ctx* c);
 
 extern "C" int wn_create(const wn_config* cfg, wn_ctx** out) {
     wn_ctx* z = nullptr;
@@ -267,6 +269,7 @@ extern "C" int wn_create(const wn_config* cfg, wn_ctx** out) {
             rc = c->cfg.compute_dtype == WN_COMPUTE_F32 ? wn_synth_f32_reserve(c, c->maxB) : pb > 0 ? wn_pipe_reserve(c, pb, c->maxT) : wn_synth_reserve(c);
         }
         if (rc == WN_OK) rc = stream_alloc(c);      // the streaming state too: wn_synth_stream_* never allocate here
+        if (rc == WN_OK && c->cfg.compute_dtype != WN_COMPUTE_F32) rc = slots_alloc(c);      // ... nor do wn_synth_slots_*
     }
     if (rc != WN_OK) { g_create_err = c->err; wn_destroy(c); return rc; }
     *out = c;
@@ -281,6 +284,7 @@ extern "C" void wn_destroy(wn_ctx* c) {
     for (float* q : c->strm.pend) if (q) hipFree(q);
     if (c->strm.gbias) hipFree(c->strm.gbias);
     if (c->strm.carry) hipFree(c->strm.carry);
+    slots_free(c);
     wn_f32_free(c);
     auto fr = [](PackedW& w) { if (w.dev) hipFree(w.dev); if (w.dev_segs) hipFree(w.dev_segs); w.dev = nullptr; w.dev_segs = nullptr; };
     for (auto& p : c->packs) { fr(p.w1); fr(p.wo); fr(p.ws); fr(p.w2T); fr(p.w1T); }
@@ -365,7 +369,7 @@ struct WnRange {
 extern "C" int wn_pack_weights(wn_ctx* c, const float* params, void* stream) {
     if (!c || !params) return WN_E_ARG;
     WnRange range("wn_pack_weights");
-    c->strm.open = false;                              // (ends an open stream: its pipeline slices / bias are of the old weights)
+    c->strm.open = false; c->slots.open = false;       // (ends an open stream / slot session: its pipeline slices / bias are of the old weights)
     return wn_launch_pack(c, params, (hipStream_t)stream);
 }
 
@@ -435,7 +439,9 @@ extern "C" int wn_optim_step(wn_ctx* c, float* p, const float* g, float* m, floa
 extern "C" int wn_get_upsampled_features(wn_ctx* c, float* out, void* stream) {
     if (!c || !out) return WN_E_ARG;
     if (c->fB <= 0) WN_FAIL(c, WN_E_STATE, "no forward/synthesis has run yet");
-    if (c->fup_pitch > 0)      // after a stream push: the span's columns of the upsampled window
+    if (c->fup_pitch < 0)      // after a push of a slot session: [B][C][n_max], row b = the rows slot b's steps of that push read (rows of slots that generated fewer: stale beyond their count)
+        WN_HIP(c, hipMemcpyAsync(out, c->slots.feat, (size_t)c->slots.feat_B * c->C * c->slots.feat_pitch * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    else if (c->fup_pitch > 0)      // after a stream push: the span's columns of the upsampled window
         WN_HIP(c, hipMemcpy2DAsync(out, (size_t)c->fT * 4, c->CUP[c->cup_final_idx] + c->fup_off, (size_t)c->fup_pitch * 4, (size_t)c->fT * 4, (size_t)c->fB * c->C,
                                    hipMemcpyDeviceToDevice, (hipStream_t)stream));
     else WN_HIP(c, hipMemcpyAsync(out, c->CUP[c->cup_final_idx], (size_t)c->fB * c->C * c->fT * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
@@ -449,7 +455,7 @@ extern "C" int wn_synthesize(wn_ctx* c, const float* cc, int32_t B, int32_t Tc, 
     if (!c->packed) WN_FAIL(c, WN_E_STATE, "wn_pack_weights must be called before wn_synthesize");
     if (B <= 0 || B > 32) WN_FAIL(c, WN_E_SHAPE, "synthesis batch %d outside (0, 32]", B);
     if (Tc <= 0) WN_FAIL(c, WN_E_SHAPE, "Tc must be positive");
-    c->strm.open = false; c->fup_pitch = 0;            // (ends an open stream: its queues are overwritten)
+    c->strm.open = false; c->slots.open = false; c->fup_pitch = 0;            // (ends an open stream / slot session: its queues are overwritten)
     int rc = wn_pipe_check(c, false);                  // a hand-off timeout of the previous pipeline run surfaces here at the latest
     if (rc) return rc;
     if (!noise) {                                      // device Philox stream keyed by `seed` (header)
@@ -469,7 +475,7 @@ extern "C" int wn_synth_check(wn_ctx* c) { if (!c) return WN_E_ARG; return wn_pi
 extern "C" int wn_synth_last_path(const wn_ctx* c) { return c ? c->synth_path : WN_E_ARG; }
 extern "C" int wn_synth_last_instances(const wn_ctx* c) { return c ? c->synth_instances : WN_E_ARG; }
 extern "C" int wn_synth_last_batched(const wn_ctx* c) { return c ? (c->synth_path == 2 ? c->synth_batchpre : 0) : WN_E_ARG; }
-extern "C" int wn_synth_pipe_dtype(wn_ctx* c, int32_t half) { if (!c) return WN_E_ARG; c->pipe_f16 = half != 0; c->strm.open = false; return WN_OK; }
+extern "C" int wn_synth_pipe_dtype(wn_ctx* c, int32_t half) { if (!c) return WN_E_ARG; c->pipe_f16 = half != 0; c->strm.open = false; c->slots.open = false; return WN_OK; }
 extern "C" int wn_synth_last_config(const wn_ctx* c, int32_t* out, int32_t cap) {
     if (!c || !out || cap < 0) return WN_E_ARG;
     int32_t v[WN_SYNTH_CFG_N] = {c->synth_path, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -622,7 +628,7 @@ extern "C" int wn_synth_stream_begin(wn_ctx* c, int32_t B, uint64_t seed, int32_
     if (!c) return WN_E_ARG;
     WnRange range("wn_synth_stream_begin");
     auto& S = c->strm;
-    S.open = false;
+    S.open = false; c->slots.open = false;            // (a stream and a slot session exclude one another)
     if (!c->packed) WN_FAIL(c, WN_E_STATE, "wn_pack_weights must be called before wn_synth_stream_begin");
     if (B <= 0 || B > 32 || B > c->maxB) WN_FAIL(c, WN_E_SHAPE, "stream batch %d outside (0, min(32, max_batch = %d)]", B, c->maxB);
     if (c->gin > 0 && (!c->have_g || c->gB != B))
@@ -706,5 +712,221 @@ extern "C" int wn_synth_stream_push(wn_ctx* c, const float* cc, int32_t Tn, int3
 extern "C" int wn_synth_stream_end(wn_ctx* c) {
     if (!c) return WN_E_ARG;
     c->strm.open = false;
+    return WN_OK;
+}
+
+// ---- synthesis slots: utterances join and leave a running batch -------------------------------------------------------------------
+// One session = B slots on one path / pipeline configuration.  What a stream keeps once (time index, pending window, seed, carried input, bias row) a
+// session keeps per slot; a push runs max_b n_out[b] steps in which every slot takes part, the ones that have nothing (more) to generate as dummies.
+static int slots_alloc(wn_ctx* c) {
+    auto& S = c->slots;
+    if (S.pend[0]) return WN_OK;
+    int l = 0, r = 0; wn_synth_stream_lookahead(&c->cfg, &l, &r);
+    S.capw = c->maxT / c->hop + l + r + 1;
+    const int nb = std::min(32, c->maxB);
+    for (float*& q : S.pend) WN_HIP(c, hipMalloc((void**)&q, (size_t)nb * c->C * S.capw * 4));
+    WN_HIP(c, hipMalloc((void**)&S.gwin, (size_t)nb * c->C * S.capw * 4));
+    WN_HIP(c, hipMalloc((void**)&S.cbt, (size_t)c->NT * c->C * 2));
+    WN_HIP(c, hipMalloc((void**)&S.feat, (size_t)c->NT * c->C * 4));
+    WN_HIP(c, hipMalloc((void**)&S.carry, 32 * 4));
+    WN_HIP(c, hipMalloc((void**)&S.tdev, 128 * 4));
+    if (c->gin > 0) WN_HIP(c, hipMalloc((void**)&S.gbias, (size_t)c->L * nb * c->G * 4));
+    return WN_OK;
+}
+static void slots_free(wn_ctx* c) {
+    auto& S = c->slots;
+    for (float* q : S.pend) if (q) hipFree(q);
+    if (S.gwin) hipFree(S.gwin); if (S.cbt) hipFree(S.cbt); if (S.feat) hipFree(S.feat); if (S.carry) hipFree(S.carry); if (S.tdev) hipFree(S.tdev); if (S.gbias) hipFree(S.gbias);
+}
+
+extern "C" int wn_synth_slots_begin(wn_ctx* c, int32_t B, int32_t steps_per_graph, void* stream) {
+    if (!c) return WN_E_ARG;
+    WnRange range("wn_synth_slots_begin");
+    auto& S = c->slots;
+    S.open = false; c->strm.open = false;                 // a slot session and a stream exclude one another
+    if (c->cfg.compute_dtype == WN_COMPUTE_F32) WN_FAIL(c, WN_E_UNSUPPORTED, "wn_synth_slots_begin: slot sessions are not built for the fp32 validation mode (compute_dtype = WN_COMPUTE_F32)");
+    if (!c->packed) WN_FAIL(c, WN_E_STATE, "wn_pack_weights must be called before wn_synth_slots_begin");
+    if (B <= 0 || B > 32 || B > c->maxB) WN_FAIL(c, WN_E_SHAPE, "slot count %d outside (0, min(32, max_batch = %d)]", B, c->maxB);
+    int rc = wn_pipe_check(c, false);
+    if (rc) return rc;
+    const int path = wn_synth_takes_pipe(c, B, steps_per_graph) ? 2 : 1;
+    if ((rc = wn_noise_reserve(c, B, c->maxT))) return rc;
+    if ((rc = path == 2 ? wn_pipe_reserve(c, B, c->maxT) : wn_synth_reserve(c))) return rc;
+    if ((rc = slots_alloc(c))) return rc;
+    wn_synth_stream_lookahead(&c->cfg, &S.left, &S.right);
+    WN_HIP(c, hipMemsetAsync(S.tdev, 0, 128 * 4, (hipStream_t)stream));
+    S.B = B; S.spg = steps_per_graph; S.path = path; S.poisoned = false; S.first_run = true;
+    for (auto& s : S.s) s = wn_ctx::WnSlots::Slot();
+    S.open = true;
+    return WN_OK;
+}
+
+static int slots_usable(wn_ctx* c, const char* who) {
+    auto& S = c->slots;
+    if (!S.open) WN_FAIL(c, WN_E_STATE, "%s: no open slot session (never begun, or ended by wn_synthesize / wn_pack_weights / wn_synth_pipe_dtype / wn_synth_stream_begin)", who);
+    if (S.poisoned) WN_FAIL(c, WN_E_STATE, "%s: a pipeline run of this session failed (wn_synth_check); begin a new session", who);
+    return WN_OK;
+}
+
+extern "C" int wn_synth_slot_open(wn_ctx* c, int32_t slot, uint64_t seed, const void* g, void* stream) {
+    if (!c) return WN_E_ARG;
+    int rc = slots_usable(c, "wn_synth_slot_open");
+    if (rc) return rc;
+    auto& S = c->slots;
+    if (slot < 0 || slot >= S.B) WN_FAIL(c, WN_E_ARG, "wn_synth_slot_open: slot %d outside [0, %d)", slot, S.B);
+    if ((c->gin > 0) != (g != nullptr)) WN_FAIL(c, WN_E_ARG, "wn_synth_slot_open: g must be given iff the model has global conditioning (gin_channels = %d)", c->gin);
+    if (S.s[slot].live) WN_FAIL(c, WN_E_STATE, "wn_synth_slot_open: slot %d carries an utterance (finish it with a final push or wn_synth_slot_abandon)", slot);
+    if (c->gin > 0 && (rc = wn_gbias_row(c, g, S.gbias, S.B, slot, (hipStream_t)stream))) return rc;
+    auto& s = S.s[slot];
+    s = wn_ctx::WnSlots::Slot(); s.live = true; s.seed = seed;
+    return WN_OK;
+}
+
+extern "C" int wn_synth_slot_abandon(wn_ctx* c, int32_t slot) {
+    if (!c) return WN_E_ARG;
+    int rc = slots_usable(c, "wn_synth_slot_abandon");
+    if (rc) return rc;
+    if (slot < 0 || slot >= c->slots.B) WN_FAIL(c, WN_E_ARG, "wn_synth_slot_abandon: slot %d outside [0, %d)", slot, c->slots.B);
+    c->slots.s[slot].live = false;
+    return WN_OK;
+}
+
+extern "C" int wn_synth_slot_frames_done(const wn_ctx* c, int32_t slot) {
+    if (!c) return WN_E_ARG;
+    if (!c->slots.open || c->slots.poisoned) return WN_E_STATE;
+    if (slot < 0 || slot >= c->slots.B) return WN_E_ARG;
+    return c->slots.s[slot].live ? (int)c->slots.s[slot].done : -1;
+}
+
+extern "C" int wn_synth_slots_end(wn_ctx* c) {
+    if (!c) return WN_E_ARG;
+    c->slots.open = false;
+    return WN_OK;
+}
+
+// every rebuilt slot's pending window in ONE launch: [C][w] dense = the kept columns of its previous window + its leading frames of the pushed block
+struct WnSlotWin { int32_t prev_cols[32], drop[32], keep[32], w[32], cur[32]; };
+__global__ void wn_slots_window_kernel(const float* __restrict__ p0, const float* __restrict__ p1, float* __restrict__ q0, float* __restrict__ q1, int64_t region,
+                                       const float* __restrict__ cnew, int Tn, int C, WnSlotWin p) {
+    const int b = blockIdx.y, w = p.w[b];
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (w <= 0 || i >= (int64_t)C * w) return;
+    const int64_t row = i / w, col = i - row * w;
+    const float* prev = (p.cur[b] ? p1 : p0) + region * b;
+    float* win = (p.cur[b] ? q0 : q1) + region * b;
+    win[i] = col < p.keep[b] ? prev[row * p.prev_cols[b] + p.drop[b] + col] : cnew[((int64_t)b * C + row) * Tn + (col - p.keep[b])];
+}
+// the windows of a group of slots side by side [g][C][w] (the upsample net takes a batch of equal width), and back: the rows of every member's span out of
+// the group's upsampled conditioning into the session's table cbt [B][n_max][C] (bf16) / feat [B][C][n_max] (fp32)
+struct WnSlotGrp { int32_t slot[32], cur[32], off[32], n[32]; };
+__global__ void wn_slots_gather_kernel(const float* __restrict__ p0, const float* __restrict__ p1, int64_t region, float* __restrict__ gwin, int64_t cw, WnSlotGrp p) {
+    const int g = blockIdx.y;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cw) return;
+    gwin[(int64_t)g * cw + i] = ((p.cur[g] ? p1 : p0) + region * p.slot[g])[i];
+}
+__global__ void wn_slots_scatter_kernel(const bf16_t* __restrict__ cbt, const float* __restrict__ cup, int64_t Tw, int C, bf16_t* __restrict__ scbt, float* __restrict__ feat,
+                                        int64_t n_max, WnSlotGrp p) {
+    const int g = blockIdx.y, n = p.n[g], b = p.slot[g];
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)n * C) return;
+    { const int64_t t = i / C, ch = i - t * C; scbt[((int64_t)b * n_max + t) * C + ch] = cbt[((int64_t)g * Tw + p.off[g] + t) * C + ch]; }
+    { const int64_t ch = i / n, t = i - ch * n; feat[((int64_t)b * C + ch) * n_max + t] = cup[((int64_t)g * C + ch) * Tw + p.off[g] + t]; }
+}
+
+extern "C" int wn_synth_slots_push(wn_ctx* c, const float* cc, int32_t Tn, const int32_t* frames, const int32_t* final_, const float* noise, const void* test_inputs,
+                                   void* out_samples, float* out_raw, int32_t out_pitch, int32_t* n_out, void* stream) {
+    if (!c) return WN_E_ARG;
+    WnRange range("wn_synth_slots_push");
+    int rc = slots_usable(c, "wn_synth_slots_push");
+    if (rc) return rc;
+    auto& S = c->slots;
+    if (Tn < 0 || (Tn > 0 && !cc) || !frames || !final_ || !n_out) WN_FAIL(c, WN_E_ARG, "wn_synth_slots_push: bad frames (Tn = %d) or a null host array", Tn);
+    if ((rc = wn_pipe_check(c, false))) return rc;       // a failed earlier push surfaces here at the latest (and poisons the session)
+    if (S.poisoned) WN_FAIL(c, WN_E_STATE, "wn_synth_slots_push: a pipeline run of this session failed; begin a new session");
+    const int B = S.B, hop = c->hop, C = c->C;
+    // ---- plan (host only: a rejected push leaves every slot as it was)
+    int64_t pushed[32], gen_end[32], wstart[32], w[32]; int nb[32]; int n_max = 0;
+    for (int b = 0; b < B; ++b) {
+        const auto& s = S.s[b];
+        nb[b] = 0; w[b] = 0; pushed[b] = s.pushed; gen_end[b] = s.done; wstart[b] = s.pend_first;
+        if (frames[b] < 0 || frames[b] > Tn) WN_FAIL(c, WN_E_ARG, "wn_synth_slots_push: frames[%d] = %d outside [0, Tn = %d]", b, frames[b], Tn);
+        if (!s.live) { if (frames[b] > 0) WN_FAIL(c, WN_E_STATE, "wn_synth_slots_push: %d frames for slot %d, which is idle (wn_synth_slot_open first)", frames[b], b); continue; }
+        pushed[b] = s.pushed + frames[b];
+        gen_end[b] = final_[b] ? pushed[b] : std::max(s.done, pushed[b] - S.right);
+        const int64_t n = (gen_end[b] - s.done) * hop;
+        wstart[b] = std::max<int64_t>(0, s.done - S.left); w[b] = pushed[b] - wstart[b];
+        if (n > c->maxT) WN_FAIL(c, WN_E_SHAPE, "wn_synth_slots_push: %lld samples for slot %d in one push exceed max_time = %d", (long long)n, b, c->maxT);
+        if (w[b] > S.capw || (n > 0 && w[b] * hop > c->NT))
+            WN_FAIL(c, WN_E_SHAPE, "wn_synth_slots_push: slot %d: a window of %lld frames (%d of left context + the frames not yet generated) exceeds the workspace", b, (long long)w[b], S.left);
+        if (s.done * hop + n > INT32_MAX) WN_FAIL(c, WN_E_SHAPE, "wn_synth_slots_push: utterance longer than 2^31 samples");
+        nb[b] = (int)n; n_max = std::max(n_max, nb[b]);
+    }
+    if (n_max > 0 && (!out_samples || out_pitch < n_max)) WN_FAIL(c, WN_E_ARG, "wn_synth_slots_push: null out_samples or out_pitch %d < %d samples", out_pitch, n_max);
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t region = (int64_t)C * S.capw;
+    S.poisoned = true;                                    // (the state advances only once everything is enqueued; a failure after the first enqueue poisons the session)
+    // ---- pending windows of the slots that received frames or dropped generated ones
+    bool rebuilt[32] = {};
+    {
+        WnSlotWin p; memset(&p, 0, sizeof p); int64_t wmax = 0;
+        for (int b = 0; b < B; ++b) {
+            const auto& s = S.s[b];
+            if (!s.live || w[b] <= 0 || (frames[b] == 0 && wstart[b] == s.pend_first)) continue;
+            p.prev_cols[b] = (int)(s.pushed - s.pend_first); p.drop[b] = (int)(wstart[b] - s.pend_first); p.keep[b] = (int)(s.pushed - wstart[b]); p.w[b] = (int)w[b]; p.cur[b] = s.cur;
+            rebuilt[b] = true; wmax = std::max(wmax, w[b]);
+        }
+        if (wmax > 0) {
+            hipLaunchKernelGGL(wn_slots_window_kernel, dim3(cdiv(C * wmax, 256), B), dim3(256), 0, st, S.pend[0], S.pend[1], S.pend[0], S.pend[1], region, cc, Tn, C, p);
+            WN_LAUNCH_CHECK(c);
+        }
+    }
+    if (n_max > 0) {
+        // ---- conditioning (wavenet.py:781-803): slots of equal window width are upsampled as one batch; every window starts at its utterance's own frame
+        // max(0, done - left) and ends at its own last pushed frame, so an edge is either the utterance's own or outside what the lookahead lets a span read
+        bool grouped[32] = {};
+        for (int b0 = 0; b0 < B; ++b0) {
+            if (nb[b0] <= 0 || grouped[b0]) continue;
+            const int64_t gw = w[b0];
+            const int gcap = (int)std::max<int64_t>(1, std::min<int64_t>(32, c->NT / (gw * hop)));
+            WnSlotGrp g; memset(&g, 0, sizeof g); int ng = 0; int nmaxg = 0;
+            for (int b = b0; b < B && ng < gcap; ++b) {
+                if (nb[b] <= 0 || grouped[b] || w[b] != gw) continue;
+                grouped[b] = true;
+                g.slot[ng] = b; g.cur[ng] = S.s[b].cur ^ (rebuilt[b] ? 1 : 0); g.off[ng] = (int)((S.s[b].done - wstart[b]) * hop); g.n[ng] = nb[b]; nmaxg = std::max(nmaxg, nb[b]); ++ng;
+            }
+            hipLaunchKernelGGL(wn_slots_gather_kernel, dim3(cdiv(C * gw, 256), ng), dim3(256), 0, st, S.pend[0], S.pend[1], region, S.gwin, C * gw, g);
+            WN_LAUNCH_CHECK(c);
+            if ((rc = wn_upsample_fwd(c, nullptr, S.gwin, ng, (int)gw, st))) return rc;
+            hipLaunchKernelGGL(wn_slots_scatter_kernel, dim3(cdiv((int64_t)nmaxg * C, 256), ng), dim3(256), 0, st, c->cbt, c->CUP[c->cup_final_idx], gw * hop, C, S.cbt, S.feat,
+                               (int64_t)n_max, g);
+            WN_LAUNCH_CHECK(c);
+        }
+        if (!noise) {      // every generating slot's own one-stream noise, continued at its sample done * hop
+            uint64_t seed[32]; int64_t first[32], cnt[32]; const int nps = wn_noise_per_step(c);
+            for (int b = 0; b < B; ++b) { seed[b] = S.s[b].seed; first[b] = S.s[b].done * hop * nps; cnt[b] = (int64_t)nb[b] * nps; }
+            if ((rc = wn_fill_noise_slots(c, c->noise_buf, B, seed, first, cnt, st))) return rc;
+            noise = c->noise_buf;
+        }
+        int32_t st0[32], snl[32]; uint32_t fresh = 0;
+        for (int b = 0; b < 32; ++b) { st0[b] = b < B ? (int)(S.s[b].done * hop) : 0; snl[b] = b < B ? nb[b] : 0; if (b < B && nb[b] > 0 && S.s[b].done == 0) fresh |= 1u << b; }
+        WnSpan sp;
+        sp.t0 = 0; sp.Tcb = n_max; sp.cbt_off = 0; sp.carry = S.carry; sp.gbias = S.gbias;
+        sp.st0 = st0; sp.snl = snl; sp.out_pitch = out_pitch; sp.cbt = S.cbt; sp.reslice = S.first_run; sp.tdev = S.tdev; sp.fresh = fresh;
+        rc = S.path == 2 ? wn_pipe_span(c, B, n_max, sp, noise, test_inputs, out_samples, out_raw, st)
+                         : wn_synth_span(c, B, n_max, sp, noise, test_inputs, out_samples, out_raw, S.spg, st);
+        if (rc) return rc;
+        S.first_run = false;
+        c->fB = B; c->fT = n_max; c->fTc = 0; c->fup_pitch = -1; S.feat_pitch = n_max; S.feat_B = B;
+    }
+    S.poisoned = false;
+    for (int b = 0; b < B; ++b) {
+        auto& s = S.s[b];
+        n_out[b] = nb[b];
+        if (!s.live) continue;
+        if (rebuilt[b]) { s.cur ^= 1; s.pend_first = wstart[b]; }
+        s.pushed = pushed[b]; s.done = gen_end[b];
+        if (final_[b]) s.live = false;
+    }
     return WN_OK;
 }

@@ -211,12 +211,31 @@ struct wn_ctx {
         float* gbias = nullptr;                                        // [L][B][G] (gin > 0)
         int32_t* carry = nullptr;                                      // [32] fed-back sample bits / class id of every stream (pipeline)
     } strm;
+    // synthesis slots (wn_synth_slots_*): B slots served by one pipeline configuration; every slot is idle or carries ONE utterance with its own
+    // time origin, seed, global condition and pending window of mel frames ([C][pushed - pend_first] dense, in the slot's region of pend[cur]).
+    // Everything the session needs is sized by slots_alloc (wn_create on inference-only contexts): nothing is allocated by a push.
+    struct WnSlots {
+        bool open = false, poisoned = false; int path = 0, B = 0, spg = 0, left = 0, right = 0, capw = 0; bool first_run = true;
+        struct Slot { bool live = false; uint64_t seed = 0; int64_t pushed = 0, done = 0, pend_first = 0; int cur = 0; } s[32];
+        float* pend[2] = {nullptr, nullptr};      // [32 regions][C * capw] pending frames of every slot (ping-pong per slot)
+        float* gwin = nullptr;                    // [group][C][w]: the windows of the slots upsampled together (equal window width)
+        bf16_t* cbt = nullptr;                    // [B][n_max][C]: the conditioning rows every slot's steps of this push read
+        float* feat = nullptr;                    // [B][C][n_max] fp32: the same rows as wn_get_upsampled_features returns them
+        float* gbias = nullptr;                   // [L][B][G] gate-bias row of every slot (gin > 0), written at wn_synth_slot_open
+        int32_t* carry = nullptr;                 // [32] the pipeline's carried next input per slot
+        int32_t* tdev = nullptr;                  // launch-per-layer path: [0..31] absolute index of every slot's next sample, [32..63] samples it generates in this push, [64] push-local step
+        int64_t feat_pitch = 0; int feat_B = 0;
+    } slots;
     int64_t fup_off = 0, fup_pitch = 0;   // wn_get_upsampled_features after a push: the span's columns [fup_off, fup_off + fT) of rows of fup_pitch
 };
 
 // one push of a stream as the synthesis paths see it: absolute first sample t0, span length T, conditioning rows cbt[b][cbt_off + t] of a
 // window of Tcb rows per stream, the stream's carry / bias; t0 == 0 starts from silence and zero queues exactly as wn_synthesize does
-struct WnSpan { int t0, Tcb, cbt_off; int32_t* carry; const float* gbias; };
+// A push of a slot session (st0 != nullptr): stream s starts at ITS absolute index st0[s] (0: silence, no past), generates snl[s] <= T samples and
+// takes part in the remaining T - snl[s] steps as a dummy that writes nothing; outputs have a row pitch of out_pitch samples; cbt is the session's
+// own table [B][Tcb][C]; reslice: first run of the session (the pipeline builds its weight images)
+struct WnSpan { int t0, Tcb, cbt_off; int32_t* carry; const float* gbias;
+                const int32_t* st0 = nullptr; const int32_t* snl = nullptr; int out_pitch = 0; const bf16_t* cbt = nullptr; bool reslice = false; int32_t* tdev = nullptr; uint32_t fresh = 0; };
 
 extern std::string g_create_err;
 
@@ -245,6 +264,9 @@ int wn_synth_f32_span(wn_ctx* ctx, int B, int T, const WnSpan& sp, const float* 
 int wn_pipe_span(wn_ctx* ctx, int B, int T, const WnSpan& sp, const float* noise, const void* test_inputs, void* out_samples, float* out_raw,
                  hipStream_t st);
 int wn_fill_noise_span(wn_ctx* ctx, float* noise, int64_t first, int64_t n, uint64_t seed, hipStream_t st);   // elements [first, first + n) of the flat stream
+// column b of noise [n_max][B][nps] = elements [first[b], first[b] + cnt[b]) of the ONE-stream noise of seed[b] (wn_fill_noise(B = 1)), every b with cnt[b] > 0 in one launch
+int wn_fill_noise_slots(wn_ctx* ctx, float* noise, int B, const uint64_t* seed, const int64_t* first, const int64_t* cnt, hipStream_t st);
+int wn_gbias_row(wn_ctx* ctx, const void* g_dev, float* table, int B, int slot, hipStream_t st);      // one slot's gate-bias row into table [L][B][G]
 void wn_synth_free(wn_ctx* ctx);
 void wn_synth_f32_free(wn_ctx* ctx);
 int wn_synth_f32_reserve(wn_ctx* ctx, int B);

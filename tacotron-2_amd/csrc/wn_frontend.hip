@@ -702,3 +702,24 @@ int wn_gin_bwd(wn_ctx* c, float* grads, hipStream_t st, bool have_colsum) {
     WN_LAUNCH_CHECK(c);
     return WN_OK;
 }
+
+// Slot sessions: the gate-bias row of ONE slot (its utterance's global condition, given at wn_synth_slot_open) into the session's own table [L][B][G];
+// the same arithmetic, in the same order, as wn_gbias_kernel computes for row b of a batch.
+__global__ void wn_gbias_row_kernel(const float* __restrict__ params, const float* __restrict__ b1sum, const void* __restrict__ g, int64_t emb_off, int n_speakers,
+                                    float* __restrict__ table, int B, int slot, int G, int gin, GinOff o) {
+    const int gi = blockIdx.x * blockDim.x + threadIdx.x, l = blockIdx.y;
+    if (gi >= G) return;
+    const float* gv = (const float*)g;
+    if (emb_off >= 0) { int id = *(const int32_t*)g; id = id < 0 ? 0 : (id >= n_speakers ? n_speakers - 1 : id); gv = params + emb_off + (int64_t)id * gin; }
+    float a = b1sum[(size_t)l * G + gi] + params[o.b[l] + gi];
+    const float* W = params + o.k[l];
+    for (int k = 0; k < gin; ++k) a += gv[k] * W[(int64_t)k * G + gi];
+    table[((size_t)l * B + slot) * G + gi] = a;
+}
+int wn_gbias_row(wn_ctx* c, const void* g_dev, float* table, int B, int slot, hipStream_t st) {
+    GinOff o; for (int l = 0; l < c->L; ++l) { o.k[l] = c->lay[l].gin_k; o.b[l] = c->lay[l].gin_b; }
+    hipLaunchKernelGGL(wn_gbias_row_kernel, dim3(cdiv(c->G, 256), c->L), dim3(256), 0, st, c->params_dev, c->b1sum, g_dev, c->cfg.use_speaker_embedding ? c->emb_off : (int64_t)-1,
+                       c->cfg.n_speakers, table, B, slot, c->G, c->gin, o);
+    WN_LAUNCH_CHECK(c);
+    return WN_OK;
+}

@@ -411,3 +411,35 @@ int wn_fill_noise_span(wn_ctx* c, float* noise, int64_t first, int64_t n, uint64
     WN_LAUNCH_CHECK(c);
     return WN_OK;
 }
+
+// Slot sessions: every slot draws from ITS OWN one-stream noise (seed_b, element t_local * nps + j: exactly wn_fill_noise(B = 1, seed_b)), written into column b of
+// the push's [n_max][B][nps] buffer.  Thread (x, b) evaluates one whole Philox group of slot b's stream -- Box-Muller pairs follow the one-stream numbering, not
+// the batch layout -- and keeps the elements of the span [first_b, first_b + cnt_b).  Slots that generate nothing (cnt 0) leave their column as it is.
+struct WnNoiseSlots { uint32_t k0[32], k1[32]; int64_t first[32], cnt[32]; };
+__global__ void wn_noise_slots_kernel(float* __restrict__ out, int B, int nps, int gaussian, WnNoiseSlots p) {
+    const int b = blockIdx.y;
+    const int64_t first = p.first[b], n = p.cnt[b];
+    const int64_t g = first / 4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (n <= 0 || g * 4 >= first + n) return;
+    float v[4];
+    wn_noise_group(g, p.k0[b], p.k1[b], gaussian, v);
+    for (int j = 0; j < 4; ++j) {
+        const int64_t e = g * 4 + j;
+        if (e < first || e >= first + n) continue;
+        const int64_t le = e - first, tl = le / nps, q = le - tl * nps;      // (first is a multiple of nps: a span starts on a sample)
+        out[(tl * B + b) * nps + q] = v[j];
+    }
+}
+int wn_fill_noise_slots(wn_ctx* c, float* noise, int B, const uint64_t* seed, const int64_t* first, const int64_t* cnt, hipStream_t st) {
+    WnNoiseSlots p; memset(&p, 0, sizeof p);
+    int64_t groups = 0;
+    for (int b = 0; b < B; ++b) {
+        p.k0[b] = (uint32_t)seed[b]; p.k1[b] = (uint32_t)(seed[b] >> 32); p.first[b] = first[b]; p.cnt[b] = cnt[b];
+        if (cnt[b] > 0) groups = std::max<int64_t>(groups, (first[b] + cnt[b] + 3) / 4 - first[b] / 4);
+    }
+    if (groups == 0) return WN_OK;
+    const int gaussian = (c->cfg.input_type != WN_INPUT_MULAW_QUANTIZE && c->O == 2) ? 1 : 0;
+    hipLaunchKernelGGL(wn_noise_slots_kernel, dim3(cdiv(groups, 256), B), dim3(256), 0, st, noise, B, wn_noise_per_step(c), gaussian, p);
+    WN_LAUNCH_CHECK(c);
+    return WN_OK;
+}

@@ -24,8 +24,14 @@ struct Synth {
     hipStream_t priv = nullptr;    // capture / replay happens on a ctx-owned stream (the caller's may be the legacy
     hipEvent_t ev0 = nullptr, ev1 = nullptr;   // NULL stream, which cannot be captured); ordered by events
     bf16_t** ring_tab = nullptr;   // device table of ring pointers
-    hipGraphExec_t gexec = nullptr; int g_steps = 0; int g_B = 0; const void* g_key[6] = {0, 0, 0, 0, 0, 0}; int g_T = 0, g_Tcb = 0;
+    hipGraphExec_t gexec = nullptr; int g_steps = 0; int g_B = 0; const void* g_key[7] = {0, 0, 0, 0, 0, 0, 0}; int g_T = 0, g_Tcb = 0;
+    // slot sessions: sl != nullptr while a push of a session is enqueued -- [0..31] absolute index of every stream's next sample, [32..63] samples it generates
+    // in this push, [64] push-local step.  A stream whose count is used up (or an idle slot) is a dummy for the rest of the push: its operand columns are
+    // zero, nothing of it is stored.  Values live in device memory, so captured graphs stay valid across pushes.
+    const int32_t* sl = nullptr;
 };
+#define WN_SL_N 32
+#define WN_SL_STEP 64
 
 __device__ __forceinline__ f32x16_t zero16() { f32x16_t z; for (int i = 0; i < 16; ++i) z[i] = 0.0f; return z; }
 
@@ -46,11 +52,13 @@ template <int NW>
 __global__ __launch_bounds__(NW * 64) void wn_synth_gate(const bf16_t* __restrict__ Apk, int ksteps, const bf16_t* __restrict__ ring, int mask,
                                                      int d, int R, const bf16_t* __restrict__ cbt, int C, int Tcb, int B,
                                                      const float* __restrict__ bias, int bias_bstride, int GH, bf16_t* __restrict__ ucur,
-                                                     const int32_t* __restrict__ t_dev, int kil) {
+                                                     const int32_t* __restrict__ t_dev, int kil, const int32_t* __restrict__ sl) {
     __shared__ float red[NW * 2 * 64 * 16];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int t = t_dev[0], tl = t - t_dev[1];      // absolute (queues) / span-local (conditioning rows cbt[n][tl], Tcb per stream)
     const int n = lane & 31, h = lane >> 5;
+    // absolute (queues) / span-local (conditioning rows cbt[n][tl], Tcb per stream); a slot session: both per stream, a dummy step multiplies zeros
+    const int t = sl ? sl[n] : t_dev[0], tl = sl ? sl[WN_SL_STEP] : t - t_dev[1];
+    const bool live = !sl || tl < sl[WN_SL_N + n];
     const int blk = blockIdx.x;
     f32x16_t acc0 = zero16(), acc1 = zero16();
     const bf16_t* A0 = Apk + ((size_t)(2 * blk) * ksteps * 64 + lane) * 8;
@@ -63,7 +71,7 @@ __global__ __launch_bounds__(NW * 64) void wn_synth_gate(const bf16_t* __restric
             bv[i] = make_uint4(0, 0, 0, 0); a0[i] = make_uint4(0, 0, 0, 0); a1[i] = make_uint4(0, 0, 0, 0);
             if (ks < ksteps) {
                 const int k0 = ks * 16 + h * 8;
-                if (n < B) {
+                if (n < B && live) {
                     if (k0 < 3 * R) {
                         // K order of the pack: [tap0 | tap1 | tap2] or, interleaved in blocks of `kil` channels, [tap0 b0 | tap1 b0 | tap2 b0 | tap0 b1 | ...]
                         int j, r;
@@ -110,10 +118,10 @@ __global__ __launch_bounds__(NW * 64) void wn_synth_out(const bf16_t* __restrict
                                                     const bf16_t* __restrict__ ring_cur, int mask_cur,
                                                     bf16_t* __restrict__ ring_next, int mask_next,
                                                     float* __restrict__ skip_acc, int first_layer, int B,
-                                                    const int32_t* __restrict__ t_dev) {
+                                                    const int32_t* __restrict__ t_dev, const int32_t* __restrict__ sl) {
     __shared__ float red[NW * 64 * 16];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int t = *t_dev;
+    const int t0_ = sl ? 0 : *t_dev;
     const int n = lane & 31, h = lane >> 5;
     const int mt = blockIdx.x;
     const int nR = R >> 5;
@@ -150,6 +158,8 @@ __global__ __launch_bounds__(NW * 64) void wn_synth_out(const bf16_t* __restrict
             *p = first_layer ? v : (*p + v);
         } else {
             const int r = mt * 32 + ch;
+            const int t = sl ? sl[nn] : t0_;
+            if (sl && sl[WN_SL_STEP] >= sl[WN_SL_N + nn]) continue;      // a dummy step writes no queue row
             const float x = bf2f(ring_cur[((size_t)(t & mask_cur) * 32 + nn) * R + r]);
             ring_next[((size_t)(t & mask_next) * 32 + nn) * R + r] = f2bf((v + out_bias[r] + x) * rho);
         }
@@ -220,12 +230,16 @@ __global__ __launch_bounds__(256) void wn_synth_sample(const float* __restrict__
                                                        const float* __restrict__ noise, const void* __restrict__ test_inputs,
                                                        void* __restrict__ out_samples, float* __restrict__ out_raw,
                                                        const float* __restrict__ Wf, const float* __restrict__ bf_, int R,
-                                                       bf16_t* __restrict__ ring0, int mask0, int B, int T, int32_t* __restrict__ t_dev) {
+                                                       bf16_t* __restrict__ ring0, int mask0, int B, int T, int32_t* __restrict__ t_dev, int32_t* __restrict__ sl) {
     __shared__ float nxt_f[32];
     __shared__ int nxt_i[32];
+    __shared__ int t_n[32];
+    __shared__ int live_n[32];
     const int tid = threadIdx.x;
-    const int t = t_dev[0], tl = t - t_dev[1];      // ring slots by the absolute index; noise, teacher forcing and outputs [.., T] by the span's
-    if (tid < B) {
+    const int t = sl ? 0 : t_dev[0], tl = sl ? sl[WN_SL_STEP] : t - t_dev[1];      // ring slots by the absolute index; noise, teacher forcing and outputs [.., T] by the span's
+    if (tid < 32) { t_n[tid] = sl ? sl[tid] : t; live_n[tid] = !sl || tl < sl[WN_SL_N + tid]; }      // (a slot session: per stream; T is then the row pitch of the outputs)
+    __syncthreads();
+    if (tid < B && live_n[tid]) {
         const int n = tid;
         const float* p = yraw + (size_t)n * OP;
         const float* nz = noise + ((size_t)tl * B + n) * nps;
@@ -251,16 +265,18 @@ __global__ __launch_bounds__(256) void wn_synth_sample(const float* __restrict__
             nxt_f[n] = test_inputs ? ((const float*)test_inputs)[(size_t)n * T + tl] : x;
         }
     }
-    if (out_raw) for (int o = tid; o < B * O; o += 256) { const int n = o / O, oc = o - n * O; out_raw[((size_t)n * O + oc) * T + tl] = yraw[(size_t)n * OP + oc]; }
+    if (out_raw) for (int o = tid; o < B * O; o += 256) { const int n = o / O, oc = o - n * O; if (live_n[n]) out_raw[((size_t)n * O + oc) * T + tl] = yraw[(size_t)n * OP + oc]; }
     __syncthreads();
     // input convolution for step t+1 into ring 0
     for (int o = tid; o < B * R; o += 256) {
         const int n = o / R, r = o - n * R;
+        if (!live_n[n]) continue;
         const float v = (mode == 2) ? Wf[(size_t)nxt_i[n] * R + r] + bf_[r] : Wf[r] * nxt_f[n] + bf_[r];
-        ring0[((size_t)((t + 1) & mask0) * 32 + n) * R + r] = f2bf(v);
+        ring0[((size_t)((t_n[n] + 1) & mask0) * 32 + n) * R + r] = f2bf(v);
     }
     __syncthreads();
-    if (tid == 0) *t_dev = t + 1;
+    if (sl) { if (tid < B && live_n[tid]) sl[tid] = t_n[tid] + 1; if (tid == 0) sl[WN_SL_STEP] = tl + 1; }
+    else if (tid == 0) *t_dev = t + 1;
 }
 
 // initial input (silence, wavenet.py:433-445) -> ring 0 slot 0; t = 0
@@ -272,6 +288,21 @@ __global__ void wn_synth_init(const float* __restrict__ Wf, const float* __restr
         ring0[((size_t)n) * R + r] = f2bf(v);
     }
     if (threadIdx.x == 0) { t_dev[0] = 0; t_dev[1] = 0; }
+}
+
+// a push of a slot session: the samples every stream generates, the push-local step, and for the slots opened with this push (bit n of `fresh`) the
+// input of their first step (silence) in ring 0 at THEIR index 0.  Nothing is cleared: a tap is valid iff t_n - k d >= 0, rows of an earlier occupant are unreachable.
+struct WnSlCounts { int32_t n[32]; };
+__global__ void wn_synth_slots_setup(const float* __restrict__ Wf, const float* __restrict__ bf_, int R, int mode, int start_id, bf16_t* __restrict__ ring0, int B,
+                                     int32_t* __restrict__ sl, WnSlCounts cnt, uint32_t fresh) {
+    for (int o = threadIdx.x; o < B * R; o += blockDim.x) {
+        const int n = o / R, r = o - n * R;
+        if (!((fresh >> n) & 1u)) continue;
+        const float v = (mode == 2) ? Wf[(size_t)start_id * R + r] + bf_[r] : bf_[r];
+        ring0[((size_t)n) * R + r] = f2bf(v);
+    }
+    if (threadIdx.x < 32) { sl[WN_SL_N + threadIdx.x] = threadIdx.x < B ? cnt.n[threadIdx.x] : 0; if ((fresh >> threadIdx.x) & 1u) sl[threadIdx.x] = 0; }
+    if (threadIdx.x == 0) sl[WN_SL_STEP] = 0;
 }
 
 void wn_synth_free(wn_ctx* c) {
@@ -293,13 +324,13 @@ static int enqueue_step(wn_ctx* c, Synth* s, const bf16_t* cbt, int Tcb, const f
         const int ksg = c->packs[l].w1.K >> 4, kso = GH >> 4;
         const float* gbias_l = c->gin > 0 ? gbias + (size_t)l * B * c->G : c->b1sum + (size_t)l * c->G;
 #define WN_LAUNCH_GATE(NW_) hipLaunchKernelGGL(wn_synth_gate<NW_>, dim3(GH / 32), dim3(NW_ * 64), 0, st, c->packs[l].w1.dev, ksg, s->ring[l], s->mask[l], \
-                           c->dil[l], R, cbt, C, Tcb, B, gbias_l, c->gin > 0 ? c->G : 0, GH, s->ucur, s->t_dev, c->packs[l].w1.kil)
+                           c->dil[l], R, cbt, C, Tcb, B, gbias_l, c->gin > 0 ? c->G : 0, GH, s->ucur, s->t_dev, c->packs[l].w1.kil, s->sl)
         if (ksg > 4 * WN_SYN_MAXK) WN_LAUNCH_GATE(8); else WN_LAUNCH_GATE(4);      // (16 waves = 1024 threads cap the kernel at 128 VGPRs: the up-front loads spill)
 #undef WN_LAUNCH_GATE
         const bool top = (l == L - 1);
 #define WN_LAUNCH_OUT(NW_) hipLaunchKernelGGL(wn_synth_out<NW_>, dim3(R / 32 + S / 32), dim3(NW_ * 64), 0, st, c->packs[l].wo.dev, c->packs[l].ws.dev, kso, R, S, s->ucur, GH, \
                            c->params_dev + c->lay[l].out_b, c->res_scale, s->ring[l], s->mask[l], top ? nullptr : s->ring[l + 1], top ? 0 : s->mask[l + 1], \
-                           s->skip_acc, l == 0 ? 1 : 0, B, s->t_dev)
+                           s->skip_acc, l == 0 ? 1 : 0, B, s->t_dev, s->sl)
         if (kso > 4 * WN_SYN_MAXK) WN_LAUNCH_OUT(8); else WN_LAUNCH_OUT(4);
 #undef WN_LAUNCH_OUT
     }
@@ -308,18 +339,19 @@ static int enqueue_step(wn_ctx* c, Synth* s, const bf16_t* cbt, int Tcb, const f
     const int mode = c->cfg.input_type == WN_INPUT_MULAW_QUANTIZE ? 2 : (c->O == 2 ? 1 : 0);
     const float lsmin = mode == 1 ? c->cfg.log_scale_min_gauss : c->cfg.log_scale_min;
     hipLaunchKernelGGL(wn_synth_sample, dim3(1), dim3(256), 0, st, s->yraw, c->O, c->OP, mode, wn_noise_per_step(c), lsmin, noise, test_inputs, out_samples, out_raw,
-                       c->params_dev + c->first.dil_k, c->params_dev + c->first.dil_b, R, s->ring[0], s->mask[0], B, T, s->t_dev);
+                       c->params_dev + c->first.dil_k, c->params_dev + c->first.dil_b, R, s->ring[0], s->mask[0], B, T, s->t_dev, const_cast<int32_t*>(s->sl));
     WN_LAUNCH_CHECK(c);
     return WN_OK;
 }
 
 // T steps from the current t_dev: graphs of steps_per_graph steps (reused while the pointers and sizes match), then single steps
 static int synth_steps(wn_ctx* c, Synth* s, const bf16_t* cbt, int Tcb, const float* gbias, const float* noise, const void* test_inputs, void* out_samples,
-                       float* out_raw, int steps_per_graph, hipStream_t st) {
-    const int T = s->T, B = s->B;
+                       float* out_raw, int steps_per_graph, hipStream_t st, int nsteps = -1) {
+    const int T = s->T, B = s->B;      // (T: the row pitch of the outputs the kernels index with; nsteps: steps to run, T unless a slot session says otherwise)
+    if (nsteps < 0) nsteps = T;
     int rc, done = 0;
-    if (steps_per_graph > 1 && T >= steps_per_graph) {
-        const void* key[6] = {noise, test_inputs, out_samples, out_raw, cbt, gbias};
+    if (steps_per_graph > 1 && nsteps >= steps_per_graph) {
+        const void* key[7] = {noise, test_inputs, out_samples, out_raw, cbt, gbias, s->sl};
         const bool reuse = s->gexec && s->g_steps == steps_per_graph && s->g_B == B && s->g_T == T && s->g_Tcb == Tcb && memcmp(key, s->g_key, sizeof key) == 0;
         if (!reuse) {
             if (s->gexec) { hipGraphExecDestroy(s->gexec); s->gexec = nullptr; }
@@ -334,9 +366,9 @@ static int synth_steps(wn_ctx* c, Synth* s, const bf16_t* cbt, int Tcb, const fl
             hipGraphDestroy(graph);
             s->g_steps = steps_per_graph; s->g_B = B; s->g_T = T; s->g_Tcb = Tcb; memcpy(s->g_key, key, sizeof key);
         }
-        for (; done + steps_per_graph <= T; done += steps_per_graph) WN_HIP(c, hipGraphLaunch(s->gexec, st));
+        for (; done + steps_per_graph <= nsteps; done += steps_per_graph) WN_HIP(c, hipGraphLaunch(s->gexec, st));
     }
-    for (; done < T; ++done) { rc = enqueue_step(c, s, cbt, Tcb, gbias, noise, test_inputs, out_samples, out_raw, st); if (rc) return rc; }
+    for (; done < nsteps; ++done) { rc = enqueue_step(c, s, cbt, Tcb, gbias, noise, test_inputs, out_samples, out_raw, st); if (rc) return rc; }
     return WN_OK;
 }
 
@@ -393,7 +425,7 @@ int wn_synth_impl(wn_ctx* c, const float* cin, int B, int Tc, const float* noise
     hipStream_t st = s->priv;
     WN_HIP(c, hipEventRecord(s->ev0, caller_st));
     WN_HIP(c, hipStreamWaitEvent(st, s->ev0, 0));
-    s->B = B; s->T = T;
+    s->B = B; s->T = T; s->sl = nullptr;
     c->fB = B; c->fT = T; c->fTc = Tc;
     // upsample the conditioning once for the whole utterance (wavenet.py:781-803); cbt[b*T+t][C]
     int rc = wn_upsample_fwd(c, nullptr, cin, B, Tc, st);
@@ -425,7 +457,20 @@ int wn_synth_span(wn_ctx* c, int B, int T, const WnSpan& sp, const float* noise,
     hipStream_t st = s->priv;
     WN_HIP(c, hipEventRecord(s->ev0, caller_st));
     WN_HIP(c, hipStreamWaitEvent(st, s->ev0, 0));
-    s->B = B; s->T = T;
+    s->B = B; s->T = T; s->sl = nullptr;
+    if (sp.st0) {      // a push of a slot session: T steps, every stream with its own index and count (device memory), outputs at a pitch of sp.out_pitch
+        const int mode = c->cfg.input_type == WN_INPUT_MULAW_QUANTIZE ? 2 : (c->O == 2 ? 1 : 0);
+        WnSlCounts cnt; for (int i = 0; i < 32; ++i) cnt.n[i] = i < B ? sp.snl[i] : 0;
+        hipLaunchKernelGGL(wn_synth_slots_setup, dim3(1), dim3(256), 0, st, c->params_dev + c->first.dil_k, c->params_dev + c->first.dil_b, R, mode, 127,
+                           s->ring[0], B, sp.tdev, cnt, sp.fresh);
+        WN_LAUNCH_CHECK(c);
+        s->sl = sp.tdev; s->T = sp.out_pitch;
+        if ((rc = synth_steps(c, s, sp.cbt, sp.Tcb, sp.gbias, noise, test_inputs, out_samples, out_raw, steps_per_graph, st, T))) { s->sl = nullptr; return rc; }
+        s->sl = nullptr;
+        WN_HIP(c, hipEventRecord(s->ev1, st));
+        WN_HIP(c, hipStreamWaitEvent(caller_st, s->ev1, 0));
+        return WN_OK;
+    }
     if (sp.t0 == 0) {
         for (int l = 0; l < L; ++l) WN_HIP(c, hipMemsetAsync(s->ring[l], 0, (size_t)(s->mask[l] + 1) * 32 * R * 2, st));
         const int mode = c->cfg.input_type == WN_INPUT_MULAW_QUANTIZE ? 2 : (c->O == 2 ? 1 : 0);

@@ -68,6 +68,11 @@ struct PipeArgs {
     // (conditioning rows, noise, teacher forcing, outputs, mailbox tags) is run-local; Tcb = conditioning rows per stream in cbt (== T for
     // wn_synthesize); carry [B]: the head leaves every stream's next input there (float bits / class id) and a run with t0 > 0 starts from it
     int32_t t0, Tcb; int32_t* carry;
+    // slot sessions (wn_synth_slots_push; the SLOT instantiations only): what is ONE scalar for a stream is per stream here -- st0[s] = absolute index of
+    // stream s's first sample of this run (0: a slot opened with this push: silence, no tap before its birth), snl[s] <= T = samples it generates; the steps
+    // t >= snl[s] (all of them for an idle slot) are DUMMY steps: they take part in every hand-off (tags stay uniform) on silence, invalid taps and a zero
+    // conditioning row, and write nothing -- no ring row, no carry, no output, no abort.  Outputs have a row pitch of out_pitch samples.
+    int32_t out_pitch; int32_t st0[32], snl[32];
 };
 
 // ---- granule I/O: 16 bytes, one write-through store / one L1-bypassing load ------------------------------------------
@@ -205,7 +210,7 @@ __global__ void wn_pipe_slice_kernel(const float* __restrict__ params, char* __r
 #define PIPE_SVC(k) do { } while (0)
 #define PIPE_SVC_T(k) do { } while (0)
 #endif
-template <int H, int MULTI, int BP, int SPEC>
+template <int H, int MULTI, int BP, int SPEC, int SLOT = 0>
 __global__ __launch_bounds__(PIPE_THREADS) void wn_synth_pipe_kernel(const PipeArgs a) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -229,10 +234,17 @@ __global__ __launch_bounds__(PIPE_THREADS) void wn_synth_pipe_kernel(const PipeA
     u32x4* const SM_ = a.SM + moff * PIPE_SG; u32x4* const SML_ = a.SML + moff * PIPE_SG;
     bf16_t* const ring_ = a.ring + (MULTI ? a.ring_unit * s0 : 0);                       // a.ring_off[l] is per STREAM: x B for this instance's layer offset
     const int Tcb = a.Tcb, t0 = a.t0;
+    const int OT = SLOT ? a.out_pitch : T;                                               // row pitch of the outputs / teacher-forcing inputs
+    // per-stream origin / length: lane i of every wave keeps stream i's pair in a VGPR, read with v_readlane (s is wave-uniform) -- no scalar memory
+    // load, hence no lgkmcnt wait, in the stream iteration (as kernel-argument loads they cost a session 0.8 us per sample at 1 stream, 2.5 at 20)
+    int v_st0 = 0, v_snl = 0;
+    if constexpr (SLOT) { const int i = min(s0 + (lane & 31), 31); v_st0 = a.st0[i]; v_snl = a.snl[i]; }
+    auto st0 = [&](int s) { if constexpr (SLOT) return __builtin_amdgcn_readlane(v_st0, s); else return t0; };
+    auto snl = [&](int s) { if constexpr (SLOT) return __builtin_amdgcn_readlane(v_snl, s); else return T; };
     const bf16_t* const cbt_ = a.cbt + (MULTI ? (int64_t)s0 * Tcb * C : 0);
-    const char* const ti_ = a.test_inputs ? (const char*)a.test_inputs + (MULTI ? (int64_t)s0 * T * 4 : 0) : nullptr;
-    char* const outs_ = (char*)a.out_samples + (MULTI ? (int64_t)s0 * T * 4 : 0);
-    float* const outr_ = a.out_raw ? a.out_raw + (MULTI ? (int64_t)s0 * a.O * T : 0) : nullptr;
+    const char* const ti_ = a.test_inputs ? (const char*)a.test_inputs + (MULTI ? (int64_t)s0 * OT * 4 : 0) : nullptr;
+    char* const outs_ = (char*)a.out_samples + (MULTI ? (int64_t)s0 * OT * 4 : 0);
+    float* const outr_ = a.out_raw ? a.out_raw + (MULTI ? (int64_t)s0 * a.O * OT : 0) : nullptr;
     const int32_t* const btab = a.block_tab + (MULTI ? inst * (a.L * P + 1) : 0);
 #ifdef WN_PIPE_SVC_BUILD
     const bool trace_on = a.trace && inst == 0;
@@ -329,7 +341,7 @@ __global__ __launch_bounds__(PIPE_THREADS) void wn_synth_pipe_kernel(const PipeA
             if (tid < 64) zpast[s * PIPE_ZS + tid] = zpart[tid] + zpart[64 + tid] + zpart[128 + tid] + zpart[192 + tid] + (a.gbias ? gb : zb[tid]);
             lds_barrier();
         };
-        if (t0 == 0) for (int s = 0; s < B; ++s) precompute(s, 0, false);      // (a resumed run pre-multiplies its first sample as a mid-run one: below)
+        if (!SLOT && t0 == 0) for (int s = 0; s < B; ++s) precompute(s, 0, false);      // (a resumed run pre-multiplies its first sample as a mid-run one: below)
         // Inside the sample loop the pre-multiplication is split (round 4): its ring reads -- rows written >= d samples ago, HBM latency
         // once the streams' queues exceed L2 -- are REQUESTED by wave 3 right after this CU published its x partial and CONSUMED after the
         // skip chain, so their latency lies under the skip matvec and the wait for the previous layer's running sum instead of in front of
@@ -342,10 +354,11 @@ __global__ __launch_bounds__(PIPE_THREADS) void wn_synth_pipe_kernel(const PipeA
             // wave-uniform parts as scalars, per-lane parts as 32-bit byte offsets (a ring of one stream is <= 8192 rows x R x 2 B; the conditioning of a
             // run is B x T x C x 2 B < 4 GB): a per-lane 64-bit multiply per candidate address cost this wave 0.35 us per stream
             const char* ringb = (const char*)(ring_ + a.ring_off[l] * B + ((int64_t)(j * B + s) * (mask + 1)) * R);
-            const int ta = t0 + tn;                                          // queues: absolute time; conditioning: this run's rows
+            const int ta = st0(s) + tn;                                      // queues: absolute time (per stream in a slot session); conditioning: this run's rows
+            const bool dead = SLOT && tn >= snl(s);                          // a dummy step: every tap invalid, a zero conditioning row
             const uint32_t row0 = (uint32_t)__builtin_amdgcn_readfirstlane(((ta - 2 * d) & mask) * R * 2), row1 = (uint32_t)__builtin_amdgcn_readfirstlane(((ta - d) & mask) * R * 2);
             const char* cb = (const char*)cbt_ + (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((s * Tcb + tn) * C) * 2;
-            const bool ok0 = ta - 2 * d >= 0, ok1 = ta - d >= 0 && !tap1_is_cur;
+            const bool ok0 = !dead && ta - 2 * d >= 0, ok1 = !dead && ta - d >= 0 && !tap1_is_cur;
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
                 const int i = lane + 64 * q, k = i * 8;
@@ -356,7 +369,7 @@ __global__ __launch_bounds__(PIPE_THREADS) void wn_synth_pipe_kernel(const PipeA
                 // global load on the layer CU's service path (profiles/r6i_pipe_svc_trace.txt)
                 const bool tap0 = k < R, is_tap = i < KR, is_cond = !is_tap && i < KP;
                 const char* src = is_tap ? ringb + (tap0 ? row0 + (uint32_t)k * 2 : row1 + (uint32_t)(k - R) * 2) : cb + (uint32_t)(k - 2 * R) * 2;
-                if ((is_tap && (tap0 ? ok0 : ok1)) || is_cond) ld_g16_nowait(dst, reinterpret_cast<const u32x4*>(src));
+                if ((is_tap && (tap0 ? ok0 : ok1)) || (is_cond && !dead)) ld_g16_nowait(dst, reinterpret_cast<const u32x4*>(src));
             }
         };
         auto pre_finish = [&](int s, int tn, bool tap1_is_cur) {
@@ -369,7 +382,7 @@ __global__ __launch_bounds__(PIPE_THREADS) void wn_synth_pipe_kernel(const PipeA
                     const int i = lane + 64 * q, k = i * 8;
                     if (i < KR) {
                         uint4 v = __builtin_bit_cast(uint4, q ? pf1 : pf0);
-                        if (k >= R && tap1_is_cur && t0 + tn - d >= 0) v = *reinterpret_cast<const uint4*>(xcur_b + (k - R));
+                        if (k >= R && tap1_is_cur && !(SLOT && tn >= snl(s)) && st0(s) + tn - d >= 0) v = *reinterpret_cast<const uint4*>(xcur_b + (k - R));
                         *reinterpret_cast<uint4*>(vec + k) = v;
                     } else if (i < KP) *reinterpret_cast<uint4*>(vec + k) = cvt8_bf16<H>(__builtin_bit_cast(uint4, q ? pf1 : pf0));      // the conditioning chunks
                 }
@@ -429,7 +442,7 @@ __global__ __launch_bounds__(PIPE_THREADS) void wn_synth_pipe_kernel(const PipeA
                 const int i = lane + 64 * q, k = i * 8;
                 if (i < KR) {
                     uint4 v = __builtin_bit_cast(uint4, q ? pf1 : pf0);
-                    if (k >= R && tap1_is_cur && t0 + tn - d >= 0) v = *reinterpret_cast<const uint4*>(xcur_b + (k - R));
+                    if (k >= R && tap1_is_cur && !(SLOT && tn >= snl(s)) && st0(s) + tn - d >= 0) v = *reinterpret_cast<const uint4*>(xcur_b + (k - R));
                     *reinterpret_cast<uint4*>(vb + k * 2) = v;
                 } else if (i < KP) *reinterpret_cast<uint4*>(vb + k * 2) = cvt8_bf16<H>(__builtin_bit_cast(uint4, q ? pf1 : pf0));
             }
@@ -533,10 +546,13 @@ __global__ __launch_bounds__(PIPE_THREADS) void wn_synth_pipe_kernel(const PipeA
         // A resumed run (t0 > 0): the first sample's pre-multiplication in the form every later one takes -- batched, or pre_issue / pre_finish -- so
         // that the samples are bit-identical to one run over the whole utterance (the prologue form above differs in the last bits).  Both past taps
         // come from the ring: the previous run's last iteration stored x(t0 - 1) there, the very bits a mid-run d = 1 layer reads from xcur_b.
-        if (t0 > 0) {
+        if (SLOT || t0 > 0) {
             for (int s = 0; s < B; ++s) { pre_issue(s, 0, false); if (BP) pre_stash(s, 0, false); else pre_finish(s, 0, false); }
             if (BP) pre_batch(0);
         }
+        // A slot session mixes both forms in one run: a slot opened with this push (st0 == 0) takes the prologue form of a one-shot run, AFTER the batch, which
+        // writes z_past for every column (its ring reads above were all invalid: rows of a previous occupant are unreachable, nothing is cleared)
+        if constexpr (SLOT) for (int s = 0; s < B; ++s) if (st0(s) == 0 && snl(s) > 0) precompute(s, 0, false);
         for (int t = 0; t < T; ++t) {
             const uint32_t want = (uint32_t)(t + 1);
             for (int s = 0; s < B; ++s) {
@@ -729,11 +745,11 @@ __global__ __launch_bounds__(PIPE_THREADS) void wn_synth_pipe_kernel(const PipeA
                 {
                     bf16_t* ringb = ring_ + a.ring_off[l] * B + ((int64_t)(j * B + s) * (mask + 1)) * R;
                     {   // (R / 8 <= 48 chunks: the first lanes of wave 0; the other waves issue the same store disabled)
-                        const bool en = tid < R / 8;
-                        st_buf16(poll_rsrc(ringb + (int64_t)((t0 + t) & mask) * R, R * 2), en ? tid * 16 : -1, __builtin_bit_cast(u32x4, *reinterpret_cast<const uint4*>(xcur_b + (en ? tid * 8 : 0))));
+                        const bool en = tid < R / 8 && (!SLOT || t < snl(s));                 // (a dummy step stores no ring row)
+                        st_buf16(poll_rsrc(ringb + (int64_t)((st0(s) + t) & mask) * R, R * 2), en ? tid * 16 : -1, __builtin_bit_cast(u32x4, *reinterpret_cast<const uint4*>(xcur_b + (en ? tid * 8 : 0))));
                     }
                     PIPE_SVC(9);
-                    if constexpr (H) {      // half has 5 exponent bits: a residual stream beyond 65504 became inf in the hand-off -- report it, do not synthesise garbage
+                    if (H && (!SLOT || t < snl(s))) {      // half has 5 exponent bits: a residual stream beyond 65504 became inf in the hand-off -- report it, do not synthesise garbage
                         for (int r = tid; r < R; r += PIPE_THREADS)      // (R <= 384 on the generic path: more channels than threads)
                             if (!(fabsf(xcur_f[r]) <= 65504.0f)) pipe_abort(abortf, 400 + l);
                     }
@@ -810,13 +826,14 @@ __global__ __launch_bounds__(PIPE_THREADS) void wn_synth_pipe_kernel(const PipeA
             }
             lds_barrier();
         };
-        if (t0 == 0) {
+        if (!SLOT && t0 == 0) {
             if (tid == 0) { nxt_f[0] = 0.0f; nxt_i[0] = a.start_id; }
             lds_barrier();
             for (int s = j; s < B; s += NH) publish_input(s, 0);          // head j of NH: the streams s = j (mod NH)
         } else {
             for (int s = j; s < B; s += NH) {                             // a resumed run: the inputs the previous run left (publish_input ends on a barrier)
-                if (tid == 0) { const int32_t v = a.carry[s0 + s]; nxt_f[0] = __int_as_float(v); nxt_i[0] = v; }
+                const bool resumed = !SLOT || (st0(s) > 0 && snl(s) > 0);      // (a slot session: a slot at its own t = 0 and a dummy start from silence)
+                if (tid == 0) { const int32_t v = resumed ? a.carry[s0 + s] : 0; nxt_f[0] = resumed ? __int_as_float(v) : 0.0f; nxt_i[0] = resumed ? v : a.start_id; }
                 lds_barrier();
                 publish_input(s, 0);
             }
@@ -825,12 +842,13 @@ __global__ __launch_bounds__(PIPE_THREADS) void wn_synth_pipe_kernel(const PipeA
         for (int t = 0; t < T; ++t) {
             const uint32_t want = (uint32_t)(t + 1);
             for (int s = j; s < B; s += NH) {
+                const bool act = !SLOT || t < snl(s);     // a dummy step of a slot session computes and publishes like any other and stores nothing
                 // (prefetch, off the critical path) this step's noise and teacher-forcing value
                 float nz_pre = 0.0f, ti_pre = 0.0f;       // nz_pre: lane i < M: -log(-log u1_i) (Gumbel); lane M: log u2 - log(1 - u2) (logistic)
                 if (mode == 0 && wave == 0) {
                     const int M = O / 3;
                     if (lane < a.nps) { const float uu = a.noise[((int64_t)t * Bn + s0 + s) * a.nps + lane]; nz_pre = (lane < M) ? -logf(-logf(uu)) : logf(uu) - logf(1.0f - uu); }
-                    if (ti_) ti_pre = ((const float*)ti_)[(int64_t)s * T + t];
+                    if (ti_) ti_pre = ((const float*)ti_)[(int64_t)s * OT + t];
                 }
                 // ---- total skip = sum of the P running sums that left the top layer (+ all skip biases), ReLU (wavenet.py:840)
                 {
@@ -911,7 +929,7 @@ __global__ __launch_bounds__(PIPE_THREADS) void wn_synth_pipe_kernel(const PipeA
                             const float ls = fmaxf(yraw[2 * M + bi], a.lsmin);
                             float x = yraw[M + bi] + expf(ls) * lgt;
                             x = fminf(fmaxf(x, -1.0f), 1.0f);
-                            ((float*)outs_)[(int64_t)s * T + t] = x;
+                            if (act) ((float*)outs_)[(int64_t)s * OT + t] = x;
                             nxt_f[0] = ti_ ? ti_pre : x;
                         }
                     }
@@ -920,8 +938,8 @@ __global__ __launch_bounds__(PIPE_THREADS) void wn_synth_pipe_kernel(const PipeA
                     if (mode == 2) {
                         float best = -INFINITY; int bi = 0;
                         for (int q = 0; q < O; ++q) { const float vv = yraw[q] - logf(-logf(nz[q])); if (vv > best) { best = vv; bi = q; } }
-                        ((int32_t*)outs_)[(int64_t)s * T + t] = bi;
-                        nxt_i[0] = ti_ ? ((const int32_t*)ti_)[(int64_t)s * T + t] : bi;
+                        if (act) ((int32_t*)outs_)[(int64_t)s * OT + t] = bi;
+                        nxt_i[0] = ti_ ? ((const int32_t*)ti_)[(int64_t)s * OT + t] : bi;
                     } else {
                         float x;
                         if (mode == 0) {
@@ -933,13 +951,16 @@ __global__ __launch_bounds__(PIPE_THREADS) void wn_synth_pipe_kernel(const PipeA
                             x = yraw[M + bi] + expf(ls) * (logf(u) - logf(1.0f - u));
                         } else x = yraw[0] + expf(fmaxf(yraw[1], a.lsmin)) * nz[0];
                         x = fminf(fmaxf(x, -1.0f), 1.0f);
-                        ((float*)outs_)[(int64_t)s * T + t] = x;
-                        nxt_f[0] = ti_ ? ((const float*)ti_)[(int64_t)s * T + t] : x;
+                        if (act) ((float*)outs_)[(int64_t)s * OT + t] = x;
+                        nxt_f[0] = ti_ ? ((const float*)ti_)[(int64_t)s * OT + t] : x;
                     }
                 }
-                if (outr_) for (int o = tid; o < O; o += PIPE_THREADS) outr_[((int64_t)s * O + o) * T + t] = yraw[o];
+                if (outr_ && act) for (int o = tid; o < O; o += PIPE_THREADS) outr_[((int64_t)s * O + o) * OT + t] = yraw[o];
                 lds_barrier();
-                if (a.carry && t + 1 == T && tid == 0) a.carry[s0 + s] = mode == 2 ? nxt_i[0] : __float_as_int(nxt_f[0]);      // the next run's first input
+                if (a.carry && t + 1 == snl(s) && tid == 0) a.carry[s0 + s] = mode == 2 ? nxt_i[0] : __float_as_int(nxt_f[0]);      // the next run's first input
+                if constexpr (SLOT) {      // the step after a slot's last one is a dummy: it starts from silence (the carry above keeps the real next input)
+                    if (t + 1 >= snl(s)) { if (tid == 0) { nxt_f[0] = 0.0f; nxt_i[0] = a.start_id; } lds_barrier(); }
+                }
                 if (trace_on && s == 0 && tid == 0 && t >= a.trace_t0 && t < a.trace_t0 + a.trace_n) a.trace[(size_t)(t - a.trace_t0) * 2 * (a.L + 2) + 2 * L + 2] = wall_clock64();
                 if (t + 1 < T) publish_input(s, t + 1);
                 if (trace_on && s == 0 && tid == 0 && t >= a.trace_t0 && t < a.trace_t0 + a.trace_n) a.trace[(size_t)(t - a.trace_t0) * 2 * (a.L + 2) + 2 * L + 3] = wall_clock64();
@@ -1214,7 +1235,8 @@ int wn_pipe_check(wn_ctx* c, bool wait) {
     const int32_t flag = *p->abort_host;
     if (flag != 0) {
         *p->abort_host = 0;
-        if (p->pending_stream && c->strm.open) c->strm.poisoned = true;      // every later push of this stream: WN_E_STATE until the next begin
+        if (p->pending_stream && c->strm.open) c->strm.poisoned = true;
+        if (p->pending_stream && c->slots.open) c->slots.poisoned = true;      // every later push of this stream: WN_E_STATE until the next begin
         (void)hipMemsetAsync(p->abort_dev + 1, 0, 4, p->priv);      // reported: the next runs start clean (ordered before them on the pipeline's stream)
         if (flag >= 400 && flag < 400 + 64)
             WN_FAIL(c, WN_E_HIP, "synthesis pipeline (fp16 storage): the residual stream of layer %d left the half-precision range (|x| > 65504); "
@@ -1243,7 +1265,7 @@ static int pipe_run(wn_ctx* c, const float* cin, int B, int T, int Tc, const WnS
     a.nps = wn_noise_per_step(c); a.lsmin = a.mode == 1 ? c->cfg.log_scale_min_gauss : c->cfg.log_scale_min; a.start_id = 127; a.spx = p->spx;
     a.slices = p->slices; a.layer_slice_bytes = p->layer_slice_bytes; a.head_slice_off = p->head_slice_off;
     // ---- slice images from the current parameters (cheap: 27 MB)
-    if (!sp || sp->t0 == 0) {
+    if (!sp || (sp->st0 ? sp->reslice : sp->t0 == 0)) {
         hipLaunchKernelGGL(wn_pipe_slice_kernel, dim3(p->nblocks), dim3(256), 0, st, c->params_dev, p->slices, p->jobs_dev, p->job_block0_dev, p->njobs, c->GH, p->f16 ? 1 : 0);
         WN_LAUNCH_CHECK(c);
         for (int l = 0; l < L; ++l) a.cin_b_off[l] = c->lay[l].cin_b;
@@ -1272,8 +1294,9 @@ static int pipe_run(wn_ctx* c, const float* cin, int B, int T, int Tc, const WnS
         if (c->gin > 0) { if ((rc = wn_gbias_fwd(c, B, st))) return rc; a.gbias = c->gbias; }      // wavenet.py:766-777
         a.cbt = c->cbt; a.t0 = 0; a.Tcb = T; a.carry = nullptr;
     } else {
-        a.cbt = c->cbt + (int64_t)sp->cbt_off * c->C; a.t0 = sp->t0; a.Tcb = sp->Tcb; a.carry = sp->carry;
+        a.cbt = (sp->cbt ? sp->cbt : c->cbt) + (int64_t)sp->cbt_off * c->C; a.t0 = sp->t0; a.Tcb = sp->Tcb; a.carry = sp->carry;
         if (c->gin > 0) a.gbias = sp->gbias;
+        if (sp->st0) { a.out_pitch = sp->out_pitch; for (int i = 0; i < 32; ++i) { a.st0[i] = i < B ? sp->st0[i] : 0; a.snl[i] = i < B ? sp->snl[i] : 0; } }
     }
     a.noise = noise; a.test_inputs = test_inputs; a.out_samples = out_samples; a.out_raw = out_raw;
     a.win_global = c->params_dev + c->first.dil_k; a.bin_global = c->params_dev + c->first.dil_b;
@@ -1320,7 +1343,11 @@ static int pipe_run(wn_ctx* c, const float* cin, int B, int T, int Tc, const WnS
 #define PK(h, m, b) {wn_synth_pipe_kernel<h, m, b, 0>, wn_synth_pipe_kernel<h, m, b, 1>, wn_synth_pipe_kernel<h, m, b, 2>}
         static const kern_t kerns[2][2][2][3] = {{{PK(0, 0, 0), PK(0, 0, 1)}, {PK(0, 1, 0), PK(0, 1, 1)}}, {{PK(1, 0, 0), PK(1, 0, 1)}, {PK(1, 1, 0), PK(1, 1, 1)}}};
 #undef PK
-        kern_t kern = kerns[p->f16 ? 1 : 0][ni > 1 ? 1 : 0][bp ? 1 : 0][spec];
+        // the slot form (per-stream time origin and length) is its own set of instantiations: the kernels above are what they were
+#define PK(h, m, b) {wn_synth_pipe_kernel<h, m, b, 0, 1>, wn_synth_pipe_kernel<h, m, b, 1, 1>, wn_synth_pipe_kernel<h, m, b, 2, 1>}
+        static const kern_t kerns_slot[2][2][2][3] = {{{PK(0, 0, 0), PK(0, 0, 1)}, {PK(0, 1, 0), PK(0, 1, 1)}}, {{PK(1, 0, 0), PK(1, 0, 1)}, {PK(1, 1, 0), PK(1, 1, 1)}}};
+#undef PK
+        kern_t kern = (sp && sp->st0 ? kerns_slot : kerns)[p->f16 ? 1 : 0][ni > 1 ? 1 : 0][bp ? 1 : 0][spec];
         c->synth_batchpre = bp ? 1 : 0;
         const int32_t cfgv[WN_SYNTH_CFG_N] = {2, ni, bp ? 1 : 0, spec, p->f16 ? 1 : 0, a.NH, a.early_from, a.abort_every, grid, Bmax};
         for (int i = 0; i < WN_SYNTH_CFG_N; ++i) c->synth_cfg[i] = cfgv[i];

@@ -81,6 +81,8 @@ TACOTRON_ONLY = dict(
 MI355 = dict(
     mi355_synthesis_chunk_frames=0,    # > 0: WaveNet.incremental (and so synthesize.py) generates through a stream, pushing this many mel frames at a
                                        # time (same samples, bit for bit); 0: one call for the whole utterance
+    mi355_synthesis_slots=0,           # N > 0: Synthesizer.synthesize sends all utterances of a call through ONE slot session of min(N, 32) slots (continuous
+                                       # batching: no padding to the longest utterance; tick = mi355_synthesis_chunk_frames or 8 frames); 0: padded batches
     mi355_steps_per_graph=0,       # synthesis path: 0 = the persistent dataflow pipeline (real time at 22.05 kHz) whenever the model fits it, else the
                                    # launch-per-layer path with 32 steps per hipGraph replay; N > 0 = that path with N steps per replay
     mi355_synthetic_data=False,    # train on LJSpeech-shaped synthetic tensors (no dataset on disk)

@@ -108,6 +108,12 @@ def load_library():
         'wn_synth_stream_begin': (ctypes.c_int, [vp, i32, u64, i32, vp]),
         'wn_synth_stream_push': (ctypes.c_int, [vp, vp, i32, i32, vp, vp, vp, vp, ctypes.POINTER(i32), vp]),
         'wn_synth_stream_end': (ctypes.c_int, [vp]),
+        'wn_synth_slots_begin': (ctypes.c_int, [vp, i32, i32, vp]),
+        'wn_synth_slot_open': (ctypes.c_int, [vp, i32, u64, vp, vp]),
+        'wn_synth_slots_push': (ctypes.c_int, [vp, vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), vp, vp, vp, vp, i32, ctypes.POINTER(i32), vp]),
+        'wn_synth_slot_abandon': (ctypes.c_int, [vp, i32]),
+        'wn_synth_slot_frames_done': (ctypes.c_int, [vp, i32]),
+        'wn_synth_slots_end': (ctypes.c_int, [vp]),
         'wn_sample': (ctypes.c_int, [vp, vp, i32, i32, vp, vp, vp]),
         'wn_mulaw': (ctypes.c_int, [vp, vp, i64, vp]),
         'wn_inv_mulaw': (ctypes.c_int, [vp, vp, i64, vp]),
@@ -360,6 +366,60 @@ class Engine:
         self._ok(self.lib.wn_synth_stream_push(self.h, _ptr(c), Tn, 1 if final else 0, _ptr(noise), _ptr(test_inputs), _ptr(out_samples),
                                                _ptr(out_raw), ctypes.byref(n), _stream()))
         return int(n.value)
+
+    # ---- synthesis slots (wn_synth_slots_*): B independent utterances that join and leave one running batch
+    def slots_begin(self, B, steps_per_graph=0):
+        """Open a session of B idle slots (path as synthesize(steps_per_graph) would take for B, kept for the session)."""
+        self._slots_B = None
+        self._ok(self.lib.wn_synth_slots_begin(self.h, int(B), int(steps_per_graph), _stream()))
+        self._slots_B = int(B)
+
+    def slot_open(self, slot, seed=0, g=None):
+        """The slot carries a new utterance from its own t = 0 with the next push.  g: this utterance's global condition, a CUDA tensor with one
+        int32 speaker id (use_speaker_embedding) or float32 [gin_channels]; None iff the model has no global conditioning."""
+        import torch
+        if g is not None:
+            g = g.contiguous()
+            _check(g, torch.int32 if self.cfg.use_speaker_embedding else torch.float32, 'g')
+            self._slot_g = getattr(self, '_slot_g', {})
+            self._slot_g[int(slot)] = g          # (the library reads it in stream order)
+        self._ok(self.lib.wn_synth_slot_open(self.h, int(slot), ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), _ptr(g), _stream()))
+
+    def slots_push(self, c, frames, final, out_samples, out_raw=None, noise=None, test_inputs=None):
+        """c [B, cin, Tn] (None: no frames); frames[b] leading frames of row b go to slot b, final[b]: its utterance ends.  out_samples
+        [B, pitch] / out_raw [B, O, pitch] / test_inputs [B, pitch] (contiguous); returns the list n_out[b] (known without synchronising)."""
+        import torch
+        B = self._slots_B if getattr(self, '_slots_B', None) else len(frames)
+        Tn = 0 if c is None else int(c.shape[-1])
+        if c is not None:
+            _check(c, torch.float32, 'c')
+            if tuple(c.shape) != (B, self.cfg.cin_channels, Tn):
+                raise ValueError('slots_push: c must be [B=%d, cin=%d, Tn] (got %s)' % (B, self.cfg.cin_channels, tuple(c.shape)))
+        if len(frames) != B or len(final) != B:
+            raise ValueError('slots_push: frames / final must have one entry per slot (%d)' % B)
+        pitch = 0 if out_samples is None else int(out_samples.shape[-1])
+        for t, name in ((out_samples, 'out_samples'), (out_raw, 'out_raw'), (test_inputs, 'test_inputs')):
+            if t is not None and (not t.is_contiguous() or int(t.shape[-1]) != pitch or int(t.shape[0]) != B):
+                raise ValueError('slots_push: %s must be contiguous [B, ..., pitch=%d]' % (name, pitch))
+        fr = (ctypes.c_int32 * B)(*[int(v) for v in frames])
+        fi = (ctypes.c_int32 * B)(*[1 if v else 0 for v in final])
+        n = (ctypes.c_int32 * B)()
+        self._ok(self.lib.wn_synth_slots_push(self.h, _ptr(c), Tn, fr, fi, _ptr(noise), _ptr(test_inputs), _ptr(out_samples), _ptr(out_raw), pitch, n, _stream()))
+        return [int(v) for v in n]
+
+    def slot_abandon(self, slot):
+        self._ok(self.lib.wn_synth_slot_abandon(self.h, int(slot)))
+
+    def slot_frames_done(self, slot):
+        """Frames generated so far for the slot's utterance, -1 for an idle slot."""
+        rc = int(self.lib.wn_synth_slot_frames_done(self.h, int(slot)))
+        if rc < -1:
+            self._ok(rc)
+        return rc
+
+    def slots_end(self):
+        self._slots_B = None
+        self._ok(self.lib.wn_synth_slots_end(self.h))
 
     def fill_noise(self, noise, B, T, seed):
         """The device noise stream of synthesize(noise=None, seed): float32 [T, B, noise_per_step]."""

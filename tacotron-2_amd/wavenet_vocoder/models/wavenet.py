@@ -84,6 +84,127 @@ class SynthesisStream(object):
         self.closed = True
 
 
+def slot_plan(lengths, B, tick_frames):
+    """Assign utterances of `lengths` frames to the B slots of a SlotSession (no GPU): input order, lowest free slot first, a slot that finished
+    at push k is refilled at push k + 1.  Every live slot receives up to `tick_frames` frames per push.  Yields, per push,
+    (opens, frames, final): opens = [(slot, utterance index)] to open before the push, frames[b] / final[b] as SlotSession.push / wn_synth_slots_push
+    take them (frames[b] counted from the utterance's next undelivered frame)."""
+    B, tick = int(B), int(tick_frames)
+    if B <= 0 or tick <= 0:
+        raise ValueError('slot_plan: B and tick_frames must be positive')
+    lengths = [int(n) for n in lengths]
+    if any(n <= 0 for n in lengths):
+        raise ValueError('slot_plan: every utterance needs at least one frame')
+    nxt, owner, left = 0, [None] * B, [0] * B
+    while nxt < len(lengths) or any(o is not None for o in owner):
+        opens = []
+        for b in range(B):
+            if owner[b] is None and nxt < len(lengths):
+                owner[b], left[b] = nxt, lengths[nxt]
+                opens.append((b, nxt))
+                nxt += 1
+        frames, final = [0] * B, [False] * B
+        for b in range(B):
+            if owner[b] is None:
+                continue
+            frames[b] = min(tick, left[b])
+            left[b] -= frames[b]
+            if left[b] == 0:
+                final[b] = True
+                owner[b] = None
+        yield opens, frames, final
+
+
+class SlotSession(object):
+    """B slots served by one pipeline configuration (WaveNet.slots): every slot is idle or carries ONE utterance with its own start, seed and
+    global condition; utterances are opened, fed mel frames, finished and replaced independently, and a slot's samples are bit-identical to a
+    one-shot run of that utterance in the same batch row.  push() returns the samples whose conditioning is now complete, per slot, as device
+    tensors (asynchronous: nothing waits for the GPU)."""
+
+    def __init__(self, model, batch, steps_per_graph=0):
+        self.model, self.B = model, int(batch)
+        self.lookahead = model.engine.stream_lookahead()
+        self.hop = model.engine.hop
+        self.done, self.pushed = [None] * self.B, [0] * self.B          # frames per live slot (None: idle)
+        model._ensure_packed()
+        model.engine.slots_begin(self.B, steps_per_graph=steps_per_graph)
+        self.closed = False
+
+    def open(self, slot, g=None, seed=None):
+        """Start an utterance in an idle slot (live with the next push).  g: its speaker id (int) or feature vector [gin_channels] when the model
+        has global conditioning.  seed None: derived as incremental() derives it."""
+        m, hp = self.model, self.model._hparams
+        if seed is None:
+            m._synth_calls = getattr(m, '_synth_calls', 0) + 1
+            seed = ((int(hp.wavenet_random_seed) << 20) + m._synth_calls) * 64 + int(slot)
+        gd = None
+        if m.global_conditioning_enabled():
+            if g is None:
+                raise ValueError('SlotSession.open: the model has global conditioning: pass g')
+            if hp.use_speaker_embedding:
+                gd = torch.as_tensor(g, dtype=torch.int32).reshape(1).to(m.device)
+            else:
+                gd = torch.as_tensor(g, dtype=torch.float32).reshape(hp.gin_channels).to(m.device)
+        m.engine.slot_open(slot, seed=seed, g=gd)
+        self.done[slot], self.pushed[slot] = 0, 0
+
+    def push(self, items, return_raw=False):
+        """items {slot: frames [cin, Tn]} or {slot: (frames, final)}: append the frames to the slots' utterances (final: the utterance ends, the slot
+        is idle afterwards).  Returns {slot: samples [n]} (or (samples, raw [O, n]) with return_raw) for every slot named."""
+        if self.closed:
+            raise RuntimeError('SlotSession: the session is closed')
+        m, hp = self.model, self.model._hparams
+        frames, final, blocks = [0] * self.B, [False] * self.B, {}
+        for b, it in items.items():
+            fr, fin = it if isinstance(it, tuple) else (it, False)
+            if self.done[b] is None:
+                raise ValueError('SlotSession.push: slot %d is idle (open it first)' % b)
+            if fr is not None and int(fr.shape[-1]) > 0:
+                if fr.dim() != 2 or fr.shape[0] != hp.cin_channels:
+                    raise ValueError('SlotSession.push: frames of slot %d must be [cin=%d, Tn] (got %s)' % (b, hp.cin_channels, tuple(fr.shape)))
+                blocks[b] = fr
+                frames[b] = int(fr.shape[-1])
+            final[b] = bool(fin)
+        Tn = max(frames)
+        cc = None
+        if Tn > 0:
+            cc = torch.zeros(self.B, hp.cin_channels, Tn, device=m.device)
+            for b, fr in blocks.items():
+                cc[b, :, :frames[b]] = fr.to(m.device, torch.float32)
+        n = [0] * self.B
+        for b in items:
+            first, end = stream_schedule(self.done[b], self.pushed[b] + frames[b], self.lookahead[1], final[b])
+            n[b] = (end - first) * self.hop
+        pitch = max(max(n), 1)
+        out = torch.empty(self.B, pitch, device=m.device, dtype=torch.float32 if m.scalar_input else torch.int32)
+        raw = torch.empty(self.B, hp.out_channels, pitch, device=m.device) if return_raw else None
+        got = m.engine.slots_push(cc, frames, final, out, raw)
+        assert got == n, (got, n)
+        res = {}
+        for b in items:
+            self.pushed[b] += frames[b]
+            self.done[b] += n[b] // self.hop
+            if final[b]:
+                self.done[b] = None
+            res[b] = (out[b, :n[b]], raw[b, :, :n[b]]) if return_raw else out[b, :n[b]]
+        return res
+
+    def abandon(self, slot):
+        """Drop the slot's utterance (frames pushed and not generated are lost); the slot is idle."""
+        self.model.engine.slot_abandon(slot)
+        self.done[slot] = None
+
+    def check(self):
+        """Wait for the last push and raise if the pipeline gave up (a half-precision pipeline whose residual stream left the half range raises
+        here: switch the engine to bf16 with pipeline_dtype(False) and run the utterances again -- the re-run is the caller's)."""
+        self.model.engine.synth_check()
+
+    def close(self):
+        if not self.closed:
+            self.model.engine.slots_end()
+        self.closed = True
+
+
 class WaveNet(object):
     def __init__(self, hparams, init=False):
         self._hparams = hparams
@@ -422,6 +543,15 @@ class WaveNet(object):
             log('WaveNet synthesis path: {} ({} streams per run)'.format(self.engine.synth_path, group))
         self.upsampled_local_features = feats
         return (out, raw) if return_raw else out
+
+    def slots(self, batch, steps_per_graph=None):
+        """Open a SlotSession of `batch` slots (<= 32, the model's engine must have been built for them): independent utterances that join and
+        leave one running batch."""
+        hp = self._hparams
+        if self.engine is None:
+            raise RuntimeError('WaveNet.slots: call build() / initialize() first')
+        spg = int(getattr(hp, 'mi355_steps_per_graph', 0)) if steps_per_graph is None else int(steps_per_graph)
+        return SlotSession(self, batch, steps_per_graph=spg)
 
     def stream(self, batch, g=None, seed=None, steps_per_graph=None):
         """Open a SynthesisStream of `batch` utterances (<= 32, the model's engine must have been built for them).  seed None: derived as

@@ -80,6 +80,10 @@ class Synthesizer(object):
             if speaker_ids is None:
                 raise RuntimeError('Please provide speaker ids (--speaker_id) to a globally conditioned WaveNet')
             g = torch.from_numpy(np.asarray(speaker_ids, dtype=np.int32).reshape(len(c_batch), 1))
+        nslots = int(getattr(hparams, 'mi355_synthesis_slots', 0))
+        if nslots > 0 and not self.synth_debug:
+            generated_wavs, upsampled_features = self._synthesize_slots(c_batch, [len(x) for x in mel_spectrograms], speaker_ids, min(nslots, 32), log_dir is not None)
+            return self._write(generated_wavs, upsampled_features, mel_spectrograms, basenames, out_dir, log_dir)
         self._ensure_capacity(len(c_batch), maxlen * hop)
         dev = self.model.device
         test_inputs = None
@@ -95,6 +99,73 @@ class Synthesizer(object):
         feats = self.model.tower_synth_upsampled_local_features[0].cpu().numpy()
         generated_wavs = [w[:length] for w, length in zip(generated, audio_lengths)]
         upsampled_features = [f[:, :length] for f, length in zip(feats, audio_lengths)]
+        return self._write(generated_wavs, upsampled_features, mel_spectrograms, basenames, out_dir, log_dir)
+
+    def _synthesize_slots(self, c_batch, lengths, speaker_ids, nslots, want_features):
+        """mi355_synthesis_slots > 0: all utterances of the call through ONE slot session (WaveNet.slots): no utterance is padded to the longest of its
+        batch, a slot that finishes takes the next utterance at the next push.  Seeds derive from (wavenet_random_seed, the model's synthesis-call
+        counter, utterance index), so two fresh runs of the same inputs agree, whatever the tick."""
+        from wavenet_vocoder.models.wavenet import slot_plan
+        from wavenet_vocoder import util as wutil
+        from wavenet_vocoder.util import is_mulaw, is_mulaw_quantize
+        hparams, hop = self._hparams, get_hop_size(self._hparams)
+        tick = int(getattr(hparams, 'mi355_synthesis_chunk_frames', 0)) or 8
+        B = min(nslots, len(lengths))
+        self._ensure_capacity(B, (tick + 8) * hop)          # a push generates at most tick + lookahead frames per slot
+        m = self.model
+        dev = m.device
+        right = m.engine.stream_lookahead()[1]
+        if (tick + right) * hop > m.max_time:
+            self._ensure_capacity(B, (tick + right) * hop)
+        m._synth_calls = getattr(m, '_synth_calls', 0) + 1
+        base = ((int(hparams.wavenet_random_seed) << 20) + m._synth_calls) << 20
+        sess = m.slots(B)
+        chunks = [[] for _ in lengths]
+        feats = [[] for _ in lengths]
+        owner, sent = [None] * B, [0] * len(lengths)
+        for opens, frames, final in slot_plan(lengths, B, tick):
+            for b, u in opens:
+                sess.open(b, g=None if not self.global_conditions else int(np.asarray(speaker_ids).reshape(-1)[u]), seed=base + u)
+                owner[b] = u
+            items = {}
+            for b in range(B):
+                if owner[b] is None:
+                    continue
+                u = owner[b]
+                blk = torch.from_numpy(np.ascontiguousarray(c_batch[u, sent[u]:sent[u] + frames[b]].T))
+                items[b] = (blk, final[b])
+                sent[u] += frames[b]
+            res = sess.push(items)
+            fe = None
+            if want_features:
+                n_max = max(int(v.shape[0]) for v in res.values())
+                if n_max > 0:
+                    fe = torch.empty(B, hparams.cin_channels, n_max, device=dev)
+                    m.engine.upsampled_features(fe)
+            for b, smp in res.items():
+                u = owner[b]
+                chunks[u].append(smp.clone())
+                if fe is not None and smp.shape[0] > 0:
+                    feats[u].append(fe[b, :, :smp.shape[0]].clone())
+                if final[b]:
+                    owner[b] = None
+        torch.cuda.synchronize()
+        sess.check()
+        sess.close()
+        wavs, ups = [], []
+        for u, n in enumerate(lengths):
+            out = torch.cat(chunks[u]) if chunks[u] else torch.zeros(0, device=dev)
+            assert out.shape[0] == n * hop, (u, out.shape, n * hop)
+            if is_mulaw_quantize(hparams.input_type):
+                out = wutil.inv_mulaw_quantize(out)
+            elif is_mulaw(hparams.input_type):
+                out = wutil.inv_mulaw(out)
+            wavs.append(out.float().cpu().numpy())
+            ups.append(torch.cat(feats[u], 1).cpu().numpy() if feats[u] else np.zeros((hparams.cin_channels, 0), np.float32))
+        return wavs, ups
+
+    def _write(self, generated_wavs, upsampled_features, mel_spectrograms, basenames, out_dir, log_dir):
+        hparams = self._hparams
         audio_filenames = []
         for i, (wav, feat, input_mel) in enumerate(zip(generated_wavs, upsampled_features, mel_spectrograms)):
             audio_filename = os.path.join(out_dir, 'wavenet-audio-{}.wav'.format(basenames[i]))
