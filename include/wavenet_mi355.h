@@ -307,6 +307,57 @@ int wn_inv_mulaw_quantize(const int32_t* q, float* x, int64_t n, void* stream);
 /* argmax over channels of [B,Q,T] logits -> int32 [B,T] (first max wins, like tf.argmax) */
 int wn_argmax_channels(const float* logits, int32_t* out, int32_t B, int32_t Q, int32_t T, void* stream);
 
+/* ---- mel analysis: wav -> mel-spectrogram (the reference's preprocessing front end: librosa.stft + librosa.filters.mel + numpy) ----
+ * A context of its own, independent of wn_ctx: no model is needed.  For an utterance of n samples the analysis gives F = 1 + n / hop_size
+ * frames (librosa.stft, center = True, pad_mode = 'constant'): frame f is the win_size samples around f * hop_size under a periodic Hann
+ * window centred in n_fft, its DFT bins 0 ... n_fft / 2, |.|^magnitude_power, the mel filters, 20 log10(max(10^(min_level_db / 20), .)) -
+ * ref_level_db, and -- signal_normalization -- one of the four _normalize variants (allow_clipping x symmetric_mels), without the assert of
+ * the two that do not clip.  Exact fp32 products (the fp32 matrix instruction) with fp32 accumulation in a fixed order: two runs, and an
+ * utterance alone or inside any batch, are bit-identical.  Optionally fused into the read of the signal:
+ *   y[s] = gain[b] * (x[s] - preemphasis * x[s - 1]),  x[-1] = 0   (audio.py:22-25 and the rescale of wavenet_preprocessor.py:76);
+ * preemphasis = 0 and gain = NULL analyse x itself.  Status codes, wn_mel_last_error and the stream convention are those of the header's top.
+ * Device memory -- the [win_size, 2 x (1 + n_fft / 2)] DFT basis (10 MB at the default geometry, padded to whole bin groups) and the mel filters -- is reserved in
+ * wn_mel_create; wn_mel_run and wn_mel_peak never allocate, and lengths travel as kernel arguments (the host array is free when the call
+ * returns).  max_batch = 0 makes a geometry-only context: nothing is reserved, no device is touched, wn_mel_num_frames works and wn_mel_run /
+ * wn_mel_peak refuse every B.  Limits: num_mels <= 128, n_fft <= 65536, and the signal span of 32 frames, 31 hop_size + win_size floats,
+ * must fit the 160 KiB LDS (WN_E_UNSUPPORTED otherwise). */
+typedef struct wn_mel_config {
+    int32_t abi_version;            /* = WN_ABI_VERSION */
+    int32_t sample_rate;            /* informational (the caller built mel_basis for it) */
+    int32_t n_fft, hop_size, win_size, num_mels;                  /* hparams.py:102-110; win_size <= n_fft, n_fft even */
+    float   magnitude_power;        /* > 0; 2 and 1 take no transcendental */
+    float   min_level_db, ref_level_db, max_abs_value;            /* hparams.py:126-133 */
+    float   preemphasis;            /* k of y[s] = x[s] - k x[s - 1]; 0: off */
+    int32_t signal_normalization, allow_clipping, symmetric_mels; /* allow_clipping = hparams allow_clipping_in_normalization */
+    int32_t max_batch;              /* utterances per call; 0: geometry-only context */
+    int64_t max_samples;            /* samples per utterance */
+} wn_mel_config;
+typedef struct wn_mel wn_mel;
+
+/* audio.py:70-77, 178-182, 243-270.  mel_basis: HOST float [num_mels, 1 + n_fft / 2] (librosa.filters.mel; any dense matrix is honoured).
+ * Validation before any device call: WN_E_SHAPE for n_fft odd, win_size > n_fft, hop_size < 1, num_mels < 1; WN_E_ARG for
+ * magnitude_power <= 0, a null pointer, a foreign abi_version.  wn_mel_last_error with NULL gives the text of a failed create. */
+int  wn_mel_create(const wn_mel_config* cfg, const float* mel_basis, wn_mel** out);
+void wn_mel_destroy(wn_mel* mel);
+const char* wn_mel_last_error(const wn_mel* mel);
+/* audio.py:178-182 (librosa.stft, center = True): 1 + n_samples / hop_size; WN_E_ARG for a NULL context or n_samples < 0 (host only) */
+int64_t wn_mel_num_frames(const wn_mel* mel, int64_t n_samples);
+/* the largest number of frames a workgroup of this context takes (32, 64 or 128; 0: geometry-only).  wn_mel_run picks 32, 64 or 128 up to this per
+ * call from the batch's frame counts; the result never depends on the pick (every frame's sums run in the same order).  Tests place utterance
+ * lengths around its multiples.  Environment at wn_mel_create: WN_MEL_TF=32|64|128 pins one tile (the A/B switch of tools/mel_timing.py). */
+int  wn_mel_frame_tile(const wn_mel* mel);
+/* peak[b] = max_s |x[s] - preemphasis * x[s - 1]| over the utterance's lengths[b] samples (0 for an empty one): exact and order independent,
+ * equal to numpy's float32 result.  With it a device-resident caller forms the gain rescaling_max / max |preem_wav| of
+ * wavenet_preprocessor.py:76 (audio.py:22-25) without a host round trip.  wav: device float [B, ld]; lengths: HOST int32 [B]; peak: device float [B]. */
+int  wn_mel_peak(wn_mel* mel, const float* wav, int64_t ld, const int32_t* lengths, int32_t B, float* peak, void* stream);
+/* audio.py:70-77 melspectrogram of a ragged batch.  wav: device float [B, ld], row b holds lengths[b] <= ld samples (HOST int32 [B]); gain:
+ * device float [B] or NULL (= 1).  out: device float [B, F_max, num_mels] (channels_first = 0: the mels/mel-*.npy layout) or [B, num_mels,
+ * F_max] (1: the layout wn_synthesize takes as c); rows f >= 1 + lengths[b] / hop_size hold the value an all-zero signal gives (-max_abs_value
+ * under the default hparams: the synthesiser's pad).  WN_E_SHAPE: B > max_batch, lengths[b] > ld or > max_samples, F_max < the frames of
+ * the longest utterance. */
+int  wn_mel_run(wn_mel* mel, const float* wav, int64_t ld, const int32_t* lengths, const float* gain, float* out, int32_t B, int32_t F_max,
+                int32_t channels_first, void* stream);
+
 /* ---- introspection ------------------------------------------------------------------------------ */
 int64_t wn_workspace_bytes(const wn_ctx* ctx);
 /* name of the kernel that dominates training time (bench.py's roofline line names it) */

@@ -1,7 +1,84 @@
-"""Audio helpers the WaveNet path needs (reference datasets/audio.py:17-20, 54-59).  The mel / Griffin-Lim
-front-end of the reference belongs to the Tacotron model and to dataset preprocessing: out of scope."""
+"""Audio helpers the WaveNet path needs (reference datasets/audio.py:9-59, 70-77, 178-270): loading, pre-emphasis, silence trimming,
+padding, and the mel analysis -- melspectrogram in numpy float64 (the pinned reference of the tests) and melspectrogram_device on the
+GPU (csrc/wn_mel.hip through _ext.MelAnalyzer; what wavenet_preprocess.py and synthesize.py --wavs_dir run).  The Griffin-Lim inversion
+and the linear spectrogram belong to the Tacotron model: out of scope."""
 import numpy as np
+from scipy import signal
 from scipy.io import wavfile
+
+
+def load_wav(path, sr):
+    """Reference audio.py:9-10 (librosa.core.load) on scipy: float32 in [-1, 1), channels averaged.  int16 / 32768, int32 / 2^31, uint8 as
+    (x - 128) / 128, float as is.  The reference resamples to sr; no resampler here matches librosa's, so another rate is an error."""
+    rate, x = wavfile.read(path)
+    if rate != sr:
+        raise ValueError('%s: sample rate %d, expected %d (resample the file first: no resampler here matches librosa\'s)' % (path, rate, sr))
+    if x.dtype == np.int16:
+        y = x.astype(np.float32) / 32768.0
+    elif x.dtype == np.int32:
+        y = (x.astype(np.float64) / 2147483648.0).astype(np.float32)
+    elif x.dtype == np.uint8:
+        y = (x.astype(np.float32) - 128.0) / 128.0
+    elif x.dtype.kind == 'f':
+        y = x.astype(np.float32)
+    else:
+        raise ValueError('%s: unsupported sample type %s' % (path, x.dtype))
+    if y.ndim == 2:
+        y = y.mean(axis=1, dtype=np.float32)
+    return y
+
+
+def preemphasis(wav, k, preemphasize=True):
+    """Reference audio.py:22-25."""
+    if preemphasize:
+        return signal.lfilter([1, -k], [1], wav)
+    return wav
+
+
+def inv_preemphasis(wav, k, inv_preemphasize=True):
+    """Reference audio.py:27-30."""
+    if inv_preemphasize:
+        return signal.lfilter([1], [1, -k], wav)
+    return wav
+
+
+def start_and_end_indices(quantized, silence_threshold=2):
+    """Reference audio.py:33-44: first / last sample further than silence_threshold from the mu-law code of silence (127)."""
+    q = np.asarray(quantized).astype(np.int64)
+    loud = np.flatnonzero(np.abs(q - 127) > silence_threshold)
+    assert loud.size > 0 and loud[-1] > 1, 'no sample above the silence threshold'      # the reference's backward scan stops at index 2
+    return int(loud[0]), int(loud[-1])
+
+
+def trim_silence(wav, hparams):
+    """Reference audio.py:46-52 == librosa.effects.trim(wav, top_db=trim_top_db, frame_length=trim_fft_size, hop_length=trim_hop_size)[0],
+    restated on numpy from librosa's published algorithm: centred, reflect-padded frames of trim_fft_size every trim_hop_size; mean square
+    per frame; a frame is non-silent when 10 log10(max(1e-10, mse)) - 10 log10(max(1e-10, max mse)) > -trim_top_db; the result runs from
+    (first non-silent frame) x hop to min(len, (last non-silent frame + 1) x hop).  No librosa exists on the build machine to pin this
+    against: it is checked against signals whose trimmed bounds the construction predicts, not against librosa itself."""
+    wav = np.asarray(wav)
+    n_fft, hop, top_db = int(hparams.trim_fft_size), int(hparams.trim_hop_size), float(hparams.trim_top_db)
+    if wav.size == 0:
+        return wav
+    y = np.pad(wav.astype(np.float64), n_fft // 2, mode='reflect') if wav.size > 1 else np.pad(wav.astype(np.float64), n_fft // 2, mode='edge')
+    n_frames = 1 + (len(y) - n_fft) // hop
+    csum = np.concatenate([[0.0], np.cumsum(y * y)])
+    starts = hop * np.arange(n_frames)
+    mse = (csum[starts + n_fft] - csum[starts]) / n_fft
+    db = 10.0 * np.log10(np.maximum(1e-10, mse)) - 10.0 * np.log10(max(1e-10, float(mse.max())))
+    loud = np.flatnonzero(db > -top_db)
+    if loud.size == 0:
+        return wav[0:0]
+    return wav[int(loud[0]) * hop: min(len(wav), (int(loud[-1]) + 1) * hop)]
+
+
+def librosa_pad_lr(x, fsize, fshift, pad_sides=1):
+    """Reference audio.py:210-219: padding that brings len(x) to (len(x) // fshift + 1) * fshift, on the right or split over both sides."""
+    assert pad_sides in (1, 2)
+    pad = (x.shape[0] // fshift + 1) * fshift - x.shape[0]
+    if pad_sides == 1:
+        return 0, pad
+    return pad // 2, pad // 2 + pad % 2
 
 
 def get_hop_size(hparams):
@@ -100,3 +177,33 @@ def melspectrogram(wav, hparams):
     if hparams.signal_normalization:
         return _normalize(S, hparams)
     return S
+
+
+def melspectrogram_device(wavs, hparams, analyzer=None):
+    """melspectrogram for a list of 1-D signals on the GPU: a list of [num_mels, F_b] float32 arrays, F_b = 1 + len // hop (the same
+    contract as melspectrogram, batched; fp32 arithmetic, csrc/wn_mel.hip).  analyzer: an _ext.MelAnalyzer to reuse (its capacity bounds the
+    batch and the longest signal); None builds one for this call."""
+    import torch
+    from wavenet_vocoder import _ext
+    wavs = [np.ascontiguousarray(w, dtype=np.float32).reshape(-1) for w in wavs]
+    if not wavs:
+        return []
+    own = analyzer is None
+    if own:
+        analyzer = _ext.MelAnalyzer(hparams, min(len(wavs), 64), max(len(w) for w in wavs))
+    try:
+        out = [None] * len(wavs)
+        order = sorted(range(len(wavs)), key=lambda i: len(wavs[i]))      # neighbours in length share a batch: little padding
+        for lo in range(0, len(order), analyzer.max_batch):
+            idx = order[lo:lo + analyzer.max_batch]
+            lens = [len(wavs[i]) for i in idx]
+            host = np.zeros((len(idx), max(1, max(lens))), dtype=np.float32)
+            for r, i in enumerate(idx):
+                host[r, :lens[r]] = wavs[i]
+            mel = analyzer.run(torch.from_numpy(host).cuda(), lens, channels_first=True).cpu().numpy()
+            for r, i in enumerate(idx):
+                out[i] = np.ascontiguousarray(mel[r, :, :1 + lens[r] // analyzer.hop])
+        return out
+    finally:
+        if own:
+            analyzer.close()

@@ -91,6 +91,8 @@ MI355 = dict(
     mi355_compute_dtype='bf16',     # 'bf16': bf16 MFMA operands, fp32 accumulation (the tuned path); 'fp32': the reference's own fp32 arithmetic for the
                                      # forward, loss AND backward (csrc/wn_f32.hip; ~13x slower: validation of a run against the reference's numerics) and
                                      # for synthesis (csrc/wn_synth_f32.hip: fp32 weights and queues like WaveNet.incremental; far from real time)
+    mi355_device_mel=False,         # mel analysis on the GPU (csrc/wn_mel.hip).  wavenet_preprocess.py turns it on unless --hparams says otherwise (False: the
+                                     # numpy float64 path, datasets.audio.melspectrogram); synthesize.py --wavs_dir always analyses on the device
 )
 
 

@@ -1,5 +1,6 @@
 """Synthesis CLI -- same flags as the reference's top-level synthesize.py; ``--model WaveNet`` synthesises audio from
-mel .npy files in --mels_dir with the checkpoint under logs-<name>/wave_<--checkpoint>."""
+mel .npy files in --mels_dir with the checkpoint under logs-<name>/wave_<--checkpoint>; ``--wavs_dir DIR`` (an addition of this tree) vocodes
+recordings instead: every wav of DIR is analysed on the GPU and re-synthesised from its own mel-spectrogram."""
 import argparse
 import os
 
@@ -29,6 +30,7 @@ def main():
     parser.add_argument('--mode', default='eval', help='mode of run: can be one of {}'.format(accepted_modes))
     parser.add_argument('--GTA', default='True', help='Ground truth aligned synthesis, defaults to True, only considered in synthesis mode')
     parser.add_argument('--text_list', default='', help='Text file contains list of texts to be synthesized. Valid if mode=eval')
+    parser.add_argument('--wavs_dir', default=None, help='WaveNet only: analyse every wav of this folder on the GPU and synthesize from those mels instead of --mels_dir')
     parser.add_argument('--speaker_id', default=None, help='Defines the speakers ids to use when running standalone Wavenet on a folder of mels.')
     args = parser.parse_args()
 

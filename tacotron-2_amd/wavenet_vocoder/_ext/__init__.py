@@ -52,6 +52,17 @@ class WnConfig(ctypes.Structure):
     ]
 
 
+class WnMelConfig(ctypes.Structure):
+    _fields_ = [
+        ('abi_version', ctypes.c_int32), ('sample_rate', ctypes.c_int32),
+        ('n_fft', ctypes.c_int32), ('hop_size', ctypes.c_int32), ('win_size', ctypes.c_int32), ('num_mels', ctypes.c_int32),
+        ('magnitude_power', ctypes.c_float), ('min_level_db', ctypes.c_float), ('ref_level_db', ctypes.c_float),
+        ('max_abs_value', ctypes.c_float), ('preemphasis', ctypes.c_float),
+        ('signal_normalization', ctypes.c_int32), ('allow_clipping', ctypes.c_int32), ('symmetric_mels', ctypes.c_int32),
+        ('max_batch', ctypes.c_int32), ('max_samples', ctypes.c_int64),
+    ]
+
+
 class WnError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__('%s: %s' % (STATUS.get(code, code), msg))
@@ -134,6 +145,13 @@ def load_library():
         'wn_workspace_bytes': (i64, [vp]),
         'wn_dominant_kernel_name': (ctypes.c_char_p, []),
         'wn_test_dropout_mask': (ctypes.c_int, [ctypes.c_uint64, i32, ctypes.c_float, i64, i64, vp]),
+        'wn_mel_create': (ctypes.c_int, [ctypes.POINTER(WnMelConfig), vp, ctypes.POINTER(vp)]),
+        'wn_mel_destroy': (None, [vp]),
+        'wn_mel_last_error': (ctypes.c_char_p, [vp]),
+        'wn_mel_num_frames': (i64, [vp, i64]),
+        'wn_mel_frame_tile': (ctypes.c_int, [vp]),
+        'wn_mel_peak': (ctypes.c_int, [vp, vp, i64, ctypes.POINTER(i32), i32, vp, vp]),
+        'wn_mel_run': (ctypes.c_int, [vp, vp, i64, ctypes.POINTER(i32), vp, vp, i32, i32, i32, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)            # AttributeError here == ABI symbol missing
@@ -564,3 +582,117 @@ def argmax_channels(logits):
     if rc != 0:
         raise WnError(rc, (lib.wn_last_error(None) or b'').decode())
     return out
+
+
+def mel_config_from_hparams(hp, max_batch, max_samples, preemphasis=0.0):
+    """hparams (reference keys, hparams.py:102-133) -> wn_mel_config.  preemphasis: the k fused into the read of the signal (0: the
+    analysed signal is the input itself, the contract of datasets.audio.melspectrogram)."""
+    from datasets.audio import get_hop_size
+    cfg = WnMelConfig()
+    cfg.abi_version = WN_ABI_VERSION
+    cfg.sample_rate = int(hp.sample_rate)
+    cfg.n_fft = int(hp.n_fft)
+    cfg.hop_size = int(get_hop_size(hp))
+    cfg.win_size = int(hp.n_fft if hp.win_size is None else hp.win_size)
+    cfg.num_mels = int(hp.num_mels)
+    cfg.magnitude_power = float(hp.magnitude_power)
+    cfg.min_level_db = float(hp.min_level_db)
+    cfg.ref_level_db = float(hp.ref_level_db)
+    cfg.max_abs_value = float(hp.max_abs_value)
+    cfg.preemphasis = float(preemphasis)
+    cfg.signal_normalization = int(bool(hp.signal_normalization))
+    cfg.allow_clipping = int(bool(hp.allow_clipping_in_normalization))
+    cfg.symmetric_mels = int(bool(hp.symmetric_mels))
+    cfg.max_batch = int(max_batch)
+    cfg.max_samples = int(max_samples)
+    return cfg
+
+
+class MelAnalyzer:
+    """One wn_mel: wav -> mel-spectrogram on the current device (csrc/wn_mel.hip; replaces datasets.audio.melspectrogram's numpy / the
+    reference's librosa on the preprocessing path).  max_batch = 0 gives a geometry-only analyzer (num_frames; no device)."""
+
+    def __init__(self, hparams, max_batch, max_samples, preemphasis=0.0, mel_basis=None):
+        """preemphasis: k of y[s] = x[s] - k x[s - 1] fused into run() and peak() (0: off).  mel_basis: [num_mels, 1 + n_fft // 2]
+        (default datasets.audio._build_mel_basis(hparams) == librosa.filters.mel)."""
+        if getattr(hparams, 'use_lws', False):
+            raise NotImplementedError('use_lws: the lws package is not available')
+        self.lib = load_library()
+        self.cfg = mel_config_from_hparams(hparams, max_batch, max_samples, preemphasis)
+        if mel_basis is None:
+            from datasets.audio import _build_mel_basis
+            mel_basis = _build_mel_basis(hparams)
+        mb = np.ascontiguousarray(mel_basis, dtype=np.float32)
+        if mb.shape != (self.cfg.num_mels, 1 + self.cfg.n_fft // 2):
+            raise ValueError('mel_basis must be [num_mels, 1 + n_fft // 2] = %r (got %r)' % ((self.cfg.num_mels, 1 + self.cfg.n_fft // 2), mb.shape))
+        h = ctypes.c_void_p()
+        rc = self.lib.wn_mel_create(ctypes.byref(self.cfg), mb.ctypes.data_as(ctypes.c_void_p), ctypes.byref(h))
+        if rc != 0:
+            raise WnError(rc, (self.lib.wn_mel_last_error(None) or b'').decode())
+        self.h = h
+        self.num_mels, self.hop = int(self.cfg.num_mels), int(self.cfg.hop_size)
+        self.max_batch, self.max_samples = int(max_batch), int(max_samples)
+
+    def _ok(self, rc):
+        if rc != 0:
+            raise WnError(rc, (self.lib.wn_mel_last_error(self.h) or b'').decode())
+
+    def num_frames(self, n):
+        r = int(self.lib.wn_mel_num_frames(self.h, int(n)))
+        if r < 0:
+            raise WnError(r, 'wn_mel_num_frames(%d)' % n)
+        return r
+
+    @property
+    def frame_tile(self):
+        return int(self.lib.wn_mel_frame_tile(self.h))
+
+    def _batch(self, wav, lengths):
+        import torch
+        _check(wav, torch.float32, 'wav')
+        if wav.dim() != 2:
+            raise ValueError('wav must be [B, ld]')
+        if len(lengths) != int(wav.shape[0]):
+            raise ValueError('one length per row of wav (%d lengths for %d rows)' % (len(lengths), int(wav.shape[0])))
+        return (ctypes.c_int32 * len(lengths))(*[int(n) for n in lengths])
+
+    def peak(self, wav, lengths, out=None):
+        """max |x[s] - k x[s - 1]| per utterance -> float32 [B] on the device."""
+        import torch
+        lens = self._batch(wav, lengths)
+        if out is None:
+            out = torch.empty(wav.shape[0], dtype=torch.float32, device=wav.device)
+        _check(out, torch.float32, 'out')
+        self._ok(self.lib.wn_mel_peak(self.h, _ptr(wav), int(wav.shape[1]), lens, len(lens), _ptr(out), _stream()))
+        return out
+
+    def run(self, wav, lengths, gain=None, channels_first=False, frames=None, out=None):
+        """wav float32 [B, ld] on the device, lengths: B ints (host) -> [B, F_max, num_mels] (channels_first: [B, num_mels, F_max]) on the
+        device; F_max = frames or the frames of the longest utterance; rows past an utterance's frames hold the zero-signal value."""
+        import torch
+        lens = self._batch(wav, lengths)
+        B = len(lens)
+        if gain is not None:
+            _check(gain, torch.float32, 'gain')
+            if gain.numel() != B:
+                raise ValueError('gain must be [B]')
+        F = int(frames) if frames is not None else max(1 + int(n) // self.hop for n in lens)
+        shape = (B, self.num_mels, F) if channels_first else (B, F, self.num_mels)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float32, device=wav.device)
+        _check(out, torch.float32, 'out')
+        if tuple(out.shape) != shape:
+            raise ValueError('out must be %r' % (shape,))
+        self._ok(self.lib.wn_mel_run(self.h, _ptr(wav), int(wav.shape[1]), lens, _ptr(gain), _ptr(out), B, F, int(bool(channels_first)), _stream()))
+        return out
+
+    def close(self):
+        if getattr(self, 'h', None):
+            self.lib.wn_mel_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

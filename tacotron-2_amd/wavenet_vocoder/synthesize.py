@@ -56,9 +56,75 @@ def run_synthesis(args, checkpoint_path, output_dir, hparams):
     log('synthesized audio waveforms at {}'.format(wav_dir))
 
 
+def analyse_wavs(paths, hparams, batch=32):
+    """The conditioning mels of recordings, as preprocessing makes them (wavenet_preprocessor.py lines 71-76, 111: pre-emphasis, rescale to
+    rescaling_max, melspectrogram) with every step on the device: wn_mel_peak gives max |preem_wav|, the gain rescaling_max / peak and the
+    pre-emphasis are fused into wn_mel_run.  -> list of [frames, num_mels] float32 (frames = 1 + samples // hop)."""
+    import torch
+    from datasets import audio
+    from wavenet_vocoder import _ext
+    wavs = [audio.load_wav(p, sr=hparams.sample_rate) for p in paths]
+    for p, w in zip(paths, wavs):
+        if w.size == 0:
+            raise RuntimeError('empty recording: {}'.format(p))
+    k = float(hparams.preemphasis) if hparams.preemphasize else 0.0
+    analyzer = _ext.MelAnalyzer(hparams, min(batch, len(wavs)), max(len(w) for w in wavs), preemphasis=k)
+    mels = [None] * len(wavs)
+    order = sorted(range(len(wavs)), key=lambda i: len(wavs[i]))
+    try:
+        for lo in range(0, len(order), analyzer.max_batch):
+            idx = order[lo:lo + analyzer.max_batch]
+            lens = [len(wavs[i]) for i in idx]
+            host = np.zeros((len(idx), max(lens)), dtype=np.float32)
+            for r, i in enumerate(idx):
+                host[r, :lens[r]] = wavs[i]
+            dev = torch.from_numpy(host).cuda()
+            gain = None
+            if hparams.rescale:
+                gain = float(hparams.rescaling_max) / analyzer.peak(dev, lens).clamp_min(1e-30)
+            c = analyzer.run(dev, lens, gain=gain, channels_first=True)          # [B, num_mels, F]: the layout the engine takes as c
+            c = c.transpose(1, 2).cpu().numpy()
+            for r, i in enumerate(idx):
+                mels[i] = np.ascontiguousarray(c[r, :1 + lens[r] // analyzer.hop])
+    finally:
+        analyzer.close()
+    return mels
+
+
+def run_wav_synthesis(args, checkpoint_path, output_dir, hparams):
+    """--wavs_dir: analysis then synthesis.  Writes wavs/wavenet-audio-<basename>.wav (mel_frames * hop samples), the analysed mel next to
+    it as wavs/mel-<basename>.npy, and wavs/map.txt rows ``recording|mel|wav``."""
+    plot_dir, wav_dir = os.path.join(output_dir, 'plots'), os.path.join(output_dir, 'wavs')
+    log(hparams_debug_string())
+    if hparams.gin_channels > 0:
+        raise RuntimeError('--wavs_dir: a globally conditioned WaveNet needs speaker ids; analyse with wavenet_preprocess.py and use --mels_dir --speaker_id')
+    paths = sorted(os.path.join(args.wavs_dir, n) for n in os.listdir(args.wavs_dir) if n.endswith('.wav'))
+    if not paths:
+        raise RuntimeError('no *.wav in {}'.format(args.wavs_dir))
+    synth = Synthesizer()
+    synth.load(checkpoint_path, hparams)
+    for d in (plot_dir, wav_dir):
+        os.makedirs(d, exist_ok=True)
+    step = int(hparams.wavenet_synthesis_batch_size)
+    with open(os.path.join(wav_dir, 'map.txt'), 'w') as index:
+        for start in tqdm(range(0, len(paths), step)):
+            batch = paths[start:start + step]
+            names = [os.path.basename(p)[:-len('.wav')] for p in batch]
+            mels = analyse_wavs(batch, hparams)
+            mel_paths = [os.path.join(wav_dir, 'mel-{}.npy'.format(n)) for n in names]
+            for mp, mel in zip(mel_paths, mels):
+                np.save(mp, mel, allow_pickle=False)
+            wavs = synth.synthesize(mels, None, names, wav_dir, plot_dir)
+            for p, mp, wav in zip(batch, mel_paths, wavs):
+                index.write('|'.join([p, mp, wav]) + '\n')
+    log('synthesized audio waveforms at {}'.format(wav_dir))
+
+
 def wavenet_synthesize(args, hparams, checkpoint):
     checkpoint_path = get_checkpoint_state(checkpoint)
     if checkpoint_path is None or not (os.path.exists(checkpoint_path) or os.path.exists(checkpoint_path + '.index')):
         raise RuntimeError('Failed to load checkpoint at {}'.format(checkpoint))
     log('loaded model at {}'.format(checkpoint_path))
+    if getattr(args, 'wavs_dir', None):
+        return run_wav_synthesis(args, checkpoint_path, 'wavenet_' + args.output_dir, hparams)
     run_synthesis(args, checkpoint_path, 'wavenet_' + args.output_dir, hparams)
