@@ -455,7 +455,7 @@ extern "C" int wn_synthesize(wn_ctx* c, const float* cc, int32_t B, int32_t Tc, 
     if (!c->packed) WN_FAIL(c, WN_E_STATE, "wn_pack_weights must be called before wn_synthesize");
     if (B <= 0 || B > 32) WN_FAIL(c, WN_E_SHAPE, "synthesis batch %d outside (0, 32]", B);
     if (Tc <= 0) WN_FAIL(c, WN_E_SHAPE, "Tc must be positive");
-    c->strm.open = false; c->slots.open = false; c->fup_pitch = 0;            // (ends an open stream / slot session: its queues are overwritten)
+    c->strm.open = false; c->slots.open = false;            // (ends an open stream / slot session: its queues are overwritten)
     int rc = wn_pipe_check(c, false);                  // a hand-off timeout of the previous pipeline run surfaces here at the latest
     if (rc) return rc;
     if (!noise) {                                      // device Philox stream keyed by `seed` (header)
@@ -611,6 +611,24 @@ __global__ void wn_stream_window_kernel(const float* __restrict__ prev, int64_t 
     win[i] = col < keep ? prev[row * prev_cols + drop + col] : cnew[row * Tn + (col - keep)];
 }
 
+// What a push of `frames` mel frames does to an utterance: frames pushed after it, the frame generation stops at (everything when final, else what the
+// right lookahead lets out), samples n it generates, and the window [wstart, pushed) of w frames its conditioning is upsampled from (the left context
+// + the frames not yet generated).  `who` names the entry (and slot) in the messages; a rejected push leaves the utterance as it was.
+struct WnPushPlan { int64_t pushed, gen_end, n, wstart, w; };
+static int plan_push(wn_ctx* c, const char* who, const WnUtt& u, int frames, bool final, int left, int right, WnPushPlan& p) {
+    p.pushed = u.pushed + frames;
+    p.gen_end = final ? p.pushed : std::max(u.done, p.pushed - right);
+    p.n = (p.gen_end - u.done) * c->hop;
+    p.wstart = std::max<int64_t>(0, u.done - left); p.w = p.pushed - p.wstart;
+    if (p.n > c->maxT) WN_FAIL(c, WN_E_SHAPE, "%s: %lld samples in one push exceed max_time = %d", who, (long long)p.n, c->maxT);
+    if (u.done * c->hop + p.n > INT32_MAX) WN_FAIL(c, WN_E_SHAPE, "%s: utterance longer than 2^31 samples", who);
+    return WN_OK;
+}
+static void commit_push(WnUtt& u, const WnPushPlan& p, bool rebuilt) {
+    if (rebuilt) { u.cur ^= 1; u.pend_first = p.wstart; }
+    u.pushed = p.pushed; u.done = p.gen_end;
+}
+
 // stream state buffers, sized for (max_batch, max_time): the window of pending frames never holds more than max_batch x max_time / hop
 // frame columns (push checks it), the bias [L][B][G], the carried inputs
 static int stream_alloc(wn_ctx* c) {
@@ -647,7 +665,7 @@ extern "C" int wn_synth_stream_begin(wn_ctx* c, int32_t B, uint64_t seed, int32_
     }
     wn_synth_stream_lookahead(&c->cfg, &S.left, &S.right);
     S.B = B; S.seed = seed; S.spg = steps_per_graph; S.path = path;
-    S.pushed = S.done = S.pend_first = 0; S.cur = 0; S.poisoned = false;
+    S.u = WnUtt(); S.poisoned = false;
     S.open = true;
     return WN_OK;
 }
@@ -664,24 +682,21 @@ extern "C" int wn_synth_stream_push(wn_ctx* c, const float* cc, int32_t Tn, int3
     int rc = wn_pipe_check(c, false);                  // a failed earlier push surfaces here at the latest (and poisons the stream)
     if (rc) return rc;
     const int B = S.B, hop = c->hop;
-    const int64_t pushed = S.pushed + Tn;
-    const int64_t gen_end = final ? pushed : std::max(S.done, pushed - S.right);
-    const int64_t n = (gen_end - S.done) * hop;
-    const int64_t wstart = std::max<int64_t>(0, S.done - S.left), w = pushed - wstart;
-    if (n > c->maxT) WN_FAIL(c, WN_E_SHAPE, "wn_synth_stream_push: %lld samples in one push exceed max_time = %d", (long long)n, c->maxT);
+    WnUtt& u = S.u; WnPushPlan pl;
+    if ((rc = plan_push(c, "wn_synth_stream_push", u, Tn, final != 0, S.left, S.right, pl))) return rc;
+    const int64_t n = pl.n, wstart = pl.wstart, w = pl.w;
     if ((int64_t)B * w * hop > c->NT)
         WN_FAIL(c, WN_E_SHAPE, "wn_synth_stream_push: a window of %lld frames (%d of left context + the frames not yet generated) x %d streams exceeds the workspace", (long long)w, S.left, B);
-    if (S.done * hop + n > INT32_MAX) WN_FAIL(c, WN_E_SHAPE, "wn_synth_stream_push: utterance longer than 2^31 samples");
     if (n > 0 && !out_samples) WN_FAIL(c, WN_E_ARG, "wn_synth_stream_push: null out_samples");
     hipStream_t st = (hipStream_t)stream;
     // pending frames [wstart, pushed): the part of the previous window still needed + the new frames, into the other buffer (the stream's
     // state advances only once everything below is enqueued; a failure after the first enqueue poisons the stream)
-    float* win = S.pend[S.cur ^ 1];
+    float* win = S.pend[u.cur ^ 1];
     S.poisoned = true;
     if (w > 0) {
         const int64_t rows = (int64_t)B * c->C;
-        hipLaunchKernelGGL(wn_stream_window_kernel, dim3(cdiv(rows * w, 256)), dim3(256), 0, st, S.pend[S.cur], S.pushed - S.pend_first, wstart - S.pend_first,
-                           S.pushed - wstart, cc, Tn, win, w, rows);
+        hipLaunchKernelGGL(wn_stream_window_kernel, dim3(cdiv(rows * w, 256)), dim3(256), 0, st, S.pend[u.cur], u.pushed - u.pend_first, wstart - u.pend_first,
+                           u.pushed - wstart, cc, Tn, win, w, rows);
         WN_LAUNCH_CHECK(c);
     }
     if (n > 0) {
@@ -691,19 +706,19 @@ extern "C" int wn_synth_stream_push(wn_ctx* c, const float* cc, int32_t Tn, int3
         if ((rc = wn_upsample_fwd(c, nullptr, win, B, (int)w, st))) return rc;
         const int nps = wn_noise_per_step(c);
         if (!noise) {      // the device stream of `seed` over the whole utterance, continued: elements [t0 B nps, (t0 + n) B nps)
-            if ((rc = wn_fill_noise_span(c, c->noise_buf, S.done * hop * B * nps, (int64_t)T * B * nps, S.seed, st))) return rc;
+            if ((rc = wn_fill_noise_span(c, c->noise_buf, u.done * hop * B * nps, (int64_t)T * B * nps, S.seed, st))) return rc;
             noise = c->noise_buf;
         }
         WnSpan sp;
-        sp.t0 = (int)(S.done * hop); sp.Tcb = (int)(w * hop); sp.cbt_off = (int)((S.done - wstart) * hop); sp.carry = S.carry; sp.gbias = S.gbias;
+        sp.t0 = (int)(u.done * hop); sp.Tcb = (int)(w * hop); sp.cbt_off = (int)((u.done - wstart) * hop); sp.carry = S.carry; sp.gbias = S.gbias;
         rc = S.path == 2 ? wn_pipe_span(c, B, T, sp, noise, test_inputs, out_samples, out_raw, st)
            : S.path == 3 ? wn_synth_f32_span(c, B, T, sp, noise, test_inputs, out_samples, out_raw, S.spg, st)
                          : wn_synth_span(c, B, T, sp, noise, test_inputs, out_samples, out_raw, S.spg, st);
         if (rc) return rc;
-        c->fB = B; c->fT = T; c->fTc = (int)(gen_end - S.done); c->fup_off = sp.cbt_off; c->fup_pitch = sp.Tcb;
+        c->fB = B; c->fT = T; c->fTc = (int)(pl.gen_end - u.done); c->fup_off = sp.cbt_off; c->fup_pitch = sp.Tcb;
     }
     S.poisoned = false;
-    S.cur ^= 1; S.pend_first = wstart; S.pushed = pushed; S.done = gen_end;
+    commit_push(u, pl, true);
     *n_out = (int32_t)n;
     if (final) S.open = false;
     return WN_OK;
@@ -795,7 +810,7 @@ extern "C" int wn_synth_slot_frames_done(const wn_ctx* c, int32_t slot) {
     if (!c) return WN_E_ARG;
     if (!c->slots.open || c->slots.poisoned) return WN_E_STATE;
     if (slot < 0 || slot >= c->slots.B) return WN_E_ARG;
-    return c->slots.s[slot].live ? (int)c->slots.s[slot].done : -1;
+    return c->slots.s[slot].live ? (int)c->slots.s[slot].u.done : -1;
 }
 
 extern "C" int wn_synth_slots_end(wn_ctx* c) {
@@ -846,21 +861,18 @@ extern "C" int wn_synth_slots_push(wn_ctx* c, const float* cc, int32_t Tn, const
     if (S.poisoned) WN_FAIL(c, WN_E_STATE, "wn_synth_slots_push: a pipeline run of this session failed; begin a new session");
     const int B = S.B, hop = c->hop, C = c->C;
     // ---- plan (host only: a rejected push leaves every slot as it was)
-    int64_t pushed[32], gen_end[32], wstart[32], w[32]; int nb[32]; int n_max = 0;
+    WnPushPlan pl[32] = {}; int64_t w[32]; int nb[32]; int n_max = 0;
     for (int b = 0; b < B; ++b) {
         const auto& s = S.s[b];
-        nb[b] = 0; w[b] = 0; pushed[b] = s.pushed; gen_end[b] = s.done; wstart[b] = s.pend_first;
+        nb[b] = 0; w[b] = 0;
         if (frames[b] < 0 || frames[b] > Tn) WN_FAIL(c, WN_E_ARG, "wn_synth_slots_push: frames[%d] = %d outside [0, Tn = %d]", b, frames[b], Tn);
         if (!s.live) { if (frames[b] > 0) WN_FAIL(c, WN_E_STATE, "wn_synth_slots_push: %d frames for slot %d, which is idle (wn_synth_slot_open first)", frames[b], b); continue; }
-        pushed[b] = s.pushed + frames[b];
-        gen_end[b] = final_[b] ? pushed[b] : std::max(s.done, pushed[b] - S.right);
-        const int64_t n = (gen_end[b] - s.done) * hop;
-        wstart[b] = std::max<int64_t>(0, s.done - S.left); w[b] = pushed[b] - wstart[b];
-        if (n > c->maxT) WN_FAIL(c, WN_E_SHAPE, "wn_synth_slots_push: %lld samples for slot %d in one push exceed max_time = %d", (long long)n, b, c->maxT);
-        if (w[b] > S.capw || (n > 0 && w[b] * hop > c->NT))
-            WN_FAIL(c, WN_E_SHAPE, "wn_synth_slots_push: slot %d: a window of %lld frames (%d of left context + the frames not yet generated) exceeds the workspace", b, (long long)w[b], S.left);
-        if (s.done * hop + n > INT32_MAX) WN_FAIL(c, WN_E_SHAPE, "wn_synth_slots_push: utterance longer than 2^31 samples");
-        nb[b] = (int)n; n_max = std::max(n_max, nb[b]);
+        char who[40]; snprintf(who, sizeof who, "wn_synth_slots_push: slot %d", b);
+        if ((rc = plan_push(c, who, s.u, frames[b], final_[b] != 0, S.left, S.right, pl[b]))) return rc;
+        w[b] = pl[b].w;
+        if (w[b] > S.capw || (pl[b].n > 0 && w[b] * hop > c->NT))
+            WN_FAIL(c, WN_E_SHAPE, "%s: a window of %lld frames (%d of left context + the frames not yet generated) exceeds the workspace", who, (long long)w[b], S.left);
+        nb[b] = (int)pl[b].n; n_max = std::max(n_max, nb[b]);
     }
     if (n_max > 0 && (!out_samples || out_pitch < n_max)) WN_FAIL(c, WN_E_ARG, "wn_synth_slots_push: null out_samples or out_pitch %d < %d samples", out_pitch, n_max);
     hipStream_t st = (hipStream_t)stream;
@@ -871,9 +883,9 @@ extern "C" int wn_synth_slots_push(wn_ctx* c, const float* cc, int32_t Tn, const
     {
         WnSlotWin p; memset(&p, 0, sizeof p); int64_t wmax = 0;
         for (int b = 0; b < B; ++b) {
-            const auto& s = S.s[b];
-            if (!s.live || w[b] <= 0 || (frames[b] == 0 && wstart[b] == s.pend_first)) continue;
-            p.prev_cols[b] = (int)(s.pushed - s.pend_first); p.drop[b] = (int)(wstart[b] - s.pend_first); p.keep[b] = (int)(s.pushed - wstart[b]); p.w[b] = (int)w[b]; p.cur[b] = s.cur;
+            const WnUtt& u = S.s[b].u; const int64_t wstart = pl[b].wstart;
+            if (!S.s[b].live || w[b] <= 0 || (frames[b] == 0 && wstart == u.pend_first)) continue;
+            p.prev_cols[b] = (int)(u.pushed - u.pend_first); p.drop[b] = (int)(wstart - u.pend_first); p.keep[b] = (int)(u.pushed - wstart); p.w[b] = (int)w[b]; p.cur[b] = u.cur;
             rebuilt[b] = true; wmax = std::max(wmax, w[b]);
         }
         if (wmax > 0) {
@@ -893,7 +905,7 @@ extern "C" int wn_synth_slots_push(wn_ctx* c, const float* cc, int32_t Tn, const
             for (int b = b0; b < B && ng < gcap; ++b) {
                 if (nb[b] <= 0 || grouped[b] || w[b] != gw) continue;
                 grouped[b] = true;
-                g.slot[ng] = b; g.cur[ng] = S.s[b].cur ^ (rebuilt[b] ? 1 : 0); g.off[ng] = (int)((S.s[b].done - wstart[b]) * hop); g.n[ng] = nb[b]; nmaxg = std::max(nmaxg, nb[b]); ++ng;
+                g.slot[ng] = b; g.cur[ng] = S.s[b].u.cur ^ (rebuilt[b] ? 1 : 0); g.off[ng] = (int)((S.s[b].u.done - pl[b].wstart) * hop); g.n[ng] = nb[b]; nmaxg = std::max(nmaxg, nb[b]); ++ng;
             }
             hipLaunchKernelGGL(wn_slots_gather_kernel, dim3(cdiv(C * gw, 256), ng), dim3(256), 0, st, S.pend[0], S.pend[1], region, S.gwin, C * gw, g);
             WN_LAUNCH_CHECK(c);
@@ -904,12 +916,12 @@ extern "C" int wn_synth_slots_push(wn_ctx* c, const float* cc, int32_t Tn, const
         }
         if (!noise) {      // every generating slot's own one-stream noise, continued at its sample done * hop
             uint64_t seed[32]; int64_t first[32], cnt[32]; const int nps = wn_noise_per_step(c);
-            for (int b = 0; b < B; ++b) { seed[b] = S.s[b].seed; first[b] = S.s[b].done * hop * nps; cnt[b] = (int64_t)nb[b] * nps; }
+            for (int b = 0; b < B; ++b) { seed[b] = S.s[b].seed; first[b] = S.s[b].u.done * hop * nps; cnt[b] = (int64_t)nb[b] * nps; }
             if ((rc = wn_fill_noise_slots(c, c->noise_buf, B, seed, first, cnt, st))) return rc;
             noise = c->noise_buf;
         }
         int32_t st0[32], snl[32]; uint32_t fresh = 0;
-        for (int b = 0; b < 32; ++b) { st0[b] = b < B ? (int)(S.s[b].done * hop) : 0; snl[b] = b < B ? nb[b] : 0; if (b < B && nb[b] > 0 && S.s[b].done == 0) fresh |= 1u << b; }
+        for (int b = 0; b < 32; ++b) { st0[b] = b < B ? (int)(S.s[b].u.done * hop) : 0; snl[b] = b < B ? nb[b] : 0; if (b < B && nb[b] > 0 && S.s[b].u.done == 0) fresh |= 1u << b; }
         WnSpan sp;
         sp.t0 = 0; sp.Tcb = n_max; sp.cbt_off = 0; sp.carry = S.carry; sp.gbias = S.gbias;
         sp.st0 = st0; sp.snl = snl; sp.out_pitch = out_pitch; sp.cbt = S.cbt; sp.reslice = S.first_run; sp.tdev = S.tdev; sp.fresh = fresh;
@@ -924,8 +936,7 @@ extern "C" int wn_synth_slots_push(wn_ctx* c, const float* cc, int32_t Tn, const
         auto& s = S.s[b];
         n_out[b] = nb[b];
         if (!s.live) continue;
-        if (rebuilt[b]) { s.cur ^= 1; s.pend_first = wstart[b]; }
-        s.pushed = pushed[b]; s.done = gen_end[b];
+        commit_push(s.u, pl[b], rebuilt[b]);
         if (final_[b]) s.live = false;
     }
     return WN_OK;

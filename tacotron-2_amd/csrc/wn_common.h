@@ -97,6 +97,10 @@ struct PackedW {          // one fragment-ordered bf16 matrix
 
 struct WnLayerPacks { PackedW w1, wo, ws, w2T, w1T; };
 
+// progress of one utterance that arrives in pushes (a stream, or one slot of a session): mel frames pushed so far, frames generated, the pending
+// window [pend_first, pushed) of mel frames and which of the two window buffers holds it
+struct WnUtt { int64_t pushed = 0, done = 0, pend_first = 0; int cur = 0; };
+
 struct wn_ctx {
     wn_config cfg;
     std::string err;
@@ -201,12 +205,12 @@ struct wn_ctx {
     void* f32 = nullptr;                  // fp32-forward state (wn_f32.hip), allocated on the first forward of a cfg.compute_dtype = WN_COMPUTE_F32 context
     bool fwd_was_f32 = false;
     float* dy32_next = nullptr;           // the next wn_loss_run also writes d y_hat in fp32 here ([rows][ldDY]; fp32 training mode)
-    // streaming synthesis (wn_synth_stream_*): frames pushed so far, frames generated, the pending window [pend_first, pushed) of mel frames
-    // ([B][C][pushed - pend_first], ping-pong), the stream's own global-conditioning bias and the pipeline's carried next input per stream
+    // streaming synthesis (wn_synth_stream_*): the utterance's progress (WnUtt; window [B][C][pushed - pend_first], ping-pong), the stream's own
+    // global-conditioning bias and the pipeline's carried next input per stream
     struct {
         bool open = false, poisoned = false; int path = 0;          // path: 1 launch-per-layer, 2 pipeline, 3 fp32 launch-per-layer
         int B = 0, spg = 0, left = 0, right = 0; uint64_t seed = 0;
-        int64_t pushed = 0, done = 0, pend_first = 0; int cur = 0;
+        WnUtt u;
         float* pend[2] = {nullptr, nullptr}; int64_t pend_cap = 0;      // floats per buffer
         float* gbias = nullptr;                                        // [L][B][G] (gin > 0)
         int32_t* carry = nullptr;                                      // [32] fed-back sample bits / class id of every stream (pipeline)
@@ -216,7 +220,7 @@ struct wn_ctx {
     // Everything the session needs is sized by slots_alloc (wn_create on inference-only contexts): nothing is allocated by a push.
     struct WnSlots {
         bool open = false, poisoned = false; int path = 0, B = 0, spg = 0, left = 0, right = 0, capw = 0; bool first_run = true;
-        struct Slot { bool live = false; uint64_t seed = 0; int64_t pushed = 0, done = 0, pend_first = 0; int cur = 0; } s[32];
+        struct Slot { bool live = false; uint64_t seed = 0; WnUtt u; } s[32];
         float* pend[2] = {nullptr, nullptr};      // [32 regions][C * capw] pending frames of every slot (ping-pong per slot)
         float* gwin = nullptr;                    // [group][C][w]: the windows of the slots upsampled together (equal window width)
         bf16_t* cbt = nullptr;                    // [B][n_max][C]: the conditioning rows every slot's steps of this push read
@@ -234,7 +238,9 @@ struct wn_ctx {
 // A push of a slot session (st0 != nullptr): stream s starts at ITS absolute index st0[s] (0: silence, no past), generates snl[s] <= T samples and
 // takes part in the remaining T - snl[s] steps as a dummy that writes nothing; outputs have a row pitch of out_pitch samples; cbt is the session's
 // own table [B][Tcb][C]; reslice: first run of the session (the pipeline builds its weight images)
-struct WnSpan { int t0, Tcb, cbt_off; int32_t* carry; const float* gbias;
+// A whole utterance (wn_synthesize) is the span t0 = 0, cbt_off = 0, Tcb = T, carry = nullptr, gbias = ctx->gbias with `whole` set: not a push, so a
+// failed run of it poisons no stream or session that is opened afterwards (wn_pipe_check)
+struct WnSpan { int t0, Tcb, cbt_off; int32_t* carry; const float* gbias; bool whole = false;
                 const int32_t* st0 = nullptr; const int32_t* snl = nullptr; int out_pitch = 0; const bf16_t* cbt = nullptr; bool reslice = false; int32_t* tdev = nullptr; uint32_t fresh = 0; };
 
 extern std::string g_create_err;
@@ -247,6 +253,29 @@ extern std::string g_create_err;
 
 static inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
+// ---- samplers: mixture.py:76-107, gaussian.py:39-52, wavenet.py:861-867.  mode 0 MoL, 1 Gaussian, 2 categorical; p: the output channels of one
+// sample at a pitch of `stride` floats; nz: its wn_noise_per_step values
+static inline int wn_sample_mode(const wn_ctx* c) { return c->cfg.input_type == WN_INPUT_MULAW_QUANTIZE ? 2 : (c->O == 2 ? 1 : 0); }
+static inline float wn_sample_lsmin(const wn_ctx* c) { return wn_sample_mode(c) == 1 ? c->cfg.log_scale_min_gauss : c->cfg.log_scale_min; }
+__device__ __forceinline__ float sample_mol(const float* p, int64_t stride, int M, const float* nz, float log_scale_min) {
+    float best = -INFINITY; int bi = 0;
+    for (int i = 0; i < M; ++i) { const float v = p[(int64_t)i * stride] - logf(-logf(nz[i])); if (v > best) { best = v; bi = i; } }
+    const float mu = p[(int64_t)(M + bi) * stride];
+    const float ls = fmaxf(p[(int64_t)(2 * M + bi) * stride], log_scale_min);
+    const float u = nz[M];
+    const float x = mu + expf(ls) * (logf(u) - logf(1.0f - u));
+    return fminf(fmaxf(x, -1.0f), 1.0f);
+}
+__device__ __forceinline__ float sample_gauss(const float* p, int64_t stride, const float* nz, float lsmin) {
+    const float x = p[0] + expf(fmaxf(p[stride], lsmin)) * nz[0];
+    return fminf(fmaxf(x, -1.0f), 1.0f);
+}
+__device__ __forceinline__ int sample_cat(const float* p, int64_t stride, int Q, const float* nz) {
+    float best = -INFINITY; int bi = 0;
+    for (int q = 0; q < Q; ++q) { const float v = p[(int64_t)q * stride] - logf(-logf(nz[q])); if (v > best) { best = v; bi = q; } }
+    return bi;
+}
+
 // ---- cross-TU entry points (host) ---------------------------------------------------------------
 int wn_build_packs(wn_ctx* ctx);
 int wn_launch_pack(wn_ctx* ctx, const float* params, hipStream_t st);
@@ -255,7 +284,7 @@ int wn_bwd_impl(wn_ctx* ctx, float* grads, hipStream_t st);
 int wn_optim_impl(wn_ctx* ctx, float* p, const float* g, float* m, float* v, float* ema, float lr, int64_t step, hipStream_t st);
 int wn_synth_impl(wn_ctx* ctx, const float* c, int B, int Tc, const float* noise, uint64_t seed,
                   const void* test_inputs, void* out_samples, float* out_raw, int steps_per_graph, hipStream_t st);
-// one push of an open stream (conditioning already upsampled into cbt): T samples on the path the stream was opened with
+// T samples of a span (conditioning already upsampled into cbt / CUP) on one of the three paths: the only way into each of them
 int wn_synth_span(wn_ctx* ctx, int B, int T, const WnSpan& sp, const float* noise, const void* test_inputs, void* out_samples, float* out_raw,
                   int steps_per_graph, hipStream_t st);
 bool wn_synth_takes_pipe(const wn_ctx* ctx, int B, int steps_per_graph);      // wn_synthesize's path choice (bf16 modes)
@@ -270,8 +299,6 @@ int wn_gbias_row(wn_ctx* ctx, const void* g_dev, float* table, int B, int slot, 
 void wn_synth_free(wn_ctx* ctx);
 void wn_synth_f32_free(wn_ctx* ctx);
 int wn_synth_f32_reserve(wn_ctx* ctx, int B);
-int wn_synth_f32_impl(wn_ctx* ctx, const float* c, int B, int Tc, const float* noise, const void* test_inputs,
-                      void* out_samples, float* out_raw, int steps_per_graph, hipStream_t st);      // fp32 weights / queues / accumulation
 void wn_pipe_free(wn_ctx* ctx);
 bool wn_pipe_eligible(const wn_ctx* ctx, int B);
 int wn_pipe_reserve(wn_ctx* ctx, int B, int T);            // size every pipeline buffer for (B, T) (no-op when already large enough)
@@ -279,8 +306,6 @@ int wn_synth_reserve(wn_ctx* ctx);                        // state of the launch
 int wn_pipe_check(wn_ctx* ctx, bool wait);                // pending abort flag of the last pipeline run -> WN_E_HIP
 int wn_noise_reserve(wn_ctx* ctx, int B, int T);
 int wn_fill_noise_impl(wn_ctx* ctx, float* noise, int B, int T, uint64_t seed, hipStream_t st);
-int wn_pipe_synthesize(wn_ctx* ctx, const float* c, int B, int Tc, const float* noise, const void* test_inputs,
-                       void* out_samples, float* out_raw, hipStream_t st);
 extern "C" int wn_noise_per_step(const wn_ctx* c);
 int wn_upsample_fwd(wn_ctx* ctx, const float* params_unused, const float* c, int B, int Tc, hipStream_t st);
 int wn_weightnorm_apply(wn_ctx* ctx, const float* raw_params, hipStream_t st);     // raw (v, g, bias) -> params_dev (effective)

@@ -306,25 +306,7 @@ extern "C" int wn_argmax_channels(const float* l, int32_t* o, int32_t B, int32_t
     if (!l || !o || B <= 0 || Q <= 0 || T <= 0) return WN_E_ARG; EW_LAUNCH(wn_argmax_kernel, (int64_t)B * T, st, l, o, B, Q, T); }
 
 // =================================================================================== samplers
-// mixture.py:76-107, gaussian.py:39-52, wavenet.py:861-867; noise [T][B][nps] supplied by the caller.
-__device__ __forceinline__ float sample_mol(const float* p, int64_t stride, int M, const float* nz, float log_scale_min) {
-    float best = -INFINITY; int bi = 0;
-    for (int i = 0; i < M; ++i) { const float v = p[(int64_t)i * stride] - logf(-logf(nz[i])); if (v > best) { best = v; bi = i; } }
-    const float mu = p[(int64_t)(M + bi) * stride];
-    const float ls = fmaxf(p[(int64_t)(2 * M + bi) * stride], log_scale_min);
-    const float u = nz[M];
-    const float x = mu + expf(ls) * (logf(u) - logf(1.0f - u));
-    return fminf(fmaxf(x, -1.0f), 1.0f);
-}
-__device__ __forceinline__ float sample_gauss(const float* p, int64_t stride, const float* nz, float lsmin) {
-    const float x = p[0] + expf(fmaxf(p[stride], lsmin)) * nz[0];
-    return fminf(fmaxf(x, -1.0f), 1.0f);
-}
-__device__ __forceinline__ int sample_cat(const float* p, int64_t stride, int Q, const float* nz) {
-    float best = -INFINITY; int bi = 0;
-    for (int q = 0; q < Q; ++q) { const float v = p[(int64_t)q * stride] - logf(-logf(nz[q])); if (v > best) { best = v; bi = q; } }
-    return bi;
-}
+// wn_sample: the samplers of wn_common.h over a whole [B][O][T] tensor; noise [T][B][nps] supplied by the caller.
 __global__ void wn_sample_kernel(const float* __restrict__ yhat, const float* __restrict__ noise, void* __restrict__ out,
                                  int B, int T, int O, int mode, int nps, float lsmin) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -337,9 +319,7 @@ __global__ void wn_sample_kernel(const float* __restrict__ yhat, const float* __
     else ((int32_t*)out)[i] = sample_cat(p, T, O, nz);
 }
 int wn_sample_impl(wn_ctx* c, const float* y_hat, int B, int T, const float* noise, void* out, hipStream_t st) {
-    const int mode = c->cfg.input_type == WN_INPUT_MULAW_QUANTIZE ? 2 : (c->O == 2 ? 1 : 0);
-    const float lsmin = mode == 1 ? c->cfg.log_scale_min_gauss : c->cfg.log_scale_min;
-    hipLaunchKernelGGL(wn_sample_kernel, dim3(cdiv((int64_t)B * T, 256)), dim3(256), 0, st, y_hat, noise, out, B, T, c->O, mode, wn_noise_per_step(c), lsmin);
+    hipLaunchKernelGGL(wn_sample_kernel, dim3(cdiv((int64_t)B * T, 256)), dim3(256), 0, st, y_hat, noise, out, B, T, c->O, wn_sample_mode(c), wn_noise_per_step(c), wn_sample_lsmin(c));
     WN_LAUNCH_CHECK(c);
     return WN_OK;
 }

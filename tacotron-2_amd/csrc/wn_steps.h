@@ -1,0 +1,92 @@
+// Host driver shared by the two launch-per-layer synthesis paths (wn_synth.hip: bf16 MFMA steps, wn_synth_f32.hip: fp32 steps).
+//
+// WnStepRunner owns what "run n steps of a span" needs besides the step itself: the ctx-owned stream the steps are captured and replayed on (the
+// caller's may be the legacy NULL stream, which cannot be captured), the two events that order it behind and in front of the caller's stream, and the
+// hipGraphExec_t of `steps` steps with the key it was captured for.  Every step kernel reads its time index from device memory, so a graph is replayed
+// unchanged for as long as the key -- every pointer and size the captured launches carry -- matches; anything else is captured again.
+//     enter(caller) -> run(n, key, step) -> leave(caller);   free() at wn_destroy.
+#pragma once
+#include "wn_common.h"
+
+struct WnStepKey {      // compared bytewise: pointers first, no padding
+    const void* p[7];   // noise, test_inputs, out_samples, out_raw, conditioning rows, gate-bias table, slot table (bf16 path; else null)
+    int steps, B, T, Tcb;   // steps per graph, streams, row pitch of the outputs, conditioning rows per stream
+};
+static_assert(sizeof(WnStepKey) == 7 * sizeof(void*) + 4 * sizeof(int), "WnStepKey is compared with memcmp");
+
+struct WnStepRunner {
+    hipStream_t st = nullptr; hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    hipGraphExec_t gexec = nullptr; WnStepKey key = {};
+
+    int create(wn_ctx* c) {      // (once; inference-only contexts: at wn_create, through the path's reserve)
+        if (!st) WN_HIP(c, hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        if (!ev0) WN_HIP(c, hipEventCreateWithFlags(&ev0, hipEventDisableTiming));
+        if (!ev1) WN_HIP(c, hipEventCreateWithFlags(&ev1, hipEventDisableTiming));
+        return WN_OK;
+    }
+    void drop_graph() { if (gexec) { hipGraphExecDestroy(gexec); gexec = nullptr; } }
+    void free() {
+        drop_graph();
+        if (ev0) hipEventDestroy(ev0);
+        if (ev1) hipEventDestroy(ev1);
+        if (st) { (void)hipStreamSynchronize(st); hipStreamDestroy(st); }
+        st = nullptr; ev0 = ev1 = nullptr;
+    }
+    // everything between enter and leave runs on `st`, after what the caller's stream holds now and before its next operation
+    int enter(wn_ctx* c, hipStream_t caller) {
+        WN_HIP(c, hipEventRecord(ev0, caller));
+        WN_HIP(c, hipStreamWaitEvent(st, ev0, 0));
+        return WN_OK;
+    }
+    int leave(wn_ctx* c, hipStream_t caller) {
+        WN_HIP(c, hipEventRecord(ev1, st));
+        WN_HIP(c, hipStreamWaitEvent(caller, ev1, 0));
+        return WN_OK;
+    }
+    // n steps: replays of the graph of k.steps steps (k.steps > 1), then single steps.  step(stream) enqueues one step and returns a WN_ code;
+    // a failed enqueue ends the capture before returning.
+    template <class Step> int run(wn_ctx* c, int n, const WnStepKey& k, Step step) {
+        int rc, done = 0;
+        if (k.steps > 1 && n >= k.steps) {
+            if (!gexec || memcmp(&k, &key, sizeof k) != 0) {
+                drop_graph();
+                hipGraph_t graph;
+                WN_HIP(c, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
+                for (int i = 0; i < k.steps; ++i)
+                    if ((rc = step(st))) { hipStreamEndCapture(st, &graph); return rc; }
+                WN_HIP(c, hipStreamEndCapture(st, &graph));
+                WN_HIP(c, hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0));
+                hipGraphDestroy(graph);
+                key = k;
+            }
+            for (; done + k.steps <= n; done += k.steps) WN_HIP(c, hipGraphLaunch(gexec, st));
+        }
+        for (; done < n; ++done) if ((rc = step(st))) return rc;
+        return WN_OK;
+    }
+};
+
+// ---- the first input of a span, for queues of bf16 (wn_synth.hip) or fp32 (wn_synth_f32.hip) elements
+__device__ __forceinline__ void wn_queue_store(bf16_t* q, float v) { *q = f2bf(v); }
+__device__ __forceinline__ void wn_queue_store(float* q, float v) { *q = v; }
+
+// initial input (silence, wavenet.py:433-445) -> queue 0 slot 0; t = 0
+template <class Q>
+__global__ void wn_synth_init(const float* __restrict__ Wf, const float* __restrict__ bf_, int R, int mode, int start_id, Q* __restrict__ ring0, int B, int32_t* t_dev) {
+    for (int o = threadIdx.x; o < B * R; o += blockDim.x) {
+        const int n = o / R, r = o - n * R;
+        wn_queue_store(ring0 + (size_t)n * R + r, (mode == 2) ? Wf[(size_t)start_id * R + r] + bf_[r] : bf_[r]);      // x = 0 for raw / mulaw
+    }
+    if (threadIdx.x == 0) { t_dev[0] = 0; t_dev[1] = 0; }
+}
+
+// A span that begins an utterance (t0 == 0) zeroes the queues (wavenet.py:815-816: `SB` streams per queue row) and starts from silence; any other one
+// continues from the queues, the time index and queue 0's next input its predecessor left, and only learns its first sample (t_dev[1]).
+template <class Q>
+static int wn_span_start(wn_ctx* c, const std::vector<Q*>& ring, const std::vector<int>& mask, int SB, int B, int32_t* t_dev, int t0, hipStream_t st) {
+    if (t0 != 0) { WN_HIP(c, hipMemsetD32Async((hipDeviceptr_t)(t_dev + 1), t0, 1, st)); return WN_OK; }
+    for (int l = 0; l < c->L; ++l) WN_HIP(c, hipMemsetAsync(ring[l], 0, (size_t)(mask[l] + 1) * SB * c->R * sizeof(Q), st));
+    hipLaunchKernelGGL(wn_synth_init<Q>, dim3(1), dim3(256), 0, st, c->params_dev + c->first.dil_k, c->params_dev + c->first.dil_b, c->R, wn_sample_mode(c), 127, ring[0], B, t_dev);
+    WN_LAUNCH_CHECK(c);
+    return WN_OK;
+}

@@ -9,8 +9,10 @@
 //     training kernels use (one coalesced 1-KiB load per wave and k-step, L2-resident), the 4 waves of
 //     a workgroup split K and reduce through LDS;
 //   * the whole step (2L+3 kernels) is captured once into a hipGraph of `steps_per_graph` steps; all
-//     kernels read the time index from device memory so the graph is replayed unchanged.
-#include "wn_common.h"
+//     kernels read the time index from device memory so the graph is replayed unchanged (WnStepRunner, wn_steps.h).
+// Host side: wn_synth_impl does the whole-utterance work of wn_synthesize once for all three paths and hands each of them a WnSpan;
+// wn_synth_span is the only way into this path (a whole utterance, a stream push, a push of a slot session).
+#include "wn_steps.h"
 #include <stdlib.h>
 
 struct Synth {
@@ -21,10 +23,7 @@ struct Synth {
     bf16_t* h2 = nullptr;          // [32][S]
     float* yraw = nullptr;         // [32][OP]
     int32_t* t_dev = nullptr;      // [0] absolute time index of the next step, [1] first sample of the running span (0 for wn_synthesize; a stream push: its t0)
-    hipStream_t priv = nullptr;    // capture / replay happens on a ctx-owned stream (the caller's may be the legacy
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;   // NULL stream, which cannot be captured); ordered by events
-    bf16_t** ring_tab = nullptr;   // device table of ring pointers
-    hipGraphExec_t gexec = nullptr; int g_steps = 0; int g_B = 0; const void* g_key[7] = {0, 0, 0, 0, 0, 0, 0}; int g_T = 0, g_Tcb = 0;
+    WnStepRunner run;              // the ctx-owned stream the steps run on, the step graph and its key
     // slot sessions: sl != nullptr while a push of a session is enqueued -- [0..31] absolute index of every stream's next sample, [32..63] samples it generates
     // in this push, [64] push-local step.  A stream whose count is used up (or an idle slot) is a dummy for the rest of the push: its operand columns are
     // zero, nothing of it is stored.  Values live in device memory, so captured graphs stay valid across pushes.
@@ -244,23 +243,11 @@ __global__ __launch_bounds__(256) void wn_synth_sample(const float* __restrict__
         const float* p = yraw + (size_t)n * OP;
         const float* nz = noise + ((size_t)tl * B + n) * nps;
         if (mode == 2) {
-            float best = -INFINITY; int bi = 0;
-            for (int q = 0; q < O; ++q) { const float v = p[q] - logf(-logf(nz[q])); if (v > best) { best = v; bi = q; } }
+            const int bi = sample_cat(p, 1, O, nz);
             ((int32_t*)out_samples)[(size_t)n * T + tl] = bi;
             nxt_i[n] = test_inputs ? ((const int32_t*)test_inputs)[(size_t)n * T + tl] : bi;
         } else {
-            float x;
-            if (mode == 0) {
-                const int M = O / 3;
-                float best = -INFINITY; int bi = 0;
-                for (int i = 0; i < M; ++i) { const float v = p[i] - logf(-logf(nz[i])); if (v > best) { best = v; bi = i; } }
-                const float ls = fmaxf(p[2 * M + bi], lsmin);
-                const float u = nz[M];
-                x = p[M + bi] + expf(ls) * (logf(u) - logf(1.0f - u));
-            } else {
-                x = p[0] + expf(fmaxf(p[1], lsmin)) * nz[0];
-            }
-            x = fminf(fmaxf(x, -1.0f), 1.0f);
+            const float x = mode == 0 ? sample_mol(p, 1, O / 3, nz, lsmin) : sample_gauss(p, 1, nz, lsmin);
             ((float*)out_samples)[(size_t)n * T + tl] = x;
             nxt_f[n] = test_inputs ? ((const float*)test_inputs)[(size_t)n * T + tl] : x;
         }
@@ -277,17 +264,6 @@ __global__ __launch_bounds__(256) void wn_synth_sample(const float* __restrict__
     __syncthreads();
     if (sl) { if (tid < B && live_n[tid]) sl[tid] = t_n[tid] + 1; if (tid == 0) sl[WN_SL_STEP] = tl + 1; }
     else if (tid == 0) *t_dev = t + 1;
-}
-
-// initial input (silence, wavenet.py:433-445) -> ring 0 slot 0; t = 0
-__global__ void wn_synth_init(const float* __restrict__ Wf, const float* __restrict__ bf_, int R, int mode, int start_id,
-                              bf16_t* __restrict__ ring0, int B, int32_t* t_dev) {
-    for (int o = threadIdx.x; o < B * R; o += blockDim.x) {
-        const int n = o / R, r = o - n * R;
-        const float v = (mode == 2) ? Wf[(size_t)start_id * R + r] + bf_[r] : bf_[r];      // x = 0 for raw / mulaw
-        ring0[((size_t)n) * R + r] = f2bf(v);
-    }
-    if (threadIdx.x == 0) { t_dev[0] = 0; t_dev[1] = 0; }
 }
 
 // a push of a slot session: the samples every stream generates, the push-local step, and for the slots opened with this push (bit n of `fresh`) the
@@ -311,8 +287,7 @@ void wn_synth_free(wn_ctx* c) {
     for (auto p : s->ring) if (p) hipFree(p);
     if (s->ucur) hipFree(s->ucur); if (s->skip_acc) hipFree(s->skip_acc); if (s->h2) hipFree(s->h2);
     if (s->yraw) hipFree(s->yraw); if (s->t_dev) hipFree(s->t_dev);
-    if (s->gexec) hipGraphExecDestroy(s->gexec);
-    if (s->ev0) hipEventDestroy(s->ev0); if (s->ev1) hipEventDestroy(s->ev1); if (s->priv) hipStreamDestroy(s->priv);
+    s->run.free();
     delete s; c->synth = nullptr;
 }
 
@@ -336,39 +311,9 @@ static int enqueue_step(wn_ctx* c, Synth* s, const bf16_t* cbt, int Tcb, const f
     }
     hipLaunchKernelGGL(wn_synth_head1, dim3(S / 32), dim3(256), 0, st, c->wh1.dev, S >> 4, S, s->skip_acc, c->skip_bias_total, c->params_dev + c->fin1_b, s->h2, B);
     hipLaunchKernelGGL(wn_synth_head2, dim3(c->OP / 32), dim3(256), 0, st, c->wh2.dev, S >> 4, S, s->h2, c->params_dev + c->fin2_b, s->yraw, c->O, c->OP, B);
-    const int mode = c->cfg.input_type == WN_INPUT_MULAW_QUANTIZE ? 2 : (c->O == 2 ? 1 : 0);
-    const float lsmin = mode == 1 ? c->cfg.log_scale_min_gauss : c->cfg.log_scale_min;
-    hipLaunchKernelGGL(wn_synth_sample, dim3(1), dim3(256), 0, st, s->yraw, c->O, c->OP, mode, wn_noise_per_step(c), lsmin, noise, test_inputs, out_samples, out_raw,
+    hipLaunchKernelGGL(wn_synth_sample, dim3(1), dim3(256), 0, st, s->yraw, c->O, c->OP, wn_sample_mode(c), wn_noise_per_step(c), wn_sample_lsmin(c), noise, test_inputs, out_samples, out_raw,
                        c->params_dev + c->first.dil_k, c->params_dev + c->first.dil_b, R, s->ring[0], s->mask[0], B, T, s->t_dev, const_cast<int32_t*>(s->sl));
     WN_LAUNCH_CHECK(c);
-    return WN_OK;
-}
-
-// T steps from the current t_dev: graphs of steps_per_graph steps (reused while the pointers and sizes match), then single steps
-static int synth_steps(wn_ctx* c, Synth* s, const bf16_t* cbt, int Tcb, const float* gbias, const float* noise, const void* test_inputs, void* out_samples,
-                       float* out_raw, int steps_per_graph, hipStream_t st, int nsteps = -1) {
-    const int T = s->T, B = s->B;      // (T: the row pitch of the outputs the kernels index with; nsteps: steps to run, T unless a slot session says otherwise)
-    if (nsteps < 0) nsteps = T;
-    int rc, done = 0;
-    if (steps_per_graph > 1 && nsteps >= steps_per_graph) {
-        const void* key[7] = {noise, test_inputs, out_samples, out_raw, cbt, gbias, s->sl};
-        const bool reuse = s->gexec && s->g_steps == steps_per_graph && s->g_B == B && s->g_T == T && s->g_Tcb == Tcb && memcmp(key, s->g_key, sizeof key) == 0;
-        if (!reuse) {
-            if (s->gexec) { hipGraphExecDestroy(s->gexec); s->gexec = nullptr; }
-            hipGraph_t graph;
-            WN_HIP(c, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-            for (int i = 0; i < steps_per_graph; ++i) {
-                rc = enqueue_step(c, s, cbt, Tcb, gbias, noise, test_inputs, out_samples, out_raw, st);
-                if (rc) { hipStreamEndCapture(st, &graph); return rc; }
-            }
-            WN_HIP(c, hipStreamEndCapture(st, &graph));
-            WN_HIP(c, hipGraphInstantiate(&s->gexec, graph, nullptr, nullptr, 0));
-            hipGraphDestroy(graph);
-            s->g_steps = steps_per_graph; s->g_B = B; s->g_T = T; s->g_Tcb = Tcb; memcpy(s->g_key, key, sizeof key);
-        }
-        for (; done + steps_per_graph <= nsteps; done += steps_per_graph) WN_HIP(c, hipGraphLaunch(s->gexec, st));
-    }
-    for (; done < nsteps; ++done) { rc = enqueue_step(c, s, cbt, Tcb, gbias, noise, test_inputs, out_samples, out_raw, st); if (rc) return rc; }
     return WN_OK;
 }
 
@@ -389,10 +334,7 @@ int wn_synth_reserve(wn_ctx* c) {
         WN_HIP(c, hipMalloc((void**)&s->h2, 32 * c->S * 2));
         WN_HIP(c, hipMalloc((void**)&s->yraw, 32 * c->OP * 4));
         WN_HIP(c, hipMalloc((void**)&s->t_dev, 8));
-        WN_HIP(c, hipStreamCreateWithFlags(&s->priv, hipStreamNonBlocking));
-        WN_HIP(c, hipEventCreateWithFlags(&s->ev0, hipEventDisableTiming));
-        WN_HIP(c, hipEventCreateWithFlags(&s->ev1, hipEventDisableTiming));
-    return WN_OK;
+    return s->run.create(c);
 }
 
 // The bf16 path of wn_synthesize(steps_per_graph) for B streams (a stream keeps the answer of its begin: the same path gives the same bits).
@@ -406,80 +348,51 @@ bool wn_synth_takes_pipe(const wn_ctx* c, int B, int steps_per_graph) {
     return want_pipe && !over_cap && wn_pipe_eligible(c, B);
 }
 
+// wn_synthesize: the whole-utterance work, once for all three paths, then the utterance as ONE span from silence on the path of steps_per_graph.
+// The conditioning is upsampled on the caller's stream: every path orders its own stream behind it when it is entered.
 int wn_synth_impl(wn_ctx* c, const float* cin, int B, int Tc, const float* noise, uint64_t, const void* test_inputs,
-                  void* out_samples, float* out_raw, int steps_per_graph, hipStream_t caller_st) {
+                  void* out_samples, float* out_raw, int steps_per_graph, hipStream_t st) {
     const int T = Tc * c->hop;
     if ((int64_t)B * T > c->NT) WN_FAIL(c, WN_E_SHAPE, "synthesis B*T = %d*%d exceeds the workspace (max_batch*max_time = %lld)", B, T, (long long)c->NT);
     if (c->gin > 0 && (!c->have_g || c->gB != B))
         WN_FAIL(c, WN_E_STATE, "global conditioning is enabled: call wn_set_global_condition with this batch (B=%d) first [wavenet.py:766-777]", B);
-    // the reference's own arithmetic (fp32 weights, queues, accumulation): its own launch-per-layer path, never the bf16 pipeline
-    if (c->cfg.compute_dtype == WN_COMPUTE_F32) return wn_synth_f32_impl(c, cin, B, Tc, noise, test_inputs, out_samples, out_raw, steps_per_graph, caller_st);
-    if (wn_synth_takes_pipe(c, B, steps_per_graph)) return wn_pipe_synthesize(c, cin, B, Tc, noise, test_inputs, out_samples, out_raw, caller_st);
-    if (steps_per_graph <= 0) steps_per_graph = 32;
-    int rc0 = wn_synth_reserve(c);
-    if (rc0) return rc0;
-    const int L = c->L, R = c->R;
-    Synth* s = c->synth;
-    c->synth_path = 1;
-    // everything below runs on the ctx-owned stream, ordered after the caller's stream and before its next op
-    hipStream_t st = s->priv;
-    WN_HIP(c, hipEventRecord(s->ev0, caller_st));
-    WN_HIP(c, hipStreamWaitEvent(st, s->ev0, 0));
-    s->B = B; s->T = T; s->sl = nullptr;
-    c->fB = B; c->fT = T; c->fTc = Tc;
-    // upsample the conditioning once for the whole utterance (wavenet.py:781-803); cbt[b*T+t][C]
-    int rc = wn_upsample_fwd(c, nullptr, cin, B, Tc, st);
+    c->fB = B; c->fT = T; c->fTc = Tc; c->fup_pitch = 0;
+    int rc = wn_upsample_fwd(c, nullptr, cin, B, Tc, st);      // cbt [B*T][C] bf16, CUP [B][C][T] fp32 (wavenet.py:781-803)
     if (rc) return rc;
-    if ((rc = wn_gbias_fwd(c, B, st))) return rc;            // global conditioning of this batch (wavenet.py:766-777)
-    for (int l = 0; l < L; ++l) WN_HIP(c, hipMemsetAsync(s->ring[l], 0, (size_t)(s->mask[l] + 1) * 32 * R * 2, st));
-    const int mode = c->cfg.input_type == WN_INPUT_MULAW_QUANTIZE ? 2 : (c->O == 2 ? 1 : 0);
-    hipLaunchKernelGGL(wn_synth_init, dim3(1), dim3(256), 0, st, c->params_dev + c->first.dil_k, c->params_dev + c->first.dil_b, R, mode, 127,
-                       s->ring[0], B, s->t_dev);
-    WN_LAUNCH_CHECK(c);
-
-    if ((rc = synth_steps(c, s, c->cbt, T, c->gbias, noise, test_inputs, out_samples, out_raw, steps_per_graph, st))) return rc;
-    WN_HIP(c, hipEventRecord(s->ev1, st));
-    WN_HIP(c, hipStreamWaitEvent(caller_st, s->ev1, 0));
-    return WN_OK;
+    if ((rc = wn_gbias_fwd(c, B, st))) return rc;              // global conditioning of this batch (wavenet.py:766-777)
+    WnSpan sp;
+    sp.t0 = 0; sp.Tcb = T; sp.cbt_off = 0; sp.carry = nullptr; sp.gbias = c->gbias; sp.whole = true;
+    // fp32: the reference's own arithmetic (fp32 weights, queues, accumulation), its own launch-per-layer path, never the bf16 pipeline
+    if (c->cfg.compute_dtype == WN_COMPUTE_F32) return wn_synth_f32_span(c, B, T, sp, noise, test_inputs, out_samples, out_raw, steps_per_graph, st);
+    if (wn_synth_takes_pipe(c, B, steps_per_graph)) return wn_pipe_span(c, B, T, sp, noise, test_inputs, out_samples, out_raw, st);
+    return wn_synth_span(c, B, T, sp, noise, test_inputs, out_samples, out_raw, steps_per_graph, st);
 }
 
-// One push of an open stream on this path: the queues, the time index and ring 0's next input are those the previous push left (its last step
-// wrote ring0[(t + 1) & mask0]); only the first push (t0 = 0) zeroes the queues and starts from silence.  The span's first sample goes to t_dev[1]
-// in device memory, so captured graphs stay valid whatever t0 is.  The conditioning rows are cbt[b][sp.cbt_off + t] of a window of sp.Tcb.
+// T steps of a span on this path.  A span with t0 > 0 continues from the queues, the time index and ring 0's next input its predecessor left (its last
+// step wrote ring0[(t + 1) & mask0]); its first sample goes to t_dev[1] in device memory, so captured graphs stay valid whatever t0 is.  The conditioning
+// rows are cbt[b][sp.cbt_off + t] of a window of sp.Tcb.  A push of a slot session (sp.st0): T steps, every stream with its own index and count in the
+// session's device table, outputs at a pitch of sp.out_pitch, conditioning rows from the session's own table.
 int wn_synth_span(wn_ctx* c, int B, int T, const WnSpan& sp, const float* noise, const void* test_inputs, void* out_samples, float* out_raw,
                   int steps_per_graph, hipStream_t caller_st) {
     int rc = wn_synth_reserve(c);
     if (rc) return rc;
-    const int L = c->L, R = c->R;
     Synth* s = c->synth;
     c->synth_path = 1;
     if (steps_per_graph <= 0) steps_per_graph = 32;
-    hipStream_t st = s->priv;
-    WN_HIP(c, hipEventRecord(s->ev0, caller_st));
-    WN_HIP(c, hipStreamWaitEvent(st, s->ev0, 0));
-    s->B = B; s->T = T; s->sl = nullptr;
-    if (sp.st0) {      // a push of a slot session: T steps, every stream with its own index and count (device memory), outputs at a pitch of sp.out_pitch
-        const int mode = c->cfg.input_type == WN_INPUT_MULAW_QUANTIZE ? 2 : (c->O == 2 ? 1 : 0);
+    if ((rc = s->run.enter(c, caller_st))) return rc;
+    hipStream_t st = s->run.st;
+    s->B = B; s->T = sp.st0 ? sp.out_pitch : T; s->sl = nullptr;      // (T of the kernels: the row pitch of the outputs)
+    if (sp.st0) {
         WnSlCounts cnt; for (int i = 0; i < 32; ++i) cnt.n[i] = i < B ? sp.snl[i] : 0;
-        hipLaunchKernelGGL(wn_synth_slots_setup, dim3(1), dim3(256), 0, st, c->params_dev + c->first.dil_k, c->params_dev + c->first.dil_b, R, mode, 127,
+        hipLaunchKernelGGL(wn_synth_slots_setup, dim3(1), dim3(256), 0, st, c->params_dev + c->first.dil_k, c->params_dev + c->first.dil_b, c->R, wn_sample_mode(c), 127,
                            s->ring[0], B, sp.tdev, cnt, sp.fresh);
         WN_LAUNCH_CHECK(c);
-        s->sl = sp.tdev; s->T = sp.out_pitch;
-        if ((rc = synth_steps(c, s, sp.cbt, sp.Tcb, sp.gbias, noise, test_inputs, out_samples, out_raw, steps_per_graph, st, T))) { s->sl = nullptr; return rc; }
-        s->sl = nullptr;
-        WN_HIP(c, hipEventRecord(s->ev1, st));
-        WN_HIP(c, hipStreamWaitEvent(caller_st, s->ev1, 0));
-        return WN_OK;
-    }
-    if (sp.t0 == 0) {
-        for (int l = 0; l < L; ++l) WN_HIP(c, hipMemsetAsync(s->ring[l], 0, (size_t)(s->mask[l] + 1) * 32 * R * 2, st));
-        const int mode = c->cfg.input_type == WN_INPUT_MULAW_QUANTIZE ? 2 : (c->O == 2 ? 1 : 0);
-        hipLaunchKernelGGL(wn_synth_init, dim3(1), dim3(256), 0, st, c->params_dev + c->first.dil_k, c->params_dev + c->first.dil_b, R, mode, 127,
-                           s->ring[0], B, s->t_dev);
-        WN_LAUNCH_CHECK(c);
-    } else WN_HIP(c, hipMemsetD32Async((hipDeviceptr_t)(s->t_dev + 1), sp.t0, 1, st));
-    if ((rc = synth_steps(c, s, c->cbt + (size_t)sp.cbt_off * c->C, sp.Tcb, sp.gbias, noise, test_inputs, out_samples, out_raw, steps_per_graph, st))) return rc;
-    WN_HIP(c, hipEventRecord(s->ev1, st));
-    WN_HIP(c, hipStreamWaitEvent(caller_st, s->ev1, 0));
-    return WN_OK;
+        s->sl = sp.tdev;
+    } else if ((rc = wn_span_start(c, s->ring, s->mask, 32, B, s->t_dev, sp.t0, st))) return rc;
+    const bf16_t* cbt = (sp.cbt ? sp.cbt : c->cbt) + (size_t)sp.cbt_off * c->C;
+    const WnStepKey key = {{noise, test_inputs, out_samples, out_raw, cbt, sp.gbias, s->sl}, steps_per_graph, B, s->T, sp.Tcb};
+    rc = s->run.run(c, T, key, [&](hipStream_t q) { return enqueue_step(c, s, cbt, sp.Tcb, sp.gbias, noise, test_inputs, out_samples, out_raw, q); });
+    s->sl = nullptr;
+    if (rc) return rc;
+    return s->run.leave(c, caller_st);
 }

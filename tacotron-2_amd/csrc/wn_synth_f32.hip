@@ -3,13 +3,14 @@
 // wavenet.py:821-886).  The real-time paths (wn_synth_pipe.hip, wn_synth.hip) keep weights and queues in bf16; this one reads
 // the fp32 parameters straight from the ctx-owned flat TF-layout buffer (no packing), keeps the Fast-WaveNet queues as fp32 ring
 // buffers and accumulates every matvec in fp32 in a fixed order, with precise tanhf / expf.  A validation mode: speed is not the
-// point (one launch per layer stage, captured in the same hipGraph scheme as the bf16 launch-per-layer path).
+// point (one launch per layer stage, captured and replayed by the same WnStepRunner as the bf16 launch-per-layer path, wn_steps.h).
+// wn_synth_f32_span is the only way in: a whole utterance arrives from wn_synth_impl as the span that starts at t0 = 0.
 //
 // Matvec shape: out[n][o] = sum_k W[k][o] * in[n][k], W row-major [K][ld] exactly as TensorFlow stores a [k, in, out] kernel
 // (reshape(kernel, [k * in, out]) of modules.py:251 is this buffer, tap 0 first), so a wave reads 64 consecutive output columns
 // of one k per load (coalesced 256 B), the input vectors of up to 8 streams sit in LDS and are read as broadcasts, the 4 waves of
 // a workgroup split K and their partial sums are added in wave order.
-#include "wn_common.h"
+#include "wn_steps.h"
 #include <stdlib.h>
 
 #define F32S_NS 8        // streams per workgroup
@@ -19,8 +20,7 @@ struct SynthF32 {
     std::vector<float*> ring; std::vector<int> mask;
     float *ucur = nullptr, *skip_acc = nullptr, *h2 = nullptr, *yraw = nullptr;
     int32_t* t_dev = nullptr;                       // [0] absolute time index of the next step, [1] first sample of the running span (a stream push's t0)
-    hipStream_t priv = nullptr; hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipGraphExec_t gexec = nullptr; int g_steps = 0, g_B = 0, g_T = 0, g_Tcb = 0; const void* g_key[6] = {0, 0, 0, 0, 0, 0};
+    WnStepRunner run;                               // the ctx-owned stream the steps run on, the step graph and its key
 };
 
 // ---- the shared core: K split over the 4 waves, one output column per lane, F32S_NS streams per workgroup.
@@ -168,23 +168,11 @@ __global__ __launch_bounds__(256) void wn_f32s_sample(const float* __restrict__ 
         const float* p = yraw + (size_t)n * OP;
         const float* nz = noise + ((size_t)tl * B + n) * nps;
         if (mode == 2) {
-            float best = -INFINITY; int bi = 0;
-            for (int q = 0; q < O; ++q) { const float v = p[q] - logf(-logf(nz[q])); if (v > best) { best = v; bi = q; } }
+            const int bi = sample_cat(p, 1, O, nz);
             ((int32_t*)out_samples)[(size_t)n * T + tl] = bi;
             nxt_i[n] = test_inputs ? ((const int32_t*)test_inputs)[(size_t)n * T + tl] : bi;
         } else {
-            float x;
-            if (mode == 0) {
-                const int M = O / 3;
-                float best = -INFINITY; int bi = 0;
-                for (int i = 0; i < M; ++i) { const float v = p[i] - logf(-logf(nz[i])); if (v > best) { best = v; bi = i; } }
-                const float ls = fmaxf(p[2 * M + bi], lsmin);
-                const float u = nz[M];
-                x = p[M + bi] + expf(ls) * (logf(u) - logf(1.0f - u));
-            } else {
-                x = p[0] + expf(fmaxf(p[1], lsmin)) * nz[0];
-            }
-            x = fminf(fmaxf(x, -1.0f), 1.0f);
+            const float x = mode == 0 ? sample_mol(p, 1, O / 3, nz, lsmin) : sample_gauss(p, 1, nz, lsmin);
             ((float*)out_samples)[(size_t)n * T + tl] = x;
             nxt_f[n] = test_inputs ? ((const float*)test_inputs)[(size_t)n * T + tl] : x;
         }
@@ -198,15 +186,6 @@ __global__ __launch_bounds__(256) void wn_f32s_sample(const float* __restrict__ 
     __syncthreads();
     if (tid == 0) *t_dev = t + 1;
 }
-// initial input (silence, wavenet.py:433-445) -> queue 0 slot 0; t = 0
-__global__ void wn_f32s_init(const float* __restrict__ Wf, const float* __restrict__ bf_, int R, int mode, int start_id,
-                             float* __restrict__ ring0, int B, int32_t* t_dev) {
-    for (int o = threadIdx.x; o < B * R; o += blockDim.x) {
-        const int n = o / R, r = o - n * R;
-        ring0[(size_t)n * R + r] = (mode == 2) ? Wf[(size_t)start_id * R + r] + bf_[r] : bf_[r];      // x = 0 for raw / mulaw
-    }
-    if (threadIdx.x == 0) { t_dev[0] = 0; t_dev[1] = 0; }
-}
 
 void wn_synth_f32_free(wn_ctx* c) {
     SynthF32* s = (SynthF32*)c->synth32;
@@ -214,10 +193,7 @@ void wn_synth_f32_free(wn_ctx* c) {
     for (float* p : s->ring) if (p) hipFree(p);
     for (float* p : {s->ucur, s->skip_acc, s->h2, s->yraw}) if (p) hipFree(p);
     if (s->t_dev) hipFree(s->t_dev);
-    if (s->gexec) hipGraphExecDestroy(s->gexec);
-    if (s->ev0) hipEventDestroy(s->ev0);
-    if (s->ev1) hipEventDestroy(s->ev1);
-    if (s->priv) { (void)hipStreamSynchronize(s->priv); hipStreamDestroy(s->priv); }
+    s->run.free();
     delete s; c->synth32 = nullptr;
 }
 
@@ -233,7 +209,7 @@ int wn_synth_f32_reserve(wn_ctx* c, int B) {
             for (float*& p : s->ring) { if (p) hipFree(p); p = nullptr; }
             for (float** p : {&s->ucur, &s->skip_acc, &s->h2, &s->yraw}) { if (*p) hipFree(*p); *p = nullptr; }
         }
-        if (s->gexec) { hipGraphExecDestroy(s->gexec); s->gexec = nullptr; }
+        s->run.drop_graph();
         s->ring.assign(L, nullptr); s->mask.assign(L, 0);
         for (int l = 0; l < L; ++l) {
             int slots = 4; while (slots < 4 * c->dil[l]) slots <<= 1;
@@ -248,10 +224,7 @@ int wn_synth_f32_reserve(wn_ctx* c, int B) {
         s->capB = B;
     }
     if (!s->t_dev) WN_HIP(c, hipMalloc((void**)&s->t_dev, 8));
-    if (!s->priv) WN_HIP(c, hipStreamCreateWithFlags(&s->priv, hipStreamNonBlocking));
-    if (!s->ev0) WN_HIP(c, hipEventCreateWithFlags(&s->ev0, hipEventDisableTiming));
-    if (!s->ev1) WN_HIP(c, hipEventCreateWithFlags(&s->ev1, hipEventDisableTiming));
-    return WN_OK;
+    return s->run.create(c);
 }
 
 static int f32s_enqueue_step(wn_ctx* c, SynthF32* s, int B, int T, const float* cup, int Tcb, const float* gbias, const float* noise, const void* test_inputs,
@@ -272,78 +245,28 @@ static int f32s_enqueue_step(wn_ctx* c, SynthF32* s, int B, int T, const float* 
                        P + c->fin1_b, 1, s->h2, S, B);
     hipLaunchKernelGGL(wn_f32s_head, dim3(cdiv(c->O, 64), ny), dim3(256), f32s_lds_bytes(S, 1), st, P + c->fin2_k, S, c->O, s->h2, (const float*)nullptr, 0,
                        P + c->fin2_b, 0, s->yraw, c->OP, B);
-    const int mode = c->cfg.input_type == WN_INPUT_MULAW_QUANTIZE ? 2 : (c->O == 2 ? 1 : 0);
-    const float lsmin = mode == 1 ? c->cfg.log_scale_min_gauss : c->cfg.log_scale_min;
-    hipLaunchKernelGGL(wn_f32s_sample, dim3(1), dim3(256), 0, st, s->yraw, c->O, c->OP, mode, wn_noise_per_step(c), lsmin, noise, test_inputs, out_samples, out_raw,
+    hipLaunchKernelGGL(wn_f32s_sample, dim3(1), dim3(256), 0, st, s->yraw, c->O, c->OP, wn_sample_mode(c), wn_noise_per_step(c), wn_sample_lsmin(c), noise, test_inputs, out_samples, out_raw,
                        P + c->first.dil_k, P + c->first.dil_b, R, s->ring[0], s->mask[0], SB, B, T, s->t_dev);
     WN_LAUNCH_CHECK(c);
     return WN_OK;
 }
 
-// sp == nullptr: wn_synthesize (upsample the whole utterance here, zero queues, silence input); else one push of a stream whose conditioning
-// window the caller upsampled (CUP final level [B][C][sp->Tcb], this span from column sp->cbt_off): the queues, the time index and queue 0's next
-// input are those the previous push left; only its first push (t0 = 0) zeroes the queues and starts from silence
-static int f32_run(wn_ctx* c, const float* cin, int B, int T, int Tc, const WnSpan* sp, const float* noise, const void* test_inputs,
-                   void* out_samples, float* out_raw, int steps_per_graph, hipStream_t caller_st) {
+// T steps of a span whose conditioning window the caller upsampled (CUP final level [B][C][sp.Tcb], this span from column sp.cbt_off): a span with
+// t0 > 0 continues from the queues, the time index and queue 0's next input its predecessor left; t0 == 0 zeroes the queues and starts from silence
+int wn_synth_f32_span(wn_ctx* c, int B, int T, const WnSpan& sp, const float* noise, const void* test_inputs, void* out_samples, float* out_raw,
+                      int steps_per_graph, hipStream_t caller_st) {
     if (3 * c->R + c->C > 2000) WN_FAIL(c, WN_E_SHAPE, "fp32 synthesis: 3 * residual_channels + cin_channels = %d input taps exceed the 64 KB LDS image of 8 streams", 3 * c->R + c->C);
     int rc = wn_synth_f32_reserve(c, B);
     if (rc) return rc;
     SynthF32* s = (SynthF32*)c->synth32;
     if (steps_per_graph <= 0) steps_per_graph = 32;
     c->synth_path = 3;
-    hipStream_t st = s->priv;                          // ctx-owned stream (the caller's may be the legacy NULL stream, which cannot be captured)
-    WN_HIP(c, hipEventRecord(s->ev0, caller_st));
-    WN_HIP(c, hipStreamWaitEvent(st, s->ev0, 0));
-    const float* cup = c->CUP[c->cup_final_idx];
-    const float* gbias = c->gbias;
-    int Tcb = T;
-    if (!sp) {
-        c->fB = B; c->fT = T; c->fTc = Tc;
-        if ((rc = wn_upsample_fwd(c, nullptr, cin, B, Tc, st))) return rc;      // fp32 [B][C][T] (wavenet.py:781-803)
-        if ((rc = wn_gbias_fwd(c, B, st))) return rc;
-    } else { cup += sp->cbt_off; Tcb = sp->Tcb; gbias = sp->gbias; }
-    const int R = c->R;
-    if (!sp || sp->t0 == 0) {
-        for (int l = 0; l < c->L; ++l) WN_HIP(c, hipMemsetAsync(s->ring[l], 0, (size_t)(s->mask[l] + 1) * s->capB * R * 4, st));      // zero queues (wavenet.py:815-816)
-        const int mode = c->cfg.input_type == WN_INPUT_MULAW_QUANTIZE ? 2 : (c->O == 2 ? 1 : 0);
-        hipLaunchKernelGGL(wn_f32s_init, dim3(1), dim3(256), 0, st, c->params_dev + c->first.dil_k, c->params_dev + c->first.dil_b, R, mode, 127, s->ring[0], B, s->t_dev);
-        WN_LAUNCH_CHECK(c);
-    } else WN_HIP(c, hipMemsetD32Async((hipDeviceptr_t)(s->t_dev + 1), sp->t0, 1, st));
-    int done = 0;
-    if (steps_per_graph > 1 && T >= steps_per_graph) {
-        const void* key[6] = {noise, test_inputs, out_samples, out_raw, cup, gbias};
-        const bool reuse = s->gexec && s->g_steps == steps_per_graph && s->g_B == B && s->g_T == T && s->g_Tcb == Tcb && memcmp(key, s->g_key, sizeof key) == 0;
-        if (!reuse) {
-            if (s->gexec) { hipGraphExecDestroy(s->gexec); s->gexec = nullptr; }
-            hipGraph_t graph;
-            WN_HIP(c, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-            for (int i = 0; i < steps_per_graph; ++i) {
-                rc = f32s_enqueue_step(c, s, B, T, cup, Tcb, gbias, noise, test_inputs, out_samples, out_raw, st);
-                if (rc) { hipStreamEndCapture(st, &graph); return rc; }
-            }
-            WN_HIP(c, hipStreamEndCapture(st, &graph));
-            WN_HIP(c, hipGraphInstantiate(&s->gexec, graph, nullptr, nullptr, 0));
-            hipGraphDestroy(graph);
-            s->g_steps = steps_per_graph; s->g_B = B; s->g_T = T; s->g_Tcb = Tcb; memcpy(s->g_key, key, sizeof key);
-        }
-        for (; done + steps_per_graph <= T; done += steps_per_graph) WN_HIP(c, hipGraphLaunch(s->gexec, st));
-    }
-    for (; done < T; ++done) { rc = f32s_enqueue_step(c, s, B, T, cup, Tcb, gbias, noise, test_inputs, out_samples, out_raw, st); if (rc) return rc; }
-    WN_HIP(c, hipEventRecord(s->ev1, st));
-    WN_HIP(c, hipStreamWaitEvent(caller_st, s->ev1, 0));
-    return WN_OK;
-}
-
-int wn_synth_f32_impl(wn_ctx* c, const float* cin, int B, int Tc, const float* noise, const void* test_inputs,
-                      void* out_samples, float* out_raw, int steps_per_graph, hipStream_t caller_st) {
-    const int T = Tc * c->hop;
-    if ((int64_t)B * T > c->NT) WN_FAIL(c, WN_E_SHAPE, "synthesis B*T = %d*%d exceeds the workspace (max_batch*max_time = %lld)", B, T, (long long)c->NT);
-    if (c->gin > 0 && (!c->have_g || c->gB != B))
-        WN_FAIL(c, WN_E_STATE, "global conditioning is enabled: call wn_set_global_condition with this batch (B=%d) first [wavenet.py:766-777]", B);
-    return f32_run(c, cin, B, T, Tc, nullptr, noise, test_inputs, out_samples, out_raw, steps_per_graph, caller_st);
-}
-
-int wn_synth_f32_span(wn_ctx* c, int B, int T, const WnSpan& sp, const float* noise, const void* test_inputs, void* out_samples, float* out_raw,
-                      int steps_per_graph, hipStream_t st) {
-    return f32_run(c, nullptr, B, T, 0, &sp, noise, test_inputs, out_samples, out_raw, steps_per_graph, st);
+    if ((rc = s->run.enter(c, caller_st))) return rc;
+    hipStream_t st = s->run.st;
+    const float* cup = c->CUP[c->cup_final_idx] + sp.cbt_off;
+    if ((rc = wn_span_start(c, s->ring, s->mask, s->capB, B, s->t_dev, sp.t0, st))) return rc;
+    const WnStepKey key = {{noise, test_inputs, out_samples, out_raw, cup, sp.gbias, nullptr}, steps_per_graph, B, T, sp.Tcb};
+    rc = s->run.run(c, T, key, [&](hipStream_t q) { return f32s_enqueue_step(c, s, B, T, cup, sp.Tcb, sp.gbias, noise, test_inputs, out_samples, out_raw, q); });
+    if (rc) return rc;
+    return s->run.leave(c, caller_st);
 }

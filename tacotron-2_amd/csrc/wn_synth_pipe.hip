@@ -27,6 +27,8 @@
 // streams alternate between two head CUs, the mailbox copy nobody reads is not written, the publishing stores are builtins the compiler's waitcnt
 // pass can count (st_buf16), the skip chain needs no barrier, and the paper model's / hparams.py's widths are compile-time constants (SPEC 1 / 2):
 // 28 us per sample for 1 ... 12 streams of the paper model, 42.5 us at hparams.py's synthesis batch of 20 (real time at 22.05 kHz; was 72).
+// Host side: wn_pipe_span is the only way in -- a whole utterance (wn_synth_impl hands it over as the span t0 = 0 with `whole` set), a push of a stream or
+// of a slot session; the conditioning rows are upsampled by the caller.
 #include "wn_common.h"
 #include <algorithm>
 #include <stdlib.h>
@@ -1246,10 +1248,10 @@ int wn_pipe_check(wn_ctx* c, bool wait) {
     return WN_OK;
 }
 
-// sp == nullptr: wn_synthesize (upsample the conditioning of the whole utterance here); else one push of a stream, whose conditioning window the caller
-// upsampled into cbt: no weight re-slice after the first push (wn_pack_weights / wn_synth_pipe_dtype end a stream, so the images cannot be stale)
-static int pipe_run(wn_ctx* c, const float* cin, int B, int T, int Tc, const WnSpan* sp, const float* noise, const void* test_inputs,
-                    void* out_samples, float* out_raw, hipStream_t caller_st) {
+// T samples of a span (the only way into the pipeline): a whole utterance, one push of a stream or of a slot session; the caller upsampled the
+// conditioning window into cbt.  The weight images are re-sliced for a whole utterance, a stream's first push (t0 == 0) and a session's first run, at
+// no other time (wn_pack_weights / wn_synth_pipe_dtype end a stream or session, so the images cannot be stale)
+int wn_pipe_span(wn_ctx* c, int B, int T, const WnSpan& sp, const float* noise, const void* test_inputs, void* out_samples, float* out_raw, hipStream_t caller_st) {
     const int L = c->L, R = c->R;
     int rc;
     if ((rc = wn_pipe_reserve(c, B, T))) return rc;
@@ -1261,11 +1263,11 @@ static int pipe_run(wn_ctx* c, const float* cin, int B, int T, int Tc, const WnS
     const int P = p->P;
     PipeArgs a = p->proto;
     a.L = L; a.P = P; a.R = R; a.G = c->G; a.GH = c->GH; a.S = c->S; a.O = c->O; a.OP = c->OP; a.C = c->C; a.Cin = c->Cin; a.B = B; a.T = T;
-    a.rho = c->res_scale; a.mode = c->cfg.input_type == WN_INPUT_MULAW_QUANTIZE ? 2 : (c->O == 2 ? 1 : 0);
-    a.nps = wn_noise_per_step(c); a.lsmin = a.mode == 1 ? c->cfg.log_scale_min_gauss : c->cfg.log_scale_min; a.start_id = 127; a.spx = p->spx;
+    a.rho = c->res_scale; a.mode = wn_sample_mode(c);
+    a.nps = wn_noise_per_step(c); a.lsmin = wn_sample_lsmin(c); a.start_id = 127; a.spx = p->spx;
     a.slices = p->slices; a.layer_slice_bytes = p->layer_slice_bytes; a.head_slice_off = p->head_slice_off;
     // ---- slice images from the current parameters (cheap: 27 MB)
-    if (!sp || (sp->st0 ? sp->reslice : sp->t0 == 0)) {
+    if (sp.st0 ? sp.reslice : sp.t0 == 0) {
         hipLaunchKernelGGL(wn_pipe_slice_kernel, dim3(p->nblocks), dim3(256), 0, st, c->params_dev, p->slices, p->jobs_dev, p->job_block0_dev, p->njobs, c->GH, p->f16 ? 1 : 0);
         WN_LAUNCH_CHECK(c);
         for (int l = 0; l < L; ++l) a.cin_b_off[l] = c->lay[l].cin_b;
@@ -1287,17 +1289,10 @@ static int pipe_run(wn_ctx* c, const float* cin, int B, int T, int Tc, const WnS
     WN_HIP(c, hipMemsetAsync(p->abort_dev, 0, 4, st));                     // the per-run flag (the sticky word [1] survives)
     WN_HIP(c, hipMemsetAsync(p->abort_dev + 64, 0, 4096, st));            // XCC table
     a.XM = p->XM; a.SM = p->SM; a.XML = p->XML; a.SML = p->SML; a.ring = p->ring; a.abort_flag = p->abort_dev; a.xcc_tab = p->abort_dev + 64;
-    // ---- conditioning for the whole utterance (wavenet.py:781-803): cbt [B*T][C] bf16
-    if (!sp) {
-        c->fB = B; c->fT = T; c->fTc = Tc;
-        if ((rc = wn_upsample_fwd(c, nullptr, cin, B, Tc, st))) return rc;
-        if (c->gin > 0) { if ((rc = wn_gbias_fwd(c, B, st))) return rc; a.gbias = c->gbias; }      // wavenet.py:766-777
-        a.cbt = c->cbt; a.t0 = 0; a.Tcb = T; a.carry = nullptr;
-    } else {
-        a.cbt = (sp->cbt ? sp->cbt : c->cbt) + (int64_t)sp->cbt_off * c->C; a.t0 = sp->t0; a.Tcb = sp->Tcb; a.carry = sp->carry;
-        if (c->gin > 0) a.gbias = sp->gbias;
-        if (sp->st0) { a.out_pitch = sp->out_pitch; for (int i = 0; i < 32; ++i) { a.st0[i] = i < B ? sp->st0[i] : 0; a.snl[i] = i < B ? sp->snl[i] : 0; } }
-    }
+    // ---- conditioning rows cbt [B][Tcb][C] bf16 (the session's own table, or the window in the workspace)
+    a.cbt = (sp.cbt ? sp.cbt : c->cbt) + (int64_t)sp.cbt_off * c->C; a.t0 = sp.t0; a.Tcb = sp.Tcb; a.carry = sp.carry;
+    if (c->gin > 0) a.gbias = sp.gbias;
+    if (sp.st0) { a.out_pitch = sp.out_pitch; for (int i = 0; i < 32; ++i) { a.st0[i] = i < B ? sp.st0[i] : 0; a.snl[i] = i < B ? sp.snl[i] : 0; } }
     a.noise = noise; a.test_inputs = test_inputs; a.out_samples = out_samples; a.out_raw = out_raw;
     a.win_global = c->params_dev + c->first.dil_k; a.bin_global = c->params_dev + c->first.dil_b;
     unsigned long long* trace_dev = nullptr; const int trace_n = 32;
@@ -1347,7 +1342,7 @@ static int pipe_run(wn_ctx* c, const float* cin, int B, int T, int Tc, const WnS
 #define PK(h, m, b) {wn_synth_pipe_kernel<h, m, b, 0, 1>, wn_synth_pipe_kernel<h, m, b, 1, 1>, wn_synth_pipe_kernel<h, m, b, 2, 1>}
         static const kern_t kerns_slot[2][2][2][3] = {{{PK(0, 0, 0), PK(0, 0, 1)}, {PK(0, 1, 0), PK(0, 1, 1)}}, {{PK(1, 0, 0), PK(1, 0, 1)}, {PK(1, 1, 0), PK(1, 1, 1)}}};
 #undef PK
-        kern_t kern = (sp && sp->st0 ? kerns_slot : kerns)[p->f16 ? 1 : 0][ni > 1 ? 1 : 0][bp ? 1 : 0][spec];
+        kern_t kern = (sp.st0 ? kerns_slot : kerns)[p->f16 ? 1 : 0][ni > 1 ? 1 : 0][bp ? 1 : 0][spec];
         c->synth_batchpre = bp ? 1 : 0;
         const int32_t cfgv[WN_SYNTH_CFG_N] = {2, ni, bp ? 1 : 0, spec, p->f16 ? 1 : 0, a.NH, a.early_from, a.abort_every, grid, Bmax};
         for (int i = 0; i < WN_SYNTH_CFG_N; ++i) c->synth_cfg[i] = cfgv[i];
@@ -1401,17 +1396,6 @@ static int pipe_run(wn_ctx* c, const float* cin, int B, int T, int Tc, const WnS
     }
     WN_HIP(c, hipEventRecord(p->ev1, st));
     WN_HIP(c, hipStreamWaitEvent(caller_st, p->ev1, 0));
-    p->pending_stream = sp != nullptr;
+    p->pending_stream = !sp.whole;
     return WN_OK;
-}
-
-int wn_pipe_synthesize(wn_ctx* c, const float* cin, int B, int Tc, const float* noise, const void* test_inputs,
-                       void* out_samples, float* out_raw, hipStream_t caller_st) {
-    const int T = Tc * c->hop;
-    if ((int64_t)B * T > c->NT) WN_FAIL(c, WN_E_SHAPE, "synthesis B*T = %d*%d exceeds the workspace (max_batch*max_time = %lld)", B, T, (long long)c->NT);
-    return pipe_run(c, cin, B, T, Tc, nullptr, noise, test_inputs, out_samples, out_raw, caller_st);
-}
-
-int wn_pipe_span(wn_ctx* c, int B, int T, const WnSpan& sp, const float* noise, const void* test_inputs, void* out_samples, float* out_raw, hipStream_t st) {
-    return pipe_run(c, nullptr, B, T, 0, &sp, noise, test_inputs, out_samples, out_raw, st);
 }

@@ -272,6 +272,35 @@ def test_stream_fp32_mode_resize():
     eng.close()
 
 
+@pytest.mark.parametrize('pushes', [[2, 2, 2], [2, 2, 3]])
+@pytest.mark.parametrize('dtype', ['bf16', 'fp32'])
+def test_stream_replays_the_step_graph_across_pushes(dtype, pushes):
+    """The captured step graph (steps_per_graph = 4) is REPLAYED by a later push when every pointer and size it carries is the same, and captured
+    again when one differs.  Pushes 1 and 2 write into the same output tensors (copied out in between; device noise, no lookahead: the noise buffer and
+    the conditioning rows are the same too), so push 2 replays push 1's graph 8 times from another t0; push 3 writes into other tensors -- and, with 3
+    frames, at another pitch -- so the graph is captured again.  32 / 48 samples per push wrap every queue (4 and 8 slots) several times."""
+    B, Tc = 3, sum(pushes)
+    kw = dict(mi355_compute_dtype='fp32') if dtype == 'fp32' else {}
+    hp, cfg, eng, params, wav, c, T = _setup(B, Tc, **kw)
+    path = 'graph-fp32' if dtype == 'fp32' else 'graph'
+    assert eng.stream_lookahead() == (0, 0)
+    ref = _oneshot(eng, cfg, c, seed=17, spg=4)
+    assert ref[2]['path'] == path
+    cd, hop = c.cuda(), cfg.hop
+    eng.stream_begin(B, seed=17, steps_per_graph=4)
+    shared = _alloc(eng, cfg, B, pushes[0] * hop)
+    outs, raws, f0 = [], [], 0
+    for i, k in enumerate(pushes):
+        out, raw = shared if i < 2 else _alloc(eng, cfg, B, k * hop)
+        assert eng.stream_push(cd[:, :, f0:f0 + k].contiguous(), out, raw, final=(i == len(pushes) - 1)) == k * hop
+        outs.append(out.clone()); raws.append(raw.clone())
+        f0 += k
+    torch.cuda.synchronize(); eng.synth_check()
+    assert eng.synth_config()['path'] == path
+    _same((torch.cat(outs, 1).cpu(), torch.cat(raws, 2).cpu()), ref)
+    eng.close()
+
+
 @pytest.mark.parametrize('utype', ['SubPixel', 'Resize'])
 def test_stream_launch_per_layer_with_lookahead(utype):
     """The launch-per-layer path (steps_per_graph = 8) with a nonzero lookahead: the window offset / stride of its conditioning rows."""
