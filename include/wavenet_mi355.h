@@ -168,6 +168,27 @@ int wn_bwd_wait_bucket(wn_ctx* ctx, int32_t i, void* stream);
 int wn_loss(wn_ctx* ctx, const float* y_hat, const void* y, const int32_t* lengths, int32_t B, int32_t T,
             int32_t shift, float* loss_out, void* stream);
 
+/* ---- validation: held-out likelihood per utterance and per sample ------------------------------ */
+/* Teacher-forced forward WITHOUT dropout on a training context of any cfg.dropout (evaluation: wavenet.py:342-405 computes the same
+ * quantity with the incremental loop), scored per utterance.  x, c, y, lengths, B, T, Tc as wn_train_fwd.  stats_out float [B,3],
+ * nll_out optional float [B,T], y_hat_out optional float [B,O,T].
+ * stats_out[b] = { sum of the negative log-likelihood (nats) over the counted positions, number of counted positions, number of counted
+ * positions whose loss is non-zero (the softmax head's denominator, modules.py:798) }; a position t is counted when t + 1 < min(lengths[b], T)
+ * (the prediction at t is scored against sample t + 1); nll_out[b][t] is its loss, 0 where it is not counted.  An utterance without a counted
+ * position gives {0, 0, 0}.  The reduction has a fixed order and uses no atomics: row b depends on row b of the inputs alone and repeats bit
+ * for bit.  The launches are those of a cfg.dropout == 0 context, so y_hat equals that context's wn_train_fwd output bit for bit.
+ * Arguments are validated as by wn_train_fwd; WN_E_STATE on inference-only contexts; needs wn_set_global_condition when gin_channels > 0;
+ * both compute_dtype values; asynchronous on `stream`; never allocates (WN_COMPUTE_F32: its first forward reserves the fp32 state, as
+ * wn_train_fwd's does); does not disturb an open stream or slot session.  Nothing is saved for a backward: wn_train_bwd returns WN_E_STATE
+ * until the next wn_train_fwd.  wn_get_upsampled_features afterwards returns this batch's features. */
+int wn_eval_fwd(wn_ctx* ctx, const void* x, const float* c, const void* y, const int32_t* lengths, int32_t B, int32_t T, int32_t Tc,
+                float* stats_out, float* nll_out, float* y_hat_out, void* stream);
+/* Stand-alone scoring of [B,O,T] network outputs (shift as wn_loss).  Writes no gradient: allowed on inference-only contexts, and it
+ * does NOT invalidate the saved backward state.  B <= max_batch, T <= max_time (WN_E_SHAPE).  stats_out / nll_out as wn_eval_fwd with
+ * the counted positions t + shift < min(lengths[b], T).  Calls on one context share its partial-sum scratch: one stream at a time. */
+int wn_score(wn_ctx* ctx, const float* y_hat, const void* y, const int32_t* lengths, int32_t B, int32_t T, int32_t shift,
+             float* stats_out, float* nll_out, void* stream);
+
 /* Optional access to activations of the last forward (wavenet.py:702 upsampled_local_features):
  * float [B, cin, T]. */
 int wn_get_upsampled_features(wn_ctx* ctx, float* out, void* stream);

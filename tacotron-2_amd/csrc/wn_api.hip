@@ -106,6 +106,7 @@ static int alloc_workspace_inference(wn_ctx* c) {
     sz(NT * c->C * 2);
     for (int i = 0; i <= c->cfg.n_upsample; ++i) sz(lvl[i] * c->C * 4);
     sz(256); sz(WN_ZERO_PAGE_BYTES);
+    sz((size_t)wn_score_part_doubles(c->maxB, c->maxT) * 8);      // wn_score partials: scoring never allocates
     c->ws_bytes = total;
     hipError_t e = hipMalloc((void**)&c->ws, total);
     if (e != hipSuccess) WN_FAIL(c, WN_E_HIP, "hipMalloc(%zu bytes inference workspace) failed: %s", total, hipGetErrorString(e));
@@ -114,6 +115,7 @@ static int alloc_workspace_inference(wn_ctx* c) {
     for (int i = 0; i <= c->cfg.n_upsample; ++i) c->CUP[i] = (float*)bump(p, lvl[i] * c->C * 4);
     c->scal = (float*)bump(p, 256);
     c->zero_page = (bf16_t*)bump(p, WN_ZERO_PAGE_BYTES);
+    c->score_part = (double*)bump(p, (size_t)wn_score_part_doubles(c->maxB, c->maxT) * 8);
     c->X = c->XD = c->TS = c->U = c->R1 = c->H2 = c->DY = c->DPRE1 = c->DSKIP = c->DZ = c->GXall = c->GX0 = c->GX1 = nullptr;
     c->YHAT = c->DC = c->DCUP[0] = c->DCUP[1] = c->CIN = c->UPPART = nullptr; c->XIN = nullptr;
     if (hipMemset(c->zero_page, 0, WN_ZERO_PAGE_BYTES) != hipSuccess) WN_FAIL(c, WN_E_HIP, "hipMemset(zero page) failed");
@@ -152,6 +154,7 @@ static int alloc_workspace(wn_ctx* c) {
     sz((size_t)WN_CS_SLOTS * WN_CS_MAXBLK * 2 * 1024 * 4);    // wn_colsum2 partials (WN_CS_SLOTS regions)
     sz(256);                               // scalars
     sz(WN_ZERO_PAGE_BYTES);                // zero page
+    sz((size_t)wn_score_part_doubles(c->maxB, c->maxT) * 8);      // wn_score / wn_eval_fwd partials
     c->ws_bytes = total;
     hipError_t e = hipMalloc((void**)&c->ws, total);
     if (e != hipSuccess) WN_FAIL(c, WN_E_HIP, "hipMalloc(%zu bytes workspace) failed: %s", total, hipGetErrorString(e));
@@ -176,6 +179,7 @@ static int alloc_workspace(wn_ctx* c) {
     c->cs_part = (float*)bump(p, (size_t)WN_CS_SLOTS * WN_CS_MAXBLK * 2 * 1024 * 4);      // exactly what wn_colsum2 addresses (was twice that: ADVICE round 3)
     c->scal = (float*)bump(p, 256);
     c->zero_page = (bf16_t*)bump(p, WN_ZERO_PAGE_BYTES);
+    c->score_part = (double*)bump(p, (size_t)wn_score_part_doubles(c->maxB, c->maxT) * 8);
     if (hipMemset(c->zero_page, 0, WN_ZERO_PAGE_BYTES) != hipSuccess) WN_FAIL(c, WN_E_HIP, "hipMemset(zero page) failed");
     return WN_OK;
 }
@@ -420,6 +424,24 @@ extern "C" int wn_train_fwd(wn_ctx* c, const void* x, const float* cc, const voi
     rc = wn_fwd_impl(c, (hipStream_t)stream, loss_out, y_hat_out);
     if (rc == WN_OK) c->have_fwd = true;
     return rc;
+}
+
+// Evaluation: the teacher-forced forward without dropout + per-utterance / per-sample scores.  x and c are read in stream order during this call's
+// launches only (no ctx-owned copies: nothing is kept for a backward), so wn_train_bwd afterwards is refused until the next wn_train_fwd.
+extern "C" int wn_eval_fwd(wn_ctx* c, const void* x, const float* cc, const void* y, const int32_t* lengths, int32_t B, int32_t T, int32_t Tc,
+                           float* stats_out, float* nll_out, float* y_hat_out, void* stream) {
+    if (!c) return WN_E_ARG;
+    WnRange range("wn_eval_fwd");
+    if (c->inference) WN_FAIL(c, WN_E_STATE, "wn_eval_fwd on an inference-only context (cfg.inference_only = 1)");
+    int rc = check_fwd_args(c, x, cc, y, lengths, B, T, Tc);
+    if (rc) return rc;
+    if (!stats_out) WN_FAIL(c, WN_E_ARG, "wn_eval_fwd: stats_out is NULL");
+    c->fx = x; c->fc = cc; c->fy = y; c->flen = lengths; c->fB = B; c->fT = T; c->fTc = Tc; c->fseed = 0; c->fup_pitch = 0;
+    c->have_fwd = false; c->have_bwd = false; c->have_loss = false;
+    rc = wn_fwd_impl(c, (hipStream_t)stream, nullptr, y_hat_out, true);
+    c->feval = false; c->fx = c->XIN; c->fc = c->CIN;      // (the borrowed pointers are in the launches; none is kept)
+    if (rc) return rc;
+    return wn_score_last_fwd(c, stats_out, nll_out, (hipStream_t)stream);
 }
 
 extern "C" int wn_train_bwd(wn_ctx* c, float* grads, void* stream) {

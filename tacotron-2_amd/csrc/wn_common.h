@@ -160,8 +160,10 @@ struct wn_ctx {
                                           // wn_gemm8p_kernel's SGPR-base form: base + 16 * lane, i.e. 1 KiB)
     int gemm8p = 0;                       // WN_GEMM8P at wn_create, bit 0: gate, bit 1: d x on the 8-phase kernel (wn_tile8p.h) where the model fits it; default 0: the 256 x 128 LDS-DMA ring kernel
     float* scal;                          // device scalars: [0]=loss sum [1]=denominator [2]=1/denominator [3]=count
+    double* score_part = nullptr;         // [max_batch][ceil(max_time / 256)][3] per-chunk partials of the validation scores (wn_loss.hip: wn_score_run); in the workspace
     // state of the last forward
     int fB = 0, fT = 0, fTc = 0; uint64_t fseed = 0; bool have_fwd = false; bool have_loss = false;
+    bool feval = false;                   // the forward being enqueued is wn_eval_fwd: no dropout whatever cfg.dropout says (the launches of a dropout == 0 context)
     const void* fx = nullptr; const void* fy = nullptr; const int32_t* flen = nullptr; const float* fc = nullptr;
     // live profiling of the dominant kernel (bench.py roofline): event pairs around every gate-GEMM launch
     bool prof = false; std::vector<hipEvent_t> pev; size_t pev_used = 0;
@@ -279,7 +281,7 @@ __device__ __forceinline__ int sample_cat(const float* p, int64_t stride, int Q,
 // ---- cross-TU entry points (host) ---------------------------------------------------------------
 int wn_build_packs(wn_ctx* ctx);
 int wn_launch_pack(wn_ctx* ctx, const float* params, hipStream_t st);
-int wn_fwd_impl(wn_ctx* ctx, hipStream_t st, float* loss_out, float* y_hat_out);
+int wn_fwd_impl(wn_ctx* ctx, hipStream_t st, float* loss_out, float* y_hat_out, bool eval = false);      // eval: dropout-free, saves nothing for a backward
 int wn_bwd_impl(wn_ctx* ctx, float* grads, hipStream_t st);
 int wn_optim_impl(wn_ctx* ctx, float* p, const float* g, float* m, float* v, float* ema, float lr, int64_t step, hipStream_t st);
 int wn_synth_impl(wn_ctx* ctx, const float* c, int B, int Tc, const float* noise, uint64_t seed,
@@ -333,5 +335,7 @@ int wn_f32_backward(wn_ctx* ctx, float* grads, hipStream_t st);       // fp32 ba
 float* wn_f32_dy(wn_ctx* ctx);                                        // fp32 d y_hat buffer of the fp32 state (allocates it)
 int wn_upsample_bwd(wn_ctx* c, const float* dc_final, float* grads, hipStream_t st);
 int wn_loss_fwd_bwd(wn_ctx* c, float* loss_out, hipStream_t st);
+int wn_score_last_fwd(wn_ctx* c, float* stats_out, float* nll_out, hipStream_t st);      // per-utterance / per-sample scores of the last forward's y_hat
+int64_t wn_score_part_doubles(int maxB, int maxT);                                          // doubles of wn_ctx::score_part
 const float* wn_f32_debug(const wn_ctx* ctx, const char* name, int layer);
 int wn_sample_impl(wn_ctx* ctx, const float* y_hat, int B, int T, const float* noise, void* out, hipStream_t st);

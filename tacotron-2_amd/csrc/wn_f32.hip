@@ -261,7 +261,7 @@ int wn_f32_forward(wn_ctx* c, hipStream_t st) {
     hipLaunchKernelGGL(wn_f32_transpose_c, dim3(cdiv(rows * C, 256)), dim3(256), 0, st, c->CUP[c->cup_final_idx], s->C32, B, C, T);
     hipLaunchKernelGGL(wn_f32_first_conv, dim3(cdiv(rows * R, 256)), dim3(256), 0, st, c->fx, P + c->first.dil_k, P + c->first.dil_b, s->X, rows, R, is_ids);
     WN_LAUNCH_CHECK(c);
-    const bool drop = c->cfg.dropout > 0.0f;
+    const bool drop = c->cfg.dropout > 0.0f && !c->feval;      // wn_eval_fwd: thresh16 stays 0
     for (int l = 0; l < L; ++l) {
         const int d = c->dil[l];
         const float* Xl = s->X + (size_t)l * NT * R;

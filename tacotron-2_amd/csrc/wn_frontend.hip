@@ -131,7 +131,7 @@ int wn_first_conv(wn_ctx* c, hipStream_t st) {
     const int64_t rows = (int64_t)c->fB * c->fT;
     const int is_ids = c->cfg.input_type == WN_INPUT_MULAW_QUANTIZE;
     uint32_t klo = 0, khi = 0; wn_layer_key(c->fseed, 0, &klo, &khi);
-    const bool drop = c->cfg.dropout > 0.0f;
+    const bool drop = c->cfg.dropout > 0.0f && !c->feval;
     hipLaunchKernelGGL(wn_first_conv_fwd, dim3(cdiv(rows * (c->R / 8), 256)), dim3(256), 0, st, c->fx,
                        c->params_dev + c->first.dil_k, c->params_dev + c->first.dil_b, c->X, drop ? c->XD : nullptr, rows, c->R, is_ids,
                        klo, khi, (uint32_t)lrintf(c->cfg.dropout * 65536.0f), 1.0f / (1.0f - c->cfg.dropout));

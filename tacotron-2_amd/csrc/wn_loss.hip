@@ -20,6 +20,53 @@ __global__ void wn_loss_prep(const int32_t* __restrict__ lengths, int B, int T, 
 }
 
 #define WN_MAX_MIX 16
+// Per-position value of the discretised mixture of logistics (mixture.py:18-74): the negative log-likelihood of yv under the M components at
+// yh[i * T] (logits), yh[(M + i) * T] (means), yh[(2 M + i) * T] (log scales).  GRAD: also what the gradient needs (wn_mol_loss: dmu, dls and the four scalars); the score
+// kernel (wn_score_kernel) takes the value alone.  One definition: the training loss and the validation score cannot drift apart.
+template <bool GRAD>
+__device__ __forceinline__ float wn_mol_position(const float* __restrict__ yh, int64_t T, int M, float yv, float num_classes, float log_scale_min,
+                                                 float* logit, float* lp, float* dmu, float* dls, float& mx_out, float& se_out, float& mlp_out, float& sw_out) {
+    // logit, lp, dmu, dls: the caller's WN_MAX_MIX-element LOCAL arrays (plain arrays: they stay in registers once this is inlined)
+    const float D = 1.0f / (num_classes - 1.0f);
+    const float logbin = logf((num_classes - 1.0f) * 0.5f);
+    float mx = -INFINITY;
+    for (int i = 0; i < M; ++i) { logit[i] = yh[(int64_t)i * T]; mx = fmaxf(mx, logit[i]); }
+    float se = 0.0f;
+    for (int i = 0; i < M; ++i) se += __expf(logit[i] - mx);
+    const float lse = logf(se);
+    float mlp = -INFINITY;
+    for (int i = 0; i < M; ++i) {
+        const float mu = yh[(int64_t)(M + i) * T];
+        const float lsr = yh[(int64_t)(2 * M + i) * T];
+        const float ls = fmaxf(lsr, log_scale_min);
+        const float cy = yv - mu, inv = __expf(-ls);
+        const float p = inv * (cy + D), m = inv * (cy - D), mid = inv * cy;
+        float l, gm, gs;          // log-prob and its derivatives wrt mu and ls
+        if (yv < -0.999f) { l = p - softplusf(p); const float s = sigmoidf_(-p); gm = -inv * s; gs = -p * s; }
+        else if (yv > 0.999f) { l = -softplusf(m); const float s = sigmoidf_(m); gm = inv * s; gs = m * s; }
+        else {
+            const float sp = sigmoidf_(p), sm = sigmoidf_(m);
+            const float cd = sp - sm;
+            if (cd > 1e-5f) {
+                l = logf(fmaxf(cd, 1e-12f));
+                const float dp = sp * (1.0f - sp), dm = sm * (1.0f - sm);
+                gm = -inv * (dp - dm) / cd; gs = (-p * dp + m * dm) / cd;
+            } else {
+                const float q2 = 1.0f - 2.0f * sigmoidf_(mid);
+                l = mid - ls - 2.0f * softplusf(mid) - logbin;
+                gm = -inv * q2; gs = -mid * q2 - 1.0f;
+            }
+        }
+        if (lsr < log_scale_min) gs = 0.0f;       // tf.maximum passes the gradient only where x >= min
+        lp[i] = l + (logit[i] - mx - lse);
+        if (GRAD) { dmu[i] = gm; dls[i] = gs; }
+        mlp = fmaxf(mlp, lp[i]);
+    }
+    float sw = 0.0f;
+    for (int i = 0; i < M; ++i) sw += __expf(lp[i] - mlp);
+    mx_out = mx; se_out = se; mlp_out = mlp; sw_out = sw;
+    return -(mlp + logf(sw));
+}
 // Discretised mixture of logistics, mixture.py:18-74 + modules.py:800-817, with its gradient.
 // one thread per (b, t): prediction at t scored against y[t+1] (wavenet.py:494-495).
 __global__ void wn_mol_loss(const float* __restrict__ yhat, const float* __restrict__ y, const int32_t* __restrict__ lengths,
@@ -39,45 +86,8 @@ __global__ void wn_mol_loss(const float* __restrict__ yhat, const float* __restr
             const float inv_den = scal[2];
             const float yv = y[(int64_t)b * T + t + shift];
             const float* yh = yhat + ((int64_t)b * 3 * M) * T + t;
-            float logit[WN_MAX_MIX], lp[WN_MAX_MIX], dmu[WN_MAX_MIX], dls[WN_MAX_MIX];
-            const float D = 1.0f / (num_classes - 1.0f);
-            const float logbin = logf((num_classes - 1.0f) * 0.5f);
-            float mx = -INFINITY;
-            for (int i = 0; i < M; ++i) { logit[i] = yh[(int64_t)i * T]; mx = fmaxf(mx, logit[i]); }
-            float se = 0.0f;
-            for (int i = 0; i < M; ++i) se += __expf(logit[i] - mx);
-            const float lse = logf(se);
-            float mlp = -INFINITY;
-            for (int i = 0; i < M; ++i) {
-                const float mu = yh[(int64_t)(M + i) * T];
-                const float lsr = yh[(int64_t)(2 * M + i) * T];
-                const float ls = fmaxf(lsr, log_scale_min);
-                const float cy = yv - mu, inv = __expf(-ls);
-                const float p = inv * (cy + D), m = inv * (cy - D), mid = inv * cy;
-                float l, gm, gs;          // log-prob and its derivatives wrt mu and ls
-                if (yv < -0.999f) { l = p - softplusf(p); const float s = sigmoidf_(-p); gm = -inv * s; gs = -p * s; }
-                else if (yv > 0.999f) { l = -softplusf(m); const float s = sigmoidf_(m); gm = inv * s; gs = m * s; }
-                else {
-                    const float sp = sigmoidf_(p), sm = sigmoidf_(m);
-                    const float cd = sp - sm;
-                    if (cd > 1e-5f) {
-                        l = logf(fmaxf(cd, 1e-12f));
-                        const float dp = sp * (1.0f - sp), dm = sm * (1.0f - sm);
-                        gm = -inv * (dp - dm) / cd; gs = (-p * dp + m * dm) / cd;
-                    } else {
-                        const float q = 1.0f - 2.0f * sigmoidf_(mid);
-                        l = mid - ls - 2.0f * softplusf(mid) - logbin;
-                        gm = -inv * q; gs = -mid * q - 1.0f;
-                    }
-                }
-                if (lsr < log_scale_min) gs = 0.0f;       // tf.maximum passes the gradient only where x >= min
-                lp[i] = l + (logit[i] - mx - lse);
-                dmu[i] = gm; dls[i] = gs;
-                mlp = fmaxf(mlp, lp[i]);
-            }
-            float sw = 0.0f;
-            for (int i = 0; i < M; ++i) sw += __expf(lp[i] - mlp);
-            const float loss = -(mlp + logf(sw));
+            float logit[WN_MAX_MIX], lp[WN_MAX_MIX], dmu[WN_MAX_MIX], dls[WN_MAX_MIX], mx, se, mlp, sw;
+            const float loss = wn_mol_position<true>(yh, T, M, yv, num_classes, log_scale_min, logit, lp, dmu, dls, mx, se, mlp, sw);
             my = loss;
             for (int i = 0; i < M; ++i) {
                 const float w = __expf(lp[i] - mlp) / sw;              // responsibility
@@ -105,6 +115,32 @@ __device__ __forceinline__ float ndtrf_(float x) {      // TF special_math._ndtr
     return 0.5f * y;
 }
 
+// Per-position value of the Gaussian head (gaussian.py:5-37): the negative log-likelihood of yv under N(mu, exp(max(lsr, log_scale_min))) -- the
+// density, or the probability of yv's quantisation bin (use_cdf) -- and its derivatives gm, gs wrt mu and the log scale (unused by the score kernel).
+__device__ __forceinline__ float wn_gauss_position(float yv, float mu, float lsr, float num_classes, float log_scale_min, int use_cdf, float& gm, float& gs) {
+    const float ls = fmaxf(lsr, log_scale_min);
+    float loss;
+    if (use_cdf) {
+        const float D = 1.0f / (num_classes - 1.0f);
+        const float sc = __expf(ls);
+        const float zp = (yv + D - mu) / sc, zm = (yv - D - mu) / sc;
+        const float diff = ndtrf_(zp) - ndtrf_(zm);
+        loss = -logf(fmaxf(diff, 1e-12f));
+        if (diff >= 1e-12f) {
+            const float c0 = 0.3989422804014327f;
+            const float pp = c0 * __expf(-0.5f * zp * zp), pm = c0 * __expf(-0.5f * zm * zm);
+            gm = (pp - pm) / (sc * diff);            // d(-lp)/dmu
+            gs = (zp * pp - zm * pm) / diff;         // d(-lp)/dls
+        } else { gm = 0.0f; gs = 0.0f; }
+    } else {
+        const float e2 = __expf(-2.0f * ls), dlt = yv - mu;
+        loss = 0.5f * (1.8378770664093453f + 2.0f * ls + dlt * dlt * e2);
+        gm = -dlt * e2; gs = 1.0f - dlt * dlt * e2;
+    }
+    if (lsr < log_scale_min) gs = 0.0f;
+    return loss;
+}
+
 // Gaussian MLE, gaussian.py:5-37 + modules.py:819-836, with its gradient.
 __global__ void wn_gauss_loss(const float* __restrict__ yhat, const float* __restrict__ y, const int32_t* __restrict__ lengths,
                               bf16_t* __restrict__ dY, int ldDY, float* __restrict__ scal, int B, int T,
@@ -120,26 +156,8 @@ __global__ void wn_gauss_loss(const float* __restrict__ yhat, const float* __res
             const float inv_den = scal[2];
             const float yv = y[(int64_t)b * T + t + shift];
             const float mu = yhat[((int64_t)b * 2) * T + t], lsr = yhat[((int64_t)b * 2 + 1) * T + t];
-            const float ls = fmaxf(lsr, log_scale_min);
-            float gm, gs, loss;
-            if (use_cdf) {
-                const float D = 1.0f / (num_classes - 1.0f);
-                const float sc = __expf(ls);
-                const float zp = (yv + D - mu) / sc, zm = (yv - D - mu) / sc;
-                const float diff = ndtrf_(zp) - ndtrf_(zm);
-                loss = -logf(fmaxf(diff, 1e-12f));
-                if (diff >= 1e-12f) {
-                    const float c0 = 0.3989422804014327f;
-                    const float pp = c0 * __expf(-0.5f * zp * zp), pm = c0 * __expf(-0.5f * zm * zm);
-                    gm = (pp - pm) / (sc * diff);            // d(-lp)/dmu
-                    gs = (zp * pp - zm * pm) / diff;         // d(-lp)/dls
-                } else { gm = 0.0f; gs = 0.0f; }
-            } else {
-                const float e2 = __expf(-2.0f * ls), dlt = yv - mu;
-                loss = 0.5f * (1.8378770664093453f + 2.0f * ls + dlt * dlt * e2);
-                gm = -dlt * e2; gs = 1.0f - dlt * dlt * e2;
-            }
-            if (lsr < log_scale_min) gs = 0.0f;
+            float gm, gs;
+            const float loss = wn_gauss_position(yv, mu, lsr, num_classes, log_scale_min, use_cdf, gm, gs);
             my = loss; g0 = gm * inv_den; g1 = gs * inv_den;
         }
         drow[0] = f2bf(g0); drow[1] = f2bf(g1);
@@ -151,6 +169,19 @@ __global__ void wn_gauss_loss(const float* __restrict__ yhat, const float* __res
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = my;
     __syncthreads();
     if (threadIdx.x == 0) { float s = 0.0f; for (int i = 0; i < (int)(blockDim.x >> 6); ++i) s += part[i]; unsafeAtomicAdd(&scal[0], s); }
+}
+
+// Per-position pieces of the softmax cross-entropy (modules.py:781-798): max and sum of exponentials over the Q logits at yh[q * T], and the loss of class tgt
+__device__ __forceinline__ void wn_ce_max_sumexp(const float* __restrict__ yh, int64_t T, int Q, float& mx, float& se) {
+    mx = -INFINITY;
+    for (int q = 0; q < Q; ++q) mx = fmaxf(mx, yh[(int64_t)q * T]);
+    se = 0.0f;
+    for (int q = 0; q < Q; ++q) se += __expf(yh[(int64_t)q * T] - mx);
+}
+__device__ __forceinline__ float wn_ce_position(const float* __restrict__ yh, int64_t T, int Q, int tgt) {
+    float mx, se;
+    wn_ce_max_sumexp(yh, T, Q, mx, se);
+    return mx + logf(se) - yh[(int64_t)tgt * T];
 }
 
 // Masked softmax cross-entropy, modules.py:781-798 (denominator = count_nonzero(masked loss)).
@@ -166,14 +197,7 @@ __global__ void wn_ce_loss(const float* __restrict__ yhat, const int32_t* __rest
         const float* yh = yhat + ((int64_t)b * Q) * T + t;
         if (pass == 0) {
             float l = 0.0f;
-            if (valid) {
-                float mx = -INFINITY;
-                for (int q = 0; q < Q; ++q) mx = fmaxf(mx, yh[(int64_t)q * T]);
-                float se = 0.0f;
-                for (int q = 0; q < Q; ++q) se += __expf(yh[(int64_t)q * T] - mx);
-                const int tgt = y[(int64_t)b * T + t + shift];
-                l = mx + logf(se) - yh[(int64_t)tgt * T];
-            }
+            if (valid) l = wn_ce_position(yh, T, Q, y[(int64_t)b * T + t + shift]);
             tmp[idx] = l; my = l; cnt = (l != 0.0f) ? 1.0f : 0.0f;
         } else {
             bf16_t* drow = dY + idx * ldDY;
@@ -181,10 +205,8 @@ __global__ void wn_ce_loss(const float* __restrict__ yhat, const int32_t* __rest
             if (!valid) { for (int q = 0; q < ldDY; ++q) drow[q] = 0; }
             else {
                 const float inv = 1.0f / scal[3];
-                float mx = -INFINITY;
-                for (int q = 0; q < Q; ++q) mx = fmaxf(mx, yh[(int64_t)q * T]);
-                float se = 0.0f;
-                for (int q = 0; q < Q; ++q) se += __expf(yh[(int64_t)q * T] - mx);
+                float mx, se;
+                wn_ce_max_sumexp(yh, T, Q, mx, se);
                 const int tgt = y[(int64_t)b * T + t + shift];
                 for (int q = 0; q < Q; ++q) {
                     const float gq = (__expf(yh[(int64_t)q * T] - mx) / se - (q == tgt ? 1.0f : 0.0f)) * inv;
@@ -251,6 +273,83 @@ extern "C" int wn_loss(wn_ctx* c, const float* y_hat, const void* y, const int32
     if (c->inference) WN_FAIL(c, WN_E_STATE, "wn_loss on an inference-only context (the loss gradient buffer is training workspace)");
     c->have_loss = false;      // DY is overwritten
     return wn_loss_run(c, y_hat, y, lengths, B, T, shift, loss_out, (hipStream_t)stream);
+}
+
+// =================================================================================== validation score
+// Per-utterance and per-sample negative log-likelihood of [B,O,T] head outputs (wn_score, wn_eval_fwd): the per-position values of the training
+// losses above (the same __device__ functions), no gradient, no training workspace.  Fixed-order reduction, no float atomics: workgroup
+// (chunk, b) covers the positions [256 chunk, 256 chunk + 256) of utterance b and writes ITS partial {sum, counted, non-zero} -- wave shuffles,
+// then the four wave sums in order -- and wn_score_finalize adds an utterance's partials in chunk order.  Row b of the result therefore depends on
+// row b of the inputs alone and is bit-identical from run to run; partials and their sums are fp64 (three doubles per 256 positions: nothing to save
+// there), so the rounding of the sum does not grow with T.
+#define WN_SCORE_CHUNK 256
+enum { WN_HEAD_MOL = 0, WN_HEAD_GAUSS = 1, WN_HEAD_CE = 2 };
+int64_t wn_score_part_doubles(int maxB, int maxT) { return (int64_t)maxB * cdiv(maxT, WN_SCORE_CHUNK) * 3; }
+__global__ __launch_bounds__(WN_SCORE_CHUNK) void wn_score_kernel(const float* __restrict__ yhat, const void* __restrict__ y, const int32_t* __restrict__ lengths,
+                                                                  float* __restrict__ nll, double* __restrict__ part, int T, int O, int head,
+                                                                  float num_classes, float log_scale_min, int use_cdf, int shift) {
+    const int b = blockIdx.y, t = blockIdx.x * WN_SCORE_CHUNK + threadIdx.x;
+    float v = 0.0f; bool counted = false;
+    if (t < T) {
+        counted = (t + shift < T) && (t + shift < lengths[b]);
+        if (counted) {
+            const float* yh = yhat + ((int64_t)b * O) * T + t;
+            if (head == WN_HEAD_CE) {
+                const int tgt = ((const int32_t*)y)[(int64_t)b * T + t + shift];
+                v = wn_ce_position(yh, T, O, min(max(tgt, 0), O - 1));      // (a class id outside [0, Q) must not read outside y_hat)
+            } else {
+                const float yv = ((const float*)y)[(int64_t)b * T + t + shift];
+                if (head == WN_HEAD_GAUSS) { float gm, gs; v = wn_gauss_position(yv, yh[0], yh[T], num_classes, log_scale_min, use_cdf, gm, gs); }
+                else {
+                    float logit[WN_MAX_MIX], lp[WN_MAX_MIX], mx, se, mlp, sw;
+                    v = wn_mol_position<false>(yh, T, O / 3, yv, num_classes, log_scale_min, logit, lp, nullptr, nullptr, mx, se, mlp, sw);
+                }
+            }
+        }
+        if (nll) nll[(int64_t)b * T + t] = v;
+    }
+    double s = (double)v, n = counted ? 1.0 : 0.0, z = (counted && v != 0.0f) ? 1.0 : 0.0;
+    for (int o = 32; o > 0; o >>= 1) { s += __shfl_down(s, o); n += __shfl_down(n, o); z += __shfl_down(z, o); }
+    __shared__ double red[3][WN_SCORE_CHUNK / 64];
+    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = s; red[1][threadIdx.x >> 6] = n; red[2][threadIdx.x >> 6] = z; }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        double a = 0.0;
+        for (int i = 0; i < WN_SCORE_CHUNK / 64; ++i) a += red[threadIdx.x][i];
+        part[((int64_t)b * gridDim.x + blockIdx.x) * 3 + threadIdx.x] = a;
+    }
+}
+// stats[b] = {sum, counted, non-zero} of utterance b: its nchunk partials added in index order
+__global__ void wn_score_finalize(const double* __restrict__ part, int B, int nchunk, float* __restrict__ stats) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B * 3) return;
+    const int b = i / 3, k = i - b * 3;
+    double a = 0.0;
+    for (int ch = 0; ch < nchunk; ++ch) a += part[((int64_t)b * nchunk + ch) * 3 + k];
+    stats[i] = (float)a;
+}
+int wn_score_run(wn_ctx* c, const float* yhat, const void* y, const int32_t* lengths, int B, int T, int shift, float* stats_out, float* nll_out, hipStream_t st) {
+    if (B <= 0 || B > c->maxB) WN_FAIL(c, WN_E_SHAPE, "score: batch %d outside (0, max_batch=%d]", B, c->maxB);
+    if (T <= 0 || T > c->maxT) WN_FAIL(c, WN_E_SHAPE, "score: time %d outside (0, max_time=%d]", T, c->maxT);
+    const int head = c->cfg.input_type == WN_INPUT_MULAW_QUANTIZE ? WN_HEAD_CE : (c->O == 2 ? WN_HEAD_GAUSS : WN_HEAD_MOL);
+    if (head == WN_HEAD_MOL && c->O / 3 > WN_MAX_MIX) WN_FAIL(c, WN_E_UNSUPPORTED, "more than %d mixture components", WN_MAX_MIX);
+    const int nchunk = cdiv(T, WN_SCORE_CHUNK);      // B * nchunk * 3 <= wn_score_part_doubles(maxB, maxT): reserved at wn_create
+    hipLaunchKernelGGL(wn_score_kernel, dim3(nchunk, B), dim3(WN_SCORE_CHUNK), 0, st, yhat, y, lengths, nll_out, c->score_part, T, c->O, head,
+                       (float)c->cfg.quantize_channels, head == WN_HEAD_GAUSS ? c->cfg.log_scale_min_gauss : c->cfg.log_scale_min, c->cfg.cdf_loss, shift);
+    hipLaunchKernelGGL(wn_score_finalize, dim3(cdiv(B * 3, 64)), dim3(64), 0, st, c->score_part, B, nchunk, stats_out);
+    WN_LAUNCH_CHECK(c);
+    return WN_OK;
+}
+// the scores of the last forward's y_hat (wn_eval_fwd): training alignment, prediction at t against sample t + 1
+int wn_score_last_fwd(wn_ctx* c, float* stats_out, float* nll_out, hipStream_t st) {
+    WnTraceScope trace_scope(c, st, WN_TR_LOSS);
+    return wn_score_run(c, c->YHAT, c->fy, c->flen, c->fB, c->fT, 1, stats_out, nll_out, st);
+}
+extern "C" int wn_score(wn_ctx* c, const float* y_hat, const void* y, const int32_t* lengths, int32_t B, int32_t T, int32_t shift,
+                        float* stats_out, float* nll_out, void* stream) {
+    if (!c || !y_hat || !y || !lengths || !stats_out) return WN_E_ARG;
+    if (shift != 0 && shift != 1) WN_FAIL(c, WN_E_ARG, "shift must be 0 or 1");
+    return wn_score_run(c, y_hat, y, lengths, B, T, shift, stats_out, nll_out, (hipStream_t)stream);
 }
 
 // =================================================================================== mu-law codec

@@ -343,7 +343,7 @@ static void mk_gate(wn_ctx* c, int l, int b0, int nb, GemmArgs& a) {
     const int R = c->R, G = c->G, GH = c->GH, C = c->C;
     const int64_t NT = c->NT;
     const int d = c->dil[l];
-    const bf16_t* XDl = c->XD + (size_t)l * NT * R;      // dropout already applied by the producer
+    const bf16_t* XDl = (c->feval ? c->X : c->XD) + (size_t)l * NT * R;      // dropout already applied by the producer (wn_eval_fwd: none, the layer input itself)
     base_args(c, a, c->packs[l].w1, b0, nb);
     a.nseg = 4;
     a.seg[0] = seg(XDl, R, 0, R, -2 * d, 0);
@@ -365,7 +365,7 @@ static void mk_out(wn_ctx* c, int l, int b0, int nb, GemmArgs& o) {
     o.e.in0 = c->X + (size_t)l * NT * R; o.e.ld_in0 = R;
     o.e.scale = c->res_scale;
     o.e.out0 = c->X + (size_t)(l + 1) * NT * R; o.e.ld_out0 = R;
-    if (c->cfg.dropout > 0.0f) {
+    if (c->cfg.dropout > 0.0f && !c->feval) {
         o.e.out1 = c->XD + (size_t)(l + 1) * NT * R; o.e.ld_out1 = R;
         set_dropout(c, l + 1, o.key_lo, o.key_hi, o.thresh16, o.keep_scale, o.drop_ld);
     }
@@ -451,8 +451,11 @@ template <class F> static int for_each_part(wn_ctx* c, hipStream_t st, F f) {
     return WN_OK;
 }
 
-int wn_fwd_impl(wn_ctx* c, hipStream_t st, float* loss_out, float* y_hat_out) {
+// eval (wn_eval_fwd): the launches of a cfg.dropout == 0 context whatever cfg.dropout is -- the gate stages X, the out convolution and the input
+// convolution write no dropped copy, the fp32 mode passes no dropout keys; only host-side arguments differ.  Nothing is saved for a backward.
+int wn_fwd_impl(wn_ctx* c, hipStream_t st, float* loss_out, float* y_hat_out, bool eval) {
     int rc;
+    c->feval = eval;
     wn_devtrace_poll(c, st, true);
     if ((rc = wn_upsample_fwd(c, nullptr, c->fc, c->fB, c->fTc, st))) return rc;     // wavenet.py:680-702
     if ((rc = wn_first_conv(c, st))) return rc;                                      // wavenet.py:705
@@ -470,8 +473,8 @@ int wn_fwd_impl(wn_ctx* c, hipStream_t st, float* loss_out, float* y_hat_out) {
         return WN_OK;
     }
     rc = for_each_part(c, st, [&](int b0, int nb, hipStream_t s, bool first, int) {
-        if (first) c->prof_rows = nb * c->fT;      // rows of one timed gate-GEMM launch (wn_profile_result)
-        return fwd_part(c, b0, nb, s, c->prof && first);
+        if (first && !eval) c->prof_rows = nb * c->fT;      // rows of one timed gate-GEMM launch (wn_profile_result)
+        return fwd_part(c, b0, nb, s, c->prof && first && !eval);      // (an evaluation forward adds nothing to a wn_profile window)
     });
     if (rc) return rc;
     if (y_hat_out) WN_HIP(c, hipMemcpyAsync(y_hat_out, c->YHAT, (size_t)c->fB * c->O * c->fT * 4, hipMemcpyDeviceToDevice, st));

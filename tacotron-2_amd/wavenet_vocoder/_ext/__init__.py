@@ -132,6 +132,8 @@ def load_library():
         'wn_inv_mulaw_quantize': (ctypes.c_int, [vp, vp, i64, vp]),
         'wn_argmax_channels': (ctypes.c_int, [vp, vp, i32, i32, i32, vp]),
         'wn_loss': (ctypes.c_int, [vp, vp, vp, vp, i32, i32, i32, vp, vp]),
+        'wn_eval_fwd': (ctypes.c_int, [vp, vp, vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]),
+        'wn_score': (ctypes.c_int, [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]),
         'wn_profile': (ctypes.c_int, [vp, i32]),
         'wn_profile_result': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(i64)]),
         'wn_profile_kernel_result': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(i64)]),
@@ -479,6 +481,39 @@ class Engine:
     def loss(self, y_hat, y, lengths, shift, loss_out):
         B, T = int(y_hat.shape[0]), int(y_hat.shape[-1])
         self._ok(self.lib.wn_loss(self.h, _ptr(y_hat), _ptr(y), _ptr(lengths), B, T, int(shift), _ptr(loss_out), _stream()))
+
+    def eval_fwd(self, x, c, y, lengths, stats_out, nll_out=None, y_hat_out=None):
+        """Teacher-forced forward WITHOUT dropout (whatever wavenet_dropout is) + scores: stats_out float32 [B, 3] = (sum of the negative
+        log-likelihood, counted positions, counted positions with a non-zero loss) per utterance, nll_out optional [B, T] per sample,
+        y_hat_out optional [B, O, T].  Saves nothing for a backward (train_bwd raises until the next train_fwd)."""
+        import torch
+        B, T = int(lengths.shape[0]), int(x.shape[-1])
+        Tc = int(c.shape[-1])
+        _check(c, torch.float32, 'c'); _check(lengths, torch.int32, 'lengths')
+        self._score_outputs(B, T, stats_out, nll_out)
+        if y_hat_out is not None:
+            _check(y_hat_out, torch.float32, 'y_hat_out')
+        self._ok(self.lib.wn_eval_fwd(self.h, _ptr(x), _ptr(c), _ptr(y), _ptr(lengths), B, T, Tc, _ptr(stats_out), _ptr(nll_out), _ptr(y_hat_out), _stream()))
+
+    def score(self, y_hat, y, lengths, shift, stats_out, nll_out=None):
+        """Scores of [B, O, T] head outputs against y (shift as loss()): stats_out / nll_out as eval_fwd.  No gradient is written: works on
+        inference-only engines and leaves a pending train_bwd valid."""
+        import torch
+        _check(y_hat, torch.float32, 'y_hat'); _check(lengths, torch.int32, 'lengths')
+        B, T = int(y_hat.shape[0]), int(y_hat.shape[-1])
+        self._score_outputs(B, T, stats_out, nll_out)
+        self._ok(self.lib.wn_score(self.h, _ptr(y_hat), _ptr(y), _ptr(lengths), B, T, int(shift), _ptr(stats_out), _ptr(nll_out), _stream()))
+
+    @staticmethod
+    def _score_outputs(B, T, stats_out, nll_out):
+        import torch
+        _check(stats_out, torch.float32, 'stats_out')
+        if tuple(stats_out.shape) != (B, 3):
+            raise ValueError('stats_out must be [B=%d, 3] (got %s)' % (B, tuple(stats_out.shape)))
+        if nll_out is not None:
+            _check(nll_out, torch.float32, 'nll_out')
+            if tuple(nll_out.shape) != (B, T):
+                raise ValueError('nll_out must be [B=%d, T=%d] (got %s)' % (B, T, tuple(nll_out.shape)))
 
     def profile(self, enable):
         self._ok(self.lib.wn_profile(self.h, int(bool(enable))))

@@ -71,6 +71,7 @@ class Feeder(object):
         train_indices = np.concatenate([train_indices, extra])
         self._train_meta = [self._metadata[i] for i in train_indices]
         self._test_meta = [self._metadata[i] for i in test_indices]
+        self._test_indices = [int(i) for i in test_indices]      # metadata rows of the test split (validation_batches)
         self.test_steps = len(self._test_meta) // hparams.wavenet_batch_size
         if hparams.wavenet_test_size is None:
             assert hparams.wavenet_test_batches == self.test_steps
@@ -313,12 +314,45 @@ class Feeder(object):
                 return cand
         return path
 
+    # ------------------------------------------------------------------ validation
+    def validation_utterances(self, split='test'):
+        """[(metadata row index, metadata row)] this rank scores, batch by batch, in validation_batches(split): metadata order; the utterances of
+        every global batch of wavenet_batch_size are dealt to the ranks in contiguous slices (a short last batch leaves the last ranks short)."""
+        if split not in ('test', 'all'):
+            raise ValueError("validation split must be 'test' or 'all' (got %r)" % (split,))
+        rows = sorted(self._test_indices) if split == 'test' else list(range(len(self._metadata)))
+        n = self._hparams.wavenet_batch_size
+        per = n // self._world
+        out = []
+        for i in range(0, len(rows), n):
+            mine = rows[i:i + n][self._rank * per:(self._rank + 1) * per]
+            if mine:
+                out.append([(r, self._metadata[r]) for r in mine])
+        return out
+
+    def validation_batches(self, split='test'):
+        """Generator over this rank's slice of the held-out split ('test'; 'all': the whole metadata file) as feeder-format device batches
+        (inputs, targets, lengths, c, g): every utterance exactly once, in metadata order, the last batch possibly smaller.  Utterances
+        longer than the time limit get a hop-aligned crop whose start is drawn from RandomState(wavenet_data_random_state + metadata row), so
+        the split is the same at every validation of every run.  Files are read directly: the training / eval queues, offsets and random
+        generators are not touched, so the sequence of training and eval batches does not depend on when (or whether) this runs."""
+        hp = self._hparams
+        dev = self._device or torch.device('cuda', torch.cuda.current_device())
+        for group in self.validation_utterances(split):
+            batch = [_limit_time([self._load_example(meta)], hp, np.random.RandomState(hp.wavenet_data_random_state + row))[0] for row, meta in group]
+            yield tuple(None if b is None else torch.from_numpy(b).to(dev) for b in self._assemble_batch(batch))
+
     # ------------------------------------------------------------------ batch assembly
     def _prepare_batch(self, batch):
         hp = self._hparams
         batch = list(batch)
         self._rng.shuffle(batch)
         batch = _limit_time(batch, hp, self._rng)
+        return self._assemble_batch(batch)
+
+    def _assemble_batch(self, batch):
+        """Padded numpy tensors of a list of (audio, mel, speaker, length) examples, in the order given."""
+        hp = self._hparams
         input_lengths = np.asarray([len(x[0]) for x in batch], dtype=np.int32)
         max_t = int(input_lengths.max())
         hop = audio.get_hop_size(hp)
@@ -410,3 +444,7 @@ class SyntheticFeeder(object):
 
     def next_eval_batch(self):
         return self._batches[0]
+
+    def validation_batches(self, split='test'):
+        """The held-out split of the synthetic data: the one eval batch (test_steps = 1), resident on the device."""
+        yield self._batches[0]

@@ -15,7 +15,7 @@ import torch
 from datasets import audio
 from infolog import log
 from wavenet_vocoder import _ext, util
-from wavenet_vocoder.parallel import allreduce_loss_and_flags, allreduce_mean_buckets_
+from wavenet_vocoder.parallel import allreduce_loss_and_flags, allreduce_mean_buckets_, validation_loss
 from wavenet_vocoder.util import is_mulaw, is_mulaw_quantize, is_scalar_input
 
 from .modules import initialize_parameters, receptive_field_size
@@ -31,6 +31,16 @@ def stream_schedule(done, pushed, right, final):
     """Frames a stream push generates (wn_synth_stream_push): [done, pushed - right) once `right` frames of context follow them, all the
     pending frames [done, pushed) with final=True.  Returns (first, end)."""
     return done, (pushed if final else max(done, pushed - right))
+
+
+def validation_summary(rows, quantized):
+    """Per-utterance score rows [(sum of the negative log-likelihood, counted samples, samples with a non-zero loss)] -> the dict
+    WaveNet.validate returns.  ``loss`` is the training definition over all rows together: sum / count, or sum / nonzero for the softmax
+    head (``quantized``; modules.py:798).  Rows without a counted sample (an utterance of one sample) add nothing."""
+    utts = [(float(s), int(round(n)), int(round(z))) for s, n, z in rows]
+    live = [u for u in utts if u[1] > 0]
+    tot = (float(np.sum([u[0] for u in live], dtype=np.float64)) if live else 0.0, sum(u[1] for u in live), sum(u[2] for u in live))
+    return {'loss': validation_loss(tot[0], tot[1], tot[2], quantized), 'sum': tot[0], 'count': tot[1], 'nonzero': tot[2], 'utterances': utts}
 
 
 class SynthesisStream(object):
@@ -421,6 +431,28 @@ class WaveNet(object):
         self.engine.train_fwd(x.contiguous(), c.contiguous(), dummy_y, lengths, 0, None, y_hat)
         self._have_fwd = False
         return torch.softmax(y_hat, dim=1) if softmax else y_hat
+
+    def validate(self, batches):
+        """Held-out likelihood: one batched dropout-free teacher-forced forward (engine.eval_fwd) per feeder-format batch (x, y, lengths, c, g)
+        of ``batches`` -- Feeder.validation_batches() -- with the parameters as currently packed (no re-pack: the weights eval_step uses).
+        Returns {'loss', 'sum', 'count', 'nonzero', 'utterances': [(sum, count, nonzero), ...]} (validation_summary), the rows in the order the
+        utterances arrived.  Nothing waits for the GPU until the one device-to-host copy of all rows at the end.  A pending backward is
+        dropped: call it between training steps."""
+        if self.engine is None:
+            raise RuntimeError('WaveNet.validate: call build() / initialize() first')
+        if getattr(self, 'inference_only', False):
+            raise RuntimeError('WaveNet.validate needs a training engine (build(inference_only=False))')
+        self._ensure_packed()
+        rows = []
+        for x, y, lengths, c, g in batches:
+            B = int(lengths.shape[0])
+            self._set_global(g, B)
+            st = torch.empty(B, 3, device=self.device)
+            self.engine.eval_fwd(x.contiguous(), c.contiguous(), y.contiguous(), lengths.contiguous(), st)
+            rows.append(st)
+        self._have_fwd = False
+        host = torch.cat(rows).cpu().tolist() if rows else []
+        return validation_summary(host, is_mulaw_quantize(self._hparams.input_type))
 
     def incremental(self, initial_input, c=None, g=None, time_length=100, test_inputs=None, softmax=True, quantize=True,
                     log_scale_min=-7.0, log_scale_min_gauss=-7.0, noise=None, return_raw=False, check=False, chunk_frames=0):

@@ -50,6 +50,27 @@ def allreduce_loss_and_flags(loss, flags):
     return vec
 
 
+def allreduce_validation_totals(totals, device=None):
+    """Totals of a validation pass over all ranks.  ``totals``: this rank's (sum of the negative log-likelihood, counted samples, samples
+    with a non-zero loss[, utterances ...]); returns the element-wise sums over the ranks as Python floats after ONE all_reduce(SUM) in
+    fp64 (exact for the counts).  Without a process group, or with one rank, the inputs come back unchanged."""
+    vals = [float(v) for v in totals]
+    if is_distributed() and world_size() > 1:
+        if device is None:      # RCCL reduces device tensors only; gloo (the CPU tests) host tensors
+            device = torch.device('cuda', torch.cuda.current_device()) if torch.distributed.get_backend() == 'nccl' else 'cpu'
+        vec = torch.tensor(vals, dtype=torch.float64, device=device)
+        torch.distributed.all_reduce(vec, op=torch.distributed.ReduceOp.SUM)
+        vals = [float(v) for v in vec.cpu()]
+    return tuple(vals)
+
+
+def validation_loss(sum_, count, nonzero, quantized):
+    """The training definition of the loss from validation totals: sum / counted samples, or sum / samples with a non-zero loss for the
+    softmax head (modules.py:798); nan when nothing was counted."""
+    den = nonzero if quantized else count
+    return float(sum_) / float(den) if den > 0 else float('nan')
+
+
 _COMM_STREAMS = {}
 
 

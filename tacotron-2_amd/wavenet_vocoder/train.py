@@ -245,6 +245,31 @@ def eval_step(model, batch, step, plot_dir, wav_dir, scalars, hparams, model_nam
     return loss
 
 
+def validation_step(model, feeder, step, scalars, hparams):
+    """Held-out loss of the whole test split (mi355_validation_interval): EVERY rank scores its slice in batched dropout-free forwards
+    (WaveNet.validate), one small all-reduce adds the totals, rank 0 logs and writes the scalar.  A rank whose pass failed says so in the
+    same collective, and every rank raises together."""
+    from wavenet_vocoder.parallel import allreduce_validation_totals, validation_loss
+    start_time = time.time()
+    error, totals = None, (0.0, 0.0, 0.0, 0.0, 1.0)
+    try:
+        res = model.validate(feeder.validation_batches())
+        totals = (res['sum'], res['count'], res['nonzero'], len(res['utterances']), 0.0)
+    except Exception as e:          # noqa: BLE001 -- raised below, after the collective every rank is waiting in
+        error = e
+    s, n, z, utts, failed = allreduce_validation_totals(totals)
+    if error is not None:
+        raise error
+    if failed > 0:
+        raise RuntimeError('the validation pass of another rank failed at step {}: stopping every rank'.format(step))
+    loss = validation_loss(s, n, z, util.is_mulaw_quantize(hparams.input_type))
+    if scalars is not None:
+        log('Validation loss for global step {}: {:.5f} ({} utterances, {} samples, {:.3f} sec)'.format(step, loss, int(utts), int(n), time.time() - start_time))
+        scalars.write(json.dumps({'step': step, 'Wavenet_eval_model/eval_stats/wavenet_validation_loss': loss,
+                                  'wavenet_validation_utterances': int(utts), 'wavenet_validation_samples': int(n)}) + '\n'); scalars.flush()
+    return loss
+
+
 def train(log_dir, args, hparams, input_path):
     save_dir = os.path.join(log_dir, 'wave_pretrained')
     plot_dir = os.path.join(log_dir, 'plots')
@@ -360,6 +385,7 @@ def train(log_dir, args, hparams, input_path):
         last_batch = batch
         feeder_error = None
         newest = (step, float('nan'))                # (step, loss) of the newest loss the host has looked at
+        val_interval = int(getattr(hparams, 'mi355_validation_interval', 0) or 0)
         while not coord.should_stop() and step < args.wavenet_train_steps:
             start_time = time.time()
             if batch is None and feeder_error is None:
@@ -380,8 +406,9 @@ def train(log_dir, args, hparams, input_path):
             step = model.add_optimizer(step)
             embed = (hparams.gin_channels > 0 and model.embedding_table is not None
                      and (step % args.embedding_interval == 0 or step == args.wavenet_train_steps or step == 1))
+            validating = val_interval > 0 and step % val_interval == 0
             writes = (step % args.summary_interval == 0 or step % args.checkpoint_interval == 0 or step % args.eval_interval == 0
-                      or step >= args.wavenet_train_steps or embed)              # the same decision on every rank
+                      or step >= args.wavenet_train_steps or embed or validating)              # the same decision on every rank
             late.push(step, torch.cat([loss_t.reshape(1).float(), model.reduced_flags.reshape(1).float()]))
             ready = late.pop_ready(keep=0 if writes else 1)
             time_window.append(time.time() - start_time)
@@ -401,6 +428,9 @@ def train(log_dir, args, hparams, input_path):
             if dp is not None and step % args.checkpoint_interval == 0:
                 from wavenet_vocoder.parallel import assert_replicas_in_sync
                 assert_replicas_in_sync(model.params, what='parameters at step {}'.format(step))
+
+            if validating:          # every rank (its slice of the test split); raises on all of them together
+                validation_step(model, feeder, step, scalars, hparams)
 
             block_error = None
             try:
