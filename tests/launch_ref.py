@@ -1,4 +1,4 @@
-"""Every launch of the training backward chain (and the forward launches that feed it) restated as ONE operation on stored buffers,
+"""Every launch of the training forward and backward chains restated as ONE operation on stored buffers,
 in float64: plain torch, no autograd (except ref_dy, see there).  Inputs are exactly the buffers the kernel reads, outputs the buffers
 it writes, so a comparison against the device sees one launch at a time: which launch, which layer, which row.
 
@@ -94,6 +94,15 @@ class Weights:
         self.fin2 = rd(eff['final_convolution_2/kernel'][0])      # [S, O]
         self.w_in = eff['input_convolution/kernel'][0].to(torch.float64)      # [Cin, R]: fp32 on the device, never rounded
         self.b_in = eff['input_convolution/bias'].to(torch.float64)
+        # the forward launches' fp32 biases (None: use_bias = False, the device reads zeros) and the fp32 global-conditioning kernel
+        f64 = lambda k: None if eff.get(k) is None else eff[k].to(torch.float64)      # noqa: E731
+        self.b_dil = [f64('ResidualConv1DGLU_%d/residual_block_causal_conv/bias' % l) for l in range(L)]
+        self.b_cin = [f64('ResidualConv1DGLU_%d/residual_block_cin_conv/bias' % l) for l in range(L)]
+        self.b_gin = [f64('ResidualConv1DGLU_%d/residual_block_gin_conv/bias' % l) for l in range(L)]
+        self.b_skip = [f64('ResidualConv1DGLU_%d/residual_block_skip_conv/bias' % l) for l in range(L)]
+        self.w_gin = [None if cfg.gin_channels <= 0 else eff['ResidualConv1DGLU_%d/residual_block_gin_conv/kernel' % l][0].to(torch.float64) for l in range(L)]      # [gin, G]
+        self.b_fin1 = eff['final_convolution_1/bias'].to(torch.float64)
+        self.b_fin2 = eff['final_convolution_2/bias'].to(torch.float64)
 
 
 def _mm(a, b):
@@ -377,4 +386,301 @@ def ref_wgrads_gin(params, cfg, gvec, ids, DZ_colsums, dtype=torch.float64):
             demb.index_add_(0, ids.long(), dg)
     if demb is not None:
         out['gc_embedding'] = demb
+    return out
+
+
+# ------------------------------------------------------------------------------------------------------------------ forward chain
+# Every function below: store=False leaves the bf16 store out of the bound (tests/test_launch_ref_cpu.py holds a plain float32 evaluation,
+# which stores nothing to bf16, to the K 2^-23 A + E part alone).  With the store the bound is 2^-8 (|ref| + e) + e, e = K 2^-23 A + E: the
+# store rounds the DEVICE's fp32 value, which is at most |ref| + e.
+TINY = 2.0 ** -126                    # v_exp_f32 / v_rcp_f32 flush denormal results: an absolute 2^-126 where a function is saturated
+TANH_D2 = 4.0 / (3.0 * 3.0 ** 0.5)    # sup |tanh''|    = 4 / (3 sqrt 3), at tanh^2 = 1/3
+SIGM_D2 = 1.0 / (6.0 * 3.0 ** 0.5)    # sup |sigmoid''| = 1 / (6 sqrt 3), at sigmoid = 1/2 +- 1 / (2 sqrt 3)
+SECOND_ORDER = 1.0 + 2.0 ** -10       # products of two of the relative errors counted in E (each below 2^-10 of a first-order term, see ref_gate)
+
+
+def _with_store(ref_abs, e, store):
+    return BF * (ref_abs + e) + e if store else e
+
+
+def ref_gate_bias(W, params, cfg, gvec, w_ulps=0):
+    """The fp32 bias vector mk_gate passes to EPI_GATE, float64, + the absolute error of the device's fp32 value: (bias, err), each [L, Bb, G],
+    Bb = 1 without global conditioning, else B (bias_bstride = G: one vector per utterance).
+      * csrc/wn_pack.hip wn_pairsum_kernel: b1sum[l] = fl(b_dil[l] + b_cin[l]) (zeros when use_bias = False): ONE rounding, 2^-24 |b_dil + b_cin|
+        <= 2^-24 (|b_dil| + |b_cin|);
+      * csrc/wn_frontend.hip wn_gbias_kernel: a = fl(b1sum + b_g), then a = fl(a + g_b[k] W_g[k]) for k < gin, sequentially.  Every addend
+        passes through at most gin + 1 further additions and each product through one rounding of its own (none if the compiler contracts
+        to an fma): (gin + 3) 2^-24 Ab, Ab = |b_dil| + |b_cin| + |b_g| + sum_k |g_b[k]| |W_g[k]|, pairsum included.
+    gvec [B, gin]: the embedding rows (an exact fp32 copy, wn_gvec_kernel) or the raw features; W_g is the fp32 kernel (never rounded).
+    w_ulps: fp32 ulps by which the device's W_g may differ from W.w_gin (weight normalisation, as in ref_x0)."""
+    L, G = W.L, W.w_dil[0].shape[-1]
+    zero = torch.zeros(G, dtype=torch.float64)
+    bias, err = [], []
+    for l in range(L):
+        bd = W.b_dil[l] if W.b_dil[l] is not None else zero
+        bc = W.b_cin[l] if W.b_cin[l] is not None else zero
+        if cfg.gin_channels <= 0 or gvec is None:
+            bias.append((bd + bc)[None])
+            err.append(U24 * (bd.abs() + bc.abs())[None])
+            continue
+        bg = W.b_gin[l] if W.b_gin[l] is not None else zero
+        gv = gvec.to(torch.float64)
+        mv = _mm(gv, W.w_gin[l])                                   # [B, G]
+        Amv = _mm(gv.abs(), W.w_gin[l].abs())
+        bias.append(bd + bc + bg + mv)
+        err.append((cfg.gin_channels + 3) * U24 * (bd.abs() + bc.abs() + bg.abs() + Amv) + w_ulps * U24 * Amv)
+    return torch.stack(bias), torch.stack(err)
+
+
+def _fast_sigmoid_err(xabs, s, one_minus_s):
+    """|fast_sigmoid(x) - sigmoid(x)| of csrc/wn_tile.h for fp32 x (arguments: upper bounds of |x|, sigmoid, 1 - sigmoid):
+        p = fl(x * c), c = fl(-log2 e): two roundings, |dp| <= 2 * 2^-24 |p|, so 2^p moves by ln 2 |dp| = 2 * 2^-24 |x| relative;
+        e = v_exp_f32(p): 1 ulp = 2 * 2^-24 relative           -> rel(e) <= 2^-24 (2 |x| + 2)
+        q = fl(1 + e): e / (1 + e) = 1 - sigmoid of rel(e), + 2^-24
+        s = v_rcp_f32(q): 1 ulp = 2 * 2^-24                     -> rel(s) <= 2^-24 ((1 - s) (2 |x| + 2) + 3)."""
+    return s * U24 * (one_minus_s * (2.0 * xabs + 2.0) + 3.0) * SECOND_ORDER + TINY
+
+
+def _fast_tanh_err(xabs, tabs, one_minus_t, half_one_plus_t):
+    """|fast_tanh(x) - tanh(x)| (arguments: upper bounds of |x|, |tanh|, 1 - tanh, (1 + tanh) / 2):
+        p = fl(x * c), c = fl(2 log2 e): 2^p moves by ln 2 |dp| = 2 * 2^-24 * 2 |x| relative; e = v_exp_f32(p): + 2 * 2^-24  -> rel(e) <= 2^-24 (4 |x| + 2)
+        q = fl(e + 1): e / (1 + e) = (1 + tanh) / 2 of rel(e), + 2^-24;   r = v_rcp_f32(q): + 2 * 2^-24
+        t = fl(1 - 2 r) (2 r is exact; one rounding, fma or not): 2 r = 1 - tanh, so |dt| <= (1 - tanh) rel(r) + 2^-24 |t|."""
+    return (one_minus_t * U24 * (half_one_plus_t * (4.0 * xabs + 2.0) + 3.0) + U24 * tabs) * SECOND_ORDER + 2.0 * TINY
+
+
+def gate_preactivation(W, l, XD, cbt, bias, want_bound=False):
+    """z [B, T, G] of layer l and (want_bound) the bound of the device's fp32 accumulator against it:
+        z = sum_j shift_time(XD, -(2 - j) d) W_dil[j] + cbt W_cin + bias       (taps before the utterance start are zero)
+    K = 3 R + C + 1: the bias is one more addend (the ring / 8-phase main loops START the accumulators at it, the 64-row tile kernel adds it in
+    the epilogue: one rounding either way).  dz = K 2^-23 A + err(bias), A = sum |x| |w| + |bias|."""
+    d = W.dil[l]
+    b, eb = bias
+    z = _mm(cbt, W.w_cin[l]) + b[:, None, :]
+    for j in range(3):
+        z = z + _mm(shift_time(XD, -(2 - j) * d), W.w_dil[l][j])
+    if not want_bound:
+        return z, None
+    A = _mm(cbt.abs(), W.w_cin[l].abs()) + b.abs()[:, None, :]
+    Xa = XD.abs()
+    for j in range(3):
+        A = A + _mm(shift_time(Xa, -(2 - j) * d), W.w_dil[l][j].abs())
+    K = 3 * XD.shape[-1] + cbt.shape[-1] + 1
+    return z, K * U23 * A + eb[:, None, :]
+
+
+def ref_gate(W, l, XD, cbt, bias, want_bound=False, store=True, z_out=None):
+    """mk_gate / EPI_GATE of layer l (modules.py:484-510): ref = (TS, U), TS = sigmoid(z_b), U = tanh(z_a) sigmoid(z_b), z = [z_a | z_b] from
+    gate_preactivation.  XD: the conv input the launch stages (XD[l]; X[l] with dropout 0 and under wn_eval_fwd); bias = (bias[l], err[l]) of
+    ref_gate_bias.  bound = (bound TS, bound U), in four steps:
+      1. the accumulator: |z_dev - z| <= dz = K 2^-23 A + err(bias) (gate_preactivation), da / db its two halves;
+      2. through the nonlinearities, exactly (Taylor with the Lagrange remainder): |tanh(z_a + da) - tanh(z_a)| <= (1 - t^2) da + da^2 sup|tanh''| / 2
+         =: Dt, |sigmoid(z_b + db) - sigmoid(z_b)| <= s (1 - s) db + db^2 sup|sigmoid''| / 2 =: Ds (sup|tanh''| = 4 / (3 sqrt 3), sup|sigmoid''| =
+         1 / (6 sqrt 3));
+      3. fast_tanh / fast_sigmoid on the DEVICE's z (_fast_tanh_err, _fast_sigmoid_err, derived there from their instruction sequence), so
+         they are evaluated at the upper ends |z| + dz, s + Ds, |t| + Dt, ...:  et = Dt + Et, es = Ds + Es;
+         u = fl(t s): |du| <= s et + |t| es + et es, + 2^-24 of the product;
+         second-order products of the relative errors inside Et / Es: every factor is below 2^-24 (4 |z| + 5) < 2^-10 for |z| < 2^11, and
+         both functions are saturated to within 2^-126 long before (|z| > 89): the factor 1 + 2^-10 (SECOND_ORDER) covers them;
+      4. the bf16 stores of TS and U: 2^-8 (|ref| + e).
+    z_out: a list that receives z (for gate_start_leak's comparison)."""
+    GH = W.w_dil[l].shape[-1] // 2
+    z, dz = gate_preactivation(W, l, XD, cbt, bias, want_bound)
+    if z_out is not None:
+        z_out.append(z)
+    za, zb = z[..., :GH], z[..., GH:]
+    t, s = torch.tanh(za), torch.sigmoid(zb)
+    u = t * s
+    if not want_bound:
+        return (s, u), None
+    da, db = dz[..., :GH], dz[..., GH:]
+    omt = 2.0 * torch.sigmoid(-2.0 * za)                           # 1 - tanh without cancellation
+    oms = torch.sigmoid(-zb)                                       # 1 - sigmoid
+    Dt = (1.0 - t * t) * da + 0.5 * TANH_D2 * da * da
+    Ds = s * oms * db + 0.5 * SIGM_D2 * db * db
+    Et = _fast_tanh_err(za.abs() + da, (t.abs() + Dt).clamp(max=1.0), (omt + Dt).clamp(max=2.0), (0.5 * (2.0 - omt + Dt)).clamp(max=1.0))
+    Es = _fast_sigmoid_err(zb.abs() + db, (s + Ds).clamp(max=1.0), (oms + Ds).clamp(max=1.0))
+    et, es = Dt + Et, Ds + Es
+    du = s * et + t.abs() * es + et * es
+    eu = du + U24 * (u.abs() + du)
+    return (s, u), (_with_store(s, es, store), _with_store(u.abs(), eu, store))
+
+
+def skip_bias_total(W):
+    """csrc/wn_pack.hip wn_vecsum_kernel: a = 0; a = fl(a + c_l b_skip[l]) for l < L, (bias, err) [S]: every term passes through one product
+    rounding (none under fma contraction) and at most L - 1 additions (0 + x is exact): L 2^-24 sum_l |c_l b_l|."""
+    S = W.w_skip[0].shape[-1]
+    b, a = torch.zeros(S, dtype=torch.float64), torch.zeros(S, dtype=torch.float64)
+    for l in range(W.L):
+        if W.b_skip[l] is not None:
+            b = b + W.skip_scale[l] * W.b_skip[l]
+            a = a + abs(W.skip_scale[l]) * W.b_skip[l].abs()
+    return b, W.L * U24 * a
+
+
+def ref_r1(W, U_all, want_bound=False, store=True):
+    """fwd_tail, the skip sum as ONE contraction (nrep = L) + EPI_STORE_BF16 with relu: R1 = relu(sum_l U[l] (c_l W_skip[l]) + skip_bias_total)
+    (wavenet.py:706-719; W.w_skip[l] holds c_l W_skip, rounded as wn_pack_kernel rounds it).  U_all: an iterable of the L tensors U[l] [B, T, GH],
+    consumed one at a time (a generator keeps one layer resident).  K = L GH + 1 (the bias is one more addend of the accumulator), + the error
+    of the fp32 bias (skip_bias_total).  E = 0: the epilogue multiplies by scale = 1 (exact); ReLU is 1-Lipschitz, so the error of the
+    accumulator carries over unchanged and no element near 0 needs excluding (a reference of 0 keeps its bound: the device may be a little
+    above 0 there)."""
+    b, eb = skip_bias_total(W)
+    v, A, n = None, None, 0
+    for l, U in enumerate(U_all):
+        r = _mm(U, W.w_skip[l])
+        v = r if v is None else v + r
+        if want_bound:
+            a = _mm(U.abs(), W.w_skip[l].abs())
+            A = a if A is None else A + a
+        n += 1
+        K = n * U.shape[-1] + 1
+    assert n == W.L, 'ref_r1 needs U of all %d layers (got %d)' % (W.L, n)
+    ref = torch.relu(v + b)
+    if not want_bound:
+        return ref, None
+    e = K * U23 * (A + b.abs()) + eb
+    return ref, _with_store(ref, e, store)
+
+
+def ref_h2(W, R1, want_bound=False, store=True):
+    """fwd_tail, final_convolution_1 + EPI_STORE_BF16 with relu: H2 = relu(R1 fin1 + b) (wavenet.py:136-149).  K = S + 1, E = 0 (scale = 1; the
+    fp32 bias is a parameter, read as stored)."""
+    ref = torch.relu(_mm(R1, W.fin1) + W.b_fin1)
+    if not want_bound:
+        return ref, None
+    e = (R1.shape[-1] + 1) * U23 * (_mm(R1.abs(), W.fin1.abs()) + W.b_fin1.abs())
+    return ref, _with_store(ref, e, store)
+
+
+def ref_yhat(W, H2, want_bound=False):
+    """fwd_tail, final_convolution_2 + EPI_STORE_F32_BOT with M_valid = O: YHAT[b, o, t] = sum_s H2[b, t, s] fin2[s, o] + b[o], fp32, layout
+    [B, O, T] (exactly O channels).  K = S; no bf16 store.  E: y = v * scale + bias with scale = 1 (exact product): ONE rounding of the sum (fma
+    or not), 2^-24 (|v| + K 2^-23 A + |b|)."""
+    v = _mm(H2, W.fin2)
+    ref = (v + W.b_fin2).permute(0, 2, 1).contiguous()
+    if not want_bound:
+        return ref, None
+    acc = H2.shape[-1] * U23 * _mm(H2.abs(), W.fin2.abs())
+    e = acc + U24 * (v.abs() + acc + W.b_fin2.abs())
+    return ref, e.permute(0, 2, 1).contiguous()
+
+
+def _shift(x, s, dim):
+    """y[..., i, ...] = x[..., i + s, ...] along dim, 0 outside."""
+    n = x.shape[dim]
+    y = torch.zeros_like(x)
+    if abs(s) >= n:
+        return y
+    if s == 0:
+        return x
+    if s > 0:
+        y.narrow(dim, 0, n - s).copy_(x.narrow(dim, s, n - s))
+    else:
+        y.narrow(dim, -s, n + s).copy_(x.narrow(dim, 0, n + s))
+    return y
+
+
+def ref_cup_level(params, cfg, i, inp, want_bound=False, rounded=True, w_ulps=0):
+    """One level of the upsample net (csrc/wn_frontend.hip wn_up_fwd / wn_up_fwd_generic; modules.py:524-770) from the level's OWN input:
+    inp [B, C, Tin] (level 0: c_in, level i: CUP[i-1]) -> CUP[i] [B, C, Tin s], s = upsample_scales[i], frequency padding pf = (fk - 1) / 2:
+        NearestNeighbor (one level, s = hop)    out[f, t s + j] = in[f, t]                                                            exact copy
+        2D        kernel [fk, s, 1, 1]          out[f, t s + j] = act(b + sum_kf in[f - kf + pf, t] K[kf, j])                         K = fk
+        SubPixel  kernel [fk, 3, 1, s]          out[f, t s + j] = act(b[j] + sum_kf sum_kt in[f + kf - pf, t + kt - 1] K[kf, kt, j])  K = 3 fk
+        Resize    kernel [fk, s, 1, 1]          out[f, to] = act(b + sum_kf sum_kt up[f + kf - pf, to + kt - (s - 1) / 2] K[kf, kt]),
+                                                up[f, tu] = in[f, tu / s]                                                             K = fk s
+        1D        kernel [1, s, C, C]           out[co, t s + j] = act(b[co] + sum_ci in[ci, t] K[j, co, ci])                         K = C
+    (taps outside the frequency / time range are zero).  fp32 kernels, never rounded; rounded=True only takes leaky_alpha as the float32 the
+    configuration struct carries.  Bound: v starts at the bias (exact) and takes K sequential v = fl(v + fl(in K)): K additions of partial
+    sums that are at most A = |b| + sum |in| |K| each, and the products' own roundings, together at most A again: (K + 1) 2^-24 A; + 2^-24 |b|;
+    LeakyRelu's alpha v is one more rounding, 2^-24 |ref|; every activation is 1-Lipschitz, so the rest carries over.  No bf16 store: CUP is
+    fp32.  w_ulps: fp32 ulps by which the device's kernel may differ (weight normalisation, as in ref_x0)."""
+    t = cfg.upsample_type
+    x = inp.to(torch.float64)
+    B, C, Tin = x.shape
+    if t == 'NearestNeighbor':
+        ref = torch.repeat_interleave(x, cfg.hop, dim=2)
+        return ref, (torch.zeros_like(ref) if want_bound else None)
+    eff = O.effective_params(params, cfg)
+    s = cfg.upsample_scales[i]
+    Kw = eff['local_conditioning_upsampling_%d/kernel' % (i + 1)].to(torch.float64)
+    b = eff['local_conditioning_upsampling_%d/bias' % (i + 1)].to(torch.float64)
+    fk = Kw.shape[0]
+    pf = (fk - 1) // 2
+
+    def run(xx, KK):
+        if t == '2D':
+            v = torch.zeros(B, C, Tin, s, dtype=torch.float64)
+            for kf in range(fk):
+                v = v + _shift(xx, pf - kf, 1)[..., None] * KK[kf, :, 0, 0]
+            return v.reshape(B, C, Tin * s), fk
+        if t == 'SubPixel':
+            v = torch.zeros(B, C, Tin, s, dtype=torch.float64)
+            for kf in range(fk):
+                xf = _shift(xx, kf - pf, 1)
+                for kt in range(3):
+                    v = v + _shift(xf, kt - 1, 2)[..., None] * KK[kf, kt, 0, :]
+            return v.reshape(B, C, Tin * s), 3 * fk
+        if t == 'Resize':
+            up = torch.repeat_interleave(xx, s, dim=2)
+            pl = (s - 1) // 2
+            v = torch.zeros(B, C, Tin * s, dtype=torch.float64)
+            for kf in range(fk):
+                xf = _shift(up, kf - pf, 1)
+                for kt in range(s):
+                    v = v + _shift(xf, kt - pl, 2) * KK[kf, kt, 0, 0]
+            return v, fk * s
+        if t == '1D':
+            v = torch.einsum('bit,joi->botj', xx, KK[0])
+            return v.reshape(B, C, Tin * s), C
+        raise ValueError(t)
+
+    v, K = run(x, Kw)
+    if t == 'SubPixel':
+        bb = b.repeat(Tin)                                         # b[j] at to = t s + j
+    elif t == '1D':
+        bb = b[:, None]
+    else:
+        bb = b
+    v = v + bb
+    act = cfg.upsample_activation
+    alpha = float(np.float32(cfg.leaky_alpha)) if rounded else float(cfg.leaky_alpha)
+    if act == 'Relu':
+        ref = torch.relu(v)
+    elif act == 'LeakyRelu':
+        ref = torch.where(v > 0, v, alpha * v)
+    else:
+        assert act in (None, 'None')
+        ref = v
+    if not want_bound:
+        return ref, None
+    Ap, _ = run(x.abs(), Kw.abs())
+    ba = (torch.zeros_like(v) + bb).abs()
+    bound = (K + 1) * U24 * (Ap + ba) + U24 * ba + w_ulps * U24 * Ap
+    if act == 'LeakyRelu':
+        bound = bound + U24 * ref.abs()
+    return ref, bound
+
+
+def ref_cbt(CUP_last):
+    """cbt, BIT-EXACT from the device's own last level: the bf16 rounding of CUP[last] [B, C, T], time-major [B, T, C] (the f2bf of the same
+    fp32 value the kernel stores to CUP)."""
+    return bf16(CUP_last).permute(0, 2, 1).contiguous()
+
+
+def gate_start_leak(W, l, XD):
+    """What z of layer l would GAIN if the taps read across the utterance start into the previous utterance's last rows (rows b T + t - (2 - j) d
+    of the flat buffer with t < (2 - j) d, b > 0): [B, T, G], zero outside the first 2 d rows of the utterances b >= 1."""
+    d = W.dil[l]
+    B, T, R = XD.shape
+    flat = rows(XD)
+    out = torch.zeros(B, T, W.w_dil[l].shape[-1], dtype=torch.float64)
+    for j in range(2):                                             # (the tap j = 2 has shift 0)
+        sft = (2 - j) * d
+        n = min(sft, T)
+        for b in range(1, B):
+            first = b * T - sft
+            skip = max(0, -first)
+            if n > skip:
+                out[b, skip:n] += _mm(flat[first + skip: first + n], W.w_dil[l][j])
     return out

@@ -1,4 +1,4 @@
-"""Launch-local parity of the backward chain against the float64 references of tests/launch_ref.py (pytest -m gpu).
+"""Launch-local parity of the forward and the backward chain against the float64 references of tests/launch_ref.py (pytest -m gpu).
 
 Every other GPU test of the backward compares final weight-gradient tensors (sums over all B x T rows) with autograd as a rel-L2 per
 tensor (1.4e-2 and wider): a fault confined to a few rows of d z or d h -- a tap that reads the next utterance at an utterance end, a
@@ -24,7 +24,14 @@ per launch kind, with the worst layer; WN_LAUNCH_LOCAL_DETAIL=1 prints every lay
 launch, layer, utterance, t, channel, tile index (row // 128) and whether the row is within 2 d of an utterance end.  For GX[l] the
 last 2 d rows of every utterance and the first 2 d rows of the next one are their own group ('GX edge'), and the tap gradients must be
 closer to the reference than HALF of what a read across the utterance start would add ('taps leak'), so a leak across b shows by name.
-The printed ratios are records, not thresholds."""
+The printed ratios are records, not thresholds.
+
+The forward chain (check_forward; check_step runs it first, and the backward checks then rest on checked TS / U / R1 / H2 / cbt): CUP0..n
+(every upsample level from the device's own input of that level), cbt (bit-exact from the device's last level), per layer TS and U (from
+the device's XD[l] -- X[l] with dropout 0 and under wn_eval_fwd -- and cbt, with the fp32 gate bias restated from the parameters), R1 (the
+device's U of all layers), H2 (the device's R1), YHAT (the device's H2; fp32, exactly O channels), same form of bound, no exclusions.
+'U start' is the forward twin of 'GX edge': the first 2d rows of every utterance b >= 1 and the rows of a partial last tile; 'start leak'
+holds |U dev - ref| on those first rows below HALF of what reading the previous utterance's last rows would add to U."""
 import os
 
 import numpy as np
@@ -32,7 +39,7 @@ import pytest
 import torch
 
 import launch_ref as LR
-from hip_util import download_grads, dropout_mask_rows, make_hp, oracle_cfg, synth_batch, upload_params
+from hip_util import SMALL, download_grads, dropout_mask_rows, make_hp, oracle_cfg, synth_batch, upload_params
 from oracle import wavenet_oracle as O
 from test_hip_bench_geometry import C5, PAPER
 from test_hip_parity import _run_fwd
@@ -140,8 +147,110 @@ def _edge_group(B, T, d):
     return g
 
 
+def _start_group(B, T, d):
+    """1 on the first 2d rows of every utterance b >= 1 and on the rows of a partial last time tile (128- and 64-row tiles)."""
+    g = torch.zeros(B, T, 1, dtype=torch.float64)
+    g[1:, :min(2 * d, T)] = 1.0
+    for tile in (128, 64):
+        if T % tile:
+            g[:, T - T % tile:] = 1.0
+    return g
+
+
+def check_forward(tag, eng, cfg, params, B, T, seed, x_in, c_in, g=None, chain_layers=None, detail=False, eval_mode=False, x_checks=True, rep=None):
+    """The buffers the forward launches wrote (after train_fwd, or after eval_fwd with eval_mode=True: the gate then staged X and nothing wrote
+    XD) against launch_ref, every element, each launch from the device's OWN inputs of that launch, one layer resident at a time:
+    CUP0..n, cbt (exact), per layer in chain_layers TS / U (+ 'U start': the first 2d rows of the utterances b >= 1 and the rows of a partial
+    last tile; there the device must also be closer to the reference than HALF of what reading the previous utterance's rows would add to U),
+    R1 (always all layers), H2, YHAT (exactly O channels).  x_checks: X0 and X_next too (check_step has them in its own loop).
+    rep: a Report to add to (the caller finishes it); otherwise a new one, finished here."""
+    L, R, G, S, C = cfg.layers, cfg.residual_channels, cfg.gate_channels, cfg.skip_out_channels, cfg.cin_channels
+    GH, Oc = G // 2, cfg.out_channels
+    n = B * T
+    chain_layers = set(range(L)) if chain_layers is None else set(chain_layers)
+    W = LR.Weights(params, cfg, rounded=True)
+    own = rep is None
+    rep = Report(tag, B, T, detail) if own else rep
+    p = float(cfg.wavenet_dropout)
+    dropped = p > 0 and not eval_mode
+    w_ulps = 8 if cfg.wavenet_weight_normalization else 0      # (both sides compute v g / ||v|| in fp32: launch_ref.ref_x0)
+
+    def dl(name, l, ch):
+        return eng.debug_copy(name, l, n, ch).cpu().double().view(B, T, ch)
+
+    # ---- upsample net: every level from the device's own input of that level; cbt from the device's own last level
+    nearest = cfg.upsample_type == 'NearestNeighbor'
+    inp = c_in.double()
+    for i in range(1 if nearest else len(cfg.upsample_scales)):
+        Tout = inp.shape[-1] * (cfg.hop if nearest else cfg.upsample_scales[i])
+        dev = eng.debug_copy('CUP', i, B * C, Tout).cpu().double().view(B, C, Tout)
+        ref, bound = LR.ref_cup_level(params, cfg, i, inp, True, w_ulps=w_ulps)
+        rep.elementwise('CUP%d' % i, 0, dev.permute(0, 2, 1), ref.permute(0, 2, 1), bound.permute(0, 2, 1))      # (reported as utterance : t at that level : frequency)
+        inp = dev
+    assert inp.shape[-1] == T
+    cbt = dl('cbt', 0, C)
+    rep.exact('cbt', 0, cbt, LR.ref_cbt(inp))
+    rep.flush('upsample')
+    del inp
+    # ---- the gate bias (b1sum / gbias are not downloadable: float64 from the parameters, with the error of the device's fp32 sums)
+    gvec = None
+    if g is not None:
+        gvec = params['gc_embedding'][g.long()] if cfg.use_speaker_embedding else g
+    bias, ebias = LR.ref_gate_bias(W, params, cfg, gvec, w_ulps=w_ulps)
+    # ---- layers
+    for l in range(L):
+        if l not in chain_layers:
+            continue
+        d = W.dil[l]
+        XD = dl('XD' if dropped else 'X', l, R)
+        TS, U = dl('TS', l, GH), dl('U', l, GH)
+        zs = []
+        (rTS, rU), (bTS, bU) = LR.ref_gate(W, l, XD, cbt, (bias[l], ebias[l]), True, z_out=zs)
+        rep.elementwise('TS', l, TS, rTS, bTS, d)
+        rep.elementwise('U', l, U, rU, bU, d)
+        grp = _start_group(B, T, d)
+        rep.elementwise('U start', l, U, rU, bU, d, group=grp)
+        if B > 1:      # a tap that read across the utterance start would move U by `leak` on the first 2d rows: the device must be far closer than that
+            z = zs[0] + LR.gate_start_leak(W, l, XD)
+            nrow = min(2 * d, T)
+            leak = float((torch.tanh(z[1:, :nrow, :GH]) * torch.sigmoid(z[1:, :nrow, GH:]) - rU[1:, :nrow]).norm())
+            err = float((U[1:, :nrow] - rU[1:, :nrow]).norm())
+            rep._note('start leak', l, err / leak if leak > 0 else 0.0, 'start leak %.1e/%.1e' % (err, leak))
+            if leak > 0 and not err < 0.5 * leak:
+                rep.fail.append('[%s] start leak layer %d (d = %d): |U dev - ref| = %.3e on the first 2d rows of the utterances b >= 1 is not below half of what reading the '
+                                'previous utterance adds (%.3e)' % (tag, l, d, err, leak))
+            del z
+        del zs, rTS, rU, bTS, bU, TS
+        if x_checks:
+            X = dl('X', l, R)
+            if l == 0:
+                rep.elementwise('X0', 0, X, *LR.ref_x0(W, x_in, True, w_ulps=w_ulps))
+            if l < L - 1:
+                rep.elementwise('X_next', l, dl('X', l + 1, R), *LR.ref_x_next(W, l, U, X, True))
+            if dropped:
+                m = torch.from_numpy(dropout_mask_rows(seed, l, 0, n, R, p)).double().view(B, T, R)
+                rep.exact('XD', l, XD, LR.ref_xd(W, X, m))
+            del X
+        del XD, U
+        rep.flush('L%02d fwd' % l)
+    # ---- skip sum (all layers, one resident at a time) and head, each from the device's own input
+    R1 = dl('R1', 0, S)
+    rep.elementwise('R1', 0, R1, *LR.ref_r1(W, (dl('U', l, GH) for l in range(L)), True))
+    H2 = dl('H2', 0, S)
+    rep.elementwise('H2', 0, H2, *LR.ref_h2(W, R1, True))
+    yhat = eng.debug_copy('YHAT', 0, B * Oc, T).cpu().double().view(B, Oc, T)
+    ref, bound = LR.ref_yhat(W, H2, True)
+    assert tuple(ref.shape) == (B, Oc, T)
+    rep.elementwise('YHAT', 0, yhat.permute(0, 2, 1), ref.permute(0, 2, 1), bound.permute(0, 2, 1))
+    rep.flush('fwd tail')
+    if own:
+        rep.finish()
+    return rep
+
+
 def check_step(tag, eng, cfg, params, B, T, lengths, seed, x_in, y_or, c_in, grads_flat, g=None, chain_layers=None, wgrad_layers=None, wgrads=True, detail=False):
-    """The device's buffers after one train_fwd + train_bwd against launch_ref, one layer resident at a time."""
+    """The device's buffers after one train_fwd + train_bwd against launch_ref, one layer resident at a time: the forward launches
+    (check_forward), then the backward chain."""
     L, R, G, S, C = cfg.layers, cfg.residual_channels, cfg.gate_channels, cfg.skip_out_channels, cfg.cin_channels
     GH, Oc = G // 2, cfg.out_channels
     ldDY = (Oc + 15) // 16 * 16
@@ -152,6 +261,7 @@ def check_step(tag, eng, cfg, params, B, T, lengths, seed, x_in, y_or, c_in, gra
     rep = Report(tag, B, T, detail)
     p = float(cfg.wavenet_dropout)
     g_dev = download_grads(eng, grads_flat) if wgrads else {}
+    check_forward(tag, eng, cfg, params, B, T, seed, x_in, c_in, g=g, chain_layers=chain_layers, x_checks=False, rep=rep)      # (X0 / X_next / XD: in the loop below)
 
     def dl(name, l, ch):
         return eng.debug_copy(name, l, n, ch).cpu().double().view(B, T, ch)
@@ -282,6 +392,68 @@ def test_launch_local_geometry_sweep(name):
                        wgrads=not cfg.wavenet_weight_normalization)      # (v / g gradients stay with the end-to-end test)
         finally:
             eng.close()
+
+
+def _x_in(r):
+    return r['y_or'] if r['cfg'].input_type == 'mulaw-quantize' else r['x_or'].view(r['B'], r['T'])
+
+
+@pytest.mark.parametrize('name', ['mol_resize_odd', 'gauss_1d', 'gauss_cdf_nn'])
+def test_launch_local_forward_upsample_types(name):
+    """The three upsamplers SMALL_CONFIGS lacks (Resize with odd scales, 1D, NearestNeighbor) at B = 3, T = the smallest multiple of the hop
+    above 128 that is no multiple of 128 (144 at hop 16, 150 at hop 15), lengths [T, 129, 2]: the forward checks inside the full check_step."""
+    from test_hip_parity import CONFIGS
+    hop = int(np.prod(dict(SMALL, **CONFIGS[name])['upsample_scales']))
+    T = {16: 144, 15: 150}[hop]
+    assert T % hop == 0 and T > 128 and T % 128 != 0
+    B, lengths = 3, [T, 129, 2]
+    r = _run_fwd(name, B=B, T=T, lengths=lengths)
+    cfg, eng = r['cfg'], r['eng']
+    assert r['T'] == T
+    try:
+        grads = torch.empty(eng.n_params, device='cuda')
+        eng.train_bwd(grads)
+        torch.cuda.synchronize()
+        check_step('%s B=%d T=%d' % (name, B, T), eng, cfg, r['params'], B, T, lengths, r['seed'], _x_in(r), r['y_or'], r['c'], grads, g=r['g'], detail=True)
+    finally:
+        eng.close()
+
+
+@pytest.mark.parametrize('B,T,lengths', [(3, 144, [144, 129, 2]), (5, 272, [272, 256, 255, 130, 16])])
+@pytest.mark.parametrize('name', ['paper_width_drop', 'mol_2d_legacy_drop'])
+def test_launch_local_eval_forward(name, B, T, lengths):
+    """wn_eval_fwd reuses the forward launches with other host arguments (the gate stages X, nothing writes XD).  After a train_fwd (whose XD
+    and DY are snapshotted) an eval_fwd on the same inputs: the forward checks hold with the gate reading X, X0 / X_next hold, XD (and DY) are
+    byte-identical to the snapshot, and the per-sample NLL it returns is wn_score's on the device's own YHAT, bit for bit."""
+    r = _run_fwd(name, B=B, T=T, lengths=lengths)
+    cfg, eng = r['cfg'], r['eng']
+    assert r['T'] == T and cfg.wavenet_dropout > 0 and cfg.input_type == 'raw'
+    L, R, Oc = cfg.layers, cfg.residual_channels, cfg.out_channels
+    ldDY = (Oc + 15) // 16 * 16
+    try:
+        snap = [eng.debug_copy('XD', l, B * T, R).cpu() for l in range(L)]
+        dy = eng.debug_copy('DY', 0, B * T, ldDY).cpu()
+        assert any(not torch.equal(snap[l], eng.debug_copy('X', l, B * T, R).cpu()) for l in range(L))      # (the training forward did drop)
+        ln = torch.tensor(lengths, dtype=torch.int32, device='cuda')
+        stats = torch.full((B, 3), float('nan'), device='cuda')
+        nll = torch.full((B, T), float('nan'), device='cuda')
+        yh = torch.full((B, Oc, T), float('nan'), device='cuda')
+        eng.eval_fwd(r['x_or'].cuda(), r['c'].cuda(), r['y_or'].cuda(), ln, stats, nll, yh)
+        torch.cuda.synchronize()
+        check_forward('%s eval B=%d T=%d' % (name, B, T), eng, cfg, r['params'], B, T, r['seed'], _x_in(r), r['c'], g=r['g'], eval_mode=True, x_checks=True)
+        for l in range(L):
+            assert torch.equal(snap[l].view(torch.int32), eng.debug_copy('XD', l, B * T, R).cpu().view(torch.int32)), 'eval_fwd wrote XD[%d]' % l
+        assert torch.equal(dy.view(torch.int32), eng.debug_copy('DY', 0, B * T, ldDY).cpu().view(torch.int32)), 'eval_fwd wrote DY'
+        yhat = eng.debug_copy('YHAT', 0, B * Oc, T).view(B, Oc, T).contiguous()
+        assert torch.equal(yhat.view(torch.int32), yh.view(torch.int32))
+        st2 = torch.full((B, 3), float('nan'), device='cuda')
+        nl2 = torch.full((B, T), float('nan'), device='cuda')
+        eng.score(yhat, r['y_or'].cuda(), ln, 1, st2, nl2)
+        torch.cuda.synchronize()
+        assert torch.equal(nll.cpu().view(torch.int32), nl2.cpu().view(torch.int32)), 'per-sample NLL of eval_fwd != wn_score on the device\'s YHAT'
+        assert torch.equal(stats.cpu().view(torch.int32), st2.cpu().view(torch.int32))
+    finally:
+        eng.close()
 
 
 # ------------------------------------------------------------------------------------------------------------------ benched geometries

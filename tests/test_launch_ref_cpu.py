@@ -7,7 +7,10 @@ z_l, the skip sum and y_hat; the oracle's own unrounded intermediates go through
 fed by the previous launch's reference output), and every output must equal autograd's to 1e-10 relative (max-abs over max-abs): both
 sides are float64 evaluations of the same expression, so 1e-10 is a derived number (~1e6 ulps of slack for the different association of
 sums of <= 1e3 terms), not a measured one.  Where the device stores s = sigmoid and u = tanh * sigmoid the chain gets exactly those,
-and recovers tanh as u / s like the kernel."""
+and recovers tanh as u / s like the kernel.
+
+The forward launches (second half of this file) are pinned the same way against the float64 oracle FORWARD, and each of their bounds,
+without its bf16 store term, against a plain float32 evaluation of the same launch."""
 import numpy as np
 import pytest
 import torch
@@ -173,3 +176,236 @@ def test_bound_is_zero_where_reference_and_operands_are_zero():
     mask = (torch.rand(B, T, R, generator=gen) > 0.05).double()
     ref, bound = LR.ref_gx(W, 1, DZ, mask, up, want_bound=True)          # d = 2: rows >= 8 see nothing
     assert float(ref[:, 8:].abs().max()) == 0 and float(bound[:, 8:].abs().max()) == 0 and float(bound[:, :6].min()) > 0
+
+
+# ------------------------------------------------------------------------------------------------------------------ forward chain
+# The forward launches of launch_ref (ref_x0 -> per layer ref_gate, ref_x_next -> ref_r1 -> ref_h2 -> ref_yhat; the upsample levels; the gate
+# bias) pinned twice:
+#   * rounded=False, chained (each launch fed by the previous launch's reference output), against the float64 oracle forward to 1e-10;
+#   * rounded=True, every bound without its bf16 store term against the SAME launch evaluated in plain float32 (float32 matmuls, the fp32
+#     bias sums in the kernels' order, fast_tanh / fast_sigmoid step by step with a correctly rounded exp2 and reciprocal -- the hardware's
+#     are allowed one ulp): a bound that a clean float32 evaluation violates is too tight before any GPU sees it.
+FWD_CASES = dict(CASES)
+FWD_CASES.update({
+    'resize_odd_leaky': (dict(upsample_type='Resize', upsample_scales=[3, 5], hop_size=15, upsample_activation='LeakyRelu'), 2, 60, [60, 31]),
+    'resize_even': (dict(upsample_type='Resize', upsample_scales=[2, 8]), 2, 64, [64, 64]),
+    'gauss_1d': (dict(out_channels=2, upsample_type='1D', log_scale_min_gauss=float(np.log(1e-7))), 2, 64, [64, 40]),
+    'gauss_cdf_nn': (dict(out_channels=2, upsample_type='NearestNeighbor', cdf_loss=True, log_scale_min_gauss=float(np.log(9.1188196e-4))), 3, 64, [64, 33, 2]),
+    'gauss_gin_raw_nobias': (dict(out_channels=2, gin_channels=8, use_speaker_embedding=False, use_bias=False, log_scale_min_gauss=float(np.log(1e-7))),
+                             3, 64, [64, 31, 2]),
+})
+
+
+def _fwd_case(name):
+    over, B, T, _ = FWD_CASES[name]
+    hp = make_hp(**dict(SMALL, **over))
+    cfg = oracle_cfg(hp)
+    assert T % cfg.hop == 0
+    params = O.init_params(cfg, seed=5339, bias_scale=0.05)
+    gen = torch.Generator().manual_seed(7)
+    for k in params:
+        if k.startswith('local_conditioning') and k.endswith('kernel'):
+            params[k] = params[k] + 0.05 * torch.randn(params[k].shape, generator=gen)
+    wav, c = synth_batch(cfg, B, T, seed=2)
+    if cfg.input_type == 'mulaw-quantize':
+        ids = torch.from_numpy(M.mulaw_quantize(wav.numpy())).long()
+        x_or, x_in = torch.nn.functional.one_hot(ids, 256).double().permute(0, 2, 1).contiguous(), ids
+    else:
+        x_or, x_in = wav.double().view(B, 1, T), wav.double()
+    g = None
+    if cfg.gin_channels > 0:
+        gg = torch.Generator().manual_seed(11)
+        g = torch.randint(0, cfg.n_speakers, (B,), generator=gg) if cfg.use_speaker_embedding else torch.randn(B, cfg.gin_channels, generator=gg)
+    masks = [None] * cfg.layers
+    if cfg.wavenet_dropout > 0:
+        masks = [torch.from_numpy(dropout_mask(99, l, B * T, cfg.residual_channels, cfg.wavenet_dropout)).double().view(B, T, -1) for l in range(cfg.layers)]
+    return cfg, params, B, T, x_or, x_in, c, g, masks
+
+
+def _level_oracle(params, cfg, i, inp):
+    """O.upsample restricted to level i: the same oracle code on a one-level configuration that holds level i's kernel and bias."""
+    import dataclasses
+    if cfg.upsample_type == 'NearestNeighbor':
+        return O.upsample(params, cfg, inp)
+    sub = dataclasses.replace(cfg, upsample_scales=[cfg.upsample_scales[i]])
+    p = {'local_conditioning_upsampling_1/' + k: params['local_conditioning_upsampling_%d/%s' % (i + 1, k)] for k in ('kernel', 'bias')}
+    return O.upsample(p, sub, inp)
+
+
+def _n_levels(cfg):
+    return 1 if cfg.upsample_type == 'NearestNeighbor' else len(cfg.upsample_scales)
+
+
+# (raw global features: the oracle casts them to float32 before its matvec, so its float64 forward does not take them; the embedding case pins the same formula)
+@pytest.mark.parametrize('name', [n for n in FWD_CASES if n != 'gauss_gin_raw_nobias'])
+def test_forward_launch_refs_equal_the_float64_oracle(name):
+    cfg, params, B, T, x_or, x_in, c, g, masks = _fwd_case(name)
+    L, GH = cfg.layers, cfg.gate_channels // 2
+    p64 = {k: v.double() for k, v in params.items()}
+    masks_or = None if masks[0] is None else [m.permute(0, 2, 1).contiguous() for m in masks]
+    y_hat, aux = O.step(p64, cfg, x_or, c.double(), dropout_masks=masks_or, return_aux=True, g=g)
+    assert y_hat.dtype == torch.float64
+    W = LR.Weights(p64, cfg, rounded=False)
+    worst = {}
+
+    def chk(kind, got, want):
+        worst[kind] = max(worst.get(kind, 0.0), _close('%s/%s' % (name, kind), got, want))
+
+    # ---- upsample net, level by level: chained against the oracle's c_up, every level against the oracle code of that level alone
+    inp = c.double()
+    for i in range(_n_levels(cfg)):
+        out, _ = LR.ref_cup_level(p64, cfg, i, inp, rounded=False)
+        chk('CUP level', out, _level_oracle(p64, cfg, i, inp))
+        inp = out
+    chk('CUP', inp, aux['c_up'])
+    cbt = inp.permute(0, 2, 1).contiguous()
+    # ---- gate bias
+    gvec = None if g is None else (p64['gc_embedding'][g] if cfg.use_speaker_embedding else g.double())
+    bias, _ = LR.ref_gate_bias(W, p64, cfg, gvec)
+    assert bias.shape == (L, B if g is not None else 1, cfg.gate_channels)
+    # ---- the chain, every launch fed by the previous launch's reference output
+    X, _ = LR.ref_x0(W, x_in)
+    chk('X0', X, _bt(aux['layer_in'][0]))
+    U_all = []
+    for l in range(L):
+        XD = X if masks[l] is None else X * masks[l] * W.keep_scale
+        (TS, U), _ = LR.ref_gate(W, l, XD, cbt, (bias[l], None))
+        zor = _bt(aux['z'][l])
+        chk('TS', TS, torch.sigmoid(zor[..., GH:]))
+        chk('U', U, _bt(aux['u'][l]))
+        if B > 1 and W.dil[l] <= 2:      # the leak is a real quantity here: a gate reference that crossed b would miss 1e-10
+            leak = LR.gate_start_leak(W, l, XD)
+            assert float(leak[1:, :2 * W.dil[l]].abs().max()) > 0 and float(leak[0].abs().max()) == 0 and float(leak[:, 2 * W.dil[l]:].abs().max()) == 0
+        U_all.append(U)
+        if l < L - 1:
+            X, _ = LR.ref_x_next(W, l, U, X)
+            chk('X_next', X, _bt(aux['layer_in'][l + 1]))
+    R1, _ = LR.ref_r1(W, iter(U_all))
+    chk('R1', R1, torch.relu(_bt(aux['skips'])))
+    H2, _ = LR.ref_h2(W, R1)
+    chk('H2', H2, _bt(torch.relu(O._conv1x1(torch.relu(aux['skips']), p64['final_convolution_1/kernel'], p64['final_convolution_1/bias']))))
+    Y, _ = LR.ref_yhat(W, H2)
+    assert Y.shape == (B, cfg.out_channels, T)
+    chk('YHAT', Y, y_hat)
+    print('\n[%s] worst max|ref - oracle| / max|oracle|: ' % name + '  '.join('%s=%.1e' % kv for kv in sorted(worst.items())))
+
+
+def _f32(t):
+    return t.to(torch.float32)
+
+
+def _exp2_cr(p):
+    """exp2 of a float32 tensor, rounded once from float64 (to within the double rounding, 2^-29 ulp)."""
+    return torch.exp2(p.double()).to(torch.float32)
+
+
+def _rcp_cr(q):
+    return (1.0 / q.double()).to(torch.float32)
+
+
+def _fast_tanh32(x):
+    e = _exp2_cr(x * torch.tensor(2.885390082, dtype=torch.float32))
+    return 1.0 - 2.0 * _rcp_cr(e + 1.0)
+
+
+def _fast_sigmoid32(x):
+    return _rcp_cr(1.0 + _exp2_cr(x * torch.tensor(-1.442695041, dtype=torch.float32)))
+
+
+def _inside(name, kind, got32, ref, bound, report):
+    err = (got32.double() - ref).abs()
+    assert got32.dtype == torch.float32 and bool((bound >= 0).all())
+    ratio = torch.where(bound > 0, err / torch.where(bound > 0, bound, torch.ones_like(bound)), torch.where(err > 0, torch.full_like(err, float('inf')), torch.zeros_like(err)))
+    worst = float(ratio.max())
+    report[kind] = max(report.get(kind, 0.0), worst)
+    assert worst <= 1.0, '%s/%s: the float32 evaluation is %.3f x the bound (without the bf16 store) at flat element %d' % (name, kind, worst, int(ratio.argmax()))
+
+
+@pytest.mark.parametrize('name', list(FWD_CASES))
+def test_forward_bounds_hold_a_float32_evaluation(name):
+    """Inputs of every launch: the bf16-emulating oracle's own intermediates (realistic magnitudes, bf16 values like the device's buffers)."""
+    cfg, params, B, T, x_or, x_in, c, g, masks = _fwd_case(name)
+    L, GH, R = cfg.layers, cfg.gate_channels // 2, cfg.residual_channels
+    masks_or = None if masks[0] is None else [m.float().permute(0, 2, 1).contiguous() for m in masks]
+    _, aux = O.step(params, cfg, x_or.float(), c, dropout_masks=masks_or, emulate_bf16=True, return_aux=True, g=g)
+    W = LR.Weights(params, cfg, rounded=True)
+    rep = {}
+    # ---- upsample levels: float32 oracle code of that level on the same input
+    inp = c
+    for i in range(_n_levels(cfg)):
+        ref, bound = LR.ref_cup_level(params, cfg, i, inp.double(), want_bound=True)
+        out32 = _level_oracle(params, cfg, i, inp)
+        _inside(name, 'CUP', out32, ref, bound, rep)
+        if cfg.upsample_type == 'NearestNeighbor':
+            assert float(bound.abs().max()) == 0.0
+        inp = out32
+    cbt = LR.ref_cbt(inp.double())
+    assert torch.equal(cbt, O.bf16_round(inp).double().permute(0, 2, 1))
+    # ---- gate bias: the fp32 sums in the kernels' order
+    gvec = None if g is None else (params['gc_embedding'][g] if cfg.use_speaker_embedding else g.float())
+    bias, ebias = LR.ref_gate_bias(W, params, cfg, gvec)
+    zero = torch.zeros(cfg.gate_channels)
+    bias32 = []
+    for l in range(L):
+        q = 'ResidualConv1DGLU_%d/' % l
+        a = params.get(q + 'residual_block_causal_conv/bias', zero) + params.get(q + 'residual_block_cin_conv/bias', zero)
+        if gvec is not None:
+            a = (a + params.get(q + 'residual_block_gin_conv/bias', zero))[None].repeat(B, 1)
+            Wg = params[q + 'residual_block_gin_conv/kernel'][0]
+            for k in range(cfg.gin_channels):
+                a = a + gvec[:, k:k + 1] * Wg[k][None]
+        else:
+            a = a[None]
+        bias32.append(a)
+        _inside(name, 'gate bias', a, bias[l], ebias[l], rep)
+    # ---- the chain
+    X = [O.bf16_round(_bt(h)).double() for h in aux['layer_in']]
+    U = [O.bf16_round(_bt(u)).double() for u in aux['u']]
+    for l in range(L):
+        XD = LR.ref_xd(W, X[l], masks[l])
+        (TS, Ur), (bTS, bU) = LR.ref_gate(W, l, XD, cbt, (bias[l], ebias[l]), want_bound=True, store=False)
+        d = W.dil[l]
+        z32 = _f32(cbt) @ _f32(W.w_cin[l]) + bias32[l][:, None, :]
+        for j in range(3):
+            z32 = z32 + _f32(LR.shift_time(XD, -(2 - j) * d)) @ _f32(W.w_dil[l][j])
+        t32, s32 = _fast_tanh32(z32[..., :GH]), _fast_sigmoid32(z32[..., GH:])
+        _inside(name, 'TS', s32, TS, bTS, rep)
+        _inside(name, 'U', t32 * s32, Ur, bU, rep)
+        _, full = LR.ref_gate(W, l, XD, cbt, (bias[l], ebias[l]), want_bound=True)
+        assert bool((full[0] >= bTS + LR.BF * TS).all()) and bool((full[1] >= bU + LR.BF * Ur.abs()).all())      # the store adds 2^-8 (|ref| + e)
+    sb, esb = LR.skip_bias_total(W)
+    sb32 = torch.zeros(cfg.skip_out_channels)
+    for l in range(L):
+        bk = params.get('ResidualConv1DGLU_%d/residual_block_skip_conv/bias' % l)
+        if bk is not None:
+            sb32 = sb32 + torch.tensor(W.skip_scale[l], dtype=torch.float32) * bk
+    _inside(name, 'skip bias', sb32, sb, esb, rep)
+    R1, bR1 = LR.ref_r1(W, iter(U), want_bound=True, store=False)
+    v32 = sb32[None, None, :].clone()
+    for l in range(L):
+        v32 = v32 + _f32(U[l]) @ _f32(W.w_skip[l])
+    _inside(name, 'R1', torch.relu(v32), R1, bR1, rep)
+    R1b = LR.bf16(R1)
+    H2, bH2 = LR.ref_h2(W, R1b, want_bound=True, store=False)
+    _inside(name, 'H2', torch.relu(_f32(R1b) @ _f32(W.fin1) + params['final_convolution_1/bias']), H2, bH2, rep)
+    H2b = LR.bf16(H2)
+    Y, bY = LR.ref_yhat(W, H2b, want_bound=True)
+    _inside(name, 'YHAT', (_f32(H2b) @ _f32(W.fin2) + params['final_convolution_2/bias']).permute(0, 2, 1), Y, bY, rep)
+    print('\n[%s] float32 evaluation / bound (no bf16 store): ' % name + '  '.join('%s=%.3f' % kv for kv in sorted(rep.items())))
+
+
+def test_gate_bound_covers_saturated_and_tiny_preactivations():
+    """fast_tanh / fast_sigmoid over the whole range the accumulator can reach, |z| up to 100 (saturation, exp2 overflow to inf and underflow
+    to 0 included): the float32 evaluation stays inside Et / Es with dz = 0."""
+    x = torch.cat([torch.linspace(-100, 100, 200001), torch.tensor([0.0, 1e-30, -1e-30, 1e-6, -1e-6, 88.7, -88.7, 43.6, -43.6])]).float()
+    xd = x.double()
+    t, s = torch.tanh(xd), torch.sigmoid(xd)
+    omt, oms = 2.0 * torch.sigmoid(-2.0 * xd), torch.sigmoid(-xd)
+    Et = LR._fast_tanh_err(xd.abs(), t.abs(), omt, 0.5 * (2.0 - omt))
+    Es = LR._fast_sigmoid_err(xd.abs(), s, oms)
+    et = (_fast_tanh32(x).double() - t).abs()
+    es = (_fast_sigmoid32(x).double() - s).abs()
+    assert bool((et <= Et).all()), float((et / Et).max())
+    assert bool((es <= Es).all()), float((es / Es).max())
+    assert float(Et.max()) < 8 * LR.U24 * 1.01 and float(Es.max()) < 40 * LR.U24      # (absolute errors of a few fp32 ulps of 1: far below the bf16 store)
+    print('\nfast_tanh err / bound %.3f, fast_sigmoid err / bound %.3f' % (float((et / Et).max()), float((es / Es).max())))
