@@ -429,6 +429,10 @@ int wn_test_gemm8p_mask(const wn_ctx* ctx);
  * (ni = 1: [L * P + heads]; else ni x [L * P + 1]).  Block b runs on XCD b % 8: a layer's P CUs share an XCD, consecutive layers stay together.
  * Returns how many instances of the model the chip holds (1 ... 3), WN_E_SHAPE if ni do not fit. */
 int wn_test_pipe_layout(int32_t L, int32_t P, int32_t ni, int32_t* role, int32_t cap_role, int32_t* blk, int32_t cap_blk, int32_t* grid, int32_t* heads);
+/* device resources this PROCESS holds through the library (csrc/wn_dev.h; no context): out[0] live device / pinned buffers, [1] live streams,
+ * [2] live events, [3] live graph execs, [4] buffer allocations ever.  Counts of the library's own handles: unlike hipMemGetInfo they do not move
+ * with other processes on the device.  Take deltas around the life of a context: [0..3] return to where they were once it is destroyed. */
+int wn_test_device_resources(int64_t out[5]);
 #endif /* WN_NO_TEST_HOOKS */
 
 #ifdef __cplusplus

@@ -1,9 +1,27 @@
 // Host side of the C ABI: context, parameter table, workspace, dispatch.
 #include "wn_common.h"
+#include <ctype.h>
+#include <dlfcn.h>
 #include <math.h>
 #include <algorithm>
 
 std::string g_create_err;
+
+// The one place where the library takes memory from and returns it to the runtime (wn_dev.h: every DevBuf / PinBuf goes through this pair).
+hipError_t wn_dev_alloc(void** p, size_t bytes, bool pinned) {
+    const hipError_t e = pinned ? hipHostMalloc(p, bytes, hipHostMallocDefault) : hipMalloc(p, bytes);
+    if (e != hipSuccess) *p = nullptr;
+    if (*p) { ++wn_dev_counts().bufs; ++wn_dev_counts().allocs; }      // (a 0-byte request may succeed with a null pointer: nothing to own, nothing counted)
+    return e;
+}
+void wn_dev_free(void* p, bool pinned) { (void)(pinned ? hipHostFree(p) : hipFree(p)); --wn_dev_counts().bufs; }
+// test hook: live device buffers, streams, events, graph execs of this process, and buffer allocations ever
+extern "C" int wn_test_device_resources(int64_t out[5]) {
+    if (!out) return WN_E_ARG;
+    const WnDevCounts& n = wn_dev_counts();
+    out[0] = n.bufs; out[1] = n.streams; out[2] = n.events; out[3] = n.gexecs; out[4] = n.allocs;
+    return WN_OK;
+}
 
 static int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
 
@@ -107,9 +125,7 @@ static int alloc_workspace_inference(wn_ctx* c) {
     for (int i = 0; i <= c->cfg.n_upsample; ++i) sz(lvl[i] * c->C * 4);
     sz(256); sz(WN_ZERO_PAGE_BYTES);
     sz((size_t)wn_score_part_doubles(c->maxB, c->maxT) * 8);      // wn_score partials: scoring never allocates
-    c->ws_bytes = total;
-    hipError_t e = hipMalloc((void**)&c->ws, total);
-    if (e != hipSuccess) WN_FAIL(c, WN_E_HIP, "hipMalloc(%zu bytes inference workspace) failed: %s", total, hipGetErrorString(e));
+    WN_HIP(c, c->ws.reserve(total));
     char* p = c->ws;
     c->cbt = (bf16_t*)bump(p, NT * c->C * 2);
     for (int i = 0; i <= c->cfg.n_upsample; ++i) c->CUP[i] = (float*)bump(p, lvl[i] * c->C * 4);
@@ -155,9 +171,7 @@ static int alloc_workspace(wn_ctx* c) {
     sz(256);                               // scalars
     sz(WN_ZERO_PAGE_BYTES);                // zero page
     sz((size_t)wn_score_part_doubles(c->maxB, c->maxT) * 8);      // wn_score / wn_eval_fwd partials
-    c->ws_bytes = total;
-    hipError_t e = hipMalloc((void**)&c->ws, total);
-    if (e != hipSuccess) WN_FAIL(c, WN_E_HIP, "hipMalloc(%zu bytes workspace) failed: %s", total, hipGetErrorString(e));
+    WN_HIP(c, c->ws.reserve(total));
     char* p = c->ws;
     c->cbt = (bf16_t*)bump(p, NT * c->C * 2);
     c->X = (bf16_t*)bump(p, (size_t)L * NT * c->R * 2);
@@ -186,7 +200,6 @@ static int alloc_workspace(wn_ctx* c) {
 
 static int stream_alloc(wn_ctx* c);
 static int slots_alloc(wn_ctx* c);
-static void slots_free(wn_ctx* c);
 
 extern "C" int wn_create(const wn_config* cfg, wn_ctx** out) {
     wn_ctx* z = nullptr;
@@ -254,10 +267,8 @@ extern "C" int wn_create(const wn_config* cfg, wn_ctx** out) {
     int rc = alloc_workspace(c);
     if (rc == WN_OK) rc = wn_build_packs(c);
     if (rc == WN_OK && !c->inference) {
-        c->wg_partial_bytes = wn_wgrad_partial_need(c);
-        if (hipMalloc((void**)&c->wg_partial, c->wg_partial_bytes) != hipSuccess) {
-            c->err = "hipMalloc(wgrad partial buffer) failed"; rc = WN_E_HIP;
-        }
+        const size_t need = wn_wgrad_partial_need(c);
+        rc = [&]() -> int { WN_HIP(c, c->wg_partial.reserve(need / 4)); return WN_OK; }();
     }
     if (rc == WN_OK && c->inference) {
         // pre-size every synthesis buffer for (max_batch, max_time): wn_synthesize never allocates on this context
@@ -280,51 +291,12 @@ extern "C" int wn_create(const wn_config* cfg, wn_ctx** out) {
     return WN_OK;
 }
 
+// Every device resource is released by its owner's destructor (wn_dev.h).  The context's own streams are drained first, so that nothing of ours still
+// runs when the buffers go; the per-path states (declared last in wn_ctx) then drain and destroy their private streams before any buffer is freed.
 extern "C" void wn_destroy(wn_ctx* c) {
     if (!c) return;
-    wn_synth_free(c);
-    wn_synth_f32_free(c);
-    wn_pipe_free(c);
-    for (float* q : c->strm.pend) if (q) hipFree(q);
-    if (c->strm.gbias) hipFree(c->strm.gbias);
-    if (c->strm.carry) hipFree(c->strm.carry);
-    slots_free(c);
-    wn_f32_free(c);
-    auto fr = [](PackedW& w) { if (w.dev) hipFree(w.dev); if (w.dev_segs) hipFree(w.dev_segs); w.dev = nullptr; w.dev_segs = nullptr; };
-    for (auto& p : c->packs) { fr(p.w1); fr(p.wo); fr(p.ws); fr(p.w2T); fr(p.w1T); }
-    fr(c->wskip); fr(c->wh1); fr(c->wh2); fr(c->wh2T); fr(c->wh1T); fr(c->wcT);
-    if (c->pack_jobs_dev) hipFree(c->pack_jobs_dev);
-    if (c->b1sum) hipFree(c->b1sum);
-    if (c->skip_bias_total) hipFree(c->skip_bias_total);
-    if (c->tensor_offsets_dev) hipFree(c->tensor_offsets_dev);
-    if (c->kprof_dev) hipFree(c->kprof_dev);
-    if (c->kclk_dev) hipFree(c->kclk_dev);
-    if (c->trace_dev) hipFree(c->trace_dev);
-    if (c->norm2_dev) hipFree(c->norm2_dev);
-    if (c->norm_spans_dev) hipFree(c->norm_spans_dev);
-    if (c->norm_first_dev) hipFree(c->norm_first_dev);
-    if (c->norm_part_dev) hipFree(c->norm_part_dev);
-    if (c->params_dev) hipFree(c->params_dev);
-    if (c->st2) { (void)hipStreamSynchronize(c->st2); hipStreamDestroy(c->st2); }      // nothing of ours may still be running on it
-    if (c->st3) { (void)hipStreamSynchronize(c->st3); hipStreamDestroy(c->st3); }
-    for (int k = 2; k < WN_MAX_PARTS; ++k) if (c->stp[k]) { (void)hipStreamSynchronize(c->stp[k]); hipStreamDestroy(c->stp[k]); }
-    for (int k = 0; k < WN_MAX_PARTS; ++k) if (c->ev_pjoin[k]) hipEventDestroy(c->ev_pjoin[k]);
-    for (int p = 0; p < WN_MAX_PARTS; ++p) for (int k = 0; k < WN_MAX_BUCKETS; ++k) if (c->ev_chain[p][k]) hipEventDestroy(c->ev_chain[p][k]);
-    for (int p = 0; p < WN_MAX_PARTS; ++p) if (c->ev_head[p]) hipEventDestroy(c->ev_head[p]);
-    for (int k = 0; k < WN_MAX_BUCKETS + 2; ++k) if (c->ev_bucket[k]) hipEventDestroy(c->ev_bucket[k]);
-    if (c->ev_w0) hipEventDestroy(c->ev_w0);
-    if (c->ev_fork) hipEventDestroy(c->ev_fork);
-    if (c->ev_join) hipEventDestroy(c->ev_join);
-    if (c->wmap_dev) hipFree(c->wmap_dev);
-    if (c->raw_dev) hipFree(c->raw_dev);
-    if (c->deff) hipFree(c->deff);
-    if (c->gvec) hipFree(c->gvec);
-    if (c->gids) hipFree(c->gids);
-    if (c->gbias) hipFree(c->gbias);
-    if (c->colsum) hipFree(c->colsum);
-    if (c->noise_buf) hipFree(c->noise_buf);
-    if (c->ws) hipFree(c->ws);
-    if (c->wg_partial) hipFree(c->wg_partial);
+    for (hipStream_t st : c->stp) if (st) (void)hipStreamSynchronize(st);      // (stp[1] is st2)
+    if (c->st3) (void)hipStreamSynchronize(c->st3);
     delete c;
 }
 
@@ -341,14 +313,12 @@ extern "C" int wn_tensor_info(const wn_ctx* c, int i, char* name, int32_t* shape
     if (offset) *offset = t.offset;
     return WN_OK;
 }
-extern "C" int64_t wn_workspace_bytes(const wn_ctx* c) { return c ? (int64_t)(c->ws_bytes + c->wg_partial_bytes) : (int64_t)WN_E_ARG; }
+extern "C" int64_t wn_workspace_bytes(const wn_ctx* c) { return c ? (int64_t)(c->ws.bytes() + c->wg_partial.bytes()) : (int64_t)WN_E_ARG; }
 extern "C" const char* wn_dominant_kernel_name(void) { return "wn_gemm_lds_kernel<2, 2, 4, 2, 32, 3, 0, 1, 3>"; }
 
 // rocTX ranges around the host side of the drop-in entry points (tracing): `rocprofv3 --marker-trace --kernel-trace` then
 // shows which call enqueued which kernels.  The marker library is looked up at run time (dlopen of libroctx64.so / the SDK's
 // librocprofiler-sdk-roctx.so; no link dependency) and only when WN_ROCTX=1: otherwise a range costs one predictable branch.
-#include <ctype.h>
-#include <dlfcn.h>
 struct WnRoctx {
     int (*push)(const char*) = nullptr; int (*pop)() = nullptr;
     WnRoctx() {
@@ -521,11 +491,10 @@ extern "C" int wn_synth_pipe_eligible(const wn_ctx* c, int32_t B) {
 
 int wn_noise_reserve(wn_ctx* c, int B, int T) {
     const size_t need = (size_t)B * T * wn_noise_per_step(c) * 4;
-    if (need <= c->noise_bytes) return WN_OK;
+    if (need <= c->noise_buf.bytes()) return WN_OK;
     if (c->inference && c->noise_buf) WN_FAIL(c, WN_E_SHAPE, "synthesis B*T = %d*%d exceeds the pre-sized noise buffer of this inference-only context", B, T);
-    if (c->noise_buf) { (void)hipDeviceSynchronize(); hipFree(c->noise_buf); c->noise_buf = nullptr; c->noise_bytes = 0; }
-    WN_HIP(c, hipMalloc((void**)&c->noise_buf, need));
-    c->noise_bytes = need;
+    if (c->noise_buf) (void)hipDeviceSynchronize();      // (growing: nothing may still read the old buffer)
+    WN_HIP(c, c->noise_buf.grow(need / 4));
     return WN_OK;
 }
 
@@ -655,12 +624,9 @@ static void commit_push(WnUtt& u, const WnPushPlan& p, bool rebuilt) {
 // frame columns (push checks it), the bias [L][B][G], the carried inputs
 static int stream_alloc(wn_ctx* c) {
     auto& S = c->strm;
-    if (!S.pend[0]) {
-        S.pend_cap = (int64_t)c->C * (c->NT / c->hop + 1);
-        for (float*& q : S.pend) WN_HIP(c, hipMalloc((void**)&q, (size_t)S.pend_cap * 4));
-    }
-    if (!S.carry) WN_HIP(c, hipMalloc((void**)&S.carry, 32 * 4));
-    if (c->gin > 0 && !S.gbias) WN_HIP(c, hipMalloc((void**)&S.gbias, (size_t)c->L * c->maxB * c->G * 4));
+    for (auto& q : S.pend) WN_HIP(c, q.reserve((size_t)c->C * (c->NT / c->hop + 1)));
+    WN_HIP(c, S.carry.reserve(32));
+    if (c->gin > 0) WN_HIP(c, S.gbias.reserve((size_t)c->L * c->maxB * c->G));
     return WN_OK;
 }
 
@@ -757,23 +723,17 @@ extern "C" int wn_synth_stream_end(wn_ctx* c) {
 // session keeps per slot; a push runs max_b n_out[b] steps in which every slot takes part, the ones that have nothing (more) to generate as dummies.
 static int slots_alloc(wn_ctx* c) {
     auto& S = c->slots;
-    if (S.pend[0]) return WN_OK;
     int l = 0, r = 0; wn_synth_stream_lookahead(&c->cfg, &l, &r);
     S.capw = c->maxT / c->hop + l + r + 1;
     const int nb = std::min(32, c->maxB);
-    for (float*& q : S.pend) WN_HIP(c, hipMalloc((void**)&q, (size_t)nb * c->C * S.capw * 4));
-    WN_HIP(c, hipMalloc((void**)&S.gwin, (size_t)nb * c->C * S.capw * 4));
-    WN_HIP(c, hipMalloc((void**)&S.cbt, (size_t)c->NT * c->C * 2));
-    WN_HIP(c, hipMalloc((void**)&S.feat, (size_t)c->NT * c->C * 4));
-    WN_HIP(c, hipMalloc((void**)&S.carry, 32 * 4));
-    WN_HIP(c, hipMalloc((void**)&S.tdev, 128 * 4));
-    if (c->gin > 0) WN_HIP(c, hipMalloc((void**)&S.gbias, (size_t)c->L * nb * c->G * 4));
+    for (auto& q : S.pend) WN_HIP(c, q.reserve((size_t)nb * c->C * S.capw));
+    WN_HIP(c, S.gwin.reserve((size_t)nb * c->C * S.capw));
+    WN_HIP(c, S.cbt.reserve((size_t)c->NT * c->C));
+    WN_HIP(c, S.feat.reserve((size_t)c->NT * c->C));
+    WN_HIP(c, S.carry.reserve(32));
+    WN_HIP(c, S.tdev.reserve(128));
+    if (c->gin > 0) WN_HIP(c, S.gbias.reserve((size_t)c->L * nb * c->G));
     return WN_OK;
-}
-static void slots_free(wn_ctx* c) {
-    auto& S = c->slots;
-    for (float* q : S.pend) if (q) hipFree(q);
-    if (S.gwin) hipFree(S.gwin); if (S.cbt) hipFree(S.cbt); if (S.feat) hipFree(S.feat); if (S.carry) hipFree(S.carry); if (S.tdev) hipFree(S.tdev); if (S.gbias) hipFree(S.gbias);
 }
 
 extern "C" int wn_synth_slots_begin(wn_ctx* c, int32_t B, int32_t steps_per_graph, void* stream) {

@@ -5,10 +5,12 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <memory>
 #include <string>
 #include <vector>
 
 #include "../../include/wavenet_mi355.h"
+#include "wn_dev.h"
 
 typedef unsigned short bf16_t;                                    // raw bf16 bits
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;      // MFMA A/B fragment (4 VGPRs)
@@ -83,7 +85,7 @@ struct WnLayerOffsets {   // offsets (floats) into the flat parameter buffer
 struct PackSeg { int64_t base; int32_t k0, nk, stride_k, stride_m; float scale; };
 
 struct PackedW {          // one fragment-ordered bf16 matrix
-    bf16_t* dev = nullptr;
+    DevBuf<bf16_t> dev;
     int32_t M = 0, K = 0;             // padded: M % 32 == 0, K % 16 == 0
     int32_t M_valid = 0;
     int32_t gate_interleave = 0;      // row permutation (see wn_pack.hip)
@@ -92,7 +94,7 @@ struct PackedW {          // one fragment-ordered bf16 matrix
                                       //      staging; 64: the K-tiles of wn_gemm8p_kernel)
                                       //      [tap0 blk0 | tap1 blk0 | tap2 blk0 | tap0 blk1 | ...] (tile engine: taps of one k-block back to back => L2 reuse)
     std::vector<PackSeg> segs;
-    PackSeg* dev_segs = nullptr;
+    DevBuf<PackSeg> dev_segs;
 };
 
 struct WnLayerPacks { PackedW w1, wo, ws, w2T, w1T; };
@@ -100,6 +102,9 @@ struct WnLayerPacks { PackedW w1, wo, ws, w2T, w1T; };
 // progress of one utterance that arrives in pushes (a stream, or one slot of a session): mel frames pushed so far, frames generated, the pending
 // window [pend_first, pushed) of mel frames and which of the two window buffers holds it
 struct WnUtt { int64_t pushed = 0, done = 0, pend_first = 0; int cur = 0; };
+
+struct Synth; struct SynthF32; struct Pipe; struct F32State;
+struct WnStateDelete { void operator()(Synth*) const; void operator()(SynthF32*) const; void operator()(Pipe*) const; void operator()(F32State*) const; };
 
 struct wn_ctx {
     wn_config cfg;
@@ -116,33 +121,33 @@ struct wn_ctx {
     // (kernel = v, g, bias, ...); params_dev holds g * v / ||v||.  Without it raw == effective.
     bool wnorm = false; int64_t n_raw = 0; std::vector<WnTensor> raw_tensors;
     struct WnMap { int64_t raw_off, eff_off, numel, g_off; int32_t cout, pad; };
-    std::vector<WnMap> wmap; void* wmap_dev = nullptr; float* raw_dev = nullptr; float* deff = nullptr;
+    std::vector<WnMap> wmap; DevBuf<WnMap> wmap_dev; DevBuf<float> raw_dev, deff;
     WnLayerOffsets first;                 // dil_k = input kernel, dil_b = input bias
     std::vector<WnLayerOffsets> lay;
     int64_t fin1_k, fin1_b, fin2_k, fin2_b;
     std::vector<int64_t> up_k, up_b;
     // packed weights
-    float* params_dev = nullptr;          // ctx-owned fp32 copy of the flat parameters taken at wn_pack_weights
+    DevBuf<float> params_dev;             // ctx-owned fp32 copy of the flat parameters taken at wn_pack_weights
     bool packed = false;
     int cup_final_idx = 0;                // CUP[cup_final_idx] = upsampled conditioning [B,C,T] fp32
     std::vector<WnLayerPacks> packs;
     PackedW wskip, wh1, wh2, wh2T, wh1T, wcT;
-    void* pack_jobs_dev = nullptr; int pack_njobs = 0, pack_nblocks = 0;   // table of the single pack launch
-    float* b1sum = nullptr;               // [L][G] dil bias + cin bias
-    float* skip_bias_total = nullptr;     // [S]
+    DevBuf<char> pack_jobs_dev; int pack_njobs = 0, pack_nblocks = 0;   // table of the single pack launch
+    DevBuf<float> b1sum;                  // [L][G] dil bias + cin bias
+    DevBuf<float> skip_bias_total;        // [S]
     // use_bias=False (hparams.py:189): the residual layers have no bias variables.  Forward READS then go to a zero tail
     // behind the ctx-owned parameter copy (offset n_params .. n_params + zpad); gradient WRITES are skipped (lbias == false).
     bool lbias = true; int zpad = 0;
     // global conditioning: gin > 0.  gvec [maxB][gin] (embedded or given g), gids [maxB], gbias [L][maxB][G] =
     // b1sum + W_g^T g + b_g per utterance (the gate epilogue's bias then has an utterance stride), colsum [L][maxB][G] =
     // sum_t dz per utterance (backward), emb_off = embedding table [n_speakers][gin] or -1.
-    int gin = 0; int64_t emb_off = -1; float* gvec = nullptr; int32_t* gids = nullptr; float* gbias = nullptr; float* colsum = nullptr;
+    int gin = 0; int64_t emb_off = -1; DevBuf<float> gvec; DevBuf<int32_t> gids; DevBuf<float> gbias, colsum;
     int gB = 0; bool have_g = false;
-    int32_t* tensor_offsets_dev = nullptr; // [ntensors+1] for the optimiser
-    float* norm2_dev = nullptr;           // [ntensors]
-    int32_t* norm_spans_dev = nullptr; int32_t* norm_first_dev = nullptr; float* norm_part_dev = nullptr; int norm_nspans = 0;   // atomic-free clip norms
-    // workspace
-    char* ws = nullptr; size_t ws_bytes = 0;
+    DevBuf<int32_t> tensor_offsets_dev;   // [ntensors+1] for the optimiser
+    DevBuf<float> norm2_dev;              // [ntensors]
+    DevBuf<int32_t> norm_spans_dev, norm_first_dev; DevBuf<float> norm_part_dev; int norm_nspans = 0;   // atomic-free clip norms
+    // workspace: ONE allocation; every pointer below down to score_part is carved from it by alloc_workspace (wn_api.hip) and owns nothing
+    DevBuf<char> ws;
     int maxB, maxT; int64_t NT;
     bf16_t* XD;                           // [L][NT][R] dropout-applied layer inputs (aliases X when dropout == 0)
     bf16_t *cbt, *X, *TS, *U, *R1, *H2, *DY, *DPRE1, *DSKIP, *DZ, *GX0, *GX1;
@@ -152,7 +157,7 @@ struct wn_ctx {
     float* cs_part = nullptr;             // partial sums of wn_colsum2: WN_CS_SLOTS regions of WN_CS_MAXBLK x 2 x 1024 floats
     float* UPPART = nullptr; int64_t uppart_floats = 0;   // partial sums of the upsample-kernel gradients (two-stage, no atomics)
     void* XIN; float* CIN;                // ctx-owned copies of the step's x and c (pointers are borrowed per call)
-    float* wg_partial = nullptr; size_t wg_partial_bytes = 0;   // split-K partial tiles of the grouped wgrad (wn_wgrad.h)
+    DevBuf<float> wg_partial;             // split-K partial tiles of the grouped wgrad (wn_wgrad.h)
     bf16_t* GXall = nullptr;              // [L+1][NT][R] gradient wrt every layer input (kept for the grouped W_out wgrad)
 #define WN_ZERO_PAGE_BYTES 4096
 #define WN_PIPE_F16_DEFAULT true       // storage type of the persistent synthesis pipeline when WN_PIPE_DTYPE is not set: IEEE half (1.2e-3 vs bf16's 8.7e-3 from the fp32 loop, same speed)
@@ -166,36 +171,33 @@ struct wn_ctx {
     bool feval = false;                   // the forward being enqueued is wn_eval_fwd: no dropout whatever cfg.dropout says (the launches of a dropout == 0 context)
     const void* fx = nullptr; const void* fy = nullptr; const int32_t* flen = nullptr; const float* fc = nullptr;
     // live profiling of the dominant kernel (bench.py roofline): event pairs around every gate-GEMM launch
-    bool prof = false; std::vector<hipEvent_t> pev; size_t pev_used = 0;
+    bool prof = false; std::vector<DevEvent> pev; size_t pev_used = 0;
     // WN_DEVTRACE=<file> (debug): in-kernel {first start, last end} stamps of EVERY tile-engine launch of one training step (the
     // WN_DEVTRACE_STEP-th wn_train_fwd, default 8) -- the device timeline of the chain without a profiler attached (rocprofv3 slows the
     // host's enqueue enough to change which stream runs ahead).  Written two steps later by wn_devtrace_poll.
-    unsigned long long* trace_dev = nullptr; int trace_n = 0, trace_calls = 0, trace_state = 0, trace_arm_at = 0;      // state: 0 idle, 1 recording, 2 recorded
+    DevBuf<unsigned long long> trace_dev; int trace_n = 0, trace_calls = 0, trace_state = 0, trace_arm_at = 0;      // state: 0 idle, 1 recording, 2 recorded
 #define WN_TRACE_MAX 1024
     struct { int epi; void* st; int rows; } trace_tag[WN_TRACE_MAX];
-    unsigned long long* kprof_dev = nullptr;      // [WN_KPROF_MAX][2] in-kernel {first start, last end} stamps of the timed gate launches
-    unsigned long long* kclk_dev = nullptr;       // [WN_KPROF_MAX][2] {shader cycles, 100 MHz ticks} of workgroup 0 of the same launches (wn_profile_kernel_clock)
+    DevBuf<unsigned long long> kprof_dev;         // [WN_KPROF_MAX][2] in-kernel {first start, last end} stamps of the timed gate launches
+    DevBuf<unsigned long long> kclk_dev;          // [WN_KPROF_MAX][2] {shader cycles, 100 MHz ticks} of workgroup 0 of the same launches (wn_profile_kernel_clock)
 #define WN_KPROF_MAX 8192
     // batch parts: the serial layer chain of the two half-batches runs on two streams so that the MFMA/power-bound GEMMs of
     // one half overlap the HBM-bound kernels of the other (fwd: gate | out conv, bwd: dx | dgate); joined before the loss / wgrads
 #define WN_MAX_PARTS 4
-    hipStream_t st2 = nullptr;            // part 1 (and the "side" work of the backward tail)
-    hipStream_t stp[WN_MAX_PARTS] = {};   // stp[k], k >= 2: further batch parts (stp[1] aliases st2)
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_pjoin[WN_MAX_PARTS] = {}; int parts = 1; int parts_req = 0; int prof_rows = 0;
+    DevStream st2;                        // part 1 (and the "side" work of the backward tail)
+    DevStream stp_own[WN_MAX_PARTS];      // owners of the further part streams (k >= 2), created on demand by parts_setup
+    hipStream_t stp[WN_MAX_PARTS] = {};   // stp[k], k >= 2: further batch parts (non-owning; stp[1] aliases st2)
+    DevEvent ev_fork, ev_join, ev_pjoin[WN_MAX_PARTS]; int parts = 1; int parts_req = 0; int prof_rows = 0;
     // gradient buckets (wn_train.hip: wn_plan_buckets): weight gradients run bucket by bucket on a third, low-priority stream under
     // the serial backward chain; ev_bucket[k] = bucket k of the flat gradient is final (index WN_MAX_BUCKETS: the whole buffer)
 #define WN_MAX_BUCKETS 8
-    hipStream_t st3 = nullptr; hipEvent_t ev_chain[WN_MAX_PARTS][WN_MAX_BUCKETS] = {}; hipEvent_t ev_bucket[WN_MAX_BUCKETS + 2] = {}; hipEvent_t ev_w0 = nullptr;
-    hipEvent_t ev_head[WN_MAX_PARTS] = {};   // d pre1 of a batch part exists (the head weight gradients may start under the chain)
+    DevStream st3; DevEvent ev_chain[WN_MAX_PARTS][WN_MAX_BUCKETS], ev_bucket[WN_MAX_BUCKETS + 2], ev_w0;
+    DevEvent ev_head[WN_MAX_PARTS];          // d pre1 of a batch part exists (the head weight gradients may start under the chain)
     int nbuckets = 0, nbuckets_early = 0, nearly_live = 0; int bucket_lo[WN_MAX_BUCKETS + 2] = {}, bucket_hi[WN_MAX_BUCKETS + 2] = {};
     int64_t bucket_off[WN_MAX_BUCKETS + 2] = {}, bucket_cnt[WN_MAX_BUCKETS + 2] = {}; bool have_bwd = false;
     bool inference = false;               // cfg.inference_only: no training workspace, synthesis state pre-sized at wn_create
-    float* noise_buf = nullptr; size_t noise_bytes = 0;      // device-drawn sampling noise [T][B][nps] (wn_synthesize with noise == NULL)
+    DevBuf<float> noise_buf;              // device-drawn sampling noise [T][B][nps] (wn_synthesize with noise == NULL)
     int synth_path = 0;                   // 0 none, 1 graph, 2 pipeline, 3 fp32 graph (wn_synth_last_path)
-    // synthesis state (lazy)
-    struct Synth* synth = nullptr;
-    void* synth32 = nullptr;              // fp32 synthesis state (wn_synth_f32.hip; cfg.compute_dtype = WN_COMPUTE_F32)
-    void* pipe = nullptr;                 // persistent synthesis pipeline state (wn_synth_pipe.hip)
     bool pipe_f16 = false;                // persistent pipeline: IEEE-half weights / hand-offs / queues instead of bf16 (WN_PIPE_DTYPE=fp16|bf16 at wn_create, wn_synth_pipe_dtype)
     int synth_instances = 0;              // pipeline instances the last wn_synthesize ran side by side (wn_synth_last_instances)
     int synth_batchpre = 0;               // the last pipeline run multiplied every stream's past taps / conditioning in ONE matrix product per sample (wn_synth_last_batched)
@@ -204,7 +206,6 @@ struct wn_ctx {
                                           // (0 generic, 1 paper widths, 2 hparams.py widths) [4] 1 = IEEE-half storage [5] head CUs [6] early requests from n streams [7] abort test every
                                           // n streams (0: once per sample) [8] workgroups launched [9] streams of the largest instance
     int pipe_cap = 0;                     // inference-only contexts: streams of ONE pipeline run the pre-sized buffers hold (0: pipeline not used / not limited)
-    void* f32 = nullptr;                  // fp32-forward state (wn_f32.hip), allocated on the first forward of a cfg.compute_dtype = WN_COMPUTE_F32 context
     bool fwd_was_f32 = false;
     float* dy32_next = nullptr;           // the next wn_loss_run also writes d y_hat in fp32 here ([rows][ldDY]; fp32 training mode)
     // streaming synthesis (wn_synth_stream_*): the utterance's progress (WnUtt; window [B][C][pushed - pend_first], ping-pong), the stream's own
@@ -213,9 +214,9 @@ struct wn_ctx {
         bool open = false, poisoned = false; int path = 0;          // path: 1 launch-per-layer, 2 pipeline, 3 fp32 launch-per-layer
         int B = 0, spg = 0, left = 0, right = 0; uint64_t seed = 0;
         WnUtt u;
-        float* pend[2] = {nullptr, nullptr}; int64_t pend_cap = 0;      // floats per buffer
-        float* gbias = nullptr;                                        // [L][B][G] (gin > 0)
-        int32_t* carry = nullptr;                                      // [32] fed-back sample bits / class id of every stream (pipeline)
+        DevBuf<float> pend[2];                                         // pend[k].cap() floats per buffer
+        DevBuf<float> gbias;                                           // [L][B][G] (gin > 0)
+        DevBuf<int32_t> carry;                                         // [32] fed-back sample bits / class id of every stream (pipeline)
     } strm;
     // synthesis slots (wn_synth_slots_*): B slots served by one pipeline configuration; every slot is idle or carries ONE utterance with its own
     // time origin, seed, global condition and pending window of mel frames ([C][pushed - pend_first] dense, in the slot's region of pend[cur]).
@@ -223,16 +224,22 @@ struct wn_ctx {
     struct WnSlots {
         bool open = false, poisoned = false; int path = 0, B = 0, spg = 0, left = 0, right = 0, capw = 0; bool first_run = true;
         struct Slot { bool live = false; uint64_t seed = 0; WnUtt u; } s[32];
-        float* pend[2] = {nullptr, nullptr};      // [32 regions][C * capw] pending frames of every slot (ping-pong per slot)
-        float* gwin = nullptr;                    // [group][C][w]: the windows of the slots upsampled together (equal window width)
-        bf16_t* cbt = nullptr;                    // [B][n_max][C]: the conditioning rows every slot's steps of this push read
-        float* feat = nullptr;                    // [B][C][n_max] fp32: the same rows as wn_get_upsampled_features returns them
-        float* gbias = nullptr;                   // [L][B][G] gate-bias row of every slot (gin > 0), written at wn_synth_slot_open
-        int32_t* carry = nullptr;                 // [32] the pipeline's carried next input per slot
-        int32_t* tdev = nullptr;                  // launch-per-layer path: [0..31] absolute index of every slot's next sample, [32..63] samples it generates in this push, [64] push-local step
+        DevBuf<float> pend[2];                    // [32 regions][C * capw] pending frames of every slot (ping-pong per slot)
+        DevBuf<float> gwin;                       // [group][C][w]: the windows of the slots upsampled together (equal window width)
+        DevBuf<bf16_t> cbt;                       // [B][n_max][C]: the conditioning rows every slot's steps of this push read
+        DevBuf<float> feat;                       // [B][C][n_max] fp32: the same rows as wn_get_upsampled_features returns them
+        DevBuf<float> gbias;                      // [L][B][G] gate-bias row of every slot (gin > 0), written at wn_synth_slot_open
+        DevBuf<int32_t> carry;                    // [32] the pipeline's carried next input per slot
+        DevBuf<int32_t> tdev;                     // launch-per-layer path: [0..31] absolute index of every slot's next sample, [32..63] samples it generates in this push, [64] push-local step
         int64_t feat_pitch = 0; int feat_B = 0;
     } slots;
     int64_t fup_off = 0, fup_pitch = 0;   // wn_get_upsampled_features after a push: the span's columns [fup_off, fup_off + fT) of rows of fup_pitch
+    // lazy per-path states, each defined (and deleted) in its own translation unit.  Declared LAST: members are destroyed in reverse order, so the private
+    // streams these states own are synchronised and destroyed before any buffer above that their work may still read is freed.
+    std::unique_ptr<F32State, WnStateDelete> f32;         // fp32-forward state (wn_f32.hip), built by the first forward of a cfg.compute_dtype = WN_COMPUTE_F32 context
+    std::unique_ptr<Synth, WnStateDelete> synth;          // launch-per-layer synthesis (wn_synth.hip)
+    std::unique_ptr<SynthF32, WnStateDelete> synth32;     // fp32 synthesis (wn_synth_f32.hip; cfg.compute_dtype = WN_COMPUTE_F32)
+    std::unique_ptr<Pipe, WnStateDelete> pipe;            // persistent synthesis pipeline (wn_synth_pipe.hip)
 };
 
 // one push of a stream as the synthesis paths see it: absolute first sample t0, span length T, conditioning rows cbt[b][cbt_off + t] of a
@@ -298,10 +305,7 @@ int wn_fill_noise_span(wn_ctx* ctx, float* noise, int64_t first, int64_t n, uint
 // column b of noise [n_max][B][nps] = elements [first[b], first[b] + cnt[b]) of the ONE-stream noise of seed[b] (wn_fill_noise(B = 1)), every b with cnt[b] > 0 in one launch
 int wn_fill_noise_slots(wn_ctx* ctx, float* noise, int B, const uint64_t* seed, const int64_t* first, const int64_t* cnt, hipStream_t st);
 int wn_gbias_row(wn_ctx* ctx, const void* g_dev, float* table, int B, int slot, hipStream_t st);      // one slot's gate-bias row into table [L][B][G]
-void wn_synth_free(wn_ctx* ctx);
-void wn_synth_f32_free(wn_ctx* ctx);
 int wn_synth_f32_reserve(wn_ctx* ctx, int B);
-void wn_pipe_free(wn_ctx* ctx);
 bool wn_pipe_eligible(const wn_ctx* ctx, int B);
 int wn_pipe_reserve(wn_ctx* ctx, int B, int T);            // size every pipeline buffer for (B, T) (no-op when already large enough)
 int wn_synth_reserve(wn_ctx* ctx);                        // state of the launch-per-layer graph path
@@ -330,9 +334,8 @@ int wn_colsum2(wn_ctx* c, const bf16_t* M, int ld, int ncols, int nvalid, const 
 size_t wn_wgrad_partial_need(wn_ctx* ctx);
 void wn_plan_buckets(wn_ctx* ctx);
 int wn_f32_forward(wn_ctx* ctx, hipStream_t st);                  // fp32-accurate forward into YHAT (wn_f32.hip)
-void wn_f32_free(wn_ctx* ctx);
 int wn_f32_backward(wn_ctx* ctx, float* grads, hipStream_t st);       // fp32 backward of the last fp32 forward (wn_f32.hip)
-float* wn_f32_dy(wn_ctx* ctx);                                        // fp32 d y_hat buffer of the fp32 state (allocates it)
+int wn_f32_dy(wn_ctx* ctx, float** dy);                               // fp32 d y_hat buffer of the fp32 state (allocates it)
 int wn_upsample_bwd(wn_ctx* c, const float* dc_final, float* grads, hipStream_t st);
 int wn_loss_fwd_bwd(wn_ctx* c, float* loss_out, hipStream_t st);
 int wn_score_last_fwd(wn_ctx* c, float* stats_out, float* nll_out, hipStream_t st);      // per-utterance / per-sample scores of the last forward's y_hat

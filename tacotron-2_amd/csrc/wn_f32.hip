@@ -12,9 +12,8 @@
 #include "wn_common.h"
 
 struct F32State {
-    float *X = nullptr, *U = nullptr, *Z = nullptr, *SK = nullptr, *H1 = nullptr, *C32 = nullptr;      // forward: X [L][NT][R], U [L][NT][GH], Z [L][NT][G] (pre-activations)
-    float *DY = nullptr, *DH1 = nullptr, *DSK = nullptr, *GU = nullptr, *DZ = nullptr, *GX[2] = {nullptr, nullptr}, *DC = nullptr, *DCT = nullptr, *PART = nullptr;      // backward (lazy)
-    size_t part_floats = 0;
+    DevBuf<float> X, U, Z, SK, H1, C32;      // forward: X [L][NT][R], U [L][NT][GH], Z [L][NT][G] (pre-activations)
+    DevBuf<float> DY, DH1, DSK, GU, DZ, GX[2], DC, DCT, PART;      // backward (lazy)
     size_t bytes = 0;
 };
 
@@ -209,18 +208,13 @@ __global__ void wn_f32_bias_relu(float* __restrict__ v, const float* __restrict_
     v[i] = fmaxf(v[i] + bias[i % S], 0.0f);
 }
 
-void wn_f32_free(wn_ctx* c) {
-    F32State* s = (F32State*)c->f32;
-    if (!s) return;
-    for (float* p : {s->X, s->U, s->Z, s->SK, s->H1, s->C32, s->DY, s->DH1, s->DSK, s->GU, s->DZ, s->GX[0], s->GX[1], s->DC, s->DCT, s->PART}) if (p) hipFree(p);
-    delete s; c->f32 = nullptr;
-}
+void WnStateDelete::operator()(F32State* s) const { delete s; }
 static int f32_reserve(wn_ctx* c) {
-    if (!c->f32) c->f32 = new F32State();
-    F32State* s = (F32State*)c->f32;
+    if (!c->f32) c->f32.reset(new F32State());
+    F32State* s = c->f32.get();
     const int64_t NT = c->NT;
     // (each buffer on its own: after a failed allocation the next call retries the missing ones only)
-    auto need = [&](float** p, size_t floats) -> int { if (!*p) WN_HIP(c, hipMalloc((void**)p, floats * 4)); return WN_OK; };
+    auto need = [&](DevBuf<float>* p, size_t floats) -> int { WN_HIP(c, p->grow(floats)); return WN_OK; };
     int rc;
     if ((rc = need(&s->X, (size_t)c->L * NT * c->R)) || (rc = need(&s->U, (size_t)c->L * NT * c->GH)) ||
         (rc = need(&s->Z, (size_t)c->L * NT * c->G)) ||      // every layer's pre-activations: the gate derivative of the backward
@@ -229,7 +223,7 @@ static int f32_reserve(wn_ctx* c) {
     return WN_OK;
 }
 const float* wn_f32_debug(const wn_ctx* c, const char* name, int layer) {
-    const F32State* s = (const F32State*)c->f32;
+    const F32State* s = c->f32.get();
     if (!s || !s->X || !s->U) return nullptr;
     if (!strcmp(name, "X")) return s->X + (size_t)layer * c->NT * c->R;
     if (!strcmp(name, "U")) return s->U + (size_t)layer * c->NT * c->GH;
@@ -253,7 +247,7 @@ static SgemmArgs mk(const float* In, int ld_in, int shift, const float* W, int l
 int wn_f32_forward(wn_ctx* c, hipStream_t st) {
     int rc = f32_reserve(c);
     if (rc) return rc;
-    F32State* s = (F32State*)c->f32;
+    F32State* s = c->f32.get();
     const int L = c->L, R = c->R, G = c->G, GH = c->GH, S = c->S, C = c->C, O = c->O, B = c->fB, T = c->fT;
     const int64_t NT = c->NT, rows = (int64_t)B * T;
     const float* P = c->params_dev;
@@ -466,20 +460,19 @@ __global__ __launch_bounds__(256) void wn_f32_colsum_utt(const float* __restrict
     if (q == 0 && g < G) colsum[(int64_t)b * G + g] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
 }
 
-float* wn_f32_dy(wn_ctx* c) {
-    F32State* s = (F32State*)c->f32;
-    if (!s) return nullptr;
-    if (!s->DY) {
-        const int ldDY = (c->O + 15) / 16 * 16;
-        if (hipMalloc((void**)&s->DY, (size_t)c->NT * ldDY * 4) != hipSuccess) return nullptr;
-    }
-    return s->DY;
+int wn_f32_dy(wn_ctx* c, float** dy) {
+    F32State* s = c->f32.get();
+    if (!s) WN_FAIL(c, WN_E_STATE, "fp32 d y_hat: no fp32 forward has run");
+    const int ldDY = (c->O + 15) / 16 * 16;
+    WN_HIP(c, s->DY.grow((size_t)c->NT * ldDY));
+    *dy = s->DY;
+    return WN_OK;
 }
 static int f32_reserve_bwd(wn_ctx* c) {
-    F32State* s = (F32State*)c->f32;
+    F32State* s = c->f32.get();
     const int64_t NT = c->NT;
-    // each buffer on its own: a failed allocation leaves the others to be reused (or freed by wn_f32_free), never leaked by a retry
-    auto need = [&](float** p, size_t floats) -> int { if (!*p) WN_HIP(c, hipMalloc((void**)p, floats * 4)); return WN_OK; };
+    // each buffer on its own: a failed allocation leaves the others to be reused (or freed with the state), never leaked by a retry
+    auto need = [&](DevBuf<float>* p, size_t floats) -> int { WN_HIP(c, p->grow(floats)); return WN_OK; };
     int rc;
     if ((rc = need(&s->DH1, (size_t)NT * c->S)) || (rc = need(&s->DSK, (size_t)NT * c->S)) || (rc = need(&s->GU, (size_t)NT * c->GH)) ||
         (rc = need(&s->DZ, (size_t)NT * c->G)) || (rc = need(&s->GX[0], (size_t)NT * c->R)) || (rc = need(&s->GX[1], (size_t)NT * c->R)) ||
@@ -489,7 +482,6 @@ static int f32_reserve_bwd(wn_ctx* c) {
         const int slabs = c->maxB * cdiv(c->maxT, 2048);
         const size_t floats = (size_t)slabs * (maxk + 1) * maxm;      // + the bias row
         if ((rc = need(&s->PART, floats))) return rc;
-        s->part_floats = floats;
     }
     return WN_OK;
 }
@@ -497,7 +489,7 @@ static int f32_reserve_bwd(wn_ctx* c) {
 // ones in the same launch (bias_out2: the twin bias of the gate pre-activation).  A == nullptr: only the column sums.
 static int wgrad32(wn_ctx* c, const float* A, int lda, int shift, int K, const float* Bm, int ldb, int M, float* out, int ldo, float alpha,
                    int drop_layer, float* bias_out, float* bias_out2, hipStream_t st) {
-    F32State* s = (F32State*)c->f32;
+    F32State* s = c->f32.get();
     WgradF32Args a; memset(&a, 0, sizeof a);
     a.A = A; a.lda = lda; a.shift = shift; a.a_ones = A == nullptr; a.Bm = Bm; a.ldb = ldb; a.M = M; a.part = s->PART;
     a.ones_row = (A != nullptr && (bias_out || bias_out2)) ? 1 : 0;
@@ -508,7 +500,7 @@ static int wgrad32(wn_ctx* c, const float* A, int lda, int shift, int K, const f
         a.keep_scale = 1.0f / (1.0f - c->cfg.dropout); a.drop_ld = lda;
     }
     const int nslab = a.B * a.slabs_per_utt;
-    if ((size_t)nslab * a.K * M > s->part_floats) WN_FAIL(c, WN_E_STATE, "fp32 weight-gradient partial buffer too small");
+    if ((size_t)nslab * a.K * M > s->PART.cap()) WN_FAIL(c, WN_E_STATE, "fp32 weight-gradient partial buffer too small");
     hipLaunchKernelGGL(wn_f32_wgrad_kernel, dim3(cdiv(a.K, SG_T), cdiv(M, SG_T), nslab), dim3(256), 0, st, a);
     if (a.a_ones)      // column sums only: the single row goes to the bias target(s)
         hipLaunchKernelGGL(wn_f32_wgrad_reduce, dim3(cdiv((int64_t)M, 256)), dim3(256), 0, st, s->PART, nslab, 1, M, (float*)nullptr, 0, alpha, 1, bias_out, bias_out2);
@@ -522,7 +514,7 @@ static int wgrad32(wn_ctx* c, const float* A, int lda, int shift, int K, const f
 // with its weight gradients computed on the spot, d c_up accumulated over the layers, input conv, upsample net (the fp32 kernels of
 // wn_frontend.hip).  Replaces optimizer.compute_gradients (wavenet.py:557) in the reference's own arithmetic.
 int wn_f32_backward(wn_ctx* c, float* grads, hipStream_t st) {
-    F32State* s = (F32State*)c->f32;
+    F32State* s = c->f32.get();
     if (!s || !s->DY) WN_FAIL(c, WN_E_STATE, "fp32 backward without an fp32 forward that computed the loss");
     int rc = f32_reserve_bwd(c);
     if (rc) return rc;

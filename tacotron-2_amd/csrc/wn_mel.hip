@@ -20,7 +20,7 @@ struct wn_mel {
     int NB = 0, G = 0, off = 0, win_pad = 0, MT = 0, FR = 0, ldb = 0, ldm = 0, n_cu = 256;      // FR: the largest frame tile / 32 this context runs
     bool fixed_tile = false;                       // WN_MEL_TF: every call runs FR (the A/B of tools/mel_timing.py)
     float min_lin = 0.f;
-    float *basis = nullptr, *melT = nullptr;       // [win_pad][G][re 32 | im 32] window x cos / -sin;  [32 G][32 MT] mel filters transposed, zero padded
+    DevBuf<float> basis, melT;                     // [win_pad][G][re 32 | im 32] window x cos / -sin;  [32 G][32 MT] mel filters transposed, zero padded
 };
 
 #define MEL_GROUP 64      // utterances per launch: their lengths travel as kernel arguments (no device copy of the host array, nothing to allocate)
@@ -242,8 +242,8 @@ extern "C" int wn_mel_create(const wn_mel_config* cfg, const float* mel_basis, w
     for (int q = 0; q < cfg->num_mels; ++q)
         for (int j = 0; j < m->NB; ++j) hm[(size_t)j * m->ldm + q] = mel_basis[(size_t)q * m->NB + j];
     int rc = [&]() -> int {
-        WN_HIP(m, hipMalloc((void**)&m->basis, hb.size() * 4));
-        WN_HIP(m, hipMalloc((void**)&m->melT, hm.size() * 4));
+        WN_HIP(m, m->basis.reserve(hb.size()));
+        WN_HIP(m, m->melT.reserve(hm.size()));
         WN_HIP(m, hipMemcpy(m->basis, hb.data(), hb.size() * 4, hipMemcpyHostToDevice));
         WN_HIP(m, hipMemcpy(m->melT, hm.data(), hm.size() * 4, hipMemcpyHostToDevice));
         // the attribute belongs to the function, not to this context: always the 160 KiB cap, so that contexts of different geometries do not lower it for one another
@@ -260,9 +260,6 @@ extern "C" int wn_mel_create(const wn_mel_config* cfg, const float* mel_basis, w
 }
 
 extern "C" void wn_mel_destroy(wn_mel* m) {
-    if (!m) return;
-    if (m->basis) (void)hipFree(m->basis);
-    if (m->melT) (void)hipFree(m->melT);
     delete m;
 }
 

@@ -67,8 +67,8 @@ static void init_pack(wn_ctx* c, PackedW& w, int M_src, int K_src, int gate_il, 
 }
 
 static int finish_pack(wn_ctx* c, PackedW& w) {
-    WN_HIP(c, hipMalloc((void**)&w.dev, (size_t)w.M * w.K * 2));
-    WN_HIP(c, hipMalloc((void**)&w.dev_segs, w.segs.size() * sizeof(PackSeg)));
+    WN_HIP(c, w.dev.reserve((size_t)w.M * w.K));
+    WN_HIP(c, w.dev_segs.reserve(w.segs.size()));
     WN_HIP(c, hipMemcpy(w.dev_segs, w.segs.data(), w.segs.size() * sizeof(PackSeg), hipMemcpyHostToDevice));
     return WN_OK;
 }
@@ -129,29 +129,29 @@ int wn_build_packs(wn_ctx* c) {
     for (int l = 0; l < L; ++l) c->wcT.segs.push_back({c->lay[l].cin_k, l * G, G, 1, G, 1.0f});
     if ((rc = finish_pack(c, c->wcT))) return rc;
 
-    WN_HIP(c, hipMalloc((void**)&c->b1sum, (size_t)L * G * 4));
-    WN_HIP(c, hipMalloc((void**)&c->skip_bias_total, (size_t)S * 4));
-    WN_HIP(c, hipMalloc((void**)&c->params_dev, (size_t)(c->n_params + c->zpad) * 4));
+    WN_HIP(c, c->b1sum.reserve((size_t)L * G));
+    WN_HIP(c, c->skip_bias_total.reserve((size_t)S));
+    WN_HIP(c, c->params_dev.reserve((size_t)(c->n_params + c->zpad)));
     WN_HIP(c, hipMemset(c->params_dev, 0, (size_t)(c->n_params + c->zpad) * 4));       // incl. the zero tail that absent biases read
     if (c->gin > 0) {
-        WN_HIP(c, hipMalloc((void**)&c->gvec, (size_t)c->maxB * c->gin * 4));
-        WN_HIP(c, hipMalloc((void**)&c->gids, (size_t)c->maxB * 4));
-        WN_HIP(c, hipMalloc((void**)&c->gbias, (size_t)L * c->maxB * G * 4));
-        WN_HIP(c, hipMalloc((void**)&c->colsum, (size_t)L * c->maxB * G * 4));
+        WN_HIP(c, c->gvec.reserve((size_t)c->maxB * c->gin));
+        WN_HIP(c, c->gids.reserve((size_t)c->maxB));
+        WN_HIP(c, c->gbias.reserve((size_t)L * c->maxB * G));
+        WN_HIP(c, c->colsum.reserve((size_t)L * c->maxB * G));
     }
     if (c->wnorm) {
-        WN_HIP(c, hipMalloc((void**)&c->raw_dev, (size_t)c->n_raw * 4));
-        WN_HIP(c, hipMalloc((void**)&c->deff, (size_t)c->n_params * 4));
-        WN_HIP(c, hipMalloc((void**)&c->wmap_dev, c->wmap.size() * sizeof(wn_ctx::WnMap)));
+        WN_HIP(c, c->raw_dev.reserve((size_t)c->n_raw));
+        WN_HIP(c, c->deff.reserve((size_t)c->n_params));
+        WN_HIP(c, c->wmap_dev.reserve(c->wmap.size()));
         WN_HIP(c, hipMemcpy(c->wmap_dev, c->wmap.data(), c->wmap.size() * sizeof(wn_ctx::WnMap), hipMemcpyHostToDevice));
     }
     const int nt = (int)c->raw_tensors.size();          // per-VARIABLE clipping (wavenet.py:586-598): v and g are separate variables
     std::vector<int32_t> offs(nt + 1);
     for (int i = 0; i < nt; ++i) offs[i] = (int32_t)c->raw_tensors[i].offset;
     offs[nt] = (int32_t)c->n_raw;
-    WN_HIP(c, hipMalloc((void**)&c->tensor_offsets_dev, (nt + 1) * 4));
+    WN_HIP(c, c->tensor_offsets_dev.reserve((nt + 1)));
     WN_HIP(c, hipMemcpy(c->tensor_offsets_dev, offs.data(), (nt + 1) * 4, hipMemcpyHostToDevice));
-    WN_HIP(c, hipMalloc((void**)&c->norm2_dev, nt * 4));
+    WN_HIP(c, c->norm2_dev.reserve(nt));
     // span table of the atomic-free clip norms (wn_norm2_span_kernel): spans of <= WN_NORM_SPAN floats that never cross a tensor;
     // tensor i owns the spans [first[i], first[i + 1])
     {
@@ -162,11 +162,11 @@ int wn_build_packs(wn_ctx* c) {
         }
         first[nt] = (int32_t)(sp.size() / 2);
         c->norm_nspans = first[nt];
-        WN_HIP(c, hipMalloc((void**)&c->norm_spans_dev, sp.size() * 4 + 8));
+        WN_HIP(c, c->norm_spans_dev.reserve(sp.size() + 2));
         WN_HIP(c, hipMemcpy(c->norm_spans_dev, sp.data(), sp.size() * 4, hipMemcpyHostToDevice));
-        WN_HIP(c, hipMalloc((void**)&c->norm_first_dev, (nt + 1) * 4));
+        WN_HIP(c, c->norm_first_dev.reserve((nt + 1)));
         WN_HIP(c, hipMemcpy(c->norm_first_dev, first.data(), (nt + 1) * 4, hipMemcpyHostToDevice));
-        WN_HIP(c, hipMalloc((void**)&c->norm_part_dev, (size_t)c->norm_nspans * 4 + 8));
+        WN_HIP(c, c->norm_part_dev.reserve((size_t)c->norm_nspans + 2));
     }
     return WN_OK;
 }
@@ -190,11 +190,11 @@ int wn_launch_pack(wn_ctx* c, const float* params, hipStream_t st) {
         }
         add_pack_job(c, jobs, nblocks, c->wskip); add_pack_job(c, jobs, nblocks, c->wh1); add_pack_job(c, jobs, nblocks, c->wh2);
         add_pack_job(c, jobs, nblocks, c->wh2T); add_pack_job(c, jobs, nblocks, c->wh1T); add_pack_job(c, jobs, nblocks, c->wcT);
-        WN_HIP(c, hipMalloc((void**)&c->pack_jobs_dev, jobs.size() * sizeof(PackJob)));
+        WN_HIP(c, c->pack_jobs_dev.reserve(jobs.size() * sizeof(PackJob)));
         WN_HIP(c, hipMemcpy(c->pack_jobs_dev, jobs.data(), jobs.size() * sizeof(PackJob), hipMemcpyHostToDevice));
         c->pack_njobs = (int)jobs.size(); c->pack_nblocks = nblocks;
     }
-    hipLaunchKernelGGL(wn_pack_kernel, dim3(c->pack_nblocks), dim3(256), 0, st, c->params_dev, (const PackJob*)c->pack_jobs_dev, c->pack_njobs);
+    hipLaunchKernelGGL(wn_pack_kernel, dim3(c->pack_nblocks), dim3(256), 0, st, c->params_dev, (const PackJob*)c->pack_jobs_dev.get(), c->pack_njobs);
     WN_LAUNCH_CHECK(c);
     if (c->L > 32) WN_FAIL(c, WN_E_UNSUPPORTED, "layers > 32");
     {

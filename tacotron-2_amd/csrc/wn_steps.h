@@ -4,7 +4,7 @@
 // caller's may be the legacy NULL stream, which cannot be captured), the two events that order it behind and in front of the caller's stream, and the
 // hipGraphExec_t of `steps` steps with the key it was captured for.  Every step kernel reads its time index from device memory, so a graph is replayed
 // unchanged for as long as the key -- every pointer and size the captured launches carry -- matches; anything else is captured again.
-//     enter(caller) -> run(n, key, step) -> leave(caller);   free() at wn_destroy.
+//     enter(caller) -> run(n, key, step) -> leave(caller);   everything is released with the runner (the stream is drained first: wn_dev.h).
 #pragma once
 #include "wn_common.h"
 
@@ -15,23 +15,17 @@ struct WnStepKey {      // compared bytewise: pointers first, no padding
 static_assert(sizeof(WnStepKey) == 7 * sizeof(void*) + 4 * sizeof(int), "WnStepKey is compared with memcmp");
 
 struct WnStepRunner {
-    hipStream_t st = nullptr; hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipGraphExec_t gexec = nullptr; WnStepKey key = {};
+    DevGraphExec gexec; WnStepKey key = {};
+    DevEvent ev0, ev1;
+    DevStream st;           // (declared last: destroyed, i.e. drained, first)
 
     int create(wn_ctx* c) {      // (once; inference-only contexts: at wn_create, through the path's reserve)
-        if (!st) WN_HIP(c, hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-        if (!ev0) WN_HIP(c, hipEventCreateWithFlags(&ev0, hipEventDisableTiming));
-        if (!ev1) WN_HIP(c, hipEventCreateWithFlags(&ev1, hipEventDisableTiming));
+        WN_HIP(c, st.create(hipStreamNonBlocking));
+        WN_HIP(c, ev0.create(hipEventDisableTiming));
+        WN_HIP(c, ev1.create(hipEventDisableTiming));
         return WN_OK;
     }
-    void drop_graph() { if (gexec) { hipGraphExecDestroy(gexec); gexec = nullptr; } }
-    void free() {
-        drop_graph();
-        if (ev0) hipEventDestroy(ev0);
-        if (ev1) hipEventDestroy(ev1);
-        if (st) { (void)hipStreamSynchronize(st); hipStreamDestroy(st); }
-        st = nullptr; ev0 = ev1 = nullptr;
-    }
+    void drop_graph() { gexec.reset(); }
     // everything between enter and leave runs on `st`, after what the caller's stream holds now and before its next operation
     int enter(wn_ctx* c, hipStream_t caller) {
         WN_HIP(c, hipEventRecord(ev0, caller));
@@ -50,13 +44,12 @@ struct WnStepRunner {
         if (k.steps > 1 && n >= k.steps) {
             if (!gexec || memcmp(&k, &key, sizeof k) != 0) {
                 drop_graph();
-                hipGraph_t graph;
+                DevGraphGuard graph;      // (destroyed on every way out, a failed instantiation included)
                 WN_HIP(c, hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
                 for (int i = 0; i < k.steps; ++i)
-                    if ((rc = step(st))) { hipStreamEndCapture(st, &graph); return rc; }
-                WN_HIP(c, hipStreamEndCapture(st, &graph));
-                WN_HIP(c, hipGraphInstantiate(&gexec, graph, nullptr, nullptr, 0));
-                hipGraphDestroy(graph);
+                    if ((rc = step(st))) { hipStreamEndCapture(st, &graph.g); return rc; }
+                WN_HIP(c, hipStreamEndCapture(st, &graph.g));
+                WN_HIP(c, gexec.instantiate(graph.g));
                 key = k;
             }
             for (; done + k.steps <= n; done += k.steps) WN_HIP(c, hipGraphLaunch(gexec, st));
@@ -83,7 +76,7 @@ __global__ void wn_synth_init(const float* __restrict__ Wf, const float* __restr
 // A span that begins an utterance (t0 == 0) zeroes the queues (wavenet.py:815-816: `SB` streams per queue row) and starts from silence; any other one
 // continues from the queues, the time index and queue 0's next input its predecessor left, and only learns its first sample (t_dev[1]).
 template <class Q>
-static int wn_span_start(wn_ctx* c, const std::vector<Q*>& ring, const std::vector<int>& mask, int SB, int B, int32_t* t_dev, int t0, hipStream_t st) {
+static int wn_span_start(wn_ctx* c, const std::vector<DevBuf<Q>>& ring, const std::vector<int>& mask, int SB, int B, int32_t* t_dev, int t0, hipStream_t st) {
     if (t0 != 0) { WN_HIP(c, hipMemsetD32Async((hipDeviceptr_t)(t_dev + 1), t0, 1, st)); return WN_OK; }
     for (int l = 0; l < c->L; ++l) WN_HIP(c, hipMemsetAsync(ring[l], 0, (size_t)(mask[l] + 1) * SB * c->R * sizeof(Q), st));
     hipLaunchKernelGGL(wn_synth_init<Q>, dim3(1), dim3(256), 0, st, c->params_dev + c->first.dil_k, c->params_dev + c->first.dil_b, c->R, wn_sample_mode(c), 127, ring[0], B, t_dev);

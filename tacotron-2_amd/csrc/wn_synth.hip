@@ -17,12 +17,12 @@
 
 struct Synth {
     int B = 0, T = 0;
-    std::vector<bf16_t*> ring; std::vector<int> mask;
-    bf16_t* ucur = nullptr;        // [32][GH]
-    float* skip_acc = nullptr;     // [32][S]
-    bf16_t* h2 = nullptr;          // [32][S]
-    float* yraw = nullptr;         // [32][OP]
-    int32_t* t_dev = nullptr;      // [0] absolute time index of the next step, [1] first sample of the running span (0 for wn_synthesize; a stream push: its t0)
+    std::vector<DevBuf<bf16_t>> ring; std::vector<int> mask;
+    DevBuf<bf16_t> ucur;           // [32][GH]
+    DevBuf<float> skip_acc;        // [32][S]
+    DevBuf<bf16_t> h2;             // [32][S]
+    DevBuf<float> yraw;            // [32][OP]
+    DevBuf<int32_t> t_dev;         // [0] absolute time index of the next step, [1] first sample of the running span (0 for wn_synthesize; a stream push: its t0)
     WnStepRunner run;              // the ctx-owned stream the steps run on, the step graph and its key
     // slot sessions: sl != nullptr while a push of a session is enqueued -- [0..31] absolute index of every stream's next sample, [32..63] samples it generates
     // in this push, [64] push-local step.  A stream whose count is used up (or an idle slot) is a dummy for the rest of the push: its operand columns are
@@ -281,15 +281,7 @@ __global__ void wn_synth_slots_setup(const float* __restrict__ Wf, const float* 
     if (threadIdx.x == 0) sl[WN_SL_STEP] = 0;
 }
 
-void wn_synth_free(wn_ctx* c) {
-    Synth* s = c->synth;
-    if (!s) return;
-    for (auto p : s->ring) if (p) hipFree(p);
-    if (s->ucur) hipFree(s->ucur); if (s->skip_acc) hipFree(s->skip_acc); if (s->h2) hipFree(s->h2);
-    if (s->yraw) hipFree(s->yraw); if (s->t_dev) hipFree(s->t_dev);
-    s->run.free();
-    delete s; c->synth = nullptr;
-}
+void WnStateDelete::operator()(Synth* s) const { delete s; }
 
 static int enqueue_step(wn_ctx* c, Synth* s, const bf16_t* cbt, int Tcb, const float* gbias, const float* noise, const void* test_inputs, void* out_samples,
                         float* out_raw, hipStream_t st) {
@@ -322,18 +314,19 @@ static int enqueue_step(wn_ctx* c, Synth* s, const bf16_t* cbt, int Tcb, const f
 int wn_synth_reserve(wn_ctx* c) {
     if (c->synth) return WN_OK;
     const int L = c->L, R = c->R;
-    Synth* s = new Synth(); c->synth = s;
-        s->ring.assign(L, nullptr); s->mask.assign(L, 0);
+    c->synth.reset(new Synth());
+    Synth* s = c->synth.get();
+        s->ring.resize(L); s->mask.assign(L, 0);
         for (int l = 0; l < L; ++l) {
             int slots = 4; while (slots < 4 * c->dil[l]) slots <<= 1;
             s->mask[l] = slots - 1;
-            WN_HIP(c, hipMalloc((void**)&s->ring[l], (size_t)slots * 32 * R * 2));
+            WN_HIP(c, s->ring[l].reserve((size_t)slots * 32 * R));
         }
-        WN_HIP(c, hipMalloc((void**)&s->ucur, 32 * c->GH * 2));
-        WN_HIP(c, hipMalloc((void**)&s->skip_acc, 32 * c->S * 4));
-        WN_HIP(c, hipMalloc((void**)&s->h2, 32 * c->S * 2));
-        WN_HIP(c, hipMalloc((void**)&s->yraw, 32 * c->OP * 4));
-        WN_HIP(c, hipMalloc((void**)&s->t_dev, 8));
+        WN_HIP(c, s->ucur.reserve(32 * c->GH));
+        WN_HIP(c, s->skip_acc.reserve(32 * c->S));
+        WN_HIP(c, s->h2.reserve(32 * c->S));
+        WN_HIP(c, s->yraw.reserve(32 * c->OP));
+        WN_HIP(c, s->t_dev.reserve(2));
     return s->run.create(c);
 }
 
@@ -376,7 +369,7 @@ int wn_synth_span(wn_ctx* c, int B, int T, const WnSpan& sp, const float* noise,
                   int steps_per_graph, hipStream_t caller_st) {
     int rc = wn_synth_reserve(c);
     if (rc) return rc;
-    Synth* s = c->synth;
+    Synth* s = c->synth.get();
     c->synth_path = 1;
     if (steps_per_graph <= 0) steps_per_graph = 32;
     if ((rc = s->run.enter(c, caller_st))) return rc;

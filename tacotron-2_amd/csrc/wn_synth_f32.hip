@@ -17,9 +17,9 @@
 
 struct SynthF32 {
     int capB = 0;                                   // streams the rings are sized for
-    std::vector<float*> ring; std::vector<int> mask;
-    float *ucur = nullptr, *skip_acc = nullptr, *h2 = nullptr, *yraw = nullptr;
-    int32_t* t_dev = nullptr;                       // [0] absolute time index of the next step, [1] first sample of the running span (a stream push's t0)
+    std::vector<DevBuf<float>> ring; std::vector<int> mask;
+    DevBuf<float> ucur, skip_acc, h2, yraw;
+    DevBuf<int32_t> t_dev;                          // [0] absolute time index of the next step, [1] first sample of the running span (a stream push's t0)
     WnStepRunner run;                               // the ctx-owned stream the steps run on, the step graph and its key
 };
 
@@ -187,43 +187,31 @@ __global__ __launch_bounds__(256) void wn_f32s_sample(const float* __restrict__ 
     if (tid == 0) *t_dev = t + 1;
 }
 
-void wn_synth_f32_free(wn_ctx* c) {
-    SynthF32* s = (SynthF32*)c->synth32;
-    if (!s) return;
-    for (float* p : s->ring) if (p) hipFree(p);
-    for (float* p : {s->ucur, s->skip_acc, s->h2, s->yraw}) if (p) hipFree(p);
-    if (s->t_dev) hipFree(s->t_dev);
-    s->run.free();
-    delete s; c->synth32 = nullptr;
-}
+void WnStateDelete::operator()(SynthF32* s) const { delete s; }
 
 // queues for `B` streams (4d slots per layer: t & (4d - 1), reads reach back 2d), per-step scratch, the capture stream
 int wn_synth_f32_reserve(wn_ctx* c, int B) {
-    if (!c->synth32) c->synth32 = new SynthF32();
-    SynthF32* s = (SynthF32*)c->synth32;
+    if (!c->synth32) c->synth32.reset(new SynthF32());
+    SynthF32* s = c->synth32.get();
     const int L = c->L, R = c->R;
     if (s->capB < B) {
         if (c->inference && s->capB > 0) WN_FAIL(c, WN_E_SHAPE, "fp32 synthesis: %d streams exceed the %d this inference-only context was sized for", B, s->capB);
-        if (s->capB > 0) {
-            (void)hipDeviceSynchronize();
-            for (float*& p : s->ring) { if (p) hipFree(p); p = nullptr; }
-            for (float** p : {&s->ucur, &s->skip_acc, &s->h2, &s->yraw}) { if (*p) hipFree(*p); *p = nullptr; }
-        }
+        if (s->capB > 0) (void)hipDeviceSynchronize();      // (growing: nothing may still read the old queues)
         s->run.drop_graph();
-        s->ring.assign(L, nullptr); s->mask.assign(L, 0);
+        s->ring.resize(L); s->mask.assign(L, 0);
         for (int l = 0; l < L; ++l) {
             int slots = 4; while (slots < 4 * c->dil[l]) slots <<= 1;
             s->mask[l] = slots - 1;
-            WN_HIP(c, hipMalloc((void**)&s->ring[l], (size_t)slots * B * R * 4));
+            WN_HIP(c, s->ring[l].grow((size_t)slots * B * R));
         }
         // per-step scratch, one row per stream, sized with the queues (wn_synthesize admits at most 32 streams)
-        WN_HIP(c, hipMalloc((void**)&s->ucur, (size_t)B * c->GH * 4));
-        WN_HIP(c, hipMalloc((void**)&s->skip_acc, (size_t)B * c->S * 4));
-        WN_HIP(c, hipMalloc((void**)&s->h2, (size_t)B * c->S * 4));
-        WN_HIP(c, hipMalloc((void**)&s->yraw, (size_t)B * c->OP * 4));
+        WN_HIP(c, s->ucur.grow((size_t)B * c->GH));
+        WN_HIP(c, s->skip_acc.grow((size_t)B * c->S));
+        WN_HIP(c, s->h2.grow((size_t)B * c->S));
+        WN_HIP(c, s->yraw.grow((size_t)B * c->OP));
         s->capB = B;
     }
-    if (!s->t_dev) WN_HIP(c, hipMalloc((void**)&s->t_dev, 8));
+    WN_HIP(c, s->t_dev.reserve(2));
     return s->run.create(c);
 }
 
@@ -258,7 +246,7 @@ int wn_synth_f32_span(wn_ctx* c, int B, int T, const WnSpan& sp, const float* no
     if (3 * c->R + c->C > 2000) WN_FAIL(c, WN_E_SHAPE, "fp32 synthesis: 3 * residual_channels + cin_channels = %d input taps exceed the 64 KB LDS image of 8 streams", 3 * c->R + c->C);
     int rc = wn_synth_f32_reserve(c, B);
     if (rc) return rc;
-    SynthF32* s = (SynthF32*)c->synth32;
+    SynthF32* s = c->synth32.get();
     if (steps_per_graph <= 0) steps_per_graph = 32;
     c->synth_path = 3;
     if ((rc = s->run.enter(c, caller_st))) return rc;

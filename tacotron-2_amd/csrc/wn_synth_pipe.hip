@@ -975,25 +975,26 @@ __global__ __launch_bounds__(PIPE_THREADS) void wn_synth_pipe_kernel(const PipeA
 // ======================================================================================================================
 struct Pipe {
     int B = 0, T = 0, P = 0, spx = 0, grid = 0;
-    char* slices = nullptr; int64_t layer_slice_bytes = 0, head_slice_off = 0, slices_bytes = 0;
-    SliceJob* jobs_dev = nullptr; int* job_block0_dev = nullptr; int njobs = 0, nblocks = 0;
-    u32x4* XM = nullptr; u32x4* SM = nullptr; u32x4* XML = nullptr; u32x4* SML = nullptr; size_t xm_bytes = 0, sm_bytes = 0;
-    bf16_t* ring = nullptr; size_t ring_bytes = 0; int ring_B = 0;
-    int32_t* abort_dev = nullptr;       // [0] flag of the running launch, [1] sticky OR of every run since the last wn_pipe_check, +256 B: XCC table
-    int32_t* abort_host = nullptr;      // pinned: the abort flag of the last run lands here asynchronously (read by wn_pipe_check)
+    DevBuf<char> slices; int64_t layer_slice_bytes = 0, head_slice_off = 0, slices_bytes = 0;
+    DevBuf<SliceJob> jobs_dev; DevBuf<int> job_block0_dev; int njobs = 0, nblocks = 0;
+    DevBuf<u32x4> XM, SM, XML, SML;     // mailboxes; XM / XML and SM / SML grow in pairs (wn_pipe_reserve)
+    DevBuf<bf16_t> ring; int ring_B = 0;
+    DevBuf<int32_t> abort_dev;          // [0] flag of the running launch, [1] sticky OR of every run since the last wn_pipe_check, +256 B: XCC table
+    PinBuf<int32_t> abort_host;         // pinned: the abort flag of the last run lands here asynchronously (read by wn_pipe_check)
     bool pending = false;               // a run has been enqueued whose flag has not been inspected yet
     bool pending_stream = false;        // ... and it was a push of the open stream: a raised flag poisons the stream
     int test_aborts = 0;
     int layer_lds = 0, head_lds = 0;
     bool f16 = false;                   // 16-bit storage type of weights / hand-offs / queues: IEEE half instead of bf16 (wn_ctx::pipe_f16 at the run)
     PipeArgs proto;
-    hipStream_t priv = nullptr; hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // several pipeline INSTANCES side by side (round 5): a model whose L * P + 1 CUs fit the chip more than once (hparams.py's defaults: 81 CUs, three
     // times by CU count, twice with the slack the dispatcher needs) serves a batch of more than 8 streams as NI independent runs of <= 8 where they fit -- the regime in which a run costs the wall time of ONE stream
 #define PIPE_MAX_INST 3
     int ni_max = 1;                                    // how many instances the chip holds (layout below)
-    int32_t* tabs_dev[PIPE_MAX_INST + 1] = {};         // [ni]: role table (256) + ni block tables (L * P + 1 each) of the ni-instance layout
+    DevBuf<int32_t> tabs_dev[PIPE_MAX_INST + 1];       // [ni]: role table (256) + ni block tables (L * P + 1 each) of the ni-instance layout
     int grid_ni[PIPE_MAX_INST + 1] = {};
+    DevEvent ev0, ev1;
+    DevStream priv;                     // (declared last: destroyed, i.e. drained, before the buffers above are freed)
 };
 
 // Which workgroup plays which CU.  Block b runs on XCD b % 8 (observed; speed only): one instance keeps the scheme of rounds 2-4 (spx consecutive
@@ -1062,17 +1063,7 @@ extern "C" int wn_test_pipe_layout(int32_t L, int32_t P, int32_t ni, int32_t* ro
 }
 #endif
 
-void wn_pipe_free(wn_ctx* c) {
-    Pipe* p = (Pipe*)c->pipe;
-    if (!p) return;
-    if (p->slices) hipFree(p->slices); if (p->jobs_dev) hipFree(p->jobs_dev); if (p->job_block0_dev) hipFree(p->job_block0_dev);
-    if (p->XM) hipFree(p->XM); if (p->SM) hipFree(p->SM); if (p->XML) hipFree(p->XML); if (p->SML) hipFree(p->SML); if (p->ring) hipFree(p->ring); if (p->abort_dev) hipFree(p->abort_dev);
-    if (p->priv) (void)hipStreamSynchronize(p->priv);
-    if (p->abort_host) hipHostFree(p->abort_host);
-    if (p->ev0) hipEventDestroy(p->ev0); if (p->ev1) hipEventDestroy(p->ev1); if (p->priv) hipStreamDestroy(p->priv);
-    for (int i = 0; i <= PIPE_MAX_INST; ++i) if (p->tabs_dev[i]) hipFree(p->tabs_dev[i]);
-    delete p; c->pipe = nullptr;
-}
+void WnStateDelete::operator()(Pipe* p) const { delete p; }
 
 // can this model run on the persistent pipeline?  (one CU per 32 gate pairs, all of a CU's weights in 160 KiB of LDS)
 bool wn_pipe_eligible(const wn_ctx* c, int B) {
@@ -1117,7 +1108,7 @@ static int pipe_build(wn_ctx* c, Pipe* p) {
     a.head_lds_static = (int)((h + 15) / 16 * 16);
     p->head_slice_off = (int64_t)L * P * p->layer_slice_bytes;
     p->slices_bytes = p->head_slice_off + al(a.head_lds_static);
-    WN_HIP(c, hipMalloc((void**)&p->slices, p->slices_bytes));
+    WN_HIP(c, p->slices.reserve(p->slices_bytes));
     WN_HIP(c, hipMemset(p->slices, 0, p->slices_bytes));
     p->layer_lds = a.layer_lds_static + (R * 2 + R * 4 + 16 * R + 8 * R + 1024 + 64 + (R + 16) * 2 + (S + 4) * 4 + (2 * R + C) * 2 + 64);      // + 256 B of z_past per stream, added at launch
     p->head_lds = a.head_lds_static + (16 * (S + 4) + S * 4 + OP * 4 + (R + 16) * 2 + 64);
@@ -1153,17 +1144,17 @@ static int pipe_build(wn_ctx* c, Pipe* p) {
     vecj(hb + a.hoff_b2, c->fin2_b, O, 1.0f, 0, 0);
     if (c->Cin == 1) { vecj(hb + a.hoff_win, c->first.dil_k, R, 1.0f, 0, 0); vecj(hb + a.hoff_bin, c->first.dil_b, R, 1.0f, 0, 0); }
     p->njobs = (int)jobs.size(); p->nblocks = nblocks;
-    WN_HIP(c, hipMalloc((void**)&p->jobs_dev, jobs.size() * sizeof(SliceJob)));
+    WN_HIP(c, p->jobs_dev.reserve(jobs.size()));
     WN_HIP(c, hipMemcpy(p->jobs_dev, jobs.data(), jobs.size() * sizeof(SliceJob), hipMemcpyHostToDevice));
-    WN_HIP(c, hipMalloc((void**)&p->job_block0_dev, b0.size() * sizeof(int)));
+    WN_HIP(c, p->job_block0_dev.reserve(b0.size()));
     WN_HIP(c, hipMemcpy(p->job_block0_dev, b0.data(), b0.size() * sizeof(int), hipMemcpyHostToDevice));
-    WN_HIP(c, hipMalloc((void**)&p->abort_dev, 256 + PIPE_MAX_INST * 4096));       // [0]: abort flag; +256: one XCC table per instance (grid <= 1024 entries)
+    WN_HIP(c, p->abort_dev.reserve((256 + PIPE_MAX_INST * 4096) / 4));       // [0]: abort flag; +256: one XCC table per instance (grid <= 1024 entries)
     WN_HIP(c, hipMemset(p->abort_dev, 0, 256 + PIPE_MAX_INST * 4096));
-    WN_HIP(c, hipHostMalloc((void**)&p->abort_host, 64, hipHostMallocDefault));
+    WN_HIP(c, p->abort_host.reserve(16));
     *p->abort_host = 0;
-    WN_HIP(c, hipStreamCreateWithFlags(&p->priv, hipStreamNonBlocking));
-    WN_HIP(c, hipEventCreateWithFlags(&p->ev0, hipEventDisableTiming));
-    WN_HIP(c, hipEventCreateWithFlags(&p->ev1, hipEventDisableTiming));
+    WN_HIP(c, p->priv.create(hipStreamNonBlocking));
+    WN_HIP(c, p->ev0.create(hipEventDisableTiming));
+    WN_HIP(c, p->ev1.create(hipEventDisableTiming));
     p->ni_max = pipe_ni_max(L, P);
     for (int ni = 1; ni <= p->ni_max; ++ni) {
         std::vector<int32_t> role, blk; int grid = 0;
@@ -1171,7 +1162,7 @@ static int pipe_build(wn_ctx* c, Pipe* p) {
         p->grid_ni[ni] = grid;
         std::vector<int32_t> all(role);                 // role table (grid) then the ni block tables (L * P + 1 each)
         all.insert(all.end(), blk.begin(), blk.end());
-        WN_HIP(c, hipMalloc((void**)&p->tabs_dev[ni], all.size() * 4));
+        WN_HIP(c, p->tabs_dev[ni].reserve(all.size()));
         WN_HIP(c, hipMemcpy(p->tabs_dev[ni], all.data(), all.size() * 4, hipMemcpyHostToDevice));
     }
     return WN_OK;
@@ -1209,27 +1200,28 @@ __global__ void wn_pipe_sticky_kernel(int32_t* f) { if (threadIdx.x == 0 && f[0]
 // wn_create on inference-only contexts, so that wn_synthesize never allocates there; training contexts get here on first use.
 int wn_pipe_reserve(wn_ctx* c, int B, int T) {
     (void)T;
-    Pipe* p = (Pipe*)c->pipe;
+    Pipe* p = c->pipe.get();
     int rc;
-    if (!p) { p = new Pipe(); c->pipe = p; if ((rc = pipe_build(c, p))) return rc; }
+    if (!p) { c->pipe.reset(p = new Pipe()); if ((rc = pipe_build(c, p))) return rc; }
     const int L = c->L, R = c->R, P = p->P;
     const size_t xm = (size_t)(L + 1) * B * P * PIPE_XG * 16, sm = (size_t)(L + 1) * B * P * PIPE_SG * 16;
     int64_t roff = 0;
     for (int l = 0; l < L; ++l) { int slots = 4; while (slots < 2 * c->dil[l] + 1) slots <<= 1; roff += (int64_t)P * B * slots * R; }
-    const bool grow = xm > p->xm_bytes || sm > p->sm_bytes || (size_t)roff * 2 > p->ring_bytes;
+    // (XML / SML are grown after XM / SM: a pair is large enough iff its second half is, also after a failed growth)
+    const bool grow = xm > p->XML.bytes() || sm > p->SML.bytes() || (size_t)roff > p->ring.cap();
     if (!grow) return WN_OK;
-    if (c->inference && p->xm_bytes) WN_FAIL(c, WN_E_SHAPE, "synthesis batch %d exceeds the pre-sized pipeline of this inference-only context", B);
+    if (c->inference && p->XM) WN_FAIL(c, WN_E_SHAPE, "synthesis batch %d exceeds the pre-sized pipeline of this inference-only context", B);
     if (p->priv) WN_HIP(c, hipStreamSynchronize(p->priv));          // (growing: nothing of ours may still read the old buffers)
-    if (xm > p->xm_bytes) { if (p->XM) hipFree(p->XM); if (p->XML) hipFree(p->XML); WN_HIP(c, hipMalloc((void**)&p->XM, xm)); WN_HIP(c, hipMalloc((void**)&p->XML, xm)); p->xm_bytes = xm; }
-    if (sm > p->sm_bytes) { if (p->SM) hipFree(p->SM); if (p->SML) hipFree(p->SML); WN_HIP(c, hipMalloc((void**)&p->SM, sm)); WN_HIP(c, hipMalloc((void**)&p->SML, sm)); p->sm_bytes = sm; }
-    if ((size_t)roff * 2 > p->ring_bytes) { if (p->ring) hipFree(p->ring); WN_HIP(c, hipMalloc((void**)&p->ring, (size_t)roff * 2)); p->ring_bytes = (size_t)roff * 2; }
+    WN_HIP(c, p->XM.grow(xm / 16)); WN_HIP(c, p->XML.grow(xm / 16));
+    WN_HIP(c, p->SM.grow(sm / 16)); WN_HIP(c, p->SML.grow(sm / 16));
+    WN_HIP(c, p->ring.grow((size_t)roff));
     return WN_OK;
 }
 
 // Abort flag of the last pipeline run.  wait = false: report it only if that run has already finished (no synchronisation);
 // wait = true: wait for it (wn_synth_check).
 int wn_pipe_check(wn_ctx* c, bool wait) {
-    Pipe* p = (Pipe*)c->pipe;
+    Pipe* p = c->pipe.get();
     if (!p || !p->pending) return WN_OK;
     if (wait) WN_HIP(c, hipEventSynchronize(p->ev1));
     else if (hipEventQuery(p->ev1) != hipSuccess) return WN_OK;     // still running: nothing to report yet
@@ -1255,7 +1247,7 @@ int wn_pipe_span(wn_ctx* c, int B, int T, const WnSpan& sp, const float* noise, 
     const int L = c->L, R = c->R;
     int rc;
     if ((rc = wn_pipe_reserve(c, B, T))) return rc;
-    Pipe* p = (Pipe*)c->pipe;
+    Pipe* p = c->pipe.get();
     p->f16 = c->pipe_f16;
     hipStream_t st = p->priv;
     WN_HIP(c, hipEventRecord(p->ev0, caller_st));
@@ -1295,7 +1287,7 @@ int wn_pipe_span(wn_ctx* c, int B, int T, const WnSpan& sp, const float* noise, 
     if (sp.st0) { a.out_pitch = sp.out_pitch; for (int i = 0; i < 32; ++i) { a.st0[i] = i < B ? sp.st0[i] : 0; a.snl[i] = i < B ? sp.snl[i] : 0; } }
     a.noise = noise; a.test_inputs = test_inputs; a.out_samples = out_samples; a.out_raw = out_raw;
     a.win_global = c->params_dev + c->first.dil_k; a.bin_global = c->params_dev + c->first.dil_b;
-    unsigned long long* trace_dev = nullptr; const int trace_n = 32;
+    DevBuf<unsigned long long> trace_dev, svc_dev; const int trace_n = 32;      // per-run diagnostics: freed on every way out
 #ifdef WN_PIPE_SVC_BUILD
     const bool want_trace = getenv("WN_PIPE_TRACE") != nullptr, want_svc = getenv("WN_PIPE_SVC_TRACE") != nullptr;
 #else
@@ -1303,13 +1295,12 @@ int wn_pipe_span(wn_ctx* c, int B, int T, const WnSpan& sp, const float* noise, 
     if (getenv("WN_PIPE_TRACE") || getenv("WN_PIPE_SVC_TRACE")) { static bool told = false; if (!told) { told = true; fprintf(stderr, "[pipe] WN_PIPE_TRACE / WN_PIPE_SVC_TRACE need the diagnostic build (python tacotron-2_amd/csrc/build.py --pipe-svc)\n"); } }
 #endif
     if (want_trace && T > 600) {
-        WN_HIP(c, hipMalloc((void**)&trace_dev, (size_t)trace_n * 2 * (L + 2) * 8));
+        WN_HIP(c, trace_dev.reserve((size_t)trace_n * 2 * (L + 2)));
         WN_HIP(c, hipMemsetAsync(trace_dev, 0, (size_t)trace_n * 2 * (L + 2) * 8, st));
         a.trace = trace_dev; a.trace_t0 = 500; a.trace_n = trace_n;
     }
-    unsigned long long* svc_dev = nullptr;
     if (want_svc && T > 600) {
-        WN_HIP(c, hipMalloc((void**)&svc_dev, (size_t)trace_n * 16 * 8));
+        WN_HIP(c, svc_dev.reserve((size_t)trace_n * 16));
         WN_HIP(c, hipMemsetAsync(svc_dev, 0, (size_t)trace_n * 16 * 8, st));
         a.svc = svc_dev; a.svc_l = L / 2; a.svc_s = B / 2; a.trace_t0 = 500; a.trace_n = trace_n;
     }
@@ -1361,7 +1352,7 @@ int wn_pipe_span(wn_ctx* c, int B, int T, const WnSpan& sp, const float* noise, 
     if (svc_dev) {        // where a layer CU's service time per stream goes (diagnostic mode: synchronises)
         WN_HIP(c, hipStreamSynchronize(st));
         std::vector<unsigned long long> h((size_t)trace_n * 16);
-        hipMemcpy(h.data(), svc_dev, h.size() * 8, hipMemcpyDeviceToHost); hipFree(svc_dev);
+        hipMemcpy(h.data(), svc_dev, h.size() * 8, hipMemcpyDeviceToHost);
         static const char* nm[10] = {"x poll", "barrier A", "x rebuild + z + gate + barrier B", "out matvec + publish x", "barrier", "skip own matvec + barrier", "skip poll + add + barrier",
                                      "skip publish", "ring store", "pre-multiplication of the next sample"};
         double d[10] = {0}; double tot = 0; int n = 0;
@@ -1378,7 +1369,7 @@ int wn_pipe_span(wn_ctx* c, int B, int T, const WnSpan& sp, const float* noise, 
     if (trace_dev) {      // per-stage latencies in units of the 100 MHz real-time counter (10 ns)   [diagnostic mode: synchronises]
         WN_HIP(c, hipStreamSynchronize(st));
         std::vector<unsigned long long> h((size_t)trace_n * 2 * (L + 2));
-        hipMemcpy(h.data(), trace_dev, h.size() * 8, hipMemcpyDeviceToHost); hipFree(trace_dev);
+        hipMemcpy(h.data(), trace_dev, h.size() * 8, hipMemcpyDeviceToHost);
         const int W = 2 * (L + 2);
         std::vector<double> hop(L + 1, 0.0), comp(L, 0.0); double hskip = 0, hconv = 0, hsamp = 0, hpub = 0, step = 0;
         for (int i = 0; i < trace_n; ++i) {

@@ -39,7 +39,7 @@ static SrcSeg seg(const bf16_t* base, int ld, int col0, int nk, int shift, int d
 }
 
 static void prof_mark(wn_ctx* c, hipStream_t st) {
-    if (c->pev_used == c->pev.size()) { hipEvent_t e; if (hipEventCreate(&e) != hipSuccess) return; c->pev.push_back(e); }
+    if (c->pev_used == c->pev.size()) { DevEvent e; if (e.create() != hipSuccess) return; c->pev.push_back(std::move(e)); }
     (void)hipEventRecord(c->pev[c->pev_used++], st);
 }
 __global__ void wn_kprof_init_kernel(unsigned long long* k, int n) {
@@ -49,7 +49,7 @@ __global__ void wn_kprof_init_kernel(unsigned long long* k, int n) {
 // Device timeline from in-kernel stamps (wn_common.h): called at the start of every wn_train_fwd and at the end of every wn_train_bwd.
 // Armed by wn_trace_arm (results through wn_trace_read) or by WN_DEVTRACE=<file> (the WN_DEVTRACE_STEP-th forward, written two steps later).
 static bool devtrace_begin(wn_ctx* c, hipStream_t st) {
-    if (!c->trace_dev && hipMalloc((void**)&c->trace_dev, (size_t)WN_TRACE_MAX * 16) != hipSuccess) return false;
+    if (c->trace_dev.reserve((size_t)WN_TRACE_MAX * 2) != hipSuccess) return false;
     hipLaunchKernelGGL(wn_kprof_init_kernel, dim3(cdiv(WN_TRACE_MAX, 256)), dim3(256), 0, st, c->trace_dev, WN_TRACE_MAX);
     c->trace_n = 0; c->trace_state = 1;
     return true;
@@ -111,9 +111,9 @@ extern "C" int wn_profile(wn_ctx* c, int32_t enable) {
     if (!c) return WN_E_ARG;
     c->prof = enable != 0; c->pev_used = 0;
     if (c->prof) {
-        if (!c->kprof_dev) WN_HIP(c, hipMalloc((void**)&c->kprof_dev, (size_t)WN_KPROF_MAX * 16));
+        WN_HIP(c, c->kprof_dev.reserve((size_t)WN_KPROF_MAX * 2));
         hipLaunchKernelGGL(wn_kprof_init_kernel, dim3(cdiv(WN_KPROF_MAX, 256)), dim3(256), 0, 0, c->kprof_dev, WN_KPROF_MAX);
-        if (!c->kclk_dev) WN_HIP(c, hipMalloc((void**)&c->kclk_dev, (size_t)WN_KPROF_MAX * 16));
+        WN_HIP(c, c->kclk_dev.reserve((size_t)WN_KPROF_MAX * 2));
         WN_HIP(c, hipMemset(c->kclk_dev, 0, (size_t)WN_KPROF_MAX * 16));
         WN_HIP(c, hipDeviceSynchronize());
     }
@@ -316,17 +316,17 @@ size_t wn_wgrad_partial_need(wn_ctx* c) {
 // ---- batch parts on two streams ---------------------------------------------------------------------------------------
 static int parts_setup(wn_ctx* c, int np) {
     if (!c->st2) {
-        WN_HIP(c, hipStreamCreateWithFlags(&c->st2, hipStreamNonBlocking));
-        WN_HIP(c, hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming));
-        WN_HIP(c, hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming));
+        WN_HIP(c, c->st2.create(hipStreamNonBlocking));
+        WN_HIP(c, c->ev_fork.create(hipEventDisableTiming));
+        WN_HIP(c, c->ev_join.create(hipEventDisableTiming));
         c->stp[1] = c->st2;
-        for (int k = 0; k < WN_MAX_PARTS; ++k) WN_HIP(c, hipEventCreateWithFlags(&c->ev_pjoin[k], hipEventDisableTiming));
+        for (int k = 0; k < WN_MAX_PARTS; ++k) WN_HIP(c, c->ev_pjoin[k].create(hipEventDisableTiming));
     }
     // further part streams only on demand: the runtime multiplexes streams onto a few hardware queues (4 by default), and a stream
     // that merely EXISTS can end up sharing a queue with -- i.e. serialising against -- one of the streams that carry the step
     // (measured: two idle extra streams cost 1.2 ms per step)
     for (int k = 2; k < np; ++k)
-        if (!c->stp[k]) WN_HIP(c, hipStreamCreateWithFlags(&c->stp[k], hipStreamNonBlocking));
+        if (!c->stp[k]) { WN_HIP(c, c->stp_own[k].create(hipStreamNonBlocking)); c->stp[k] = c->stp_own[k]; }
     return WN_OK;
 }
 static int n_parts(wn_ctx* c) {
@@ -465,8 +465,7 @@ int wn_fwd_impl(wn_ctx* c, hipStream_t st, float* loss_out, float* y_hat_out, bo
         if ((rc = wn_f32_forward(c, st))) return rc;
         if (y_hat_out) WN_HIP(c, hipMemcpyAsync(y_hat_out, c->YHAT, (size_t)c->fB * c->O * c->fT * 4, hipMemcpyDeviceToDevice, st));
         if (loss_out) {      // the loss kernel also writes d y_hat in fp32 for wn_f32_backward
-            c->dy32_next = wn_f32_dy(c);
-            if (!c->dy32_next) WN_FAIL(c, WN_E_HIP, "hipMalloc(fp32 d y_hat) failed");
+            if ((rc = wn_f32_dy(c, &c->dy32_next))) return rc;
             if ((rc = wn_loss_fwd_bwd(c, loss_out, st))) return rc;
         }
         c->have_loss = loss_out != nullptr;
@@ -579,12 +578,12 @@ static int buckets_setup(wn_ctx* c) {
     if (c->st3) return WN_OK;
     int lo_pri = 0, hi_pri = 0;
     WN_HIP(c, hipDeviceGetStreamPriorityRange(&lo_pri, &hi_pri));            // (least, greatest)
-    WN_HIP(c, hipStreamCreateWithPriority(&c->st3, hipStreamNonBlocking, lo_pri));
+    WN_HIP(c, c->st3.create_with_priority(hipStreamNonBlocking, lo_pri));
     for (int p = 0; p < WN_MAX_PARTS; ++p)
-        for (int k = 0; k < WN_MAX_BUCKETS; ++k) WN_HIP(c, hipEventCreateWithFlags(&c->ev_chain[p][k], hipEventDisableTiming));
-    for (int p = 0; p < WN_MAX_PARTS; ++p) WN_HIP(c, hipEventCreateWithFlags(&c->ev_head[p], hipEventDisableTiming));
-    for (int k = 0; k < WN_MAX_BUCKETS + 2; ++k) WN_HIP(c, hipEventCreateWithFlags(&c->ev_bucket[k], hipEventDisableTiming));
-    WN_HIP(c, hipEventCreateWithFlags(&c->ev_w0, hipEventDisableTiming));
+        for (int k = 0; k < WN_MAX_BUCKETS; ++k) WN_HIP(c, c->ev_chain[p][k].create(hipEventDisableTiming));
+    for (int p = 0; p < WN_MAX_PARTS; ++p) WN_HIP(c, c->ev_head[p].create(hipEventDisableTiming));
+    for (int k = 0; k < WN_MAX_BUCKETS + 2; ++k) WN_HIP(c, c->ev_bucket[k].create(hipEventDisableTiming));
+    WN_HIP(c, c->ev_w0.create(hipEventDisableTiming));
     return WN_OK;
 }
 // bucket table (fixed at wn_create): early buckets = layer groups from the top, then [input conv + lowest layers], then the tail

@@ -557,7 +557,7 @@ static inline bool wn_wgrad_v2_ok(const WgBatchArgs& a) {
 }
 static int launch_wgrad_batch(wn_ctx* c, WgBatchArgs& a, hipStream_t st) {
     wn_wgrad_plan(a);
-    if (wn_wgrad_partial_bytes(a) > c->wg_partial_bytes) WN_FAIL(c, WN_E_STATE, "wgrad partial buffer too small (%zu > %zu)", wn_wgrad_partial_bytes(a), c->wg_partial_bytes);
+    if (wn_wgrad_partial_bytes(a) > c->wg_partial.bytes()) WN_FAIL(c, WN_E_STATE, "wgrad partial buffer too small (%zu > %zu)", wn_wgrad_partial_bytes(a), c->wg_partial.bytes());
     a.partial = c->wg_partial; a.zero = c->zero_page; a.kprof = nullptr;
     if (c->trace_state == 1 && c->trace_n < WN_TRACE_MAX) {      // WN_DEVTRACE: tag 100 + na
         a.kprof = c->trace_dev + 2 * c->trace_n;

@@ -682,6 +682,21 @@ def test_c_abi_host_side_under_address_and_ub_sanitizers():
     assert r.returncode == 0 and '4 passed' in r.stdout, r.stdout[-1500:] + r.stderr[-1500:]
 
 
+def test_device_buffer_owners_under_address_and_ub_sanitizers(tmp_path):
+    """csrc/wn_dev.h: DevBuf / PinBuf in a stand-alone host program (tests/host/devbuf_main.cpp: its own main, its own counting allocator that can
+    fail the k-th allocation) built with ASAN + UBSAN and run as an ordinary child process.  The program asserts that reserve / grow / reset / moves
+    keep the live count exact, that a failed growth leaves pointer, capacity and count untouched (the destructor then frees once: a double free is
+    the sanitizer's to report; LeakSanitizer watches for a block nobody frees), and that failing every allocation of a scripted sequence in turn always ends with nothing live."""
+    exe = str(tmp_path / 'devbuf_main')
+    r = subprocess.run(['hipcc', '-std=c++20', '-O1', '-g', '-Wall', '-Xarch_host', '-fsanitize=address,undefined', '-Xarch_host', '-fno-sanitize-recover=undefined',
+                        '-I', os.path.join(ROOT, 'tacotron-2_amd', 'csrc'), os.path.join(ROOT, 'tests', 'host', 'devbuf_main.cpp'), '-o', exe],
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+    env = dict(os.environ, ASAN_OPTIONS='detect_leaks=1:abort_on_error=1', UBSAN_OPTIONS='halt_on_error=1:print_stacktrace=1')
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120, env=env)
+    assert r.returncode == 0 and 'devbuf ok' in r.stdout, r.stdout[-1500:] + r.stderr[-3000:]
+
+
 def test_bench_cpu_synthesis_baseline_leg():
     """bench.py's CPU synthesis baseline: the oracle incremental loop in the reference's queue formulation and with ring
     buffers, on a bounded sample, reporting samples/s and the extrapolated real-time factor."""

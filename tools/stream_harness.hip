@@ -8,6 +8,7 @@
 //   hipcc --offload-arch=gfx950 -O3 -std=c++20 -I tacotron-2_amd/csrc -I tools tools/stream_harness.hip -o tools/stream_harness
 //   tools/stream_harness [B=8] [T=11000] [rounds=3]
 #include "wn_tile_wb.h"
+#include "wn_ctx_stub.h"
 #include "power_sampler.h"
 #include <vector>
 #include <random>

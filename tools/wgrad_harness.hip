@@ -1,7 +1,9 @@
 // Stand-alone check + timing of the weight-gradient kernels (run on the GPU box): v1 (per layer, ds_read_u16 gathers,
 // atomics) vs v2 (grouped over layers, LDS-DMA ring + ds_read_b64_tr_b16, partial tiles + reduce).
 // Same math, different summation order => compare with a tolerance.
+//   hipcc --offload-arch=gfx950 -O3 -std=c++20 -I tacotron-2_amd/csrc -I tools tools/wgrad_harness.hip -o tools/wgrad_harness
 #include "wn_wgrad.h"
+#include "wn_ctx_stub.h"
 #include <vector>
 #include <random>
 #include <functional>
@@ -27,7 +29,7 @@ int main(int argc, char** argv) {
     int fails = 0;
     wn_ctx ctx;
     CK(hipMalloc(&ctx.zero_page, 256)); CK(hipMemset(ctx.zero_page, 0, 256));
-    ctx.wg_partial_bytes = (size_t)1 << 30; CK(hipMalloc(&ctx.wg_partial, ctx.wg_partial_bytes));
+    CK(ctx.wg_partial.reserve((size_t)1 << 28));      // 1 GiB of split-K partial tiles
     for (int cfg = 0; cfg < 2; ++cfg) {
         const int B = cfg == 0 ? 8 : 3, T = cfg == 0 ? 11000 : 1111, L = cfg == 0 ? 6 : 3;
         const int R = 256, G = 512, GH = 256, S = 256, C = 80;
