@@ -219,6 +219,28 @@ int wn_synthesize(wn_ctx* ctx, const float* c, int32_t B, int32_t Tc, const floa
 int wn_noise_per_step(const wn_ctx* ctx);
 /* The device noise stream of wn_synthesize(noise = NULL, seed): fills float [T, B, noise_per_step]. */
 int wn_fill_noise(wn_ctx* ctx, float* noise, int32_t B, int32_t T, uint64_t seed, void* stream);
+/* ---- sampling temperature: tempered noise for every head, path and slot ---------------------------------------------------------
+ * All samplers consume noise in a form where temperature is a change of the NOISE ENTRY, not of the sampler:
+ *   select   (Gumbel-max choice of a mixture component / a class)  argmax(logit_i - log(-log u_i))     u' = exp(-(-ln u)^tau)        (the Gumbel term x tau)
+ *   logistic (MoL: the draw of the chosen component)               mu + exp(ls) (log u - log(1 - u))   u' = 1 / (1 + exp(-tau logit u))  (the logit x tau)
+ *   normal   (Gaussian head)                                       mu + exp(ls) eps                    eps' = tau eps
+ * with u' clamped to the samplers' range [1e-5, 1 - 1e-5].  tau_scale applies to the logistic / normal draw, tau_select to the select entries
+ * (MoL: the first M of a sample's M + 1 entries; softmax: all Q; the Gaussian head has none).  Valid: finite, 0 <= tau <= 2, else WN_E_ARG.
+ * tau == 1 returns the entry untouched (bit-identical to the untempered run); tau == 0 is the deterministic decode: the arg-max component's
+ * mean clipped to [-1, 1] / the arg-max class (entries become the constants exp(-1), 0.5, 0).  For tau <= 1 the clamp never acts; for tau > 1 it
+ * TRUNCATES the tails (an entry that would leave the range is pulled back to its end), so the tails are lighter than tau asks for.
+ * The context's pair (default (1, 1) at wn_create) is HOST state read by wn_synthesize and by every wn_synth_stream_push at the time of the call:
+ * setting it ends no stream or session, and wn_pack_weights does not reset it.  Device noise (noise == NULL) is generated already tempered;
+ * caller noise with a pair other than (1, 1) is tempered into the context's noise buffer (reserved exactly as for device noise: an
+ * inference-only context keeps its pre-sized buffer and its WN_E_SHAPE) and the run reads that copy -- the caller's buffer is not written; with
+ * (1, 1) the caller's pointer is passed through as before.  wn_fill_noise stays UNTEMPERED: bit for bit,
+ *   wn_synthesize(noise = NULL, seed) at tau  ==  wn_synthesize(noise = wn_temper_noise(wn_fill_noise(seed), tau)) at (1, 1).
+ * No sampling kernel changes and the per-sample time is unchanged: the work is fused into the noise kernels that run once before a span. */
+int wn_synth_set_temperature(wn_ctx* ctx, float tau_scale, float tau_select);
+int wn_synth_get_temperature(const wn_ctx* ctx, float* tau_scale, float* tau_select);
+/* Temper a noise buffer: in / out device float [T, B, noise_per_step] of this context's head, in == out allowed; asynchronous on `stream`.
+ * Also the way to give wn_sample (the train-time log path) a temperature: temper the noise it is passed. */
+int wn_temper_noise(wn_ctx* ctx, const float* in, float* out, int32_t B, int32_t T, float tau_scale, float tau_select, void* stream);
 /* wn_synthesize enqueues and returns (no device synchronisation).  The persistent pipeline bounds every hand-off spin; if one times
  * out (a workgroup was not resident) the kernels leave early and raise a device flag.  wn_synth_check waits for the LAST
  * wn_synthesize of this context to finish and returns WN_E_HIP (+ wn_last_error) if that happened, WN_OK otherwise; the next
@@ -290,7 +312,9 @@ int wn_synth_stream_end(wn_ctx* ctx);
  * utterances are opened, fed, finished and replaced independently.  A slot's out_samples / out_raw depend only on the session's B and configuration,
  * the slot index and the slot's own frames, noise, teacher forcing and condition -- not on how the frames were cut into pushes, when the slot was
  * opened, what the other slots do or what occupied it before -- and are bit-identical to ONE wn_synthesize of the same B and steps_per_graph with the
- * utterance's frames in batch row = slot index and, for device noise, column b of the [T, B, nps] noise = wn_fill_noise(B = 1, T, seed_b).
+ * utterance's frames in batch row = slot index and, for device noise, column b of the [T, B, nps] noise = wn_fill_noise(B = 1, T, seed_b) tempered
+ * (wn_temper_noise) by slot b's pair -- the context's pair at wn_synth_slot_open, or what wn_synth_set_slot_temperature set since, push by push; caller
+ * noise is tempered column by column in the same way into the context's buffer.
  * Frames -> samples follow wn_synth_stream_lookahead per slot: a slot generates its frames [done, pushed - frames_right), all of them with final.
  * A push runs max_b n_out[b] steps; slots with nothing (more) to generate take part as dummy steps that write nothing (no queue row, no output
  * element, no abort).  Reopening a slot clears nothing: a tap before the utterance's own t = 0 is invalid per slot.
@@ -304,6 +328,9 @@ int wn_synth_slots_begin(wn_ctx* ctx, int32_t B, int32_t steps_per_graph, void* 
 /* The slot becomes live at its own t = 0 with the next push.  g: this utterance's global condition on the device -- one int32 speaker id
  * (use_speaker_embedding) or float [gin_channels]; NULL iff gin_channels <= 0.  seed: the slot's device noise (noise = NULL pushes). */
 int wn_synth_slot_open(wn_ctx* ctx, int32_t slot, uint64_t seed, const void* g, void* stream);
+/* Override the sampling temperature of a LIVE slot (wn_synth_slot_open copied the context's pair into it), from the next push on (host only).
+ * WN_E_STATE without a session or for an idle slot; WN_E_ARG for a slot outside the session or a temperature outside [0, 2]. */
+int wn_synth_set_slot_temperature(wn_ctx* ctx, int32_t slot, float tau_scale, float tau_select);
 /* c float [B, cin, Tn] (rows of idle slots ignored); frames[b] in [0, Tn] (host): the leading frames of row b appended to slot b; final_[b] != 0
  * (host): slot b's utterance ends with these frames and the slot is idle afterwards.  n_out[b] (host) = samples generated for slot b, known at
  * enqueue time.  out_samples [B, out_pitch] (float / int32 as wn_synthesize), optional out_raw [B, O, out_pitch], optional test_inputs
@@ -316,7 +343,7 @@ int wn_synth_slot_abandon(wn_ctx* ctx, int32_t slot);              /* drop a liv
 int wn_synth_slot_frames_done(const wn_ctx* ctx, int32_t slot);    /* frames generated so far, -1 idle; WN_E_ARG / WN_E_STATE */
 int wn_synth_slots_end(wn_ctx* ctx);
 
-/* Stand-alone samplers on [B,O,T] parameters (train-time log path, wavenet.py:302-325). */
+/* Stand-alone samplers on [B,O,T] parameters (train-time log path, wavenet.py:302-325).  Temperature: wn_temper_noise on `noise` first. */
 int wn_sample(wn_ctx* ctx, const float* y_hat, int32_t B, int32_t T, const float* noise /*[T,B,nps]*/,
               void* out /* float [B,T] or int32 [B,T] */, void* stream);
 
@@ -421,6 +448,13 @@ int wn_set_batch_parts(wn_ctx* ctx, int32_t parts);
  * (wn_layer_key / wn_drop_quad): out[i] = 1 if element first + i of the [rows][R] layer input is kept, else 0.  No context, no GPU:
  * pins the numpy mirror the parity tests hand to the oracle. */
 int wn_test_dropout_mask(uint64_t seed, int32_t layer, float p, int64_t first, int64_t n, uint8_t* out);
+/* wn_temper_noise evaluated ON THE HOST by the very function the noise kernels inline (csrc/wn_temper.h): in / out HOST float [rows, nps], in == out
+ * allowed; mode 0 MoL (nps - 1 select entries, then the logistic draw), 1 Gaussian, 2 softmax.  No context, no GPU.  WN_E_ARG: a temperature outside [0, 2]
+ * or not finite, nps < 1, a mode outside 0 ... 2, a null pointer. */
+int wn_test_temper_noise(int32_t mode, int32_t nps, const float* in, float* out, int64_t rows, float tau_scale, float tau_select);
+/* the fill of wn_synthesize(noise = NULL, seed) at a pair, alone: the device noise stream generated ALREADY TEMPERED into noise [T, B, noise_per_step]
+ * (16-byte aligned).  Equal, bit for bit, to wn_fill_noise followed by wn_temper_noise; tools/temperature_timing.py times it. */
+int wn_test_fill_noise_tempered(wn_ctx* ctx, float* noise, int32_t B, int32_t T, uint64_t seed, float tau_scale, float tau_select, void* stream);
 /* which launches of this context take the 8-phase kernel (csrc/wn_tile8p.h; WN_GEMM8P in the environment of wn_create -- an A/B switch,
  * default 0): bit 0 = the gate GEMM, bit 1 = d x.  A model that does not fit the kernel reports 0 whatever the switch says. */
 int wn_test_gemm8p_mask(const wn_ctx* ctx);

@@ -1,5 +1,6 @@
 // Host side of the C ABI: context, parameter table, workspace, dispatch.
 #include "wn_common.h"
+#include "wn_temper.h"
 #include <ctype.h>
 #include <dlfcn.h>
 #include <math.h>
@@ -450,10 +451,12 @@ extern "C" int wn_synthesize(wn_ctx* c, const float* cc, int32_t B, int32_t Tc, 
     c->strm.open = false; c->slots.open = false;            // (ends an open stream / slot session: its queues are overwritten)
     int rc = wn_pipe_check(c, false);                  // a hand-off timeout of the previous pipeline run surfaces here at the latest
     if (rc) return rc;
-    if (!noise) {                                      // device Philox stream keyed by `seed` (header)
+    const bool tempered = c->tau_scale != 1.0f || c->tau_select != 1.0f;
+    if (!noise || tempered) {                          // device Philox stream keyed by `seed` (header), generated already tempered; or the tempered copy of the caller's noise
         const int T = Tc * c->hop;
         if ((rc = wn_noise_reserve(c, B, T))) return rc;
-        if ((rc = wn_fill_noise_impl(c, c->noise_buf, B, T, seed, (hipStream_t)stream))) return rc;
+        if ((rc = noise ? wn_temper_noise_impl(c, noise, c->noise_buf, B, T, c->tau_scale, c->tau_select, (hipStream_t)stream)
+                        : wn_fill_noise_impl(c, c->noise_buf, B, T, seed, c->tau_scale, c->tau_select, (hipStream_t)stream))) return rc;
         noise = c->noise_buf;
     }
     return wn_synth_impl(c, cc, B, Tc, noise, seed, test_inputs, out_samples, out_raw, steps_per_graph, (hipStream_t)stream);
@@ -461,7 +464,46 @@ extern "C" int wn_synthesize(wn_ctx* c, const float* cc, int32_t B, int32_t Tc, 
 
 extern "C" int wn_fill_noise(wn_ctx* c, float* noise, int32_t B, int32_t T, uint64_t seed, void* stream) {
     if (!c || !noise || B <= 0 || T <= 0) return WN_E_ARG;
-    return wn_fill_noise_impl(c, noise, B, T, seed, (hipStream_t)stream);
+    return wn_fill_noise_impl(c, noise, B, T, seed, 1.0f, 1.0f, (hipStream_t)stream);      // untempered: the documented way to reproduce a device-noise run (wn_temper_noise)
+}
+
+// ---- sampling temperature (wn_temper.h): host state of the context / of a live slot; the noise kernels do the work
+static int tau_check(wn_ctx* c, const char* who, float tau_scale, float tau_select) {
+    if (!wn_tau_valid(tau_scale) || !wn_tau_valid(tau_select))
+        WN_FAIL(c, WN_E_ARG, "%s: temperatures (%g, %g) must be finite and in [0, 2]", who, (double)tau_scale, (double)tau_select);
+    return WN_OK;
+}
+extern "C" int wn_synth_set_temperature(wn_ctx* c, float tau_scale, float tau_select) {
+    if (!c) return WN_E_ARG;
+    int rc = tau_check(c, "wn_synth_set_temperature", tau_scale, tau_select);
+    if (rc) return rc;
+    c->tau_scale = tau_scale; c->tau_select = tau_select;
+    return WN_OK;
+}
+extern "C" int wn_synth_get_temperature(const wn_ctx* c, float* tau_scale, float* tau_select) {
+    if (!c || !tau_scale || !tau_select) return WN_E_ARG;
+    *tau_scale = c->tau_scale; *tau_select = c->tau_select;
+    return WN_OK;
+}
+extern "C" int wn_temper_noise(wn_ctx* c, const float* in, float* out, int32_t B, int32_t T, float tau_scale, float tau_select, void* stream) {
+    if (!c) return WN_E_ARG;
+    if (!in || !out || B <= 0 || T <= 0) WN_FAIL(c, WN_E_ARG, "wn_temper_noise: null buffer or B = %d, T = %d not positive", B, T);
+    int rc = tau_check(c, "wn_temper_noise", tau_scale, tau_select);
+    if (rc) return rc;
+    return wn_temper_noise_impl(c, in, out, B, T, tau_scale, tau_select, (hipStream_t)stream);
+}
+extern "C" int wn_test_fill_noise_tempered(wn_ctx* c, float* noise, int32_t B, int32_t T, uint64_t seed, float tau_scale, float tau_select, void* stream) {
+    if (!c || !noise || B <= 0 || T <= 0) return WN_E_ARG;
+    int rc = tau_check(c, "wn_test_fill_noise_tempered", tau_scale, tau_select);
+    if (rc) return rc;
+    return wn_fill_noise_impl(c, noise, B, T, seed, tau_scale, tau_select, (hipStream_t)stream);
+}
+// test hook: the same function on the host (no context, no GPU)
+extern "C" int wn_test_temper_noise(int32_t mode, int32_t nps, const float* in, float* out, int64_t rows, float tau_scale, float tau_select) {
+    if (!in || !out || rows < 0 || mode < 0 || mode > 2 || nps < 1 || !wn_tau_valid(tau_scale) || !wn_tau_valid(tau_select)) return WN_E_ARG;
+    for (int64_t r = 0; r < rows; ++r)
+        for (int q = 0; q < nps; ++q) out[r * nps + q] = wn_temper_entry(in[r * nps + q], mode, nps, q, tau_scale, tau_select);
+    return WN_OK;
 }
 extern "C" int wn_synth_check(wn_ctx* c) { if (!c) return WN_E_ARG; return wn_pipe_check(c, true); }
 extern "C" int wn_synth_last_path(const wn_ctx* c) { return c ? c->synth_path : WN_E_ARG; }
@@ -693,8 +735,11 @@ extern "C" int wn_synth_stream_push(wn_ctx* c, const float* cc, int32_t Tn, int3
         // artificial window edge touches out of the span (and a window edge at frame 0 / the final frame is the utterance's own edge)
         if ((rc = wn_upsample_fwd(c, nullptr, win, B, (int)w, st))) return rc;
         const int nps = wn_noise_per_step(c);
-        if (!noise) {      // the device stream of `seed` over the whole utterance, continued: elements [t0 B nps, (t0 + n) B nps)
-            if ((rc = wn_fill_noise_span(c, c->noise_buf, u.done * hop * B * nps, (int64_t)T * B * nps, S.seed, st))) return rc;
+        if (!noise) {      // the device stream of `seed` over the whole utterance, continued: elements [t0 B nps, (t0 + n) B nps), tempered by the context's pair as it is NOW
+            if ((rc = wn_fill_noise_span(c, c->noise_buf, u.done * hop * B * nps, (int64_t)T * B * nps, S.seed, c->tau_scale, c->tau_select, st))) return rc;
+            noise = c->noise_buf;
+        } else if (c->tau_scale != 1.0f || c->tau_select != 1.0f) {      // the run reads a tempered copy (T <= max_time: reserved at wn_synth_stream_begin); the caller's buffer is not written
+            if ((rc = wn_temper_noise_impl(c, noise, c->noise_buf, B, T, c->tau_scale, c->tau_select, st))) return rc;
             noise = c->noise_buf;
         }
         WnSpan sp;
@@ -775,7 +820,19 @@ extern "C" int wn_synth_slot_open(wn_ctx* c, int32_t slot, uint64_t seed, const 
     if (S.s[slot].live) WN_FAIL(c, WN_E_STATE, "wn_synth_slot_open: slot %d carries an utterance (finish it with a final push or wn_synth_slot_abandon)", slot);
     if (c->gin > 0 && (rc = wn_gbias_row(c, g, S.gbias, S.B, slot, (hipStream_t)stream))) return rc;
     auto& s = S.s[slot];
-    s = wn_ctx::WnSlots::Slot(); s.live = true; s.seed = seed;
+    s = wn_ctx::WnSlots::Slot(); s.live = true; s.seed = seed; s.tau_scale = c->tau_scale; s.tau_select = c->tau_select;
+    return WN_OK;
+}
+
+extern "C" int wn_synth_set_slot_temperature(wn_ctx* c, int32_t slot, float tau_scale, float tau_select) {
+    if (!c) return WN_E_ARG;
+    int rc = slots_usable(c, "wn_synth_set_slot_temperature");
+    if (rc) return rc;
+    auto& S = c->slots;
+    if (slot < 0 || slot >= S.B) WN_FAIL(c, WN_E_ARG, "wn_synth_set_slot_temperature: slot %d outside [0, %d)", slot, S.B);
+    if ((rc = tau_check(c, "wn_synth_set_slot_temperature", tau_scale, tau_select))) return rc;
+    if (!S.s[slot].live) WN_FAIL(c, WN_E_STATE, "wn_synth_set_slot_temperature: slot %d is idle (wn_synth_slot_open first)", slot);
+    S.s[slot].tau_scale = tau_scale; S.s[slot].tau_select = tau_select;      // host state: from the next push on
     return WN_OK;
 }
 
@@ -896,10 +953,15 @@ extern "C" int wn_synth_slots_push(wn_ctx* c, const float* cc, int32_t Tn, const
                                (int64_t)n_max, g);
             WN_LAUNCH_CHECK(c);
         }
+        float ts[32], tsel[32]; bool tempered = false;      // every slot's own pair; rows of slots that do not generate are ignored
+        for (int b = 0; b < B; ++b) { ts[b] = S.s[b].tau_scale; tsel[b] = S.s[b].tau_select; tempered |= nb[b] > 0 && (ts[b] != 1.0f || tsel[b] != 1.0f); }
         if (!noise) {      // every generating slot's own one-stream noise, continued at its sample done * hop
             uint64_t seed[32]; int64_t first[32], cnt[32]; const int nps = wn_noise_per_step(c);
             for (int b = 0; b < B; ++b) { seed[b] = S.s[b].seed; first[b] = S.s[b].u.done * hop * nps; cnt[b] = (int64_t)nb[b] * nps; }
-            if ((rc = wn_fill_noise_slots(c, c->noise_buf, B, seed, first, cnt, st))) return rc;
+            if ((rc = wn_fill_noise_slots(c, c->noise_buf, B, seed, first, cnt, ts, tsel, st))) return rc;
+            noise = c->noise_buf;
+        } else if (tempered) {      // a tempered copy, column by column (n_max <= max_time: reserved at wn_synth_slots_begin); the caller's buffer is not written
+            if ((rc = wn_temper_noise_cols(c, noise, c->noise_buf, B, n_max, ts, tsel, st))) return rc;
             noise = c->noise_buf;
         }
         int32_t st0[32], snl[32]; uint32_t fresh = 0;

@@ -196,7 +196,8 @@ struct wn_ctx {
     int nbuckets = 0, nbuckets_early = 0, nearly_live = 0; int bucket_lo[WN_MAX_BUCKETS + 2] = {}, bucket_hi[WN_MAX_BUCKETS + 2] = {};
     int64_t bucket_off[WN_MAX_BUCKETS + 2] = {}, bucket_cnt[WN_MAX_BUCKETS + 2] = {}; bool have_bwd = false;
     bool inference = false;               // cfg.inference_only: no training workspace, synthesis state pre-sized at wn_create
-    DevBuf<float> noise_buf;              // device-drawn sampling noise [T][B][nps] (wn_synthesize with noise == NULL)
+    DevBuf<float> noise_buf;              // device-drawn sampling noise [T][B][nps] (wn_synthesize with noise == NULL), or the tempered copy of the caller's
+    float tau_scale = 1.0f, tau_select = 1.0f;   // sampling temperature of wn_synthesize / stream pushes / newly opened slots (wn_synth_set_temperature; host state)
     int synth_path = 0;                   // 0 none, 1 graph, 2 pipeline, 3 fp32 graph (wn_synth_last_path)
     bool pipe_f16 = false;                // persistent pipeline: IEEE-half weights / hand-offs / queues instead of bf16 (WN_PIPE_DTYPE=fp16|bf16 at wn_create, wn_synth_pipe_dtype)
     int synth_instances = 0;              // pipeline instances the last wn_synthesize ran side by side (wn_synth_last_instances)
@@ -223,7 +224,7 @@ struct wn_ctx {
     // Everything the session needs is sized by slots_alloc (wn_create on inference-only contexts): nothing is allocated by a push.
     struct WnSlots {
         bool open = false, poisoned = false; int path = 0, B = 0, spg = 0, left = 0, right = 0, capw = 0; bool first_run = true;
-        struct Slot { bool live = false; uint64_t seed = 0; WnUtt u; } s[32];
+        struct Slot { bool live = false; uint64_t seed = 0; WnUtt u; float tau_scale = 1.0f, tau_select = 1.0f; } s[32];      // (the pair: copied from the context at wn_synth_slot_open)
         DevBuf<float> pend[2];                    // [32 regions][C * capw] pending frames of every slot (ping-pong per slot)
         DevBuf<float> gwin;                       // [group][C][w]: the windows of the slots upsampled together (equal window width)
         DevBuf<bf16_t> cbt;                       // [B][n_max][C]: the conditioning rows every slot's steps of this push read
@@ -301,9 +302,13 @@ int wn_synth_f32_span(wn_ctx* ctx, int B, int T, const WnSpan& sp, const float* 
                       int steps_per_graph, hipStream_t st);
 int wn_pipe_span(wn_ctx* ctx, int B, int T, const WnSpan& sp, const float* noise, const void* test_inputs, void* out_samples, float* out_raw,
                  hipStream_t st);
-int wn_fill_noise_span(wn_ctx* ctx, float* noise, int64_t first, int64_t n, uint64_t seed, hipStream_t st);   // elements [first, first + n) of the flat stream
+// (every fill takes the sampling temperature it fuses into its stores: wn_temper.h; (1, 1) stores the stream itself)
+int wn_fill_noise_span(wn_ctx* ctx, float* noise, int64_t first, int64_t n, uint64_t seed, float tau_scale, float tau_select, hipStream_t st);   // elements [first, first + n) of the flat stream
 // column b of noise [n_max][B][nps] = elements [first[b], first[b] + cnt[b]) of the ONE-stream noise of seed[b] (wn_fill_noise(B = 1)), every b with cnt[b] > 0 in one launch
-int wn_fill_noise_slots(wn_ctx* ctx, float* noise, int B, const uint64_t* seed, const int64_t* first, const int64_t* cnt, hipStream_t st);
+int wn_fill_noise_slots(wn_ctx* ctx, float* noise, int B, const uint64_t* seed, const int64_t* first, const int64_t* cnt, const float* tau_scale, const float* tau_select, hipStream_t st);
+// caller noise in [T][B][nps] tempered into out (in == out allowed): one pair, or column b by ITS pair (tau_scale[b], tau_select[b]), B <= 32
+int wn_temper_noise_impl(wn_ctx* ctx, const float* in, float* out, int B, int T, float tau_scale, float tau_select, hipStream_t st);
+int wn_temper_noise_cols(wn_ctx* ctx, const float* in, float* out, int B, int T, const float* tau_scale, const float* tau_select, hipStream_t st);
 int wn_gbias_row(wn_ctx* ctx, const void* g_dev, float* table, int B, int slot, hipStream_t st);      // one slot's gate-bias row into table [L][B][G]
 int wn_synth_f32_reserve(wn_ctx* ctx, int B);
 bool wn_pipe_eligible(const wn_ctx* ctx, int B);
@@ -311,7 +316,7 @@ int wn_pipe_reserve(wn_ctx* ctx, int B, int T);            // size every pipelin
 int wn_synth_reserve(wn_ctx* ctx);                        // state of the launch-per-layer graph path
 int wn_pipe_check(wn_ctx* ctx, bool wait);                // pending abort flag of the last pipeline run -> WN_E_HIP
 int wn_noise_reserve(wn_ctx* ctx, int B, int T);
-int wn_fill_noise_impl(wn_ctx* ctx, float* noise, int B, int T, uint64_t seed, hipStream_t st);
+int wn_fill_noise_impl(wn_ctx* ctx, float* noise, int B, int T, uint64_t seed, float tau_scale, float tau_select, hipStream_t st);
 extern "C" int wn_noise_per_step(const wn_ctx* c);
 int wn_upsample_fwd(wn_ctx* ctx, const float* params_unused, const float* c, int B, int Tc, hipStream_t st);
 int wn_weightnorm_apply(wn_ctx* ctx, const float* raw_params, hipStream_t st);     // raw (v, g, bias) -> params_dev (effective)

@@ -3,6 +3,7 @@
 // (util.py:30-129).
 #include "wn_common.h"
 #include "wn_mulaw_tables.h"
+#include "wn_temper.h"
 #include <math.h>
 #include <algorithm>
 
@@ -456,37 +457,51 @@ __device__ __forceinline__ void wn_noise_group(int64_t g, uint32_t k0, uint32_t 
         for (int j = 0; j < 4; ++j) v[j] = fminf(fmaxf(wn_u01(w[j]), 1e-5f), 1.0f - 1e-5f);     // exact ops only (no rounding: any compiler, and the numpy mirror, give the same bits)
     }
 }
-__global__ void wn_noise_kernel(float* __restrict__ out, int64_t n, uint32_t k0, uint32_t k1, int gaussian) {
+// Sampling temperature (wn_temper.h) is fused into the stores of the three fill kernels: `mode` (0 MoL, 1 Gaussian, 2 softmax) and the element's index
+// q inside its sample's nps entries name the kind of entry; with both temperatures 1 the stored value is the generated one, bit for bit.
+__global__ void wn_noise_kernel(float* __restrict__ out, int64_t n, uint32_t k0, uint32_t k1, int mode, int nps, float tau_scale, float tau_select) {
     const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g * 4 >= n) return;
     float v[4];
-    wn_noise_group(g, k0, k1, gaussian, v);
+    wn_noise_group(g, k0, k1, mode == 1, v);
+    if (tau_scale != 1.0f || tau_select != 1.0f) {
+        int q = (int)((g * 4) % nps);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { v[j] = wn_temper_entry(v[j], mode, nps, q, tau_scale, tau_select); if (++q == nps) q = 0; }
+    }
     if (g * 4 + 3 < n) *reinterpret_cast<float4*>(out + g * 4) = make_float4(v[0], v[1], v[2], v[3]);
     else for (int j = 0; j < 4 && g * 4 + j < n; ++j) out[g * 4 + j] = v[j];
 }
-int wn_fill_noise_impl(wn_ctx* c, float* noise, int B, int T, uint64_t seed, hipStream_t st) {
+int wn_fill_noise_impl(wn_ctx* c, float* noise, int B, int T, uint64_t seed, float tau_scale, float tau_select, hipStream_t st) {
     const int64_t n = (int64_t)B * T * wn_noise_per_step(c);
     if ((reinterpret_cast<uintptr_t>(noise) & 15) != 0) WN_FAIL(c, WN_E_ARG, "noise buffer must be 16-byte aligned");
-    const int gaussian = (c->cfg.input_type != WN_INPUT_MULAW_QUANTIZE && c->O == 2) ? 1 : 0;
-    hipLaunchKernelGGL(wn_noise_kernel, dim3(cdiv((n + 3) / 4, 256)), dim3(256), 0, st, noise, n, (uint32_t)seed, (uint32_t)(seed >> 32), gaussian);
+    hipLaunchKernelGGL(wn_noise_kernel, dim3(cdiv((n + 3) / 4, 256)), dim3(256), 0, st, noise, n, (uint32_t)seed, (uint32_t)(seed >> 32), wn_sample_mode(c), wn_noise_per_step(c),
+                       tau_scale, tau_select);
     WN_LAUNCH_CHECK(c);
     return WN_OK;
 }
 
 // elements [first, first + n) of the same stream into out[0 .. n): a streaming push starting at sample t0 starts at element t0 * B * nps, not
 // necessarily on a group boundary -- thread i evaluates group first / 4 + i whole (the same code as above) and keeps the elements in range
-__global__ void wn_noise_span_kernel(float* __restrict__ out, int64_t first, int64_t n, uint32_t k0, uint32_t k1, int gaussian) {
+__global__ void wn_noise_span_kernel(float* __restrict__ out, int64_t first, int64_t n, uint32_t k0, uint32_t k1, int mode, int nps, float tau_scale, float tau_select) {
     const int64_t g = first / 4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (g * 4 >= first + n) return;
     float v[4];
-    wn_noise_group(g, k0, k1, gaussian, v);
-    for (int j = 0; j < 4; ++j) { const int64_t e = g * 4 + j; if (e >= first && e < first + n) out[e - first] = v[j]; }
+    wn_noise_group(g, k0, k1, mode == 1, v);
+    const bool temper = tau_scale != 1.0f || tau_select != 1.0f;
+    int q = temper ? (int)((g * 4) % nps) : 0;      // (rows start at multiples of nps: the index inside a sample follows from the element index alone)
+    for (int j = 0; j < 4; ++j) {
+        const int64_t e = g * 4 + j;
+        float w = v[j];
+        if (temper) { w = wn_temper_entry(w, mode, nps, q, tau_scale, tau_select); if (++q == nps) q = 0; }
+        if (e >= first && e < first + n) out[e - first] = w;
+    }
 }
-int wn_fill_noise_span(wn_ctx* c, float* noise, int64_t first, int64_t n, uint64_t seed, hipStream_t st) {
+int wn_fill_noise_span(wn_ctx* c, float* noise, int64_t first, int64_t n, uint64_t seed, float tau_scale, float tau_select, hipStream_t st) {
     if (n <= 0) return WN_OK;
-    const int gaussian = (c->cfg.input_type != WN_INPUT_MULAW_QUANTIZE && c->O == 2) ? 1 : 0;
     const int64_t groups = (first + n + 3) / 4 - first / 4;
-    hipLaunchKernelGGL(wn_noise_span_kernel, dim3(cdiv(groups, 256)), dim3(256), 0, st, noise, first, n, (uint32_t)seed, (uint32_t)(seed >> 32), gaussian);
+    hipLaunchKernelGGL(wn_noise_span_kernel, dim3(cdiv(groups, 256)), dim3(256), 0, st, noise, first, n, (uint32_t)seed, (uint32_t)(seed >> 32), wn_sample_mode(c), wn_noise_per_step(c),
+                       tau_scale, tau_select);
     WN_LAUNCH_CHECK(c);
     return WN_OK;
 }
@@ -494,31 +509,72 @@ int wn_fill_noise_span(wn_ctx* c, float* noise, int64_t first, int64_t n, uint64
 // Slot sessions: every slot draws from ITS OWN one-stream noise (seed_b, element t_local * nps + j: exactly wn_fill_noise(B = 1, seed_b)), written into column b of
 // the push's [n_max][B][nps] buffer.  Thread (x, b) evaluates one whole Philox group of slot b's stream -- Box-Muller pairs follow the one-stream numbering, not
 // the batch layout -- and keeps the elements of the span [first_b, first_b + cnt_b).  Slots that generate nothing (cnt 0) leave their column as it is.
-struct WnNoiseSlots { uint32_t k0[32], k1[32]; int64_t first[32], cnt[32]; };
-__global__ void wn_noise_slots_kernel(float* __restrict__ out, int B, int nps, int gaussian, WnNoiseSlots p) {
+// Every slot's entries are tempered by the slot's own pair.
+struct WnNoiseSlots { uint32_t k0[32], k1[32]; int64_t first[32], cnt[32]; float tau_scale[32], tau_select[32]; };
+__global__ void wn_noise_slots_kernel(float* __restrict__ out, int B, int nps, int mode, WnNoiseSlots p) {
     const int b = blockIdx.y;
     const int64_t first = p.first[b], n = p.cnt[b];
     const int64_t g = first / 4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (n <= 0 || g * 4 >= first + n) return;
     float v[4];
-    wn_noise_group(g, p.k0[b], p.k1[b], gaussian, v);
+    wn_noise_group(g, p.k0[b], p.k1[b], mode == 1, v);
+    const float ts = p.tau_scale[b], tsel = p.tau_select[b];
     for (int j = 0; j < 4; ++j) {
         const int64_t e = g * 4 + j;
         if (e < first || e >= first + n) continue;
         const int64_t le = e - first, tl = le / nps, q = le - tl * nps;      // (first is a multiple of nps: a span starts on a sample)
-        out[(tl * B + b) * nps + q] = v[j];
+        out[(tl * B + b) * nps + q] = wn_temper_entry(v[j], mode, nps, (int)q, ts, tsel);
     }
 }
-int wn_fill_noise_slots(wn_ctx* c, float* noise, int B, const uint64_t* seed, const int64_t* first, const int64_t* cnt, hipStream_t st) {
+int wn_fill_noise_slots(wn_ctx* c, float* noise, int B, const uint64_t* seed, const int64_t* first, const int64_t* cnt, const float* tau_scale, const float* tau_select, hipStream_t st) {
     WnNoiseSlots p; memset(&p, 0, sizeof p);
     int64_t groups = 0;
     for (int b = 0; b < B; ++b) {
-        p.k0[b] = (uint32_t)seed[b]; p.k1[b] = (uint32_t)(seed[b] >> 32); p.first[b] = first[b]; p.cnt[b] = cnt[b];
+        p.k0[b] = (uint32_t)seed[b]; p.k1[b] = (uint32_t)(seed[b] >> 32); p.first[b] = first[b]; p.cnt[b] = cnt[b]; p.tau_scale[b] = tau_scale[b]; p.tau_select[b] = tau_select[b];
         if (cnt[b] > 0) groups = std::max<int64_t>(groups, (first[b] + cnt[b] + 3) / 4 - first[b] / 4);
     }
     if (groups == 0) return WN_OK;
-    const int gaussian = (c->cfg.input_type != WN_INPUT_MULAW_QUANTIZE && c->O == 2) ? 1 : 0;
-    hipLaunchKernelGGL(wn_noise_slots_kernel, dim3(cdiv(groups, 256), B), dim3(256), 0, st, noise, B, wn_noise_per_step(c), gaussian, p);
+    hipLaunchKernelGGL(wn_noise_slots_kernel, dim3(cdiv(groups, 256), B), dim3(256), 0, st, noise, B, wn_noise_per_step(c), wn_sample_mode(c), p);
     WN_LAUNCH_CHECK(c);
     return WN_OK;
+}
+
+// Temper a caller's noise buffer (wn_temper_noise; caller noise of a run at a pair other than (1, 1)): in [T][B][nps] -> out, in == out allowed (a thread
+// reads its elements before it writes them).  Four elements per thread and one 16-byte access each way, as wn_noise_kernel, when both buffers are
+// 16-byte aligned (VEC); else element by element.  percol: column b = (element / nps) % B takes ITS pair (the slots of a session), else pair 0.
+struct WnTauCols { float tau_scale[32], tau_select[32]; };
+template <bool VEC>
+__global__ void wn_temper_kernel(const float* in, float* out, int64_t n, int mode, int nps, int B, int percol, WnTauCols p) {
+    const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g * 4 >= n) return;
+    const int cnt = g * 4 + 3 < n ? 4 : (int)(n - g * 4);
+    float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (VEC && cnt == 4) { const float4 f = *reinterpret_cast<const float4*>(in + g * 4); v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w; }
+    else for (int j = 0; j < cnt; ++j) v[j] = in[g * 4 + j];
+    const int64_t s0 = (g * 4) / nps;
+    int q = (int)(g * 4 - s0 * nps), col = percol ? (int)(s0 % B) : 0;
+    for (int j = 0; j < cnt; ++j) {
+        v[j] = wn_temper_entry(v[j], mode, nps, q, p.tau_scale[col], p.tau_select[col]);
+        if (++q == nps) { q = 0; if (percol && ++col == B) col = 0; }
+    }
+    if (VEC && cnt == 4) *reinterpret_cast<float4*>(out + g * 4) = make_float4(v[0], v[1], v[2], v[3]);
+    else for (int j = 0; j < cnt; ++j) out[g * 4 + j] = v[j];
+}
+static int temper_launch(wn_ctx* c, const float* in, float* out, int64_t n, int B, int percol, const WnTauCols& p, hipStream_t st) {
+    if (n <= 0) return WN_OK;
+    const bool vec = ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
+    if (vec) hipLaunchKernelGGL(wn_temper_kernel<true>, dim3(cdiv((n + 3) / 4, 256)), dim3(256), 0, st, in, out, n, wn_sample_mode(c), wn_noise_per_step(c), B, percol, p);
+    else hipLaunchKernelGGL(wn_temper_kernel<false>, dim3(cdiv((n + 3) / 4, 256)), dim3(256), 0, st, in, out, n, wn_sample_mode(c), wn_noise_per_step(c), B, percol, p);
+    WN_LAUNCH_CHECK(c);
+    return WN_OK;
+}
+int wn_temper_noise_impl(wn_ctx* c, const float* in, float* out, int B, int T, float tau_scale, float tau_select, hipStream_t st) {
+    WnTauCols p; memset(&p, 0, sizeof p);
+    p.tau_scale[0] = tau_scale; p.tau_select[0] = tau_select;
+    return temper_launch(c, in, out, (int64_t)B * T * wn_noise_per_step(c), B, 0, p, st);
+}
+int wn_temper_noise_cols(wn_ctx* c, const float* in, float* out, int B, int T, const float* tau_scale, const float* tau_select, hipStream_t st) {
+    WnTauCols p; memset(&p, 0, sizeof p);
+    for (int b = 0; b < B && b < 32; ++b) { p.tau_scale[b] = tau_scale[b]; p.tau_select[b] = tau_select[b]; }
+    return temper_launch(c, in, out, (int64_t)B * T * wn_noise_per_step(c), B, 1, p, st);
 }

@@ -81,6 +81,9 @@ TACOTRON_ONLY = dict(
 MI355 = dict(
     mi355_synthesis_chunk_frames=0,    # > 0: WaveNet.incremental (and so synthesize.py) generates through a stream, pushing this many mel frames at a
                                        # time (same samples, bit for bit); 0: one call for the whole utterance
+    mi355_synthesis_temperature=1.0,   # sampling temperature of synthesis, in [0, 2]: scales the logistic / normal draw of the scalar heads, the class choice of the
+                                       # softmax head; 0.6 ... 0.9 lowers the noise floor of a sampled vocoder, 0 is the deterministic decode (WaveNet.incremental(temperature=))
+    mi355_synthesis_mixture_temperature=1.0,   # mixture-of-logistics head only: temperature of the component choice, in [0, 2] (0: the arg-max component)
     mi355_synthesis_slots=0,           # N > 0: Synthesizer.synthesize sends all utterances of a call through ONE slot session of min(N, 32) slots (continuous
                                        # batching: no padding to the longest utterance; tick = mi355_synthesis_chunk_frames or 8 frames); 0: padded batches
     mi355_steps_per_graph=0,       # synthesis path: 0 = the persistent dataflow pipeline (real time at 22.05 kHz) whenever the model fits it, else the

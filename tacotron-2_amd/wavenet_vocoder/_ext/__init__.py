@@ -106,6 +106,12 @@ def load_library():
         'wn_synthesize': (ctypes.c_int, [vp, vp, i32, i32, vp, u64, vp, vp, vp, i32, vp]),
         'wn_noise_per_step': (ctypes.c_int, [vp]),
         'wn_fill_noise': (ctypes.c_int, [vp, vp, i32, i32, u64, vp]),
+        'wn_synth_set_temperature': (ctypes.c_int, [vp, f32, f32]),
+        'wn_synth_get_temperature': (ctypes.c_int, [vp, ctypes.POINTER(f32), ctypes.POINTER(f32)]),
+        'wn_synth_set_slot_temperature': (ctypes.c_int, [vp, i32, f32, f32]),
+        'wn_temper_noise': (ctypes.c_int, [vp, vp, vp, i32, i32, f32, f32, vp]),
+        'wn_test_temper_noise': (ctypes.c_int, [i32, i32, vp, vp, i64, f32, f32]),
+        'wn_test_fill_noise_tempered': (ctypes.c_int, [vp, vp, i32, i32, u64, f32, f32, vp]),
         'wn_synth_check': (ctypes.c_int, [vp]),
         'wn_synth_last_path': (ctypes.c_int, [vp]),
         'wn_test_gemm8p_mask': (ctypes.c_int, [vp]),
@@ -449,6 +455,45 @@ class Engine:
         self._ok(self.lib.wn_fill_noise(self.h, _ptr(noise), int(B), int(T), ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), _stream()))
         return noise
 
+    # ---- sampling temperature (wn_synth_set_temperature ...): a pair (tau_scale: the logistic / normal draw, tau_select: the Gumbel choices)
+    def set_temperature(self, tau_scale=1.0, tau_select=1.0):
+        """Sampling temperature of the next synthesize() / stream pushes / slots opened from now on (host state; (1, 1) at creation; each in
+        [0, 2]; 0: the deterministic decode).  Ends no stream or session."""
+        self._ok(self.lib.wn_synth_set_temperature(self.h, float(tau_scale), float(tau_select)))
+
+    @property
+    def temperature(self):
+        """(tau_scale, tau_select) of the context."""
+        a, b = ctypes.c_float(), ctypes.c_float()
+        self._ok(self.lib.wn_synth_get_temperature(self.h, ctypes.byref(a), ctypes.byref(b)))
+        return float(a.value), float(b.value)
+
+    def slot_temperature(self, slot, tau_scale=1.0, tau_select=1.0):
+        """Override the pair of a LIVE slot (slot_open copied the context's), from the next push on."""
+        self._ok(self.lib.wn_synth_set_slot_temperature(self.h, int(slot), float(tau_scale), float(tau_select)))
+
+    def temper_noise(self, noise, tau_scale=1.0, tau_select=1.0, out=None):
+        """noise float32 [T, B, noise_per_step] tempered into `out` (None: a new tensor; `noise` itself: in place).  fill_noise + temper_noise
+        reproduce a device-noise run at a temperature with an explicit buffer at (1, 1), bit for bit."""
+        import torch
+        _check(noise, torch.float32, 'noise')
+        if noise.dim() != 3 or int(noise.shape[2]) != self.noise_per_step:
+            raise ValueError('temper_noise: noise must be [T, B, noise_per_step=%d] (got %s)' % (self.noise_per_step, tuple(noise.shape)))
+        if out is None:
+            out = torch.empty_like(noise)
+        _check(out, torch.float32, 'out')
+        if tuple(out.shape) != tuple(noise.shape):
+            raise ValueError('temper_noise: out must have the shape of noise')
+        self._ok(self.lib.wn_temper_noise(self.h, _ptr(noise), _ptr(out), int(noise.shape[1]), int(noise.shape[0]), float(tau_scale), float(tau_select), _stream()))
+        return out
+
+    def fill_noise_tempered(self, noise, B, T, seed, tau_scale, tau_select):
+        """Test hook: the fill synthesize(noise=None, seed) runs at a pair, alone (== fill_noise + temper_noise, bit for bit)."""
+        import torch
+        _check(noise, torch.float32, 'noise')
+        self._ok(self.lib.wn_test_fill_noise_tempered(self.h, _ptr(noise), int(B), int(T), ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), float(tau_scale), float(tau_select), _stream()))
+        return noise
+
     def synth_check(self):
         """Wait for the last synthesize of this engine and raise if the pipeline gave up on a hand-off."""
         self._ok(self.lib.wn_synth_check(self.h))
@@ -573,6 +618,20 @@ def stream_lookahead(cfg):
     if rc != 0:
         raise WnError(rc, 'wn_synth_stream_lookahead: bad configuration')
     return int(left.value), int(right.value)
+
+
+def temper_noise_host(mode, noise, tau_scale=1.0, tau_select=1.0):
+    """wn_test_temper_noise: the device's tempering function evaluated on the host (no context, no GPU).  noise: float32 numpy [rows, nps];
+    mode 0 MoL (nps - 1 select entries + the logistic draw), 1 Gaussian, 2 softmax.  Returns a new array."""
+    a = np.ascontiguousarray(noise, dtype=np.float32)
+    if a.ndim != 2:
+        raise ValueError('temper_noise_host: noise must be [rows, nps]')
+    out = np.empty_like(a)
+    rc = load_library().wn_test_temper_noise(int(mode), int(a.shape[1]), a.ctypes.data_as(ctypes.c_void_p), out.ctypes.data_as(ctypes.c_void_p),
+                                             ctypes.c_int64(a.shape[0]), float(tau_scale), float(tau_select))
+    if rc != 0:
+        raise WnError(rc, 'wn_test_temper_noise(mode=%r, nps=%d, tau=(%r, %r))' % (mode, a.shape[1] if a.ndim == 2 else -1, tau_scale, tau_select))
+    return out
 
 
 def learning_rate(schedule, init_lr, step, decay_rate=0.5, decay_steps=200000, warmup=4000.0):

@@ -43,12 +43,29 @@ def validation_summary(rows, quantized):
     return {'loss': validation_loss(tot[0], tot[1], tot[2], quantized), 'sum': tot[0], 'count': tot[1], 'nonzero': tot[2], 'utterances': utts}
 
 
+def temperature_pair(hparams, temperature=None, mixture_temperature=None):
+    """(tau_scale, tau_select) of the engine for this model's head.  ``temperature`` scales the logistic / normal draw of the scalar heads and
+    is the class-choice temperature of the softmax head (which has no other noise); ``mixture_temperature`` is the mixture-of-logistics head's
+    component-choice temperature and a ValueError with any other head.  None: the hparams value (mi355_synthesis_temperature /
+    mi355_synthesis_mixture_temperature, default 1.0).  Each in [0, 2]; 0 is the deterministic decode (the engine validates the range)."""
+    t = float(getattr(hparams, 'mi355_synthesis_temperature', 1.0) if temperature is None else temperature)
+    mt = float(getattr(hparams, 'mi355_synthesis_mixture_temperature', 1.0) if mixture_temperature is None else mixture_temperature)
+    softmax = is_mulaw_quantize(hparams.input_type)
+    if softmax or int(hparams.out_channels) == 2:
+        if mixture_temperature is not None or mt != 1.0:
+            raise ValueError('mixture_temperature applies to the mixture-of-logistics head only (this model has the {} head)'.format(
+                'softmax' if softmax else 'Gaussian'))
+        return (1.0, t) if softmax else (t, 1.0)
+    return (t, mt)
+
+
 class SynthesisStream(object):
     """Generation of B utterances chunk by chunk as their mel frames arrive (WaveNet.stream): the samples are bit-identical to one
     WaveNet.incremental-style run over the concatenated frames with the same seed.  push() returns the samples whose conditioning is now
     complete, as a device tensor [B, n] (asynchronous: nothing waits for the GPU)."""
 
-    def __init__(self, model, batch, g=None, seed=0, steps_per_graph=0):
+    def __init__(self, model, batch, g=None, seed=0, steps_per_graph=0, temperature=None):
+        """temperature: the engine's pair (tau_scale, tau_select) for this stream's pushes (temperature_pair); None: the engine's pair as it is."""
         self.model, self.B = model, int(batch)
         self.lookahead = model.engine.stream_lookahead()
         self.done = self.pushed = 0
@@ -56,6 +73,8 @@ class SynthesisStream(object):
         model._ensure_packed()
         if model.global_conditioning_enabled():
             model._set_global(g, self.B)
+        if temperature is not None:
+            model.engine.set_temperature(*temperature)
         model.engine.stream_begin(self.B, seed=seed, steps_per_graph=steps_per_graph)
         self.closed = False
 
@@ -140,10 +159,12 @@ class SlotSession(object):
         model.engine.slots_begin(self.B, steps_per_graph=steps_per_graph)
         self.closed = False
 
-    def open(self, slot, g=None, seed=None):
+    def open(self, slot, g=None, seed=None, temperature=None, mixture_temperature=None):
         """Start an utterance in an idle slot (live with the next push).  g: its speaker id (int) or feature vector [gin_channels] when the model
-        has global conditioning.  seed None: derived as incremental() derives it."""
+        has global conditioning.  seed None: derived as incremental() derives it.  temperature / mixture_temperature: this utterance's sampling
+        temperature (temperature_pair; None: the hparams values)."""
         m, hp = self.model, self.model._hparams
+        pair = temperature_pair(hp, temperature, mixture_temperature)
         if seed is None:
             m._synth_calls = getattr(m, '_synth_calls', 0) + 1
             seed = ((int(hp.wavenet_random_seed) << 20) + m._synth_calls) * 64 + int(slot)
@@ -156,6 +177,7 @@ class SlotSession(object):
             else:
                 gd = torch.as_tensor(g, dtype=torch.float32).reshape(hp.gin_channels).to(m.device)
         m.engine.slot_open(slot, seed=seed, g=gd)
+        m.engine.slot_temperature(slot, *pair)
         self.done[slot], self.pushed[slot] = 0, 0
 
     def push(self, items, return_raw=False):
@@ -314,7 +336,8 @@ class WaveNet(object):
             c0 = c[idx:idx + 1, :, :length // hop].contiguous()
             ti = None if hp.wavenet_natural_eval else y0.reshape(1, -1).contiguous()
             g0 = None if g is None else torch.as_tensor(g)[idx:idx + 1]
-            out, raw = self.incremental(None, c=c0, g=g0, time_length=length, test_inputs=ti, return_raw=True, check=True)
+            out, raw = self.incremental(None, c=c0, g=g0, time_length=length, test_inputs=ti, return_raw=True, check=True,      # (evaluation samples at the model's own scale)
+                                        temperature=1.0, mixture_temperature=None if (not self.scalar_input or hp.out_channels == 2) else 1.0)
             tgt = y0.reshape(1, -1)
             ln = torch.tensor([length], dtype=torch.int32, device=raw.device)
             self.engine.loss(raw, tgt.contiguous(), ln, 0, self._loss_dev)          # no shift: wavenet.py:497-506
@@ -455,21 +478,26 @@ class WaveNet(object):
         return validation_summary(host, is_mulaw_quantize(self._hparams.input_type))
 
     def incremental(self, initial_input, c=None, g=None, time_length=100, test_inputs=None, softmax=True, quantize=True,
-                    log_scale_min=-7.0, log_scale_min_gauss=-7.0, noise=None, return_raw=False, check=False, chunk_frames=0):
+                    log_scale_min=-7.0, log_scale_min_gauss=-7.0, noise=None, return_raw=False, check=False, chunk_frames=0,
+                    temperature=None, mixture_temperature=None):
         """Fast-WaveNet generation with ring-buffer queues: c [B,cin,Tc] -> samples [B,T] (wavenet.py:724-911).
         ``initial_input`` is accepted for signature parity; generation always starts from the reference's silence
         frame (wavenet.py:433-445).  ``noise`` [T,B,noise_per_step] may be supplied for reproducible draws.
         ``check``: wait for the generation and verify it; if the persistent pipeline gave up on a hand-off (a workgroup was not
         resident -- the reference's loop cannot fail this way) the batch is re-run ONCE on the launch-per-layer graph path.
         ``chunk_frames`` > 0: every group goes through a stream (wn_synth_stream_push) fed this many mel frames at a time -- the same samples,
-        bit for bit (same seed and stream grouping), as the one call per group of chunk_frames = 0."""
+        bit for bit (same seed and stream grouping), as the one call per group of chunk_frames = 0.
+        ``temperature`` / ``mixture_temperature``: sampling temperature (temperature_pair; None: the hparams values), for device noise and for
+        ``noise`` alike; the fallback re-runs keep it."""
         hp = self._hparams
+        pair = temperature_pair(hp, temperature, mixture_temperature)
         B, Tc = int(c.shape[0]), int(c.shape[-1])
         hop = audio.get_hop_size(hp)
         T = Tc * hop
         if self.engine is None:
             self.build(B, T)
         self._ensure_packed()
+        self.engine.set_temperature(*pair)                 # host state of the engine: every run below, the re-runs included, reads it
         dev = c.device
         # noise None: drawn on the device (Philox keyed by (wavenet_random_seed, call counter)): U(1e-5, 1 - 1e-5) as mixture.py:91,104,
         # standard normal for the Gaussian head (gaussian.py:50), Gumbel uniforms for tf.multinomial (wavenet.py:865)
@@ -570,9 +598,10 @@ class WaveNet(object):
             else:
                 log('WaveNet synthesis: {} -- re-running this batch on the launch-per-layer graph path'.format(e))
                 group = attempt(32)
-        if getattr(self, '_logged_synth_path', None) != self.engine.synth_path:
-            self._logged_synth_path = self.engine.synth_path
-            log('WaveNet synthesis path: {} ({} streams per run)'.format(self.engine.synth_path, group))
+        if getattr(self, '_logged_synth_path', None) != (self.engine.synth_path, pair):
+            self._logged_synth_path = (self.engine.synth_path, pair)
+            log('WaveNet synthesis path: {} ({} streams per run{})'.format(
+                self.engine.synth_path, group, '' if pair == (1.0, 1.0) else '; sampling temperature {:g}, choice temperature {:g}'.format(*pair)))
         self.upsampled_local_features = feats
         return (out, raw) if return_raw else out
 
@@ -585,17 +614,18 @@ class WaveNet(object):
         spg = int(getattr(hp, 'mi355_steps_per_graph', 0)) if steps_per_graph is None else int(steps_per_graph)
         return SlotSession(self, batch, steps_per_graph=spg)
 
-    def stream(self, batch, g=None, seed=None, steps_per_graph=None):
+    def stream(self, batch, g=None, seed=None, steps_per_graph=None, temperature=None, mixture_temperature=None):
         """Open a SynthesisStream of `batch` utterances (<= 32, the model's engine must have been built for them).  seed None: derived as
-        incremental() derives it."""
+        incremental() derives it.  temperature / mixture_temperature: as incremental()."""
         hp = self._hparams
+        pair = temperature_pair(hp, temperature, mixture_temperature)
         if self.engine is None:
             self.build(batch, audio.get_hop_size(hp) * 64, inference_only=True)
         if seed is None:
             self._synth_calls = getattr(self, '_synth_calls', 0) + 1
             seed = ((int(hp.wavenet_random_seed) << 20) + self._synth_calls) * 64
         spg = int(getattr(hp, 'mi355_steps_per_graph', 0)) if steps_per_graph is None else int(steps_per_graph)
-        return SynthesisStream(self, batch, g=g, seed=seed, steps_per_graph=spg)
+        return SynthesisStream(self, batch, g=g, seed=seed, steps_per_graph=spg, temperature=pair)
 
     # ------------------------------------------------------------------ checkpoint state
     def state_dict(self):

@@ -105,7 +105,7 @@ class Synthesizer(object):
         """mi355_synthesis_slots > 0: all utterances of the call through ONE slot session (WaveNet.slots): no utterance is padded to the longest of its
         batch, a slot that finishes takes the next utterance at the next push.  Seeds derive from (wavenet_random_seed, the model's synthesis-call
         counter, utterance index), so two fresh runs of the same inputs agree, whatever the tick."""
-        from wavenet_vocoder.models.wavenet import slot_plan
+        from wavenet_vocoder.models.wavenet import slot_plan, temperature_pair
         from wavenet_vocoder import util as wutil
         from wavenet_vocoder.util import is_mulaw, is_mulaw_quantize
         hparams, hop = self._hparams, get_hop_size(self._hparams)
@@ -120,6 +120,10 @@ class Synthesizer(object):
         m._synth_calls = getattr(m, '_synth_calls', 0) + 1
         base = ((int(hparams.wavenet_random_seed) << 20) + m._synth_calls) << 20
         sess = m.slots(B)
+        pair = temperature_pair(hparams)                  # every utterance is opened at the hparams temperature (SlotSession.open)
+        if pair != (1.0, 1.0) and getattr(self, '_logged_temperature', None) != pair:
+            self._logged_temperature = pair
+            log('WaveNet synthesis slots: sampling temperature {:g}, choice temperature {:g}'.format(*pair))
         chunks = [[] for _ in lengths]
         feats = [[] for _ in lengths]
         owner, sent = [None] * B, [0] * len(lengths)
