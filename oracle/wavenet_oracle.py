@@ -329,7 +329,8 @@ def global_features(params, cfg, g):
         return None
     if cfg.use_speaker_embedding:
         return params['gc_embedding'][torch.as_tensor(g).long().reshape(-1)]
-    return torch.as_tensor(g).float().reshape(-1, cfg.gin_channels)
+    g = torch.as_tensor(g)
+    return (g if g.dtype == torch.float64 else g.float()).reshape(-1, cfg.gin_channels)      # (float64 features stay float64: the fp64 runs of step)
 
 
 def _conv1x1(x, K, b):
