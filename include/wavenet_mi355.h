@@ -343,6 +343,59 @@ int wn_synth_slot_abandon(wn_ctx* ctx, int32_t slot);              /* drop a liv
 int wn_synth_slot_frames_done(const wn_ctx* ctx, int32_t slot);    /* frames generated so far, -1 idle; WN_E_ARG / WN_E_STATE */
 int wn_synth_slots_end(wn_ctx* ctx);
 
+/* ---- folded synthesis: ONE utterance generated as overlapping segments that run side by side (WaveRNN's fold_with_overlap / xfade_and_unfold) ----
+ * Streams and slots spend the width of a run on more utterances; a folded run spends it on one.  The utterances are cut into rows; row r generates
+ * the mel frames [first, first + frames) of utterance `utt` from a cold start (silence, zero queues, its own t = 0) as one row of ONE slot-form span.
+ * Its samples before frame `keep` are warm-up and are discarded; over the frames [keep, keep + fade) it fades in against the fade-out of the previous
+ * row of the same utterance; from keep + fade on it is the output until the next row's fade begins.  A row is NOT the continuation of its predecessor:
+ * the waveform differs from the one-shot run's after the first seam (how audible a seam is depends on the model; nothing here smooths beyond the fade).
+ * Rules a plan obeys (wn_fold_check; wn_fold_plan's output does): rows are sorted by utterance, every utterance 0 ... U - 1 has at least one;
+ * 0 <= first <= keep, fade >= 0, keep + fade <= first + frames <= the utterance's frames, frames >= 1; the first row of an utterance has first = keep =
+ * fade = 0, its last row ends at the utterance's last frame; consecutive rows r, r + 1 of an utterance: keep[r+1] + fade[r+1] == first[r] + frames[r]
+ * and keep[r+1] >= keep[r] + fade[r]. */
+typedef struct wn_fold_row { int32_t utt, first, frames, keep, fade; } wn_fold_row;   /* all in mel frames of utterance `utt` */
+/* Planner (host only: no context, no GPU; deterministic).  Every utterance gets one row; the remaining rows, up to rows_max <= 32, go one at a time to
+ * the utterance whose rows are currently longest (frames / rows; ties: the lowest index), until another row would leave it fewer than min_keep new
+ * frames per row -- an utterance shorter than 2 * min_keep stays one row, so a folded run of it is the one-shot run.  An utterance of F frames in k rows
+ * has the boundaries a_j = floor(j F / k); row j has keep = a_j, first = max(0, a_j - warm), fade = min(fade, a_{j+1} - a_j) for j > 0 and ends at
+ * a_{j+1} + fade of row j + 1 (F for the last).  Returns the number of rows written to rows[0 .. cap), WN_E_ARG (null pointer, U < 1, a length < 1,
+ * warm / fade < 0, min_keep < 1) or WN_E_SHAPE (rows_max outside [U, 32], cap too small). */
+int wn_fold_plan(const int32_t* utt_frames, int32_t U, int32_t rows_max, int32_t warm, int32_t fade, int32_t min_keep, wn_fold_row* rows, int32_t cap);
+/* The rules above on a caller's plan (host only).  WN_OK, or WN_E_ARG with a message naming the row in msg[0 .. cap) (msg may be NULL). */
+int wn_fold_check(const int32_t* utt_frames, int32_t U, const wn_fold_row* rows, int32_t n_rows, char* msg, int32_t cap);
+/* One call, asynchronous on `stream`, never synchronises.  c float [U, cin, F_max], F_max = max_u utt_frames[u] (utterance u: its leading utt_frames[u] frames), utt_frames
+ * and rows HOST arrays (free when the call returns), rows validated by wn_fold_check (WN_E_ARG naming the row).  With n_max = max_r frames[r] * hop it enqueues
+ *   (a) the upsample net ONCE over the whole utterances (utterances of equal length as one batch): a row reads exactly the conditioning rows the one-shot
+ *       run reads, whatever the lookahead of 'SubPixel' / 'Resize';
+ *   (b) the fold: rows [first * hop, (first + frames) * hop) of each row's utterance into the session table [n_rows][n_max][cin] (and test_inputs likewise);
+ *   (c) the gate-bias row of each row's utterance; g: device, U int32 speaker ids (use_speaker_embedding) or float [U, gin_channels]; NULL iff gin_channels <= 0;
+ *   (d) noise [n_max, n_rows, noise_per_step] or NULL: column r = the one-stream device noise of seed + r (wn_fill_noise(B = 1, seed + r)); either is
+ *       tempered by the context's pair;
+ *   (e) ONE span in the slot form (every row from its own t = 0, frames[r] * hop samples, dummy steps behind) on the path wn_synthesize(steps_per_graph) would
+ *       take for n_rows streams: row r is bit-identical to row r of ONE wn_synthesize(B = n_rows) whose row r holds these conditioning rows;
+ *   (f) the unfold: out_wav float [U, wav_pitch], wav_pitch >= max_u utt_frames[u] * hop: the DECODED waveform in [-1, 1] (wn_inv_mulaw / wn_inv_mulaw_quantize
+ *       of the model-domain samples; identity for 'raw'), fl(fl(a * w_out[i]) + fl(b * w_in[i])) inside a fade of n = fade * hop samples (a: the previous row,
+ *       b: this one) and the row's decoded sample elsewhere; elements beyond an utterance's length keep the caller's bytes.  fade_kind 0, equal power:
+ *       w_in[i] = sin(pi / 2 * (i + 0.5) / n), w_out[i] = cos(pi / 2 * (i + 0.5) / n); 1, linear: w_in[i] = (i + 0.5) / n, w_out[i] = 1 - w_in[i] -- float32
+ *       tables computed on the host in double.  No atomics, a fixed order: two runs agree bit for bit.
+ * test_inputs optional [U, wav_pitch] teacher forcing in the MODEL domain (float / int32 ids as wn_synthesize); out_rows optional [n_rows, row_pitch] model-domain
+ * samples of every row, out_raw optional float [n_rows, out_channels, row_pitch], row_pitch >= n_max when either is given (elements beyond a row's samples keep
+ * the caller's bytes).  Without out_rows the rows live in context scratch of max_batch x max_time elements, as the gathered test_inputs do: n_rows x row_pitch
+ * must fit it then.
+ * WN_E_SHAPE: n_rows > min(32, max_batch), n_max > max_time, n_rows x n_max or a group's utterances x frames x hop beyond max_batch x max_time.  WN_E_UNSUPPORTED on
+ * compute_dtype = WN_COMPUTE_F32 (as slot sessions); WN_E_STATE before wn_pack_weights.  Ends an open stream or slot session, as wn_synthesize does; a failed pipeline
+ * run is reported by wn_synth_check / the next call and poisons nothing opened afterwards.  Allocates what a slot session of n_rows would (nothing on inference-only
+ * contexts: the row scratch is reserved with the slot tables).  wn_get_upsampled_features afterwards returns [n_rows, cin, n_max], as after a slot push.
+ * wn_set_global_condition is not used. */
+int wn_synthesize_folded(wn_ctx* ctx, const float* c /*[U, cin, F_max]*/, const int32_t* utt_frames /*host [U]*/, int32_t U,
+                         const wn_fold_row* rows /*host*/, int32_t n_rows, int32_t fade_kind /*0 equal power, 1 linear*/,
+                         const void* g, const float* noise, uint64_t seed, const void* test_inputs,
+                         float* out_wav /*[U, wav_pitch]*/, int32_t wav_pitch,
+                         void* out_rows /*optional [n_rows, row_pitch]*/, float* out_raw /*optional [n_rows, O, row_pitch]*/,
+                         int32_t row_pitch, int32_t steps_per_graph, void* stream);
+/* test hook of the tables above (host only): w_in / w_out float [n]; WN_E_ARG for n < 1, a kind outside 0 ... 1 or a null pointer */
+int wn_fold_weights(int32_t fade_kind, int32_t n, float* w_in, float* w_out);
+
 /* Stand-alone samplers on [B,O,T] parameters (train-time log path, wavenet.py:302-325).  Temperature: wn_temper_noise on `noise` first. */
 int wn_sample(wn_ctx* ctx, const float* y_hat, int32_t B, int32_t T, const float* noise /*[T,B,nps]*/,
               void* out /* float [B,T] or int32 [B,T] */, void* stream);
@@ -467,6 +520,11 @@ int wn_test_pipe_layout(int32_t L, int32_t P, int32_t ni, int32_t* role, int32_t
  * [2] live events, [3] live graph execs, [4] buffer allocations ever.  Counts of the library's own handles: unlike hipMemGetInfo they do not move
  * with other processes on the device.  Take deltas around the life of a context: [0..3] return to where they were once it is destroyed. */
 int wn_test_device_resources(int64_t out[5]);
+/* device time of what a folded run adds around its span, by events on the caller's stream (tools/fold_timing.py): after wn_test_fold_timing(ctx, 1) every
+ * wn_synthesize_folded records them; wn_test_fold_times SYNCHRONISES on the last run's and fills ms[0] the whole-utterance upsample (with the gather in front
+ * of it), [1] the fold kernel, [2] the unfold kernel -- of the last group of equally long utterances when there are several.  WN_E_STATE without such a run. */
+int wn_test_fold_timing(wn_ctx* ctx, int32_t enable);
+int wn_test_fold_times(wn_ctx* ctx, double ms[3]);
 #endif /* WN_NO_TEST_HOOKS */
 
 #ifdef __cplusplus

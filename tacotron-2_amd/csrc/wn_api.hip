@@ -200,7 +200,6 @@ static int alloc_workspace(wn_ctx* c) {
 }
 
 static int stream_alloc(wn_ctx* c);
-static int slots_alloc(wn_ctx* c);
 
 extern "C" int wn_create(const wn_config* cfg, wn_ctx** out) {
     wn_ctx* z = nullptr;
@@ -285,7 +284,7 @@ extern "C" int wn_create(const wn_config* cfg, wn_ctx** out) {
             rc = c->cfg.compute_dtype == WN_COMPUTE_F32 ? wn_synth_f32_reserve(c, c->maxB) : pb > 0 ? wn_pipe_reserve(c, pb, c->maxT) : wn_synth_reserve(c);
         }
         if (rc == WN_OK) rc = stream_alloc(c);      // the streaming state too: wn_synth_stream_* never allocate here
-        if (rc == WN_OK && c->cfg.compute_dtype != WN_COMPUTE_F32) rc = slots_alloc(c);      // ... nor do wn_synth_slots_*
+        if (rc == WN_OK && c->cfg.compute_dtype != WN_COMPUTE_F32) rc = wn_slots_alloc(c);      // ... nor do wn_synth_slots_* and wn_synthesize_folded
     }
     if (rc != WN_OK) { g_create_err = c->err; wn_destroy(c); return rc; }
     *out = c;
@@ -766,7 +765,7 @@ extern "C" int wn_synth_stream_end(wn_ctx* c) {
 // ---- synthesis slots: utterances join and leave a running batch -------------------------------------------------------------------
 // One session = B slots on one path / pipeline configuration.  What a stream keeps once (time index, pending window, seed, carried input, bias row) a
 // session keeps per slot; a push runs max_b n_out[b] steps in which every slot takes part, the ones that have nothing (more) to generate as dummies.
-static int slots_alloc(wn_ctx* c) {
+int wn_slots_alloc(wn_ctx* c) {
     auto& S = c->slots;
     int l = 0, r = 0; wn_synth_stream_lookahead(&c->cfg, &l, &r);
     S.capw = c->maxT / c->hop + l + r + 1;
@@ -778,6 +777,11 @@ static int slots_alloc(wn_ctx* c) {
     WN_HIP(c, S.carry.reserve(32));
     WN_HIP(c, S.tdev.reserve(128));
     if (c->gin > 0) WN_HIP(c, S.gbias.reserve((size_t)c->L * nb * c->G));
+    // folded synthesis: whole utterances of up to max_batch x max_time samples in all, the rows' samples / teacher-forcing inputs, the fade tables
+    WN_HIP(c, S.fwin.reserve((size_t)c->C * (c->NT / c->hop + 1)));
+    WN_HIP(c, S.frow.reserve((size_t)c->NT));
+    WN_HIP(c, S.fti.reserve((size_t)c->NT));
+    WN_HIP(c, S.fw.reserve((size_t)2 * c->NT));
     return WN_OK;
 }
 
@@ -794,7 +798,7 @@ extern "C" int wn_synth_slots_begin(wn_ctx* c, int32_t B, int32_t steps_per_grap
     const int path = wn_synth_takes_pipe(c, B, steps_per_graph) ? 2 : 1;
     if ((rc = wn_noise_reserve(c, B, c->maxT))) return rc;
     if ((rc = path == 2 ? wn_pipe_reserve(c, B, c->maxT) : wn_synth_reserve(c))) return rc;
-    if ((rc = slots_alloc(c))) return rc;
+    if ((rc = wn_slots_alloc(c))) return rc;
     wn_synth_stream_lookahead(&c->cfg, &S.left, &S.right);
     WN_HIP(c, hipMemsetAsync(S.tdev, 0, 128 * 4, (hipStream_t)stream));
     S.B = B; S.spg = steps_per_graph; S.path = path; S.poisoned = false; S.first_run = true;

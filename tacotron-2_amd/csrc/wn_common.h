@@ -233,6 +233,11 @@ struct wn_ctx {
         DevBuf<int32_t> carry;                    // [32] the pipeline's carried next input per slot
         DevBuf<int32_t> tdev;                     // launch-per-layer path: [0..31] absolute index of every slot's next sample, [32..63] samples it generates in this push, [64] push-local step
         int64_t feat_pitch = 0; int feat_B = 0;
+        // folded synthesis (wn_synthesize_folded, wn_fold.hip) runs ONE slot-form span on the tables above; its own scratch, sized with them:
+        DevBuf<float> fwin;                       // [group][C][F]: the whole utterances of equal length that are upsampled together
+        DevBuf<int32_t> frow, fti;                // [n_rows][row_pitch]: the rows' model-domain samples when the caller does not take them / their gathered teacher-forcing inputs
+        DevBuf<float> fw;                         // cross-fade weights: for every distinct fade length n, w_in[n] then w_out[n]
+        DevEvent fev[5]; bool ftime = false, ftimed = false;      // wn_test_fold_timing: events around the upsample, the fold kernel and the unfold kernel of a folded run
     } slots;
     int64_t fup_off = 0, fup_pitch = 0;   // wn_get_upsampled_features after a push: the span's columns [fup_off, fup_off + fT) of rows of fup_pitch
     // lazy per-path states, each defined (and deleted) in its own translation unit.  Declared LAST: members are destroyed in reverse order, so the private
@@ -310,6 +315,7 @@ int wn_fill_noise_slots(wn_ctx* ctx, float* noise, int B, const uint64_t* seed, 
 int wn_temper_noise_impl(wn_ctx* ctx, const float* in, float* out, int B, int T, float tau_scale, float tau_select, hipStream_t st);
 int wn_temper_noise_cols(wn_ctx* ctx, const float* in, float* out, int B, int T, const float* tau_scale, const float* tau_select, hipStream_t st);
 int wn_gbias_row(wn_ctx* ctx, const void* g_dev, float* table, int B, int slot, hipStream_t st);      // one slot's gate-bias row into table [L][B][G]
+int wn_slots_alloc(wn_ctx* ctx);                           // tables of a slot session / a folded run, sized for (max_batch, max_time) (wn_create on inference-only contexts)
 int wn_synth_f32_reserve(wn_ctx* ctx, int B);
 bool wn_pipe_eligible(const wn_ctx* ctx, int B);
 int wn_pipe_reserve(wn_ctx* ctx, int B, int T);            // size every pipeline buffer for (B, T) (no-op when already large enough)

@@ -86,6 +86,13 @@ MI355 = dict(
     mi355_synthesis_mixture_temperature=1.0,   # mixture-of-logistics head only: temperature of the component choice, in [0, 2] (0: the arg-max component)
     mi355_synthesis_slots=0,           # N > 0: Synthesizer.synthesize sends all utterances of a call through ONE slot session of min(N, 32) slots (continuous
                                        # batching: no padding to the longest utterance; tick = mi355_synthesis_chunk_frames or 8 frames); 0: padded batches
+    mi355_synthesis_fold_rows=0,       # N > 0: Synthesizer.synthesize generates through WaveNet.folded: every utterance is cut into overlapping segments that run side by
+                                       # side as up to min(N, 32) rows of one batch and are cross-faded back (groups of utterances whose rows fit 32); 0: off.
+                                       # Not with mi355_synthesis_slots.  Segments start cold: the waveform is not the one-shot run's after the first seam
+    mi355_synthesis_fold_warm=4,       # mel frames a segment generates and discards before the part it contributes (50 ms at hop 275)
+    mi355_synthesis_fold_fade=2,       # mel frames of cross-fade between consecutive segments (25 ms); equal power
+    mi355_synthesis_fold_min_frames=40,    # no segment contributes fewer new frames than this (~0.5 s): shorter utterances stay one row, i.e. the one-shot run.
+                                       # These three follow WaveRNN practice (11 000 / 550 samples); they have not been tuned by ear on a trained model of this tree
     mi355_steps_per_graph=0,       # synthesis path: 0 = the persistent dataflow pipeline (real time at 22.05 kHz) whenever the model fits it, else the
                                    # launch-per-layer path with 32 steps per hipGraph replay; N > 0 = that path with N steps per replay
     mi355_synthetic_data=False,    # train on LJSpeech-shaped synthetic tensors (no dataset on disk)

@@ -63,6 +63,14 @@ class WnMelConfig(ctypes.Structure):
     ]
 
 
+class WnFoldRow(ctypes.Structure):
+    """wn_fold_row: one row of a folded run, in mel frames of utterance `utt`."""
+    _fields_ = [('utt', ctypes.c_int32), ('first', ctypes.c_int32), ('frames', ctypes.c_int32), ('keep', ctypes.c_int32), ('fade', ctypes.c_int32)]
+
+
+FADE_KINDS = {'equal_power': 0, 'linear': 1}
+
+
 class WnError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__('%s: %s' % (STATUS.get(code, code), msg))
@@ -132,6 +140,12 @@ def load_library():
         'wn_synth_slot_abandon': (ctypes.c_int, [vp, i32]),
         'wn_synth_slot_frames_done': (ctypes.c_int, [vp, i32]),
         'wn_synth_slots_end': (ctypes.c_int, [vp]),
+        'wn_fold_plan': (ctypes.c_int, [ctypes.POINTER(i32), i32, i32, i32, i32, i32, ctypes.POINTER(WnFoldRow), i32]),
+        'wn_fold_check': (ctypes.c_int, [ctypes.POINTER(i32), i32, ctypes.POINTER(WnFoldRow), i32, ctypes.c_char_p, i32]),
+        'wn_fold_weights': (ctypes.c_int, [i32, i32, vp, vp]),
+        'wn_synthesize_folded': (ctypes.c_int, [vp, vp, ctypes.POINTER(i32), i32, ctypes.POINTER(WnFoldRow), i32, i32, vp, vp, u64, vp, vp, i32, vp, vp, i32, i32, vp]),
+        'wn_test_fold_timing': (ctypes.c_int, [vp, i32]),
+        'wn_test_fold_times': (ctypes.c_int, [vp, ctypes.POINTER(ctypes.c_double)]),
         'wn_sample': (ctypes.c_int, [vp, vp, i32, i32, vp, vp, vp]),
         'wn_mulaw': (ctypes.c_int, [vp, vp, i64, vp]),
         'wn_inv_mulaw': (ctypes.c_int, [vp, vp, i64, vp]),
@@ -448,6 +462,39 @@ class Engine:
         self._slots_B = None
         self._ok(self.lib.wn_synth_slots_end(self.h))
 
+    # ---- folded synthesis (wn_synthesize_folded): utterances cut into overlapping rows that run side by side and are cross-faded back
+    def synthesize_folded(self, c, utt_frames, rows, out_wav, fade_kind='equal_power', g=None, noise=None, seed=0, test_inputs=None, out_rows=None, out_raw=None,
+                          steps_per_graph=0):
+        """c float32 [U, cin, F_max]; utt_frames: U ints; rows: the plan, (utt, first, frames, keep, fade) tuples (fold_plan); out_wav float32 [U, wav_pitch]
+        receives the decoded, cross-faded waveforms.  Optional: g (int32 [U] speaker ids / float32 [U, gin]), noise [n_max, n_rows, nps], test_inputs
+        [U, wav_pitch] (model domain), out_rows [n_rows, row_pitch] / out_raw [n_rows, O, row_pitch].  Asynchronous, as synthesize()."""
+        import torch
+        _check(c, torch.float32, 'c'); _check(out_wav, torch.float32, 'out_wav')
+        U, n_rows = len(utt_frames), len(rows)
+        if c.dim() != 3 or int(c.shape[0]) != U or int(c.shape[1]) != self.cfg.cin_channels or int(c.shape[2]) != max(int(f) for f in utt_frames):
+            raise ValueError('synthesize_folded: c must be [U=%d, cin=%d, F_max=%d] (got %s)' % (U, self.cfg.cin_channels, max(int(f) for f in utt_frames), tuple(c.shape)))
+        if out_wav.dim() != 2 or int(out_wav.shape[0]) != U:
+            raise ValueError('synthesize_folded: out_wav must be [U=%d, wav_pitch]' % U)
+        wav_pitch = int(out_wav.shape[1])
+        if test_inputs is not None and (not test_inputs.is_contiguous() or tuple(test_inputs.shape) != (U, wav_pitch)):
+            raise ValueError('synthesize_folded: test_inputs must be contiguous [U=%d, wav_pitch=%d]' % (U, wav_pitch))
+        row_pitch = 0
+        for t, name in ((out_rows, 'out_rows'), (out_raw, 'out_raw')):
+            if t is None:
+                continue
+            if not t.is_contiguous() or int(t.shape[0]) != n_rows or (row_pitch and int(t.shape[-1]) != row_pitch):
+                raise ValueError('synthesize_folded: %s must be contiguous [n_rows=%d, ..., row_pitch]' % (name, n_rows))
+            row_pitch = int(t.shape[-1])
+        if g is not None:
+            g = g.contiguous()
+            _check(g, torch.int32 if self.cfg.use_speaker_embedding else torch.float32, 'g')
+        if fade_kind not in FADE_KINDS:
+            raise ValueError("fade_kind must be 'equal_power' or 'linear' (got %r)" % (fade_kind,))
+        uf = (ctypes.c_int32 * U)(*[int(f) for f in utt_frames])
+        rw = _fold_rows(rows)
+        self._ok(self.lib.wn_synthesize_folded(self.h, _ptr(c), uf, U, rw, n_rows, FADE_KINDS[fade_kind], _ptr(g), _ptr(noise), ctypes.c_uint64(int(seed) & (2 ** 64 - 1)),
+                                               _ptr(test_inputs), _ptr(out_wav), wav_pitch, _ptr(out_rows), _ptr(out_raw), row_pitch, int(steps_per_graph), _stream()))
+
     def fill_noise(self, noise, B, T, seed):
         """The device noise stream of synthesize(noise=None, seed): float32 [T, B, noise_per_step]."""
         import torch
@@ -618,6 +665,43 @@ def stream_lookahead(cfg):
     if rc != 0:
         raise WnError(rc, 'wn_synth_stream_lookahead: bad configuration')
     return int(left.value), int(right.value)
+
+
+def _fold_rows(rows):
+    arr = (WnFoldRow * max(len(rows), 1))()
+    for i, r in enumerate(rows):
+        arr[i].utt, arr[i].first, arr[i].frames, arr[i].keep, arr[i].fade = (int(v) for v in r)
+    return arr
+
+
+def fold_plan(utt_frames, rows_max, warm=4, fade=2, min_keep=40):
+    """wn_fold_plan (host only: no context, no GPU): the rows of a folded run of utterances of utt_frames[u] mel frames, as (utt, first, frames, keep, fade) tuples."""
+    U = len(utt_frames)
+    uf = (ctypes.c_int32 * max(U, 1))(*[int(f) for f in utt_frames])
+    rows = (WnFoldRow * 32)()
+    n = load_library().wn_fold_plan(uf, U, int(rows_max), int(warm), int(fade), int(min_keep), rows, 32)
+    if n < 0:
+        raise WnError(n, 'wn_fold_plan(frames=%r, rows_max=%r, warm=%r, fade=%r, min_keep=%r)' % (list(utt_frames), rows_max, warm, fade, min_keep))
+    return [(int(r.utt), int(r.first), int(r.frames), int(r.keep), int(r.fade)) for r in rows[:n]]
+
+
+def fold_check(utt_frames, rows):
+    """wn_fold_check (host only): raises WnError(WN_E_ARG) naming the row that breaks a rule of a folded plan."""
+    U = len(utt_frames)
+    uf = (ctypes.c_int32 * max(U, 1))(*[int(f) for f in utt_frames])
+    msg = ctypes.create_string_buffer(400)
+    rc = load_library().wn_fold_check(uf, U, _fold_rows(rows), len(rows), msg, 400)
+    if rc != 0:
+        raise WnError(rc, msg.value.decode())
+
+
+def fold_weights(fade_kind, n):
+    """(w_in, w_out) float32 [n]: the cross-fade tables wn_synthesize_folded uploads for a fade of n samples (host only)."""
+    w_in, w_out = np.empty(int(n), np.float32), np.empty(int(n), np.float32)
+    rc = load_library().wn_fold_weights(FADE_KINDS[fade_kind], int(n), w_in.ctypes.data_as(ctypes.c_void_p), w_out.ctypes.data_as(ctypes.c_void_p))
+    if rc != 0:
+        raise WnError(rc, 'wn_fold_weights(%r, %r)' % (fade_kind, n))
+    return w_in, w_out
 
 
 def temper_noise_host(mode, noise, tau_scale=1.0, tau_select=1.0):

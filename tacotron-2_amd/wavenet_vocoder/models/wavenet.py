@@ -59,6 +59,33 @@ def temperature_pair(hparams, temperature=None, mixture_temperature=None):
     return (t, mt)
 
 
+def fold_capacity(utt_frames, plan, hop):
+    """(batch, time) an engine needs for a folded run of this plan: every row fits max_time, and the whole utterances of one length, which are
+    upsampled together, fit batch x time samples (wn_synthesize_folded's WN_E_SHAPE rules)."""
+    n_rows = len(plan)
+    n_max = max(r[2] for r in plan) * hop
+    by_len = {}
+    for f in utt_frames:
+        by_len[int(f)] = by_len.get(int(f), 0) + 1
+    need = max(f * k * hop for f, k in by_len.items())
+    return n_rows, max(n_max, -(-need // n_rows))
+
+
+def unfold_features(plan, feats, hop):
+    """The upsampled conditioning of every whole utterance from the rows of a folded run (Engine.upsampled_features: [n_rows, cin, n_max]): row r
+    contributes the frames from its keep to the next row's keep.  Equal to the features of the one-shot run (the rows were gathered from them)."""
+    out = []
+    for u in sorted({r[0] for r in plan}):
+        idx = [i for i, r in enumerate(plan) if r[0] == u]
+        parts = []
+        for k, i in enumerate(idx):
+            _, first, frames, keep, _ = plan[i]
+            end = plan[idx[k + 1]][3] if k + 1 < len(idx) else first + frames
+            parts.append(feats[i, :, (keep - first) * hop:(end - first) * hop])
+        out.append(torch.cat(parts, 1))
+    return out
+
+
 class SynthesisStream(object):
     """Generation of B utterances chunk by chunk as their mel frames arrive (WaveNet.stream): the samples are bit-identical to one
     WaveNet.incremental-style run over the concatenated frames with the same seed.  push() returns the samples whose conditioning is now
@@ -604,6 +631,109 @@ class WaveNet(object):
                 self.engine.synth_path, group, '' if pair == (1.0, 1.0) else '; sampling temperature {:g}, choice temperature {:g}'.format(*pair)))
         self.upsampled_local_features = feats
         return (out, raw) if return_raw else out
+
+    def folded(self, c_list, g=None, rows=20, warm=4, fade=2, min_keep=40, fade_kind='equal_power', temperature=None, mixture_temperature=None, noise=None,
+               test_inputs=None, return_rows=False, check=False):
+        """Folded ("batched") generation: every utterance of c_list ([cin, F_u] mel frames each) is cut into overlapping rows, the rows run side by side as
+        ONE batch -- each from a cold start, `warm` frames before the part it contributes -- and are cross-faded (`fade` frames; 'equal_power' or 'linear')
+        back into one waveform per utterance on the device (wn_synthesize_folded).  rows: the number of rows of the run (<= 32; the planner, _ext.fold_plan,
+        gives every utterance one and the rest to the longest, never fewer than min_keep new frames per row), or an explicit plan [(utt, first, frames,
+        keep, fade)].  Returns a list of float waveforms in [-1, 1] (decoded: not the model domain); return_rows: also a dict with the plan, the rows'
+        model-domain samples, raw outputs and upsampled features.  g: one speaker id / feature row per utterance.  noise [n_max, n_rows, noise_per_step] /
+        test_inputs (one model-domain tensor [F_u * hop] per utterance) as incremental(); the seed is derived as incremental() derives it (row r draws the
+        one-stream noise of seed + r).  check: wait and verify; a pipeline run that gave up on a hand-off is re-run ONCE on the launch-per-layer path.
+        rows = 20 is the measured minimum of the wall time of a 5 s utterance on the paper model (profiles/fold_timing.json; 12 rows are within its spread).
+        An utterance in one row is its one-shot run.  The defaults (~0.5 s per row, 50 ms warm-up, 25 ms fade at hop 275) follow WaveRNN practice; nobody
+        has listened to them on a trained model of this tree."""
+        hp = self._hparams
+        pair = temperature_pair(hp, temperature, mixture_temperature)
+        hop = audio.get_hop_size(hp)
+        U = len(c_list)
+        if U < 1:
+            raise ValueError('WaveNet.folded: no utterance')
+        frames = [int(c.shape[-1]) for c in c_list]
+        for c in c_list:
+            if c.dim() != 2 or int(c.shape[0]) != hp.cin_channels or int(c.shape[1]) < 1:
+                raise ValueError('WaveNet.folded: every utterance must be [cin={}, frames >= 1] (got {})'.format(hp.cin_channels, tuple(c.shape)))
+        if fade_kind not in _ext.FADE_KINDS:
+            raise ValueError("WaveNet.folded: fade_kind must be 'equal_power' or 'linear' (got {!r})".format(fade_kind))
+        try:
+            if isinstance(rows, int):
+                if not U <= rows <= 32:
+                    raise ValueError('WaveNet.folded: rows = {} outside [{} utterances, 32]'.format(rows, U))
+                plan = _ext.fold_plan(frames, rows, warm, fade, min_keep)
+            else:
+                plan = [tuple(int(v) for v in r) for r in rows]
+                if len(plan) > 32:
+                    raise ValueError('WaveNet.folded: {} rows (at most 32)'.format(len(plan)))
+                _ext.fold_check(frames, plan)
+        except _ext.WnError as e:
+            raise ValueError(str(e))
+        n_rows, n_max, F_max = len(plan), max(r[2] for r in plan) * hop, max(frames)
+        if g is None and self.global_conditioning_enabled():
+            raise ValueError('global conditioning is enabled (gin_channels > 0) but no g was given')
+        if test_inputs is not None and len(test_inputs) != U:
+            raise ValueError('WaveNet.folded: test_inputs needs one tensor per utterance')
+        if self.engine is None:
+            self.build(*fold_capacity(frames, plan, hop), inference_only=True)
+        self._ensure_packed()
+        self.engine.set_temperature(*pair)
+        dev = self.device
+        self._synth_calls = getattr(self, '_synth_calls', 0) + 1
+        seed = ((int(hp.wavenet_random_seed) << 20) + self._synth_calls) * 64
+        cc = torch.zeros(U, hp.cin_channels, F_max, device=dev)
+        for u, c in enumerate(c_list):
+            cc[u, :, :frames[u]] = c.to(dev, torch.float32)
+        T_max = F_max * hop
+        wav = torch.zeros(U, T_max, device=dev)
+        dt = torch.float32 if self.scalar_input else torch.int32
+        ti = None
+        if test_inputs is not None:
+            ti = torch.zeros(U, T_max, device=dev, dtype=dt)
+            for u, t in enumerate(test_inputs):
+                t = t.reshape(-1)[:frames[u] * hop]
+                assert t.shape[0] == frames[u] * hop, 'teacher-forcing inputs must cover the whole synthesis length'
+                ti[u, :t.shape[0]] = t.to(dev, dt)
+        gt = None
+        if self.global_conditioning_enabled():
+            gt = torch.as_tensor(g, device=dev)
+            gt = (gt.reshape(U).to(torch.int32) if self.embed_speakers is not None else gt.reshape(U, hp.gin_channels).to(torch.float32)).contiguous()
+        out_rows = torch.zeros(n_rows, n_max, device=dev, dtype=dt) if return_rows else None
+        out_raw = torch.zeros(n_rows, hp.out_channels, n_max, device=dev) if return_rows else None
+        nz = None if noise is None else noise.to(dev, torch.float32).contiguous()
+        spg = int(getattr(hp, 'mi355_steps_per_graph', 0))
+
+        def attempt(spg_):
+            self.engine.synthesize_folded(cc, frames, plan, wav, fade_kind=fade_kind, g=gt, noise=nz, seed=seed, test_inputs=ti, out_rows=out_rows, out_raw=out_raw,
+                                          steps_per_graph=spg_)
+            if check:
+                torch.cuda.synchronize()
+                self.engine.synth_check()
+
+        try:
+            attempt(spg)
+        except _ext.WnError as e:
+            out_of_range = 'half-precision range' in str(e)
+            if not check or self.engine.synth_path != 'pipeline' or not ('timed out' in str(e) or out_of_range):
+                raise
+            self.synth_fallbacks = getattr(self, 'synth_fallbacks', 0) + 1
+            torch.cuda.synchronize()
+            if out_of_range:
+                log('WaveNet folded synthesis: {} -- re-running with bf16 pipeline storage'.format(e))
+                self.engine.pipeline_dtype(False)
+                attempt(spg)
+            else:
+                log('WaveNet folded synthesis: {} -- re-running on the launch-per-layer graph path'.format(e))
+                attempt(32)
+        if getattr(self, '_logged_fold', None) != (self.engine.synth_path, n_rows):
+            self._logged_fold = (self.engine.synth_path, n_rows)
+            log('WaveNet folded synthesis: {} utterance(s) in {} rows of <= {} samples, path {}'.format(U, n_rows, n_max, self.engine.synth_path))
+        wavs = [wav[u, :frames[u] * hop] for u in range(U)]
+        if not return_rows:
+            return wavs
+        feats = torch.empty(n_rows, hp.cin_channels, n_max, device=dev)
+        self.engine.upsampled_features(feats)
+        return wavs, {'plan': plan, 'rows': out_rows, 'raw': out_raw, 'features': feats, 'seed': seed}
 
     def slots(self, batch, steps_per_graph=None):
         """Open a SlotSession of `batch` slots (<= 32, the model's engine must have been built for them): independent utterances that join and

@@ -80,6 +80,12 @@ class Synthesizer(object):
             if speaker_ids is None:
                 raise RuntimeError('Please provide speaker ids (--speaker_id) to a globally conditioned WaveNet')
             g = torch.from_numpy(np.asarray(speaker_ids, dtype=np.int32).reshape(len(c_batch), 1))
+        nfold = int(getattr(hparams, 'mi355_synthesis_fold_rows', 0))
+        if nfold > 0 and int(getattr(hparams, 'mi355_synthesis_slots', 0)) > 0:
+            raise ValueError('mi355_synthesis_fold_rows and mi355_synthesis_slots are both > 0: choose one')
+        if nfold > 0 and not self.synth_debug:
+            generated_wavs, upsampled_features = self._synthesize_folded(c_batch, [len(x) for x in mel_spectrograms], speaker_ids, min(nfold, 32), log_dir is not None)
+            return self._write(generated_wavs, upsampled_features, mel_spectrograms, basenames, out_dir, log_dir)
         nslots = int(getattr(hparams, 'mi355_synthesis_slots', 0))
         if nslots > 0 and not self.synth_debug:
             generated_wavs, upsampled_features = self._synthesize_slots(c_batch, [len(x) for x in mel_spectrograms], speaker_ids, min(nslots, 32), log_dir is not None)
@@ -100,6 +106,32 @@ class Synthesizer(object):
         generated_wavs = [w[:length] for w, length in zip(generated, audio_lengths)]
         upsampled_features = [f[:, :length] for f, length in zip(feats, audio_lengths)]
         return self._write(generated_wavs, upsampled_features, mel_spectrograms, basenames, out_dir, log_dir)
+
+    def _synthesize_folded(self, c_batch, lengths, speaker_ids, nrows, want_features):
+        """mi355_synthesis_fold_rows > 0: the utterances of the call through WaveNet.folded, in groups of consecutive utterances whose rows fit nrows (every
+        utterance takes at least one row, so at most nrows utterances per group).  Seeds derive from (wavenet_random_seed, the model's synthesis-call
+        counter), so two fresh runs of the same inputs agree."""
+        from wavenet_vocoder import _ext
+        from wavenet_vocoder.models.wavenet import fold_capacity, unfold_features
+        hparams, hop = self._hparams, get_hop_size(self._hparams)
+        warm, fade = int(hparams.mi355_synthesis_fold_warm), int(hparams.mi355_synthesis_fold_fade)
+        min_keep = int(hparams.mi355_synthesis_fold_min_frames)
+        groups = [list(range(u0, min(u0 + nrows, len(lengths)))) for u0 in range(0, len(lengths), nrows)]
+        plans = [_ext.fold_plan([lengths[u] for u in grp], nrows, warm, fade, min_keep) for grp in groups]
+        caps = [fold_capacity([lengths[u] for u in grp], plan, hop) for grp, plan in zip(groups, plans)]
+        self._ensure_capacity(max(c[0] for c in caps), max(c[1] for c in caps))
+        wavs, ups = [], []
+        ids = None if not self.global_conditions else np.asarray(speaker_ids).reshape(-1)
+        for grp, plan in zip(groups, plans):
+            cl = [torch.from_numpy(np.ascontiguousarray(c_batch[u, :lengths[u]].T)) for u in grp]
+            res = self.model.folded(cl, g=None if ids is None else [int(ids[u]) for u in grp], rows=plan, check=True, return_rows=want_features)
+            if want_features:
+                res, info = res
+                ups += [f.cpu().numpy() for f in unfold_features(plan, info['features'], hop)]
+            else:
+                ups += [np.zeros((hparams.cin_channels, 0), np.float32) for _ in grp]
+            wavs += [w.float().cpu().numpy() for w in res]
+        return wavs, ups
 
     def _synthesize_slots(self, c_batch, lengths, speaker_ids, nslots, want_features):
         """mi355_synthesis_slots > 0: all utterances of the call through ONE slot session (WaveNet.slots): no utterance is padded to the longest of its
