@@ -197,6 +197,9 @@ def test_train_backward(name):
 
 
 def test_optimizer_step_matches_tf_adam():
+    """Whole values of p, m, v, ema against the oracle at allclose tolerances, one model, one step, ema0 = p0.  The EMA's movement here
+    ((1 - decay) |dp| ~ 7e-8) is below this test's own atol + rtol |ema|: tests/test_hip_heads.py owns the increments (m - m0, v - v0, p - p0,
+    ema - ema0 of every element under a derived float32 bound, ema0 != p0, five models, steps 0 / 41 / 1e6)."""
     r = _run_fwd('mol_2d')
     eng = r['eng']
     n = eng.n_params
