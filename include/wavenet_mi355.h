@@ -459,6 +459,42 @@ int  wn_mel_peak(wn_mel* mel, const float* wav, int64_t ld, const int32_t* lengt
 int  wn_mel_run(wn_mel* mel, const float* wav, int64_t ld, const int32_t* lengths, const float* gain, float* out, int32_t B, int32_t F_max,
                 int32_t channels_first, void* stream);
 
+/* ---- output stage: model-domain samples -> de-emphasised float32 and / or 16-bit PCM on the device -------------------------------
+ * A handle of its own, independent of wn_ctx: it takes any device buffer a synthesis call produced (wn_synthesize, wn_synth_stream_push,
+ * wn_synth_slots_push: in_type = the model's input type; wn_synthesize_folded's out_wav: in_type 0).  Per sample, strictly in sample order,
+ *   x = decode(in)                      exactly wn_inv_mulaw (1) / wn_inv_mulaw_quantize (2), the identity for 0
+ *   y[t] = fl32(fl32(k y[t-1]) + x[t])  a separately rounded multiply and add (never an fma); k = 0 does no arithmetic: y has the bits of x
+ *   PCM = trunc(clamp(fl32(y s), -32767, 32767))
+ * so a row is bit-identical however it is cut into pushes.  Results of magnitude below 2^-126 are unspecified (flushed or gradual).  One workgroup
+ * per row walks it in blocks: all lanes decode into LDS, one lane runs the chain, all lanes convert and store; rows of a call run side by side.
+ * The carried state (y[-1] per row) and a scratch for wn_post_finish's peaks are reserved in wn_post_create; no call allocates or synchronises, lengths
+ * travel as kernel arguments (the host arrays are free when the call returns).  Calls on one handle belong on one stream at a time.  Elements of a row
+ * beyond n[b] keep the caller's bytes in both outputs.  Validation before any device call: WN_E_ARG for a null pointer, a foreign abi_version,
+ * max_rows < 1, in_type outside 0 ... 2, deemphasis outside [0, 1) or not finite, gain not finite or <= 0, B < 1, a negative n[b], no output at all
+ * (push) or no out_f32 (finish); WN_E_SHAPE for B > max_rows or a pitch (in elements) smaller than the longest row. */
+typedef struct wn_post_config {
+    int32_t abi_version;   /* = WN_ABI_VERSION */
+    int32_t max_rows;      /* rows of carried state, >= 1 */
+    int32_t in_type;       /* 0: float, already a waveform ('raw', or wn_synthesize_folded's out_wav)
+                              1: float mu-law domain ('mulaw')      2: int32 class ids ('mulaw-quantize') */
+    float   deemphasis;    /* k of y[t] = x[t] + k y[t-1]; 0 <= k < 1; 0: off */
+    float   gain;          /* wn_post_push only: PCM = y * gain * 32767; finite, > 0 */
+} wn_post_config;
+typedef struct wn_post wn_post;
+int  wn_post_create(const wn_post_config* cfg, wn_post** out);
+void wn_post_destroy(wn_post* p);
+const char* wn_post_last_error(const wn_post* p);   /* NULL: text of the last failed create */
+/* chunk form: continues row b's filter from where its last push left it; restart[b] != 0 (NULL: none) starts row b from y[-1] = 0.  n[b] = 0 leaves
+ * row b's state alone unless it is restarted.  s = (float)(gain * 32767.0).  n, restart: HOST int32 [B]; out_f32 / out_pcm: device [B, out_pitch], either
+ * may be NULL; clipped: device int32 [B] or NULL, the number of samples of THIS call with |fl32(y s)| > 32767 (written, not accumulated). */
+int wn_post_push(wn_post* p, const void* in, int64_t in_pitch, const int32_t* n, const int32_t* restart, int32_t B,
+                 float* out_f32, int16_t* out_pcm, int64_t out_pitch, int32_t* clipped, void* stream);
+/* whole-utterance form: every row from y[-1] = 0 and peak-normalised as save_wavenet_wav does it (audio.py:17-20): peak[b] = max_t |y[b, t]| over the
+ * row's n[b] samples, s = (float)(32767.0 / max(0.01, (double)peak[b])) formed on the device.  Two launches (chain + peak, then the conversion), no host
+ * synchronisation.  Neither reads nor writes the carried state.  out_f32 required, out_pcm and peak (device float [B]) optional. */
+int wn_post_finish(wn_post* p, const void* in, int64_t in_pitch, const int32_t* n, int32_t B,
+                   float* out_f32, int16_t* out_pcm, int64_t out_pitch, float* peak, void* stream);
+
 /* ---- introspection ------------------------------------------------------------------------------ */
 int64_t wn_workspace_bytes(const wn_ctx* ctx);
 /* name of the kernel that dominates training time (bench.py's roofline line names it) */
@@ -525,6 +561,10 @@ int wn_test_device_resources(int64_t out[5]);
  * of it), [1] the fold kernel, [2] the unfold kernel -- of the last group of equally long utterances when there are several.  WN_E_STATE without such a run. */
 int wn_test_fold_timing(wn_ctx* ctx, int32_t enable);
 int wn_test_fold_times(wn_ctx* ctx, double ms[3]);
+/* the output stage's arithmetic on the host (no handle, no GPU): one row of n samples of cfg->in_type from y[-1] = carry_in, PCM scale pcm_scale as given
+ * (cfg->gain is validated and not used).  out_f32 / out_pcm [n] and carry_out (y[n - 1]; carry_in for n = 0) are each optional.  WN_E_ARG as wn_post_create,
+ * for in = NULL with n > 0, and for n < 0. */
+int wn_test_post_host(const wn_post_config* cfg, const void* in, int64_t n, float carry_in, float pcm_scale, float* out_f32, int16_t* out_pcm, float* carry_out);
 #endif /* WN_NO_TEST_HOOKS */
 
 #ifdef __cplusplus

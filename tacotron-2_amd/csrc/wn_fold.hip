@@ -4,7 +4,7 @@
 // table; several rows read the same source, which wn_slots_scatter_kernel cannot express) and the unfold (decode + cross-fade).  The synthesis paths
 // are entered through their span entries as they are.
 #include "wn_common.h"
-#include "wn_mulaw_tables.h"
+#include "wn_post.h"
 #include <math.h>
 #include <algorithm>
 #include <vector>
@@ -128,13 +128,8 @@ __global__ void wn_fold_kernel(const bf16_t* __restrict__ cbt, const float* __re
 }
 
 // (f) decode of a model-domain sample: the arithmetic of wn_inv_mulaw_kernel / wn_inv_mulaw_quantize_kernel (wn_loss.hip), identity for 'raw'
-template <int TYPE> __device__ __forceinline__ float fold_decode(int32_t bits) {
-    if (TYPE == WN_INPUT_MULAW_QUANTIZE) return WN_MULAW_DECODE[min(max(bits, 0), 255)];
-    const float v = __int_as_float(bits);
-    if (TYPE == WN_INPUT_RAW) return v;
-    const float s = (v > 0.0f) ? 1.0f : (v < 0.0f ? -1.0f : 0.0f);
-    return (float)((double)s * (1.0 / 255.0) * (pow(256.0, fabs((double)v)) - 1.0));
-}
+// (wn_post.h: shared with the output stage)
+template <int TYPE> __device__ __forceinline__ float fold_decode(int32_t bits) { return wn_decode_sample<TYPE>(bits); }
 __device__ __forceinline__ float fold_xfade(float a, float w_out, float b, float w_in) {
 #pragma clang fp contract(off)
     const float x = a * w_out;

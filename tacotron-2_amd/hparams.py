@@ -93,6 +93,11 @@ MI355 = dict(
     mi355_synthesis_fold_fade=2,       # mel frames of cross-fade between consecutive segments (25 ms); equal power
     mi355_synthesis_fold_min_frames=40,    # no segment contributes fewer new frames than this (~0.5 s): shorter utterances stay one row, i.e. the one-shot run.
                                        # These three follow WaveRNN practice (11 000 / 550 samples); they have not been tuned by ear on a trained model of this tree
+    mi355_output_deemphasis=False,     # True: the wavs Synthesizer writes are de-emphasised with hparams.preemphasis (the inverse of the preprocessing's pre-emphasis,
+                                       # which the reference's save_wavenet_wav accepts and ignores); False: written as generated, as the reference writes them
+    mi355_output_stage='host',         # 'host': audio.inv_preemphasis + save_wavenet_wav on numpy; 'device': decode, de-emphasis, peak normalisation and the int16
+                                       # cast on the device (csrc/wn_post.hip, OutputStage.finish) on every synthesis route; the same files without de-emphasis
+    mi355_output_gain=1.0,             # gain of the playable chunks of streams and slot sessions (WaveNet.output_stage): PCM = y * gain * 32767, clamped
     mi355_steps_per_graph=0,       # synthesis path: 0 = the persistent dataflow pipeline (real time at 22.05 kHz) whenever the model fits it, else the
                                    # launch-per-layer path with 32 steps per hipGraph replay; N > 0 = that path with N steps per replay
     mi355_synthetic_data=False,    # train on LJSpeech-shaped synthetic tensors (no dataset on disk)

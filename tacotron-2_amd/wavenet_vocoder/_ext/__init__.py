@@ -63,6 +63,10 @@ class WnMelConfig(ctypes.Structure):
     ]
 
 
+class WnPostConfig(ctypes.Structure):
+    _fields_ = [('abi_version', ctypes.c_int32), ('max_rows', ctypes.c_int32), ('in_type', ctypes.c_int32), ('deemphasis', ctypes.c_float), ('gain', ctypes.c_float)]
+
+
 class WnFoldRow(ctypes.Structure):
     """wn_fold_row: one row of a folded run, in mel frames of utterance `utt`."""
     _fields_ = [('utt', ctypes.c_int32), ('first', ctypes.c_int32), ('frames', ctypes.c_int32), ('keep', ctypes.c_int32), ('fade', ctypes.c_int32)]
@@ -175,6 +179,12 @@ def load_library():
         'wn_mel_frame_tile': (ctypes.c_int, [vp]),
         'wn_mel_peak': (ctypes.c_int, [vp, vp, i64, ctypes.POINTER(i32), i32, vp, vp]),
         'wn_mel_run': (ctypes.c_int, [vp, vp, i64, ctypes.POINTER(i32), vp, vp, i32, i32, i32, vp]),
+        'wn_post_create': (ctypes.c_int, [ctypes.POINTER(WnPostConfig), ctypes.POINTER(vp)]),
+        'wn_post_destroy': (None, [vp]),
+        'wn_post_last_error': (ctypes.c_char_p, [vp]),
+        'wn_post_push': (ctypes.c_int, [vp, vp, i64, ctypes.POINTER(i32), ctypes.POINTER(i32), i32, vp, vp, i64, vp, vp]),
+        'wn_post_finish': (ctypes.c_int, [vp, vp, i64, ctypes.POINTER(i32), i32, vp, vp, i64, vp, vp]),
+        'wn_test_post_host': (ctypes.c_int, [ctypes.POINTER(WnPostConfig), vp, i64, f32, f32, vp, vp, ctypes.POINTER(f32)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)            # AttributeError here == ABI symbol missing
@@ -868,6 +878,114 @@ class MelAnalyzer:
     def close(self):
         if getattr(self, 'h', None):
             self.lib.wn_mel_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def post_config(max_rows, in_type, deemphasis=0.0, gain=1.0):
+    """wn_post_config.  in_type: 0 / 'raw' (a float waveform), 1 / 'mulaw', 2 / 'mulaw-quantize'."""
+    cfg = WnPostConfig()
+    cfg.abi_version = WN_ABI_VERSION
+    cfg.max_rows = int(max_rows)
+    cfg.in_type = INPUT_TYPES[in_type] if in_type in INPUT_TYPES else int(in_type)
+    cfg.deemphasis = float(deemphasis)
+    cfg.gain = float(gain)
+    return cfg
+
+
+def post_host(samples, in_type, deemphasis=0.0, carry_in=0.0, pcm_scale=32767.0):
+    """wn_test_post_host: the output stage's arithmetic on the host (no handle, no GPU) over one row.  samples: numpy float32 (in_type 0 / 1) or int32 (2)
+    [n].  Returns (y float32 [n], pcm int16 [n], carry_out)."""
+    cfg = post_config(1, in_type, deemphasis)
+    a = np.ascontiguousarray(samples, dtype=np.int32 if cfg.in_type == 2 else np.float32).reshape(-1)
+    y, q, carry = np.empty(a.size, np.float32), np.empty(a.size, np.int16), ctypes.c_float(0.0)
+    rc = load_library().wn_test_post_host(ctypes.byref(cfg), a.ctypes.data_as(ctypes.c_void_p), ctypes.c_int64(a.size), float(carry_in), float(pcm_scale),
+                                          y.ctypes.data_as(ctypes.c_void_p), q.ctypes.data_as(ctypes.c_void_p), ctypes.byref(carry))
+    if rc != 0:
+        raise WnError(rc, (load_library().wn_post_last_error(None) or b'').decode())
+    return y, q, np.float32(carry.value)
+
+
+class OutputStage:
+    """One wn_post: model-domain samples -> de-emphasised float32 and / or int16 PCM on the current device (csrc/wn_post.hip), asynchronously, with the
+    filter state carried per row across push() calls: a row is bit-identical however it is cut into pushes.  Use one stage from one stream at a time."""
+
+    def __init__(self, hparams, rows, deemphasis=None, gain=1.0, in_type=None):
+        """in_type None: hparams.input_type ('raw' / 0 also takes WaveNet.folded's decoded waveforms).  deemphasis None: hparams.preemphasis if
+        hparams.preemphasize else 0 (off).  gain: push() only, PCM = y * gain * 32767."""
+        self.lib = load_library()
+        if in_type is None:
+            in_type = hparams.input_type
+        if in_type not in INPUT_TYPES and in_type not in (0, 1, 2):
+            raise ValueError('in_type must be one of raw / mulaw / mulaw-quantize or 0 ... 2 (got %r)' % (in_type,))
+        if deemphasis is None:
+            deemphasis = float(hparams.preemphasis) if hparams.preemphasize else 0.0
+        self.cfg = post_config(rows, in_type, deemphasis, gain)
+        h = ctypes.c_void_p()
+        rc = self.lib.wn_post_create(ctypes.byref(self.cfg), ctypes.byref(h))
+        if rc != 0:
+            raise WnError(rc, (self.lib.wn_post_last_error(None) or b'').decode())
+        self.h = h
+        self.rows, self.in_type, self.deemphasis, self.gain = int(rows), int(self.cfg.in_type), float(self.cfg.deemphasis), float(self.cfg.gain)
+
+    def _ok(self, rc):
+        if rc != 0:
+            raise WnError(rc, (self.lib.wn_post_last_error(self.h) or b'').decode())
+
+    def _rows(self, samples, n):
+        import torch
+        _check(samples, torch.int32 if self.in_type == 2 else torch.float32, 'samples')
+        if samples.dim() == 1:
+            samples = samples.reshape(1, -1)
+        if samples.dim() != 2:
+            raise ValueError('samples must be [B, pitch]')
+        B, pitch = int(samples.shape[0]), int(samples.shape[1])
+        n = [pitch] * B if n is None else [int(v) for v in n]
+        if len(n) != B:
+            raise ValueError('one length per row of samples (%d lengths for %d rows)' % (len(n), B))
+        return samples, B, pitch, n, (ctypes.c_int32 * B)(*n)
+
+    def push(self, samples, n=None, restart=None, pcm=True, float_out=False, clipped=False):
+        """samples [B, pitch] on the device (float32, or int32 class ids), n: B ints (None: the whole pitch), restart: B flags (None: none; True: all).
+        Continues every row's filter where its last push left it.  Returns the int16 chunk [B, pitch] (pcm), the float32 one (float_out) and the clipped
+        counts int32 [B] (clipped) -- one tensor, or a tuple in that order, on the device; elements beyond n[b] are zero."""
+        import torch
+        samples, B, pitch, n, nc = self._rows(samples, n)
+        if not (pcm or float_out):
+            raise ValueError('OutputStage.push: nothing to return (pcm and float_out are both off)')
+        rs = None
+        if restart is not None:
+            flags = [1] * B if restart is True else [int(bool(v)) for v in restart]
+            if len(flags) != B:
+                raise ValueError('one restart flag per row')
+            rs = (ctypes.c_int32 * B)(*flags)
+        q = torch.zeros(B, pitch, dtype=torch.int16, device=samples.device) if pcm else None
+        y = torch.zeros(B, pitch, dtype=torch.float32, device=samples.device) if float_out else None
+        cl = torch.zeros(B, dtype=torch.int32, device=samples.device) if clipped else None
+        self._ok(self.lib.wn_post_push(self.h, _ptr(samples), pitch, nc, rs, B, _ptr(y), _ptr(q), pitch, _ptr(cl), _stream()))
+        res = tuple(t for t in (q, y, cl) if t is not None)
+        return res[0] if len(res) == 1 else res
+
+    def finish(self, samples, lengths, pcm=True, peak=False):
+        """Whole utterances: every row from y[-1] = 0, peak-normalised as save_wavenet_wav does.  Returns (y float32 [B, pitch], int16 [B, pitch]) with pcm,
+        else y; peak: also the peaks float32 [B].  The carried state of push() is neither read nor written."""
+        import torch
+        samples, B, pitch, n, nc = self._rows(samples, lengths)
+        y = torch.zeros(B, pitch, dtype=torch.float32, device=samples.device)
+        q = torch.zeros(B, pitch, dtype=torch.int16, device=samples.device) if pcm else None
+        pk = torch.zeros(B, dtype=torch.float32, device=samples.device) if peak else None
+        self._ok(self.lib.wn_post_finish(self.h, _ptr(samples), pitch, nc, B, _ptr(y), _ptr(q), pitch, _ptr(pk), _stream()))
+        res = tuple(t for t in (y, q, pk) if t is not None)
+        return res[0] if len(res) == 1 else res
+
+    def close(self):
+        if getattr(self, 'h', None):
+            self.lib.wn_post_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -86,6 +86,14 @@ def unfold_features(plan, feats, hop):
     return out
 
 
+def _post_push(post, post_output, out, n, restart):
+    """One OutputStage.push of a synthesis push: out [B, pitch] model-domain samples, n / restart per row.  Returns what post_output names: the int16
+    chunk ('pcm'), the float32 one ('float') or both as (pcm, float) ('both'), [B, pitch] on the device."""
+    if post_output not in ('pcm', 'float', 'both'):
+        raise ValueError("post_output must be 'pcm', 'float' or 'both' (got {!r})".format(post_output))
+    return post.push(out, n=n, restart=restart, pcm=post_output != 'float', float_out=post_output != 'pcm')
+
+
 class SynthesisStream(object):
     """Generation of B utterances chunk by chunk as their mel frames arrive (WaveNet.stream): the samples are bit-identical to one
     WaveNet.incremental-style run over the concatenated frames with the same seed.  push() returns the samples whose conditioning is now
@@ -105,9 +113,11 @@ class SynthesisStream(object):
         model.engine.stream_begin(self.B, seed=seed, steps_per_graph=steps_per_graph)
         self.closed = False
 
-    def push(self, c_frames=None, final=False, noise=None, test_inputs=None, return_raw=False):
+    def push(self, c_frames=None, final=False, noise=None, test_inputs=None, return_raw=False, post=None, post_output='pcm'):
         """c_frames [B, cin, Tn] (None or Tn = 0: no new frames); noise [n, B, noise_per_step] / test_inputs [B, n] of the span this push
-        generates (its length follows from stream_schedule and the lookahead)."""
+        generates (its length follows from stream_schedule and the lookahead).  post: an OutputStage (WaveNet.output_stage) of >= B rows: the
+        playable chunk [B, n] -- decoded, de-emphasised, int16 at the stage's gain (post_output 'float': float32; 'both': (int16, float32)) -- is
+        returned as a last element beside the samples; the stage's filter runs on from push to push, restarted at the stream's first one."""
         if self.closed:
             raise RuntimeError('SynthesisStream: the stream is closed')
         m = self.model
@@ -130,8 +140,16 @@ class SynthesisStream(object):
         self.done = end
         if final:
             self.closed = True
+        chunk = None
+        if post is not None:
+            chunk = _post_push(post, post_output, out, [n] * self.B, None if getattr(self, '_post_started', False) else True)
+            self._post_started = True
+            chunk = tuple(t[:, :n] for t in chunk) if isinstance(chunk, tuple) else chunk[:, :n]
         out = out[:, :n]
-        return (out, raw[:, :, :n]) if return_raw else out
+        res = (out, raw[:, :, :n]) if return_raw else (out,)
+        if post is not None:
+            res = res + (chunk,)
+        return res if len(res) > 1 else res[0]
 
     def close(self):
         """Abandon the stream (frames pushed and not yet generated are dropped)."""
@@ -182,6 +200,7 @@ class SlotSession(object):
         self.lookahead = model.engine.stream_lookahead()
         self.hop = model.engine.hop
         self.done, self.pushed = [None] * self.B, [0] * self.B          # frames per live slot (None: idle)
+        self._post_restart = set()                                      # slots opened since their last push: an output stage starts them from y[-1] = 0
         model._ensure_packed()
         model.engine.slots_begin(self.B, steps_per_graph=steps_per_graph)
         self.closed = False
@@ -206,10 +225,13 @@ class SlotSession(object):
         m.engine.slot_open(slot, seed=seed, g=gd)
         m.engine.slot_temperature(slot, *pair)
         self.done[slot], self.pushed[slot] = 0, 0
+        self._post_restart.add(int(slot))
 
-    def push(self, items, return_raw=False):
+    def push(self, items, return_raw=False, post=None, post_output='pcm'):
         """items {slot: frames [cin, Tn]} or {slot: (frames, final)}: append the frames to the slots' utterances (final: the utterance ends, the slot
-        is idle afterwards).  Returns {slot: samples [n]} (or (samples, raw [O, n]) with return_raw) for every slot named."""
+        is idle afterwards).  Returns {slot: samples [n]} (or (samples, raw [O, n]) with return_raw) for every slot named.  post: an OutputStage of
+        >= B rows (row = slot): every slot's playable chunk [n] (SynthesisStream.push) follows as a last element; a slot's filter runs on from push
+        to push and starts afresh at the first push after its open()."""
         if self.closed:
             raise RuntimeError('SlotSession: the session is closed')
         m, hp = self.model, self.model._hparams
@@ -239,13 +261,20 @@ class SlotSession(object):
         raw = torch.empty(self.B, hp.out_channels, pitch, device=m.device) if return_raw else None
         got = m.engine.slots_push(cc, frames, final, out, raw)
         assert got == n, (got, n)
+        chunk = None
+        if post is not None:
+            chunk = _post_push(post, post_output, out, n, [int(b in self._post_restart and b in items) for b in range(self.B)])
+            self._post_restart -= set(items)
         res = {}
         for b in items:
             self.pushed[b] += frames[b]
             self.done[b] += n[b] // self.hop
             if final[b]:
                 self.done[b] = None
-            res[b] = (out[b, :n[b]], raw[b, :, :n[b]]) if return_raw else out[b, :n[b]]
+            r = (out[b, :n[b]], raw[b, :, :n[b]]) if return_raw else (out[b, :n[b]],)
+            if post is not None:
+                r = r + (tuple(t[b, :n[b]] for t in chunk) if isinstance(chunk, tuple) else chunk[b, :n[b]],)
+            res[b] = r if len(r) > 1 else r[0]
         return res
 
     def abandon(self, slot):
@@ -506,7 +535,7 @@ class WaveNet(object):
 
     def incremental(self, initial_input, c=None, g=None, time_length=100, test_inputs=None, softmax=True, quantize=True,
                     log_scale_min=-7.0, log_scale_min_gauss=-7.0, noise=None, return_raw=False, check=False, chunk_frames=0,
-                    temperature=None, mixture_temperature=None):
+                    temperature=None, mixture_temperature=None, post=None):
         """Fast-WaveNet generation with ring-buffer queues: c [B,cin,Tc] -> samples [B,T] (wavenet.py:724-911).
         ``initial_input`` is accepted for signature parity; generation always starts from the reference's silence
         frame (wavenet.py:433-445).  ``noise`` [T,B,noise_per_step] may be supplied for reproducible draws.
@@ -515,7 +544,9 @@ class WaveNet(object):
         ``chunk_frames`` > 0: every group goes through a stream (wn_synth_stream_push) fed this many mel frames at a time -- the same samples,
         bit for bit (same seed and stream grouping), as the one call per group of chunk_frames = 0.
         ``temperature`` / ``mixture_temperature``: sampling temperature (temperature_pair; None: the hparams values), for device noise and for
-        ``noise`` alike; the fallback re-runs keep it."""
+        ``noise`` alike; the fallback re-runs keep it.
+        ``post``: an OutputStage of >= B rows: the whole utterances through its finish() -- (float32 [B, T] de-emphasised, int16 [B, T] peak-normalised
+        as save_wavenet_wav does), returned as a last element beside the samples."""
         hp = self._hparams
         pair = temperature_pair(hp, temperature, mixture_temperature)
         B, Tc = int(c.shape[0]), int(c.shape[-1])
@@ -630,10 +661,13 @@ class WaveNet(object):
             log('WaveNet synthesis path: {} ({} streams per run{})'.format(
                 self.engine.synth_path, group, '' if pair == (1.0, 1.0) else '; sampling temperature {:g}, choice temperature {:g}'.format(*pair)))
         self.upsampled_local_features = feats
-        return (out, raw) if return_raw else out
+        res = (out, raw) if return_raw else (out,)
+        if post is not None:
+            res = res + (post.finish(out, [T] * B),)
+        return res if len(res) > 1 else res[0]
 
     def folded(self, c_list, g=None, rows=20, warm=4, fade=2, min_keep=40, fade_kind='equal_power', temperature=None, mixture_temperature=None, noise=None,
-               test_inputs=None, return_rows=False, check=False):
+               test_inputs=None, return_rows=False, check=False, post=None):
         """Folded ("batched") generation: every utterance of c_list ([cin, F_u] mel frames each) is cut into overlapping rows, the rows run side by side as
         ONE batch -- each from a cold start, `warm` frames before the part it contributes -- and are cross-faded (`fade` frames; 'equal_power' or 'linear')
         back into one waveform per utterance on the device (wn_synthesize_folded).  rows: the number of rows of the run (<= 32; the planner, _ext.fold_plan,
@@ -644,7 +678,9 @@ class WaveNet(object):
         one-stream noise of seed + r).  check: wait and verify; a pipeline run that gave up on a hand-off is re-run ONCE on the launch-per-layer path.
         rows = 20 is the measured minimum of the wall time of a 5 s utterance on the paper model (profiles/fold_timing.json; 12 rows are within its spread).
         An utterance in one row is its one-shot run.  The defaults (~0.5 s per row, 50 ms warm-up, 25 ms fade at hop 275) follow WaveRNN practice; nobody
-        has listened to them on a trained model of this tree."""
+        has listened to them on a trained model of this tree.
+        post: an OutputStage with in_type 0 ('raw': the waveforms are decoded already) of >= len(c_list) rows: the waveforms through its finish(); a list of
+        (float32 de-emphasised, int16 peak-normalised) per utterance follows as a last element."""
         hp = self._hparams
         pair = temperature_pair(hp, temperature, mixture_temperature)
         hop = audio.get_hop_size(hp)
@@ -655,6 +691,8 @@ class WaveNet(object):
         for c in c_list:
             if c.dim() != 2 or int(c.shape[0]) != hp.cin_channels or int(c.shape[1]) < 1:
                 raise ValueError('WaveNet.folded: every utterance must be [cin={}, frames >= 1] (got {})'.format(hp.cin_channels, tuple(c.shape)))
+        if post is not None and post.in_type != 0:
+            raise ValueError("WaveNet.folded: post must be an output stage of in_type 'raw' (the folded waveform is decoded already)")
         if fade_kind not in _ext.FADE_KINDS:
             raise ValueError("WaveNet.folded: fade_kind must be 'equal_power' or 'linear' (got {!r})".format(fade_kind))
         try:
@@ -729,11 +767,22 @@ class WaveNet(object):
             self._logged_fold = (self.engine.synth_path, n_rows)
             log('WaveNet folded synthesis: {} utterance(s) in {} rows of <= {} samples, path {}'.format(U, n_rows, n_max, self.engine.synth_path))
         wavs = [wav[u, :frames[u] * hop] for u in range(U)]
+        posts = None
+        if post is not None:
+            py, pq = post.finish(wav, [f * hop for f in frames])
+            posts = [(py[u, :frames[u] * hop], pq[u, :frames[u] * hop]) for u in range(U)]
         if not return_rows:
-            return wavs
+            return wavs if post is None else (wavs, posts)
         feats = torch.empty(n_rows, hp.cin_channels, n_max, device=dev)
         self.engine.upsampled_features(feats)
-        return wavs, {'plan': plan, 'rows': out_rows, 'raw': out_raw, 'features': feats, 'seed': seed}
+        info = {'plan': plan, 'rows': out_rows, 'raw': out_raw, 'features': feats, 'seed': seed}
+        return (wavs, info) if post is None else (wavs, info, posts)
+
+    def output_stage(self, rows, **kw):
+        """An _ext.OutputStage of `rows` rows for this model's samples (in_type and de-emphasis from the hparams; gain: mi355_output_gain): the post=
+        argument of incremental / folded (in_type='raw') / SynthesisStream.push / SlotSession.push."""
+        kw.setdefault('gain', float(getattr(self._hparams, 'mi355_output_gain', 1.0)))
+        return _ext.OutputStage(self._hparams, rows, **kw)
 
     def slots(self, batch, steps_per_graph=None):
         """Open a SlotSession of `batch` slots (<= 32, the model's engine must have been built for them): independent utterances that join and

@@ -5,7 +5,9 @@ import os
 import numpy as np
 import torch
 
-from datasets.audio import get_hop_size, melspectrogram, save_wavenet_wav
+from scipy.io import wavfile
+
+from datasets.audio import get_hop_size, inv_preemphasis, melspectrogram, save_wavenet_wav
 from infolog import log
 from wavenet_vocoder import util
 from wavenet_vocoder.models import create_model
@@ -36,6 +38,34 @@ class Synthesizer(object):
             else:
                 self._state = torch.load(checkpoint_path, map_location='cpu')
         self._capacity = (0, 0)
+        self._post_stages = {}
+
+    def _output_mode(self):
+        """(device, k): whether the written wavs come from the device output stage (mi355_output_stage), and the de-emphasis coefficient they get
+        (mi355_output_deemphasis: hparams.preemphasis when the data was pre-emphasised; 0: written as generated).  The coefficient is the float32 value
+        the device filter multiplies by, on the host path too: the two paths then differ by rounding alone (0.97 as a double is 3e-8 away, which the
+        recursion amplifies to more int16 flips than all of the float32 arithmetic causes)."""
+        hparams = self._hparams
+        stage = str(getattr(hparams, 'mi355_output_stage', 'host'))
+        if stage not in ('host', 'device'):
+            raise ValueError("mi355_output_stage must be 'host' or 'device' (got {!r})".format(stage))
+        deem = bool(getattr(hparams, 'mi355_output_deemphasis', False)) and bool(hparams.preemphasize)
+        return stage == 'device', (float(np.float32(hparams.preemphasis)) if deem else 0.0)
+
+    def _stage(self, rows, in_type, k):
+        """The output stage of (in_type, k) with at least `rows` rows (kept: a stage is a handle with device state)."""
+        st = self._post_stages.get((in_type, k))
+        if st is None or st.rows < rows:
+            if st is not None:
+                st.close()
+            st = self._post_stages[(in_type, k)] = self.model.output_stage(rows, in_type=in_type, deemphasis=k)
+        return st
+
+    def _finish_device(self, wav, lengths, k):
+        """Decoded waveforms [B, pitch] on the device -> (de-emphasised float32, peak-normalised int16) per utterance on the host (OutputStage.finish)."""
+        y, q = self._stage(int(wav.shape[0]), 'raw', k).finish(wav.float().contiguous(), lengths)
+        y, q = y.cpu().numpy(), q.cpu().numpy()
+        return [y[b, :n] for b, n in enumerate(lengths)], [q[b, :n] for b, n in enumerate(lengths)]
 
     def _ensure_capacity(self, batch, time_steps):
         if batch <= self._capacity[0] and time_steps <= self._capacity[1]:
@@ -84,12 +114,12 @@ class Synthesizer(object):
         if nfold > 0 and int(getattr(hparams, 'mi355_synthesis_slots', 0)) > 0:
             raise ValueError('mi355_synthesis_fold_rows and mi355_synthesis_slots are both > 0: choose one')
         if nfold > 0 and not self.synth_debug:
-            generated_wavs, upsampled_features = self._synthesize_folded(c_batch, [len(x) for x in mel_spectrograms], speaker_ids, min(nfold, 32), log_dir is not None)
-            return self._write(generated_wavs, upsampled_features, mel_spectrograms, basenames, out_dir, log_dir)
+            generated_wavs, upsampled_features, pcm = self._synthesize_folded(c_batch, [len(x) for x in mel_spectrograms], speaker_ids, min(nfold, 32), log_dir is not None)
+            return self._write(generated_wavs, upsampled_features, mel_spectrograms, basenames, out_dir, log_dir, pcm)
         nslots = int(getattr(hparams, 'mi355_synthesis_slots', 0))
         if nslots > 0 and not self.synth_debug:
-            generated_wavs, upsampled_features = self._synthesize_slots(c_batch, [len(x) for x in mel_spectrograms], speaker_ids, min(nslots, 32), log_dir is not None)
-            return self._write(generated_wavs, upsampled_features, mel_spectrograms, basenames, out_dir, log_dir)
+            generated_wavs, upsampled_features, pcm = self._synthesize_slots(c_batch, [len(x) for x in mel_spectrograms], speaker_ids, min(nslots, 32), log_dir is not None)
+            return self._write(generated_wavs, upsampled_features, mel_spectrograms, basenames, out_dir, log_dir, pcm)
         self._ensure_capacity(len(c_batch), maxlen * hop)
         dev = self.model.device
         test_inputs = None
@@ -101,11 +131,16 @@ class Synthesizer(object):
         self.model.initialize(None, torch.from_numpy(c_batch).to(dev), None if g is None else g.to(dev), None, test_inputs=test_inputs)
         torch.cuda.synchronize()
         self.model.engine.synth_check()           # the generation is enqueued asynchronously: a pipeline hand-off timeout surfaces here
-        generated = self.model.tower_y_hat[0].float().cpu().numpy()
+        device, k = self._output_mode()
+        pcm = None
+        if device:
+            generated_wavs, pcm = self._finish_device(self.model.tower_y_hat[0], audio_lengths, k)
+        else:
+            generated = self.model.tower_y_hat[0].float().cpu().numpy()
+            generated_wavs = [w[:length] for w, length in zip(generated, audio_lengths)]
         feats = self.model.tower_synth_upsampled_local_features[0].cpu().numpy()
-        generated_wavs = [w[:length] for w, length in zip(generated, audio_lengths)]
         upsampled_features = [f[:, :length] for f, length in zip(feats, audio_lengths)]
-        return self._write(generated_wavs, upsampled_features, mel_spectrograms, basenames, out_dir, log_dir)
+        return self._write(generated_wavs, upsampled_features, mel_spectrograms, basenames, out_dir, log_dir, pcm)
 
     def _synthesize_folded(self, c_batch, lengths, speaker_ids, nrows, want_features):
         """mi355_synthesis_fold_rows > 0: the utterances of the call through WaveNet.folded, in groups of consecutive utterances whose rows fit nrows (every
@@ -121,17 +156,24 @@ class Synthesizer(object):
         caps = [fold_capacity([lengths[u] for u in grp], plan, hop) for grp, plan in zip(groups, plans)]
         self._ensure_capacity(max(c[0] for c in caps), max(c[1] for c in caps))
         wavs, ups = [], []
+        device, k = self._output_mode()
+        pcm = [] if device else None
         ids = None if not self.global_conditions else np.asarray(speaker_ids).reshape(-1)
         for grp, plan in zip(groups, plans):
             cl = [torch.from_numpy(np.ascontiguousarray(c_batch[u, :lengths[u]].T)) for u in grp]
-            res = self.model.folded(cl, g=None if ids is None else [int(ids[u]) for u in grp], rows=plan, check=True, return_rows=want_features)
+            res = self.model.folded(cl, g=None if ids is None else [int(ids[u]) for u in grp], rows=plan, check=True, return_rows=want_features,
+                                    post=self._stage(len(grp), 'raw', k) if device else None)
+            if device:          # the written waveform is the stage's: de-emphasised float32 for the plots, int16 for the file
+                posts = res[-1]
+                res = res[0] if len(res) == 2 else res[:2]
+                pcm += [q.cpu().numpy() for _, q in posts]
             if want_features:
                 res, info = res
                 ups += [f.cpu().numpy() for f in unfold_features(plan, info['features'], hop)]
             else:
                 ups += [np.zeros((hparams.cin_channels, 0), np.float32) for _ in grp]
-            wavs += [w.float().cpu().numpy() for w in res]
-        return wavs, ups
+            wavs += [w.float().cpu().numpy() for w in ([y for y, _ in posts] if device else res)]
+        return wavs, ups, pcm
 
     def _synthesize_slots(self, c_batch, lengths, speaker_ids, nslots, want_features):
         """mi355_synthesis_slots > 0: all utterances of the call through ONE slot session (WaveNet.slots): no utterance is padded to the longest of its
@@ -156,6 +198,8 @@ class Synthesizer(object):
         if pair != (1.0, 1.0) and getattr(self, '_logged_temperature', None) != pair:
             self._logged_temperature = pair
             log('WaveNet synthesis slots: sampling temperature {:g}, choice temperature {:g}'.format(*pair))
+        device, k = self._output_mode()
+        decode = self._stage(B, hparams.input_type, 0.0) if device else None      # per push: the decode alone; the whole utterance is finished below
         chunks = [[] for _ in lengths]
         feats = [[] for _ in lengths]
         owner, sent = [None] * B, [0] * len(lengths)
@@ -171,7 +215,9 @@ class Synthesizer(object):
                 blk = torch.from_numpy(np.ascontiguousarray(c_batch[u, sent[u]:sent[u] + frames[b]].T))
                 items[b] = (blk, final[b])
                 sent[u] += frames[b]
-            res = sess.push(items)
+            res = sess.push(items, post=decode, post_output='float')
+            if device:
+                res = {b: y for b, (_, y) in res.items()}
             fe = None
             if want_features:
                 n_max = max(int(v.shape[0]) for v in res.values())
@@ -188,24 +234,38 @@ class Synthesizer(object):
         torch.cuda.synchronize()
         sess.check()
         sess.close()
-        wavs, ups = [], []
+        wavs, ups, pcm = [], [], None
+        if device:
+            rows = torch.zeros(len(lengths), max(lengths) * hop, device=dev)
+            for u, n in enumerate(lengths):
+                if chunks[u]:
+                    rows[u, :n * hop] = torch.cat(chunks[u])
+            wavs, pcm = self._finish_device(rows, [n * hop for n in lengths], k)
         for u, n in enumerate(lengths):
-            out = torch.cat(chunks[u]) if chunks[u] else torch.zeros(0, device=dev)
-            assert out.shape[0] == n * hop, (u, out.shape, n * hop)
-            if is_mulaw_quantize(hparams.input_type):
-                out = wutil.inv_mulaw_quantize(out)
-            elif is_mulaw(hparams.input_type):
-                out = wutil.inv_mulaw(out)
-            wavs.append(out.float().cpu().numpy())
+            if not device:
+                out = torch.cat(chunks[u]) if chunks[u] else torch.zeros(0, device=dev)
+                assert out.shape[0] == n * hop, (u, out.shape, n * hop)
+                if is_mulaw_quantize(hparams.input_type):
+                    out = wutil.inv_mulaw_quantize(out)
+                elif is_mulaw(hparams.input_type):
+                    out = wutil.inv_mulaw(out)
+                wavs.append(out.float().cpu().numpy())
             ups.append(torch.cat(feats[u], 1).cpu().numpy() if feats[u] else np.zeros((hparams.cin_channels, 0), np.float32))
-        return wavs, ups
+        return wavs, ups, pcm
 
-    def _write(self, generated_wavs, upsampled_features, mel_spectrograms, basenames, out_dir, log_dir):
+    def _write(self, generated_wavs, upsampled_features, mel_spectrograms, basenames, out_dir, log_dir, pcm=None):
+        """pcm: the device output stage's int16 per utterance (mi355_output_stage = 'device': generated_wavs are its de-emphasised floats); None: the host path."""
         hparams = self._hparams
+        k = self._output_mode()[1]
         audio_filenames = []
         for i, (wav, feat, input_mel) in enumerate(zip(generated_wavs, upsampled_features, mel_spectrograms)):
             audio_filename = os.path.join(out_dir, 'wavenet-audio-{}.wav'.format(basenames[i]))
-            save_wavenet_wav(wav, audio_filename, sr=hparams.sample_rate, inv_preemphasize=hparams.preemphasize, k=hparams.preemphasis)
+            if pcm is not None:
+                wavfile.write(audio_filename, hparams.sample_rate, pcm[i])
+            else:
+                if k != 0.0:
+                    wav = inv_preemphasis(wav, k).astype(np.float32)
+                save_wavenet_wav(wav, audio_filename, sr=hparams.sample_rate, inv_preemphasize=hparams.preemphasize, k=hparams.preemphasis)
             audio_filenames.append(audio_filename)
             if log_dir is not None:
                 try:
