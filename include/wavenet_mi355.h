@@ -495,6 +495,48 @@ int wn_post_push(wn_post* p, const void* in, int64_t in_pitch, const int32_t* n,
 int wn_post_finish(wn_post* p, const void* in, int64_t in_pitch, const int32_t* n, int32_t B,
                    float* out_f32, int16_t* out_pcm, int64_t out_pitch, float* peak, void* stream);
 
+/* ---- reconstruction check: how far the mel-spectrogram a of a generated signal is from the conditioning b it was generated from ----
+ * A handle of its own, independent of the model context, like the mel analysis and the output stage: it takes any two device mel buffers, each
+ * channels-first [B, num_mels, pitch] (how the synthesis calls take c, and the analysis' channels-first output) or channels-last [B, pitch, num_mels]
+ * (the mel-*.npy layout), pitch >= the longest row; row b compares its first frames[b] frames and elements at f >= frames[b] are never read into a
+ * result.  All float32, every operation rounded on its own except the dot products, which are fused multiply-adds in channel order.  D is the
+ * orthonormal DCT-II table D[k][m] = sqrt(2 / M) cos(pi k (m + 1/2) / M), M = num_mels, formed in double on the host, rounded to float32.  Per frame
+ *   d[m] = unit_db * (a[m] - b[m])
+ *   0 bias = mean_m d[m]          1 l1  = mean_m |d[m]|          2 lsd  = sqrt(mean_m d[m]^2)
+ *   3 mcd  = sqrt(0.5 * sum_{k = 1 ... n_cep} (sum_m D[k][m] d[m])^2)
+ *   4 l1c  = mean_m |d[m] - bias_b|                              5 lsdc = sqrt(mean_m (d[m] - bias_b)^2)
+ * with bias_b the mean of row b's bias over its frames: the level offset of the utterance, which the compensated distances 4 and 5 leave out.  mcd in
+ * the usual units: for mels that are 20 log10 of an amplitude, d = (20 / ln 10) e with e the difference of the log amplitudes, so the DCT coefficients
+ * are c_k = (20 / ln 10) dc_k, and the customary (10 / ln 10) sqrt(2 sum_k dc_k^2) = (10 / ln 10) (ln 10 / 20) sqrt(2 sum_k c_k^2) = sqrt(0.5 sum_k c_k^2).
+ * Coefficient 0 (the level) is left out.  Outputs: per_frame[b][j][f], j = 0 ... 5 as numbered; summary[b] = the mean over the row's frames of each of
+ * the six, then worst = max_f l1c; marks[b] = the frame of worst (the first maximum; -1 for an empty row), then the number of frames with
+ * l1c > alarm_db.  An empty row gives zeros and -1.  Three passes over launch groups of 32 rows on the caller's stream, no host synchronisation: the
+ * per-frame 0 ... 3; bias_b and the means of 0 ... 3; 4 and 5 with the remaining reductions.  Two reads of a and b in all, every one coalesced in
+ * either layout (a workgroup stages 64 frames x num_mels through LDS and sums over channels from there in one order).  Reductions run in a fixed
+ * order without atomics: the 6 F + 7 + 2 results of a row depend on that row's own frames alone -- not on B, its index, the launch group, the
+ * pitches, the layouts, per_frame being asked for, or the run -- bit for bit.  The DCT table and the per-frame scratch [max_batch, 6, max_frames]
+ * that stands in for a NULL per_frame are reserved at creation; no run allocates or synchronises, and frames travel as kernel arguments (the
+ * host array is free when the call returns).  max_batch = 0 makes a validation-only handle that touches no device and refuses every run.
+ * Validation before any device call: WN_E_ARG for a null pointer, a foreign abi_version, num_mels outside 1 ... 128, n_cep outside
+ * [0, num_mels - 1], unit_db not finite or <= 0, alarm_db not finite or < 0, a negative max_batch or max_frames, B < 1, a negative frames[b];
+ * WN_E_SHAPE for B > max_batch, frames[b] > max_frames, or a pitch (either input's, or out_pitch with per_frame given) smaller than the longest row. */
+typedef struct wn_melcmp_config {
+    int32_t abi_version;   /* = WN_ABI_VERSION */
+    int32_t num_mels;      /* 1 ... 128 (the mel analysis' limit) */
+    int32_t n_cep;         /* cepstral coefficients 1 ... n_cep of the distance, 0 <= n_cep <= num_mels - 1; 0: mcd is 0 */
+    float   unit_db;       /* level units per unit of the inputs, finite, > 0 (normalised mels: -min_level_db / (2 max_abs_value) resp. / max_abs_value; 1 otherwise) */
+    float   alarm_db;      /* finite, >= 0: a frame counts as alarmed when its l1c exceeds it */
+    int32_t max_batch;     /* rows per call; 0: a validation-only handle that touches no device and refuses every run */
+    int32_t max_frames;    /* frames per row (sizes the handle's per-frame scratch) */
+} wn_melcmp_config;
+typedef struct wn_melcmp wn_melcmp;
+int  wn_melcmp_create(const wn_melcmp_config* cfg, wn_melcmp** out);
+void wn_melcmp_destroy(wn_melcmp* h);
+const char* wn_melcmp_last_error(const wn_melcmp* h);   /* NULL: text of the last failed create */
+/* a, b: device float; frames: HOST int32 [B]; per_frame: device float [B, 6, out_pitch] or NULL; summary: device float [B, 7]; marks: device int32 [B, 2] */
+int  wn_melcmp_run(wn_melcmp* h, const float* a, int32_t a_channels_first, int64_t a_pitch, const float* b, int32_t b_channels_first, int64_t b_pitch,
+                   const int32_t* frames, int32_t B, float* per_frame, int64_t out_pitch, float* summary, int32_t* marks, void* stream);
+
 /* ---- introspection ------------------------------------------------------------------------------ */
 int64_t wn_workspace_bytes(const wn_ctx* ctx);
 /* name of the kernel that dominates training time (bench.py's roofline line names it) */
@@ -565,6 +607,11 @@ int wn_test_fold_times(wn_ctx* ctx, double ms[3]);
  * (cfg->gain is validated and not used).  out_f32 / out_pcm [n] and carry_out (y[n - 1]; carry_in for n = 0) are each optional.  WN_E_ARG as wn_post_create,
  * for in = NULL with n > 0, and for n < 0. */
 int wn_test_post_host(const wn_post_config* cfg, const void* in, int64_t n, float carry_in, float pcm_scale, float* out_f32, int16_t* out_pcm, float* carry_out);
+/* the reconstruction check on the host (no handle, no GPU): the arguments of a run with every pointer in HOST memory, evaluated by the very per-frame
+ * and reduction functions the kernels inline (csrc/wn_melcmp.h), in the device's order: the same bits.  cfg->max_batch / max_frames of 0 here mean B and
+ * the longest row.  Validates as a create followed by a run. */
+int wn_test_melcmp_host(const wn_melcmp_config* cfg, const float* a, int32_t a_channels_first, int64_t a_pitch, const float* b, int32_t b_channels_first,
+                        int64_t b_pitch, const int32_t* frames, int32_t B, float* per_frame, int64_t out_pitch, float* summary, int32_t* marks);
 #endif /* WN_NO_TEST_HOOKS */
 
 #ifdef __cplusplus

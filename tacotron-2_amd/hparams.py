@@ -98,6 +98,11 @@ MI355 = dict(
     mi355_output_stage='host',         # 'host': audio.inv_preemphasis + save_wavenet_wav on numpy; 'device': decode, de-emphasis, peak normalisation and the int16
                                        # cast on the device (csrc/wn_post.hip, OutputStage.finish) on every synthesis route; the same files without de-emphasis
     mi355_output_gain=1.0,             # gain of the playable chunks of streams and slot sessions (WaveNet.output_stage): PCM = y * gain * 32767, clamped
+    mi355_reconstruction_check=False,  # True: every utterance Synthesizer.synthesize generates (all three routes) and the item eval_step generates is analysed as preprocessing
+                                       # analyses a recording and compared with its conditioning on the device (csrc/wn_melcmp.hip): one row per utterance appended to
+                                       # wavs/reconstruction.tsv, one log line, two scalars beside the eval loss.  The wavs, map.txt and plots are byte-identical either way
+    mi355_reconstruction_alarm_db=6.0, # a frame whose level-compensated mean |difference| exceeds this counts as alarmed.  A guess: nobody has a trained checkpoint of this tree,
+                                       # so what a good model scores is unknown; set it from the clean score of your own model
     mi355_steps_per_graph=0,       # synthesis path: 0 = the persistent dataflow pipeline (real time at 22.05 kHz) whenever the model fits it, else the
                                    # launch-per-layer path with 32 steps per hipGraph replay; N > 0 = that path with N steps per replay
     mi355_synthetic_data=False,    # train on LJSpeech-shaped synthetic tensors (no dataset on disk)

@@ -67,6 +67,11 @@ class WnPostConfig(ctypes.Structure):
     _fields_ = [('abi_version', ctypes.c_int32), ('max_rows', ctypes.c_int32), ('in_type', ctypes.c_int32), ('deemphasis', ctypes.c_float), ('gain', ctypes.c_float)]
 
 
+class WnMelcmpConfig(ctypes.Structure):
+    _fields_ = [('abi_version', ctypes.c_int32), ('num_mels', ctypes.c_int32), ('n_cep', ctypes.c_int32), ('unit_db', ctypes.c_float), ('alarm_db', ctypes.c_float),
+                ('max_batch', ctypes.c_int32), ('max_frames', ctypes.c_int32)]
+
+
 class WnFoldRow(ctypes.Structure):
     """wn_fold_row: one row of a folded run, in mel frames of utterance `utt`."""
     _fields_ = [('utt', ctypes.c_int32), ('first', ctypes.c_int32), ('frames', ctypes.c_int32), ('keep', ctypes.c_int32), ('fade', ctypes.c_int32)]
@@ -185,6 +190,11 @@ def load_library():
         'wn_post_push': (ctypes.c_int, [vp, vp, i64, ctypes.POINTER(i32), ctypes.POINTER(i32), i32, vp, vp, i64, vp, vp]),
         'wn_post_finish': (ctypes.c_int, [vp, vp, i64, ctypes.POINTER(i32), i32, vp, vp, i64, vp, vp]),
         'wn_test_post_host': (ctypes.c_int, [ctypes.POINTER(WnPostConfig), vp, i64, f32, f32, vp, vp, ctypes.POINTER(f32)]),
+        'wn_melcmp_create': (ctypes.c_int, [ctypes.POINTER(WnMelcmpConfig), ctypes.POINTER(vp)]),
+        'wn_melcmp_destroy': (None, [vp]),
+        'wn_melcmp_last_error': (ctypes.c_char_p, [vp]),
+        'wn_melcmp_run': (ctypes.c_int, [vp, vp, i32, i64, vp, i32, i64, ctypes.POINTER(i32), i32, vp, i64, vp, vp, vp]),
+        'wn_test_melcmp_host': (ctypes.c_int, [ctypes.POINTER(WnMelcmpConfig), vp, i32, i64, vp, i32, i64, ctypes.POINTER(i32), i32, vp, i64, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)            # AttributeError here == ABI symbol missing
@@ -986,6 +996,110 @@ class OutputStage:
     def close(self):
         if getattr(self, 'h', None):
             self.lib.wn_post_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+MELCMP_KINDS = ('bias', 'l1', 'lsd', 'mcd', 'l1c', 'lsdc')      # per_frame[b][j], and summary[b][j]; summary[b][6] is worst
+
+
+def melcmp_unit_db(hp):
+    """level units (dB) per unit of a mel as hparams normalise it (datasets.audio._normalize): the symmetric range spans -min_level_db over
+    2 max_abs_value, the asymmetric one over max_abs_value; an unnormalised mel is in dB already."""
+    if not hp.signal_normalization:
+        return 1.0
+    return -float(hp.min_level_db) / ((2.0 if hp.symmetric_mels else 1.0) * float(hp.max_abs_value))
+
+
+def melcmp_config(num_mels, n_cep=13, unit_db=1.0, alarm_db=0.0, max_batch=0, max_frames=0):
+    cfg = WnMelcmpConfig()
+    cfg.abi_version = WN_ABI_VERSION
+    cfg.num_mels, cfg.n_cep, cfg.unit_db, cfg.alarm_db = int(num_mels), int(n_cep), float(unit_db), float(alarm_db)
+    cfg.max_batch, cfg.max_frames = int(max_batch), int(max_frames)
+    return cfg
+
+
+def _melcmp_geometry(t, channels_first, num_mels, name):
+    if t.ndim != 3 or int(t.shape[1 if channels_first else 2]) != num_mels:
+        raise ValueError('%s must be %s (got %r)' % (name, '[B, num_mels, pitch]' if channels_first else '[B, pitch, num_mels]', tuple(t.shape)))
+    return int(t.shape[0]), int(t.shape[2 if channels_first else 1])
+
+
+def melcmp_host(a, b, frames, num_mels=None, n_cep=13, unit_db=1.0, alarm_db=0.0, a_channels_first=True, b_channels_first=True, per_frame=True, out_pitch=None):
+    """wn_test_melcmp_host: the reconstruction check on the host (no handle, no GPU), in the device's order.  a, b: numpy float32, each
+    [B, num_mels, pitch] (channels_first) or [B, pitch, num_mels].  Returns a dict: summary float32 [B, 7], marks int32 [B, 2] and, with per_frame,
+    per_frame float32 [B, 6, out_pitch] (elements beyond a row's frames keep the NaN they are created with)."""
+    a, b = np.ascontiguousarray(a, dtype=np.float32), np.ascontiguousarray(b, dtype=np.float32)
+    M = int(a.shape[1 if a_channels_first else 2]) if num_mels is None else int(num_mels)
+    B, ap = _melcmp_geometry(a, a_channels_first, M, 'a')
+    B2, bp = _melcmp_geometry(b, b_channels_first, M, 'b')
+    fr = [int(f) for f in frames]
+    if B2 != B or len(fr) != B:
+        raise ValueError('a, b and frames must have one entry per row')
+    cfg = melcmp_config(M, n_cep, unit_db, alarm_db)
+    op = max(fr + [0]) if out_pitch is None else int(out_pitch)
+    pf = np.full((B, 6, op), np.nan, np.float32) if per_frame else None
+    sm, mk = np.full((B, 7), np.nan, np.float32), np.full((B, 2), -7, np.int32)
+    vp = ctypes.c_void_p
+    rc = load_library().wn_test_melcmp_host(ctypes.byref(cfg), a.ctypes.data_as(vp), int(bool(a_channels_first)), ap, b.ctypes.data_as(vp), int(bool(b_channels_first)), bp,
+                                            (ctypes.c_int32 * B)(*fr), B, pf.ctypes.data_as(vp) if per_frame else None, op, sm.ctypes.data_as(vp), mk.ctypes.data_as(vp))
+    if rc != 0:
+        raise WnError(rc, (load_library().wn_melcmp_last_error(None) or b'').decode())
+    res = {'summary': sm, 'marks': mk}
+    if per_frame:
+        res['per_frame'] = pf
+    return res
+
+
+class MelCompare:
+    """One wn_melcmp: distances between two mel-spectrograms per frame and per row on the current device (csrc/wn_melcmp.hip), asynchronously.
+    max_batch = 0 gives a validation-only handle (no device; every run is refused)."""
+
+    def __init__(self, num_mels, max_batch, max_frames, n_cep=13, unit_db=1.0, alarm_db=0.0):
+        self.lib = load_library()
+        self.cfg = melcmp_config(num_mels, n_cep, unit_db, alarm_db, max_batch, max_frames)
+        h = ctypes.c_void_p()
+        rc = self.lib.wn_melcmp_create(ctypes.byref(self.cfg), ctypes.byref(h))
+        if rc != 0:
+            raise WnError(rc, (self.lib.wn_melcmp_last_error(None) or b'').decode())
+        self.h = h
+        self.num_mels, self.n_cep, self.max_batch, self.max_frames = int(num_mels), int(n_cep), int(max_batch), int(max_frames)
+        self.unit_db, self.alarm_db = float(self.cfg.unit_db), float(self.cfg.alarm_db)
+
+    def _ok(self, rc):
+        if rc != 0:
+            raise WnError(rc, (self.lib.wn_melcmp_last_error(self.h) or b'').decode())
+
+    def run(self, a, b, frames, a_channels_first=True, b_channels_first=True, per_frame=False):
+        """a, b float32 on the device, each [B, num_mels, pitch] (channels_first) or [B, pitch, num_mels]; frames: B ints (host).  Returns a dict of
+        device tensors: 'summary' float32 [B, 7] (the means of MELCMP_KINDS, then worst), 'marks' int32 [B, 2] (worst frame, alarmed frames) and, with
+        per_frame, 'per_frame' float32 [B, 6, pitch of the longest row] (elements beyond a row's frames are zero)."""
+        import torch
+        _check(a, torch.float32, 'a'); _check(b, torch.float32, 'b')
+        B, ap = _melcmp_geometry(a, a_channels_first, self.num_mels, 'a')
+        B2, bp = _melcmp_geometry(b, b_channels_first, self.num_mels, 'b')
+        fr = [int(f) for f in frames]
+        if B2 != B or len(fr) != B:
+            raise ValueError('a, b and frames must have one entry per row')
+        op = max(fr + [0])
+        pf = torch.zeros(B, 6, op, dtype=torch.float32, device=a.device) if per_frame else None
+        sm = torch.zeros(B, 7, dtype=torch.float32, device=a.device)
+        mk = torch.zeros(B, 2, dtype=torch.int32, device=a.device)
+        self._ok(self.lib.wn_melcmp_run(self.h, _ptr(a), int(bool(a_channels_first)), ap, _ptr(b), int(bool(b_channels_first)), bp, (ctypes.c_int32 * B)(*fr), B,
+                                        _ptr(pf), op, _ptr(sm), _ptr(mk), _stream()))
+        res = {'summary': sm, 'marks': mk}
+        if per_frame:
+            res['per_frame'] = pf
+        return res
+
+    def close(self):
+        if getattr(self, 'h', None):
+            self.lib.wn_melcmp_destroy(self.h)
             self.h = None
 
     def __del__(self):

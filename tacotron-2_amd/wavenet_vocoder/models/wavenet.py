@@ -784,6 +784,14 @@ class WaveNet(object):
         kw.setdefault('gain', float(getattr(self._hparams, 'mi355_output_gain', 1.0)))
         return _ext.OutputStage(self._hparams, rows, **kw)
 
+    def reconstruction_check(self, rows, max_samples, preemphasis=None, alarm_db=None):
+        """A ReconstructionCheck (wavenet_vocoder/reconstruction.py) for up to `rows` utterances of up to `max_samples` samples of this model: the
+        mel of generated audio against the conditioning it was generated from, per frame and per utterance, on the device.  preemphasis None:
+        hparams.preemphasis if hparams.preemphasize else 0, as preprocessing analyses; alarm_db None: mi355_reconstruction_alarm_db.  ValueError when
+        cin_channels != num_mels (the conditioning is no mel of this analysis)."""
+        from wavenet_vocoder.reconstruction import ReconstructionCheck
+        return ReconstructionCheck(self._hparams, rows, max_samples, preemphasis=preemphasis, alarm_db=alarm_db)
+
     def slots(self, batch, steps_per_graph=None):
         """Open a SlotSession of `batch` slots (<= 32, the model's engine must have been built for them): independent utterances that join and
         leave one running batch."""

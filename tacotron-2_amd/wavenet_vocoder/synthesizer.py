@@ -39,6 +39,7 @@ class Synthesizer(object):
                 self._state = torch.load(checkpoint_path, map_location='cpu')
         self._capacity = (0, 0)
         self._post_stages = {}
+        self._recon = None
 
     def _output_mode(self):
         """(device, k): whether the written wavs come from the device output stage (mi355_output_stage), and the de-emphasis coefficient they get
@@ -66,6 +67,33 @@ class Synthesizer(object):
         y, q = self._stage(int(wav.shape[0]), 'raw', k).finish(wav.float().contiguous(), lengths)
         y, q = y.cpu().numpy(), q.cpu().numpy()
         return [y[b, :n] for b, n in enumerate(lengths)], [q[b, :n] for b, n in enumerate(lengths)]
+
+    def _reconstruction(self, decoded, generated_wavs, cond, lengths, basenames, out_dir):
+        """mi355_reconstruction_check: every utterance of the call scored against its conditioning (WaveNet.reconstruction_check), one row each appended to
+        <out_dir>/reconstruction.tsv and one log line.  decoded: the decoded model-domain samples [B, >= lengths[b] * hop] on the device (the device output
+        stage's input), or None on the host path: then what is about to be written, generated_wavs, is uploaded.  cond: [B, Tc, num_mels], the
+        conditioning as the analysis scales it (clipped, before normalize_for_wavenet).  Reads results only: nothing the call writes otherwise changes."""
+        if not bool(getattr(self._hparams, 'mi355_reconstruction_check', False)):
+            return None
+        from wavenet_vocoder import reconstruction
+        hop = get_hop_size(self._hparams)
+        dev = self.model.device
+        n = [int(f) * hop for f in lengths]
+        if decoded is None:
+            host = np.zeros((len(n), max(n)), np.float32)
+            for b, w in enumerate(generated_wavs):
+                host[b, :n[b]] = np.asarray(w, np.float32)[:n[b]]
+            decoded = torch.from_numpy(host).to(dev)
+        decoded = decoded.float().contiguous()
+        chk = self._recon
+        if chk is None or chk.rows < len(n) or chk.max_samples < max(n):
+            if chk is not None:
+                chk.close()
+            chk = self._recon = self.model.reconstruction_check(max(len(n), chk.rows if chk else 0), max(max(n), chk.max_samples if chk else 0))
+        table = chk.score(decoded, n, torch.from_numpy(np.ascontiguousarray(cond, dtype=np.float32)).to(dev), frames=list(lengths), c_channels_first=False)
+        reconstruction.append_tsv(os.path.join(out_dir, 'reconstruction.tsv'), basenames, lengths, table)
+        log(reconstruction.log_line(basenames, table))
+        return table
 
     def _ensure_capacity(self, batch, time_steps):
         if batch <= self._capacity[0] and time_steps <= self._capacity[1]:
@@ -102,6 +130,7 @@ class Synthesizer(object):
         if hparams.clip_for_wavenet:
             mel_spectrograms = [np.clip(x, T2_output_range[0], T2_output_range[1]) for x in mel_spectrograms]
         c_batch = np.stack([_pad_inputs(x, maxlen, _pad=T2_output_range[0]) for x in mel_spectrograms]).astype(np.float32)
+        cond, frames = c_batch, [len(x) for x in mel_spectrograms]          # the conditioning in the analysis' own scale: what a reconstruction check compares with
         if hparams.normalize_for_wavenet:
             c_batch = _interp(c_batch, T2_output_range).astype(np.float32)
         # global condition: int32 speaker ids [B, 1] (reference synthesizer.py:72)
@@ -114,11 +143,13 @@ class Synthesizer(object):
         if nfold > 0 and int(getattr(hparams, 'mi355_synthesis_slots', 0)) > 0:
             raise ValueError('mi355_synthesis_fold_rows and mi355_synthesis_slots are both > 0: choose one')
         if nfold > 0 and not self.synth_debug:
-            generated_wavs, upsampled_features, pcm = self._synthesize_folded(c_batch, [len(x) for x in mel_spectrograms], speaker_ids, min(nfold, 32), log_dir is not None)
+            generated_wavs, upsampled_features, pcm, decoded = self._synthesize_folded(c_batch, frames, speaker_ids, min(nfold, 32), log_dir is not None)
+            self._reconstruction(decoded, generated_wavs, cond, frames, basenames, out_dir)
             return self._write(generated_wavs, upsampled_features, mel_spectrograms, basenames, out_dir, log_dir, pcm)
         nslots = int(getattr(hparams, 'mi355_synthesis_slots', 0))
         if nslots > 0 and not self.synth_debug:
-            generated_wavs, upsampled_features, pcm = self._synthesize_slots(c_batch, [len(x) for x in mel_spectrograms], speaker_ids, min(nslots, 32), log_dir is not None)
+            generated_wavs, upsampled_features, pcm, decoded = self._synthesize_slots(c_batch, frames, speaker_ids, min(nslots, 32), log_dir is not None)
+            self._reconstruction(decoded, generated_wavs, cond, frames, basenames, out_dir)
             return self._write(generated_wavs, upsampled_features, mel_spectrograms, basenames, out_dir, log_dir, pcm)
         self._ensure_capacity(len(c_batch), maxlen * hop)
         dev = self.model.device
@@ -140,6 +171,8 @@ class Synthesizer(object):
             generated_wavs = [w[:length] for w, length in zip(generated, audio_lengths)]
         feats = self.model.tower_synth_upsampled_local_features[0].cpu().numpy()
         upsampled_features = [f[:, :length] for f, length in zip(feats, audio_lengths)]
+        if not self.synth_debug:
+            self._reconstruction(self.model.tower_y_hat[0] if device else None, generated_wavs, cond, frames, basenames, out_dir)
         return self._write(generated_wavs, upsampled_features, mel_spectrograms, basenames, out_dir, log_dir, pcm)
 
     def _synthesize_folded(self, c_batch, lengths, speaker_ids, nrows, want_features):
@@ -158,6 +191,8 @@ class Synthesizer(object):
         wavs, ups = [], []
         device, k = self._output_mode()
         pcm = [] if device else None
+        check = device and bool(getattr(hparams, 'mi355_reconstruction_check', False))
+        decoded = torch.zeros(len(lengths), max(lengths) * hop, device=self.model.device) if check else None      # out_wav of every group, kept on the device
         ids = None if not self.global_conditions else np.asarray(speaker_ids).reshape(-1)
         for grp, plan in zip(groups, plans):
             cl = [torch.from_numpy(np.ascontiguousarray(c_batch[u, :lengths[u]].T)) for u in grp]
@@ -166,6 +201,9 @@ class Synthesizer(object):
             if device:          # the written waveform is the stage's: de-emphasised float32 for the plots, int16 for the file
                 posts = res[-1]
                 res = res[0] if len(res) == 2 else res[:2]
+                if check:
+                    for u, w in zip(grp, res[0] if want_features else res):
+                        decoded[u, :w.shape[0]] = w
                 pcm += [q.cpu().numpy() for _, q in posts]
             if want_features:
                 res, info = res
@@ -173,7 +211,7 @@ class Synthesizer(object):
             else:
                 ups += [np.zeros((hparams.cin_channels, 0), np.float32) for _ in grp]
             wavs += [w.float().cpu().numpy() for w in ([y for y, _ in posts] if device else res)]
-        return wavs, ups, pcm
+        return wavs, ups, pcm, decoded
 
     def _synthesize_slots(self, c_batch, lengths, speaker_ids, nslots, want_features):
         """mi355_synthesis_slots > 0: all utterances of the call through ONE slot session (WaveNet.slots): no utterance is padded to the longest of its
@@ -234,7 +272,7 @@ class Synthesizer(object):
         torch.cuda.synchronize()
         sess.check()
         sess.close()
-        wavs, ups, pcm = [], [], None
+        wavs, ups, pcm, rows = [], [], None, None
         if device:
             rows = torch.zeros(len(lengths), max(lengths) * hop, device=dev)
             for u, n in enumerate(lengths):
@@ -251,7 +289,7 @@ class Synthesizer(object):
                     out = wutil.inv_mulaw(out)
                 wavs.append(out.float().cpu().numpy())
             ups.append(torch.cat(feats[u], 1).cpu().numpy() if feats[u] else np.zeros((hparams.cin_channels, 0), np.float32))
-        return wavs, ups, pcm
+        return wavs, ups, pcm, rows      # rows: every utterance's decoded chunks, kept on the device until it finished (None on the host path)
 
     def _write(self, generated_wavs, upsampled_features, mel_spectrograms, basenames, out_dir, log_dir, pcm=None):
         """pcm: the device output stage's int16 per utterance (mi355_output_stage = 'device': generated_wavs are its de-emphasised floats); None: the host path."""

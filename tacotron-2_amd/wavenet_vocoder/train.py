@@ -241,8 +241,34 @@ def eval_step(model, batch, step, plot_dir, wav_dir, scalars, hparams, model_nam
     except Exception as e:
         log('plotting skipped: {}'.format(e))
     log('Eval loss for global step {}: {:.3f}'.format(step, loss))
-    scalars.write(json.dumps({'step': step, 'Wavenet_eval_model/eval_stats/wavenet_eval_loss': loss}) + '\n'); scalars.flush()
+    row = {'step': step, 'Wavenet_eval_model/eval_stats/wavenet_eval_loss': loss}
+    if bool(getattr(hparams, 'mi355_reconstruction_check', False)):
+        try:
+            row.update(_reconstruction_scalars(model, hparams))
+        except Exception as e:      # like the plotting: never kills a training run
+            log('reconstruction check skipped: {}'.format(e))
+    scalars.write(json.dumps(row) + '\n'); scalars.flush()
     return loss
+
+
+def _reconstruction_scalars(model, hparams):
+    """The generated item of eval_step scored against its conditioning on the device (WaveNet.reconstruction_check): the number behind the
+    reconstruction plot.  The feeder hands the model c scaled to [0, 1] under normalize_for_wavenet; the analysis writes hparams' mel range."""
+    wav = model.tower_y_hat[0].float().reshape(1, -1).contiguous()
+    c = model.tower_eval_c[0].float().unsqueeze(0)                      # [cin, Tc] of item 0, as initialize() stores it
+    if hparams.normalize_for_wavenet:
+        lo, hi = (-hparams.max_abs_value, hparams.max_abs_value) if hparams.symmetric_mels else (0, hparams.max_abs_value)
+        c = c * (hi - lo) + lo
+    n = int(wav.shape[1])
+    chk = model.reconstruction_check(1, n)
+    try:
+        frames = min(n // chk.hop, int(c.shape[2]))
+        t = chk.score(wav, [n], c.contiguous(), frames=[frames])[0]
+    finally:
+        chk.close()
+    log('Eval reconstruction: bias {:+.2f} dB, l1c {:.2f} dB, mcd {:.2f} dB over {} frames (worst frame {} at {:.2f} dB)'.format(t[0], t[4], t[3], frames, int(t[7]), t[6]))
+    return {'Wavenet_eval_model/eval_stats/wavenet_eval_reconstruction_l1c_db': float(t[4]),
+            'Wavenet_eval_model/eval_stats/wavenet_eval_reconstruction_mcd_db': float(t[3])}
 
 
 def validation_step(model, feeder, step, scalars, hparams):
