@@ -537,6 +537,42 @@ const char* wn_melcmp_last_error(const wn_melcmp* h);   /* NULL: text of the las
 int  wn_melcmp_run(wn_melcmp* h, const float* a, int32_t a_channels_first, int64_t a_pitch, const float* b, int32_t b_channels_first, int64_t b_pitch,
                    const int32_t* frames, int32_t B, float* per_frame, int64_t out_pitch, float* summary, int32_t* marks, void* stream);
 
+/* ---- training summaries: histograms and per-tensor norms on the device ---------------------------
+ * What the reference's add_train_stats writes every summary_interval steps (wavenet_vocoder/train.py:41-56: tf.summary.histogram of the decoded outputs,
+ * the targets, the Gaussian head's means and log-scales and of the per-variable gradient norms, and max_gradient_norm = the largest of those norms) needs two
+ * reductions: the histogram of a ragged batch and the L2 norm of every tensor of a flat buffer.  This module does both where the data is, with its own
+ * handle and no context.  Histogram: TensorFlow's default summary buckets -- WN_HIST_BUCKETS ascending limits (wn_stats_hist_limits); a finite float32 x
+ * belongs to the bucket of the first limit strictly greater than x widened to double -- plus summary[8] = {num, min, max, sum, sum_squares, n_nan, n_pos_inf,
+ * n_neg_inf}; non-finite values enter their counter and nothing else, elements beyond lengths[b] and in the pitch gap are never read, an empty histogram
+ * has min = max = 0.  Row b is x + b * pitch, so a pointer offset and a pitch address one channel of a [B, O, T] tensor.  Per-tensor statistics: a table of
+ * disjoint (offset, count) runs of a flat float32 buffer, set once; per run out[nt, 4] = {sum of squares, max |x|, non-finite count, element count}, the
+ * first two over the finite elements.  Every sum is a double in a fixed order (csrc/wn_stats.h): results are bit-identical from run to run and to the host
+ * hooks; no float atomics, nothing waits across workgroups (a store pass and a sum pass per call).  Outputs are written whole: nothing to clear.  After
+ * wn_stats_create nothing allocates and every run is asynchronous on `stream` (wn_stats_set_tensors copies its table synchronously).
+ * Validation before any device call: WN_E_ARG for a null pointer, a foreign abi_version, a negative size (max_rows or max_tensors above 65535, max_time < 1
+ * with max_rows > 0), B < 1, T < 1, nt < 1, a count <= 0, a negative offset, overlapping tensors; WN_E_SHAPE for B > max_rows, T > max_time, pitch < T,
+ * nt > max_tensors, and for a tensor run on a validation-only handle; WN_E_STATE for wn_stats_tensors before wn_stats_set_tensors. */
+#define WN_HIST_BUCKETS 1551
+typedef struct wn_stats_config {
+    int32_t abi_version;   /* = WN_ABI_VERSION */
+    int32_t max_rows;      /* rows of a histogram call; 0: a validation-only handle that touches no device and refuses every run */
+    int32_t max_time;      /* elements per row */
+    int32_t max_tensors;   /* entries of the tensor table; 0: no tensor statistics */
+} wn_stats_config;
+typedef struct wn_stats wn_stats;
+int  wn_stats_create(const wn_stats_config* cfg, wn_stats** out);
+void wn_stats_destroy(wn_stats* h);
+const char* wn_stats_last_error(const wn_stats* h);   /* NULL: text of the last failed create or host hook */
+/* host only: the first min(cap, WN_HIST_BUCKETS) limits into out (out may be NULL with cap = 0); returns WN_HIST_BUCKETS */
+int  wn_stats_hist_limits(double* out, int32_t cap);
+/* x: device float, row b at x + b * pitch; lengths: DEVICE int32 [B] (held inside [0, T]) or NULL = every row T long; bucket: device int64 [WN_HIST_BUCKETS];
+ * summary: device double [8] */
+int  wn_stats_histogram(wn_stats* h, const float* x, int64_t pitch, const int32_t* lengths, int32_t B, int32_t T, int64_t* bucket, double* summary, void* stream);
+/* offsets, counts: HOST int64 [nt] (floats into the flat buffer) */
+int  wn_stats_set_tensors(wn_stats* h, const int64_t* offsets, const int64_t* counts, int32_t nt);
+/* flat: device float; out: device double [nt, 4] */
+int  wn_stats_tensors(wn_stats* h, const float* flat, double* out, void* stream);
+
 /* ---- introspection ------------------------------------------------------------------------------ */
 int64_t wn_workspace_bytes(const wn_ctx* ctx);
 /* name of the kernel that dominates training time (bench.py's roofline line names it) */
@@ -612,6 +648,11 @@ int wn_test_post_host(const wn_post_config* cfg, const void* in, int64_t n, floa
  * the longest row.  Validates as a create followed by a run. */
 int wn_test_melcmp_host(const wn_melcmp_config* cfg, const float* a, int32_t a_channels_first, int64_t a_pitch, const float* b, int32_t b_channels_first,
                         int64_t b_pitch, const int32_t* frames, int32_t B, float* per_frame, int64_t out_pitch, float* summary, int32_t* marks);
+/* the training-summary statistics on the host (no handle, no GPU): the arguments of wn_stats_histogram / wn_stats_tensors with every pointer in HOST memory,
+ * evaluated by the very element steps, cuts and joins the kernels inline (csrc/wn_stats.h), in the device's order: the same bits.  No max_rows / max_time /
+ * max_tensors limit applies; otherwise validated as the device calls. */
+int wn_test_stats_hist_host(const float* x, int64_t pitch, const int32_t* lengths, int32_t B, int32_t T, int64_t* bucket, double* summary);
+int wn_test_stats_tensors_host(const float* flat, const int64_t* offsets, const int64_t* counts, int32_t nt, double* out);
 #endif /* WN_NO_TEST_HOOKS */
 
 #ifdef __cplusplus

@@ -108,7 +108,11 @@ MI355 = dict(
     mi355_synthetic_data=False,    # train on LJSpeech-shaped synthetic tensors (no dataset on disk)
     mi355_validation_interval=0,   # N > 0: every N training steps every rank scores its slice of the test split in batched dropout-free forwards
                                    # (WaveNet.validate: held-out negative log-likelihood per sample, training definition of the loss); 0: off
-    mi355_grad_buckets=3,          # data-parallel training: pieces of the flat gradient that are all-reduced while the backward is still running
+    mi355_train_stats=False,       # True: at every step that writes a summary rank 0 also writes what the reference's add_train_stats writes (train.py:41-56): per-tensor
+                                   # gradient norms (wavenet_events/gradient_norms.jsonl), histograms of the decoded outputs, the targets, the Gaussian head's means and
+                                   # log-scales and of the gradient norms (histograms.jsonl), and max / global gradient norm scalars, all reduced on the device
+                                   # (csrc/wn_stats.hip).  False: every file is byte-identical to a run without the key, and nothing of it runs
+    mi355_grad_buckets=3,        # data-parallel training: pieces of the flat gradient that are all-reduced while the backward is still running
     mi355_synthesize_with_ema=False,   # Synthesizer.load: pack the EMA shadow weights instead of the raw ones
     mi355_compute_dtype='bf16',     # 'bf16': bf16 MFMA operands, fp32 accumulation (the tuned path); 'fp32': the reference's own fp32 arithmetic for the
                                      # forward, loss AND backward (csrc/wn_f32.hip; ~13x slower: validation of a run against the reference's numerics) and

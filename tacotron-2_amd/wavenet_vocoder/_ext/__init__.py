@@ -72,6 +72,10 @@ class WnMelcmpConfig(ctypes.Structure):
                 ('max_batch', ctypes.c_int32), ('max_frames', ctypes.c_int32)]
 
 
+class WnStatsConfig(ctypes.Structure):
+    _fields_ = [('abi_version', ctypes.c_int32), ('max_rows', ctypes.c_int32), ('max_time', ctypes.c_int32), ('max_tensors', ctypes.c_int32)]
+
+
 class WnFoldRow(ctypes.Structure):
     """wn_fold_row: one row of a folded run, in mel frames of utterance `utt`."""
     _fields_ = [('utt', ctypes.c_int32), ('first', ctypes.c_int32), ('frames', ctypes.c_int32), ('keep', ctypes.c_int32), ('fade', ctypes.c_int32)]
@@ -195,6 +199,15 @@ def load_library():
         'wn_melcmp_last_error': (ctypes.c_char_p, [vp]),
         'wn_melcmp_run': (ctypes.c_int, [vp, vp, i32, i64, vp, i32, i64, ctypes.POINTER(i32), i32, vp, i64, vp, vp, vp]),
         'wn_test_melcmp_host': (ctypes.c_int, [ctypes.POINTER(WnMelcmpConfig), vp, i32, i64, vp, i32, i64, ctypes.POINTER(i32), i32, vp, i64, vp, vp]),
+        'wn_stats_create': (ctypes.c_int, [ctypes.POINTER(WnStatsConfig), ctypes.POINTER(vp)]),
+        'wn_stats_destroy': (None, [vp]),
+        'wn_stats_last_error': (ctypes.c_char_p, [vp]),
+        'wn_stats_hist_limits': (ctypes.c_int, [vp, i32]),
+        'wn_stats_histogram': (ctypes.c_int, [vp, vp, i64, vp, i32, i32, vp, vp, vp]),
+        'wn_stats_set_tensors': (ctypes.c_int, [vp, vp, vp, i32]),
+        'wn_stats_tensors': (ctypes.c_int, [vp, vp, vp, vp]),
+        'wn_test_stats_hist_host': (ctypes.c_int, [vp, i64, vp, i32, i32, vp, vp]),
+        'wn_test_stats_tensors_host': (ctypes.c_int, [vp, vp, vp, i32, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)            # AttributeError here == ABI symbol missing
@@ -1100,6 +1113,195 @@ class MelCompare:
     def close(self):
         if getattr(self, 'h', None):
             self.lib.wn_melcmp_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---- training summaries (csrc/wn_stats.hip)
+WN_HIST_BUCKETS = 1551
+HIST_SUMMARY = ('num', 'min', 'max', 'sum', 'sum_squares', 'n_nan', 'n_pos_inf', 'n_neg_inf')      # summary[8] of a histogram
+TENSOR_STATS = ('sum_squares', 'max_abs', 'nonfinite', 'count')                                     # out[t][4] of the per-tensor statistics
+_hist_limits = None
+
+
+def hist_limits():
+    """wn_stats_hist_limits: the WN_HIST_BUCKETS ascending bucket limits (TensorFlow's default summary table) as float64.  Host only."""
+    global _hist_limits
+    if _hist_limits is None:
+        out = np.zeros(WN_HIST_BUCKETS, np.float64)
+        n = load_library().wn_stats_hist_limits(out.ctypes.data_as(ctypes.c_void_p), WN_HIST_BUCKETS)
+        if n != WN_HIST_BUCKETS:
+            raise WnError(n, (load_library().wn_stats_last_error(None) or b'').decode())
+        out.setflags(write=False)
+        _hist_limits = out
+    return _hist_limits
+
+
+def stats_config(max_rows=0, max_time=0, max_tensors=0):
+    cfg = WnStatsConfig()
+    cfg.abi_version = WN_ABI_VERSION
+    cfg.max_rows, cfg.max_time, cfg.max_tensors = int(max_rows), int(max_time), int(max_tensors)
+    return cfg
+
+
+def _hist_dict(bucket, summary):
+    res = {'bucket': bucket}
+    for k, v in zip(HIST_SUMMARY, summary):
+        res[k] = float(v) if k in ('min', 'max', 'sum', 'sum_squares') else int(v)
+    return res
+
+
+def _hist_geometry(shape, channel, T=None):
+    """(B, T, pitch in floats, offset in floats) of x [B, P] or of channel `channel` of x [B, O, P]; T: the rows' length (None: P; else 1 <= T <= P)"""
+    P = int(shape[-1])
+    T = P if T is None else int(T)
+    if T > P:
+        raise ValueError('T (%d) exceeds the last dimension (%d)' % (T, P))
+    if channel is None:
+        if len(shape) != 2:
+            raise ValueError('x must be [B, T] (or [B, O, T] with channel=) (got %r)' % (tuple(shape),))
+        return int(shape[0]), T, P, 0
+    if len(shape) != 3 or not 0 <= int(channel) < int(shape[1]):
+        raise ValueError('x must be [B, O, T] with 0 <= channel < O (got %r, channel %r)' % (tuple(shape), channel))
+    return int(shape[0]), T, int(shape[1]) * P, int(channel) * P
+
+
+def _tensor_table(tensors):
+    """layout (name -> (shape, offset), Engine.layout) or [(offset, count)] -> names, int64 offsets, int64 counts"""
+    if hasattr(tensors, 'items'):
+        names = list(tensors)
+        pairs = [(int(off), int(np.prod(shape))) for shape, off in tensors.values()]
+    else:
+        pairs = [(int(o), int(c)) for o, c in tensors]
+        names = ['tensor_%d' % i for i in range(len(pairs))]
+    return names, np.array([p[0] for p in pairs], np.int64), np.array([p[1] for p in pairs], np.int64)
+
+
+class TrainStats:
+    """One wn_stats: the histogram of a ragged batch and the per-tensor statistics of a flat buffer on the current device (csrc/wn_stats.hip), with
+    pre-allocated outputs.  tensors: Engine.layout (name -> (shape, offset)) or [(offset, count)], set once.  max_rows = 0 gives a validation-only
+    handle (no device; every run is refused); the *_host methods and encode / decode need no handle's device at all."""
+
+    def __init__(self, max_rows, max_time, tensors=None):
+        self.lib = load_library()
+        self.names, self._off, self._cnt = _tensor_table(tensors) if tensors is not None else ([], np.zeros(0, np.int64), np.zeros(0, np.int64))
+        self.cfg = stats_config(max_rows, max_time, len(self.names))
+        h = ctypes.c_void_p()
+        rc = self.lib.wn_stats_create(ctypes.byref(self.cfg), ctypes.byref(h))
+        if rc != 0:
+            raise WnError(rc, (self.lib.wn_stats_last_error(None) or b'').decode())
+        self.h = h
+        self.max_rows, self.max_time = int(max_rows), int(max_time)
+        self._bucket = self._summary = self._tout = None
+        if self.names:
+            self._ok(self.lib.wn_stats_set_tensors(self.h, self._off.ctypes.data_as(ctypes.c_void_p), self._cnt.ctypes.data_as(ctypes.c_void_p), len(self.names)))
+        if self.max_rows > 0:
+            import torch
+            self._bucket = torch.zeros(WN_HIST_BUCKETS, dtype=torch.int64, device='cuda')
+            self._summary = torch.zeros(8, dtype=torch.float64, device='cuda')
+            self._tout = torch.zeros(max(len(self.names), 1), 4, dtype=torch.float64, device='cuda')
+
+    def _ok(self, rc):
+        if rc != 0:
+            raise WnError(rc, (self.lib.wn_stats_last_error(self.h) or b'').decode())
+
+    def histogram(self, x, lengths=None, channel=None, T=None):
+        """x float32 on the device, [B, T] or -- with channel -- [B, O, T] of which channel `channel` is taken; lengths: int32 [B] on the device (elements
+        at t >= lengths[b] are not read) or None; T: the rows' length when the last dimension is a longer pitch.  Returns a dict on the host: 'bucket' int64 [WN_HIST_BUCKETS] and the HIST_SUMMARY fields.  Waits for
+        the device (one copy of 12 KB)."""
+        import torch
+        _check(x, torch.float32, 'x')
+        B, T, pitch, off = _hist_geometry(x.shape, channel, T)
+        if lengths is not None:
+            _check(lengths, torch.int32, 'lengths')
+            if int(lengths.numel()) != B:
+                raise ValueError('lengths must have one entry per row')
+        self._ok(self.lib.wn_stats_histogram(self.h, ctypes.c_void_p(x.data_ptr() + 4 * off), pitch, _ptr(lengths), B, T, _ptr(self._bucket), _ptr(self._summary), _stream()))
+        return _hist_dict(self._bucket.cpu().numpy(), self._summary.cpu().numpy())
+
+    def tensor_stats(self, flat):
+        """flat: float32 on the device, covering every tensor of the table.  Returns float64 [nt, 4] on the host (TENSOR_STATS).  Waits for the device."""
+        import torch
+        _check(flat, torch.float32, 'flat')
+        if not self.names:
+            raise ValueError('TrainStats.tensor_stats: the handle was created without a tensor table')
+        if int((self._off + self._cnt).max()) > int(flat.numel()):
+            raise ValueError('flat has %d elements, the tensor table reaches %d' % (int(flat.numel()), int((self._off + self._cnt).max())))
+        self._ok(self.lib.wn_stats_tensors(self.h, _ptr(flat), _ptr(self._tout), _stream()))
+        return self._tout[:len(self.names)].cpu().numpy()
+
+    @staticmethod
+    def histogram_host(x, lengths=None, channel=None, T=None):
+        """wn_test_stats_hist_host: histogram() of numpy float32 data on the host (no GPU), in the device's order: the same bits."""
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        B, T, pitch, off = _hist_geometry(x.shape, channel, T)
+        ln = None
+        if lengths is not None:
+            ln = np.ascontiguousarray(lengths, dtype=np.int32)
+            if ln.size != B:
+                raise ValueError('lengths must have one entry per row')
+        bucket, summary = np.full(WN_HIST_BUCKETS, -1, np.int64), np.full(8, np.nan, np.float64)
+        vp = ctypes.c_void_p
+        rc = load_library().wn_test_stats_hist_host(vp(x.ctypes.data + 4 * off), pitch, None if ln is None else ln.ctypes.data_as(vp), B, T,
+                                                    bucket.ctypes.data_as(vp), summary.ctypes.data_as(vp))
+        if rc != 0:
+            raise WnError(rc, (load_library().wn_stats_last_error(None) or b'').decode())
+        return _hist_dict(bucket, summary)
+
+    @staticmethod
+    def tensor_stats_host(flat, tensors):
+        """wn_test_stats_tensors_host: tensor_stats() of a numpy float32 buffer on the host (no GPU), in the device's order."""
+        flat = np.ascontiguousarray(flat, dtype=np.float32)
+        _, off, cnt = _tensor_table(tensors)
+        if off.size and int((off + cnt).max()) > flat.size:
+            raise ValueError('flat has %d elements, the tensor table reaches %d' % (flat.size, int((off + cnt).max())))
+        out = np.full((max(off.size, 1), 4), np.nan, np.float64)
+        vp = ctypes.c_void_p
+        rc = load_library().wn_test_stats_tensors_host(flat.ctypes.data_as(vp), off.ctypes.data_as(vp), cnt.ctypes.data_as(vp), int(off.size), out.ctypes.data_as(vp))
+        if rc != 0:
+            raise WnError(rc, (load_library().wn_stats_last_error(None) or b'').decode())
+        return out[:off.size]
+
+    @staticmethod
+    def encode(hist):
+        """A histogram dict as TensorFlow encodes a HistogramProto: min, max, num, sum, sum_squares, and bucket_limit / bucket with every run of empty
+        buckets collapsed into ONE zero entry that carries the run's last limit, so only limits of non-empty buckets (and of the ends of empty runs)
+        appear.  Plain floats and ints: a JSON row."""
+        limits, counts = hist_limits(), hist['bucket']
+        lim, cnt, i, n = [], [], 0, len(counts)
+        while i < n:
+            end, c = float(limits[i]), int(counts[i])
+            i += 1
+            if c <= 0:
+                while i < n and counts[i] <= 0:
+                    end, c = float(limits[i]), int(counts[i])
+                    i += 1
+            lim.append(end); cnt.append(c)
+        res = {k: (float(hist[k]) if k in ('min', 'max', 'sum', 'sum_squares') else int(hist[k])) for k in HIST_SUMMARY}
+        res['bucket_limit'], res['bucket'] = lim, cnt
+        return res
+
+    @staticmethod
+    def decode(enc):
+        """The int64 [WN_HIST_BUCKETS] counts of an encode()d histogram."""
+        limits = hist_limits()
+        out = np.zeros(WN_HIST_BUCKETS, np.int64)
+        for end, c in zip(enc['bucket_limit'], enc['bucket']):
+            if c:
+                i = int(np.searchsorted(limits, end, side='left'))
+                if i >= WN_HIST_BUCKETS or limits[i] != end:
+                    raise ValueError('bucket_limit %r is no limit of the table' % (end,))
+                out[i] = int(c)
+        return out
+
+    def close(self):
+        if getattr(self, 'h', None):
+            self.lib.wn_stats_destroy(self.h)
             self.h = None
 
     def __del__(self):

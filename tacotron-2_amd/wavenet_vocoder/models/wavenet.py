@@ -363,8 +363,9 @@ class WaveNet(object):
         self._dirty = True
 
     # ------------------------------------------------------------------ reference-shaped API
-    def initialize(self, y, c, g, input_lengths, x=None, synthesis_length=None, test_inputs=None, split_infos=None):
-        """Train (x given), eval (y given, x None) or synthesis (neither) -- wavenet.py:218-473."""
+    def initialize(self, y, c, g, input_lengths, x=None, synthesis_length=None, test_inputs=None, split_infos=None, keep_y_hat=False):
+        """Train (x given), eval (y given, x None) or synthesis (neither) -- wavenet.py:218-473.  keep_y_hat (training): the forward also copies its
+        y_hat [B, out_channels, T] of the whole batch to ``self._y_hat_train`` (the training summaries read it); the step itself is unchanged."""
         hp = self._hparams
         self.is_training = x is not None
         self.is_evaluating = not self.is_training and y is not None
@@ -377,9 +378,9 @@ class WaveNet(object):
             rank = self._dist.get_rank() if (self._dist is not None and self._world > 1) else 0
             self._seed = dropout_seed(hp.wavenet_random_seed, self.global_step, rank)
             self.tower_y, self.tower_input_lengths, self.tower_c = [y], [input_lengths], [c]
-            self._y_hat_train = None
+            self._y_hat_train = torch.empty(B, hp.out_channels, T, device=self.device) if keep_y_hat else None
             self._set_global(g, B)
-            self.engine.train_fwd(x.contiguous(), c.contiguous(), y.contiguous(), input_lengths, self._seed, self._loss_dev)
+            self.engine.train_fwd(x.contiguous(), c.contiguous(), y.contiguous(), input_lengths, self._seed, self._loss_dev, self._y_hat_train)
             self._have_fwd = True
             return
         if self.is_evaluating:
@@ -791,6 +792,41 @@ class WaveNet(object):
         cin_channels != num_mels (the conditioning is no mel of this analysis)."""
         from wavenet_vocoder.reconstruction import ReconstructionCheck
         return ReconstructionCheck(self._hparams, rows, max_samples, preemphasis=preemphasis, alarm_db=alarm_db)
+
+    def train_stats(self):
+        """The model's _ext.TrainStats (csrc/wn_stats.hip), built at the first call: histograms of up to max_batch rows of max_time samples and the
+        per-tensor statistics of a flat buffer in the engine's layout (``grads``, ``params``, the Adam slots)."""
+        if self.engine is None:
+            raise RuntimeError('WaveNet.train_stats: call build() / initialize() first')
+        if getattr(self, '_train_stats', None) is None:
+            self._train_stats = _ext.TrainStats(self.max_batch, self.max_time, self.engine.layout)
+        return self._train_stats
+
+    def train_outputs(self, y, step):
+        """The kept training forward (initialize(keep_y_hat=True)) decoded as the reference's training tower decodes it for its summaries
+        (wavenet.py:296-328): arg-max + inv_mulaw_quantize for the softmax head, one draw of the scalar heads' distribution (inv_mulaw where the input
+        type asks for it), next to the targets decoded the same way.  The draw's noise comes from a generator of its own seeded from
+        (wavenet_random_seed, step): the global generator, and with it the run, are untouched.  Returns (outputs, targets), float32 [B, T] each."""
+        hp = self._hparams
+        y_hat = getattr(self, '_y_hat_train', None)
+        if y_hat is None:
+            raise RuntimeError('WaveNet.train_outputs: the last training initialize() did not keep its y_hat (keep_y_hat=True)')
+        B, T = int(y_hat.shape[0]), int(y_hat.shape[-1])
+        if is_mulaw_quantize(hp.input_type):
+            return util.inv_mulaw_quantize(_ext.argmax_channels(y_hat)), util.inv_mulaw_quantize(y.reshape(B, T))
+        gen = torch.Generator(device=y_hat.device)
+        gen.manual_seed((int(hp.wavenet_random_seed) * 1000003 + int(step)) & 0x7FFFFFFFFFFFFFFF)
+        nps = self.engine.noise_per_step
+        if hp.out_channels == 2:
+            noise = torch.randn(T, B, nps, device=y_hat.device, generator=gen)
+        else:
+            noise = torch.rand(T, B, nps, device=y_hat.device, generator=gen) * (1 - 2e-5) + 1e-5
+        out = torch.empty(B, T, device=y_hat.device)
+        self.engine.sample(y_hat, noise, out)
+        target = y.reshape(B, T).float().contiguous()
+        if is_mulaw(hp.input_type):
+            out, target = util.inv_mulaw(out), util.inv_mulaw(target)
+        return out, target
 
     def slots(self, batch, steps_per_graph=None):
         """Open a SlotSession of `batch` slots (<= 32, the model's engine must have been built for them): independent utterances that join and

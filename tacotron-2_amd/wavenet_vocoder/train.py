@@ -271,6 +271,37 @@ def _reconstruction_scalars(model, hparams):
             'Wavenet_eval_model/eval_stats/wavenet_eval_reconstruction_mcd_db': float(t[3])}
 
 
+def add_train_stats(model, batch, step, tensorboard_dir, hparams):
+    """What the reference's add_train_stats writes at a summary step (train.py:41-56), reduced on the device by the model's TrainStats
+    (csrc/wn_stats.hip): one row of per-tensor gradient statistics to gradient_norms.jsonl, histogram rows (encoded as TensorFlow encodes a
+    HistogramProto) of the decoded outputs and the targets of tower 0, the Gaussian head's means and log-scales, and of the gradient norms to
+    histograms.jsonl.  ``model.grads`` is the gradient as add_optimizer leaves it: all-reduced, unclipped (self.gradients of wavenet.py:583).
+    Padding (t >= lengths[b]) is left out of the output histograms.  Returns the new keys of the scalars row."""
+    stats = model.train_stats()
+    x, y, lengths, c, g = batch
+    ts = np.asarray(stats.tensor_stats(model.grads), dtype=np.float64)
+    names = list(stats.names)
+    norms = np.sqrt(ts[:, 0])
+    worst = int(np.argmax(norms))
+    with open(os.path.join(tensorboard_dir, 'gradient_norms.jsonl'), 'a') as f:
+        f.write(json.dumps({'step': step, 'names': names, 'norm': [float(v) for v in norms], 'max_abs': [float(v) for v in ts[:, 1]],
+                            'nonfinite': [int(v) for v in ts[:, 2]]}) + '\n')
+    rows = [('gradient_norm', stats.histogram_host(norms.astype(np.float32).reshape(1, -1)))]
+    outputs, targets = model.train_outputs(y, step)
+    rows.append(('wav_outputs 0', stats.histogram(outputs, lengths)))
+    rows.append(('wav_targets 0', stats.histogram(targets, lengths)))
+    if util.is_scalar_input(hparams.input_type) and hparams.out_channels == 2:
+        rows.append(('gaussian_means 0', stats.histogram(model._y_hat_train, lengths, channel=0)))
+        rows.append(('gaussian_log_scales 0', stats.histogram(model._y_hat_train, lengths, channel=1)))
+    with open(os.path.join(tensorboard_dir, 'histograms.jsonl'), 'a') as f:
+        for tag, h in rows:
+            f.write(json.dumps(dict(stats.encode(h), step=step, tag=tag)) + '\n')
+    return {'wavenet_stats/max_gradient_norm': float(norms[worst]), 'wavenet_stats/max_gradient_norm_tensor': names[worst],
+            'wavenet_stats/global_gradient_norm': float(np.sqrt(np.sum(ts[:, 0], dtype=np.float64))),
+            'wavenet_stats/clipped_tensors': int(np.sum(norms > float(hparams.wavenet_gradient_max_norm))),
+            'wavenet_stats/nonfinite_gradients': int(np.sum(ts[:, 2]))}
+
+
 def validation_step(model, feeder, step, scalars, hparams):
     """Held-out loss of the whole test split (mi355_validation_interval): EVERY rank scores its slice in batched dropout-free forwards
     (WaveNet.validate), one small all-reduce adds the totals, rank 0 logs and writes the scalar.  A rank whose pass failed says so in the
@@ -412,6 +443,7 @@ def train(log_dir, args, hparams, input_path):
         feeder_error = None
         newest = (step, float('nan'))                # (step, loss) of the newest loss the host has looked at
         val_interval = int(getattr(hparams, 'mi355_validation_interval', 0) or 0)
+        train_stats = bool(getattr(hparams, 'mi355_train_stats', False))
         while not coord.should_stop() and step < args.wavenet_train_steps:
             start_time = time.time()
             if batch is None and feeder_error is None:
@@ -427,7 +459,10 @@ def train(log_dir, args, hparams, input_path):
                 # late read (one step later, or in this very step when it is a writing step) and leaves there
                 batch = last_batch
             x, y, lengths, c, g = batch
-            model.initialize(y, c, g, lengths, x=x)
+            if train_stats and rank == 0 and (step + 1) % args.summary_interval == 0:
+                model.initialize(y, c, g, lengths, x=x, keep_y_hat=True)      # the coming step writes a summary: its forward keeps y_hat of the whole batch
+            else:
+                model.initialize(y, c, g, lengths, x=x)
             loss_t = model.add_loss(flags=flag_const[1 if feeder_error is not None else 0])      # data parallel: ONE 2-float all-reduce (loss mean, flag count)
             step = model.add_optimizer(step)
             embed = (hparams.gin_channels > 0 and model.embedding_table is not None
@@ -464,9 +499,15 @@ def train(log_dir, args, hparams, input_path):
                     log('\nWriting summary at step {}'.format(step))
                     gmax = float(model.grads.abs().max().item())
                     n_samples = int(lengths.sum().item()) * world
-                    scalars.write(json.dumps({'step': newest[0], 'wavenet_loss': newest[1], 'wavenet_learning_rate': model.learning_rate,
-                                              'wavenet_max_gradient_norm': gmax,
-                                              'audio_samples_per_sec': n_samples / max(time_window.average, 1e-9)}) + '\n')
+                    row = {'step': newest[0], 'wavenet_loss': newest[1], 'wavenet_learning_rate': model.learning_rate,
+                           'wavenet_max_gradient_norm': gmax,
+                           'audio_samples_per_sec': n_samples / max(time_window.average, 1e-9)}
+                    if train_stats:
+                        try:
+                            row.update(add_train_stats(model, batch, step, tensorboard_dir, hparams))
+                        except Exception as e:      # like the plotting: never kills a training run
+                            log('training summaries skipped: {}'.format(e))
+                    scalars.write(json.dumps(row) + '\n')
                     scalars.flush()
 
                 if (step % args.checkpoint_interval == 0 or step == args.wavenet_train_steps) and rank == 0:
