@@ -586,7 +586,12 @@ const char* wn_dominant_kernel_name(void);
 /* copy an internal activation buffer of the last step to `out` as fp32 ("X","U","TS","DZ","R1","H2","DY","DSKIP","DPRE1","GX0",
  * "GX1","cbt" are bf16 [rows][channels]; "YHAT","DC","CUP" fp32).  "GX" with layer 0 ... L is d L / d h_layer as the backward chain
  * keeps it (layer L: the zero-filled top), "XD" with layer 0 ... L-1 the dropout-applied conv input (the same buffer as "X" when
- * dropout is 0); a layer outside these ranges is WN_E_ARG. */
+ * dropout is 0); a layer outside these ranges is WN_E_ARG.
+ * The weight path (fp32, `layer` ignored, n above the buffer's length is WN_E_ARG, WN_E_STATE before wn_pack_weights; all but "DEFF" also on
+ * inference-only contexts): "PARAMS" the context's EFFECTIVE parameter copy (n_params floats in the effective layout: the raw tensors without
+ * the gains, each 8-float aligned, in wn_tensor_info order); "DEFF" the gradients with respect to the effective parameters that the last
+ * wn_train_bwd left (same layout; weight-normalised contexts after a wn_train_bwd, WN_E_STATE otherwise); "B1SUM" [L, G] dilated-conv bias +
+ * conditioning bias; "SKIPB" [S] the scaled sum of the skip biases. */
 int wn_debug_copy(wn_ctx* ctx, const char* name, int32_t layer, float* out, int64_t n, void* stream);
 /* live HIP-event timing of the dominant training kernel (the gate GEMM, one launch per layer and step), recorded on the launch
  * stream between wn_profile(ctx,1) and wn_profile_result -- which SYNCHRONISES on the recorded events (bench only). */
@@ -625,6 +630,13 @@ int wn_test_fill_noise_tempered(wn_ctx* ctx, float* noise, int32_t B, int32_t T,
 /* which launches of this context take the 8-phase kernel (csrc/wn_tile8p.h; WN_GEMM8P in the environment of wn_create -- an A/B switch,
  * default 0): bit 0 = the gate GEMM, bit 1 = d x.  A model that does not fit the kernel reports 0 whatever the switch says. */
 int wn_test_gemm8p_mask(const wn_ctx* ctx);
+/* The fragment-ordered bf16 operand packs that wn_pack_weights wrote.  kind: "w1", "wo", "ws", "w2T", "w1T" (one per layer) or "wskip", "wh1",
+ * "wh2", "wh2T", "wh1T", "wcT" (`layer` ignored).  wn_test_pack_info: out = {M, K, kil, gate_interleave} (padded sizes; kil = 0 / 32 / 64 the
+ * K interleave of the three taps).  wn_test_pack_copy: the M * K elements IN STORAGE ORDER, bf16 -> fp32, nothing un-shuffled, into the device
+ * buffer out of n floats (SYNCHRONISES the device).  WN_E_ARG: unknown kind, layer outside [0, L), n < M * K, null pointer; WN_E_STATE: before
+ * wn_pack_weights. */
+int wn_test_pack_info(wn_ctx* ctx, const char* kind, int32_t layer, int32_t out[4]);
+int wn_test_pack_copy(wn_ctx* ctx, const char* kind, int32_t layer, float* out, int64_t n);
 /* the workgroup tables of the persistent synthesis pipeline for a model of L layers x P CUs per layer cut into ni instances (host logic only: no
  * context, no GPU): role[b] of workgroup b = layer << 8 | j, bit 23: a head (j = its index), bits 24-25: instance, -1: none; blk = the inverse
  * (ni = 1: [L * P + heads]; else ni x [L * P + 1]).  Block b runs on XCD b % 8: a layer's P CUs share an XCD, consecutive layers stay together.

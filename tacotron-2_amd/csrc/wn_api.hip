@@ -558,6 +558,24 @@ __global__ void wn_bf16_to_f32(const bf16_t* __restrict__ in, float* __restrict_
 }
 extern "C" int wn_debug_copy(wn_ctx* c, const char* name, int32_t layer, float* out, int64_t n, void* stream) {
     if (!c || !name || !out || n <= 0) return WN_E_ARG;
+    {   // the weight path: the context's own parameter copy, the effective-kernel gradients and the two bias sums (sized buffers: n is checked)
+        const std::string w = name;
+        const float* src = nullptr; int64_t len = 0;
+        if (w == "PARAMS") { src = c->params_dev; len = c->n_params; }
+        else if (w == "B1SUM") { src = c->b1sum; len = (int64_t)c->L * c->G; }
+        else if (w == "SKIPB") { src = c->skip_bias_total; len = c->S; }
+        else if (w == "DEFF") {
+            if (!c->wnorm) WN_FAIL(c, WN_E_STATE, "wn_debug_copy('DEFF'): the context has no weight normalisation (the gradients of wn_train_bwd are the effective ones)");
+            if (!c->have_bwd) WN_FAIL(c, WN_E_STATE, "wn_debug_copy('DEFF'): no wn_train_bwd has run since the last forward");
+            src = c->deff; len = c->n_params;
+        }
+        if (src) {
+            if (!c->packed) WN_FAIL(c, WN_E_STATE, "wn_debug_copy('%s'): wn_pack_weights has not run yet", name);
+            if (n > len) WN_FAIL(c, WN_E_ARG, "wn_debug_copy('%s'): n = %lld exceeds the buffer's %lld floats", name, (long long)n, (long long)len);
+            WN_HIP(c, hipMemcpyAsync(out, src, (size_t)n * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+            return WN_OK;
+        }
+    }
     if (c->inference && strcmp(name, "cbt") != 0 && strcmp(name, "CUP") != 0) WN_FAIL(c, WN_E_STATE, "wn_debug_copy('%s'): no training workspace on an inference-only context", name);
     const int64_t NT = c->NT;
     const bf16_t* b = nullptr; const float* f = nullptr;
@@ -590,6 +608,49 @@ extern "C" int wn_debug_copy(wn_ctx* c, const char* name, int32_t layer, float* 
     hipStream_t st = (hipStream_t)stream;
     if (b) { hipLaunchKernelGGL(wn_bf16_to_f32, dim3(cdiv(n, 256)), dim3(256), 0, st, b, out, n); WN_LAUNCH_CHECK(c); }
     else WN_HIP(c, hipMemcpyAsync(out, f, (size_t)n * 4, hipMemcpyDeviceToDevice, st));
+    return WN_OK;
+}
+
+// ---- test hooks: the fragment-ordered bf16 packs as wn_pack_kernel stored them (no un-shuffling)
+static const PackedW* find_pack(const wn_ctx* c, const char* kind, int32_t layer, bool* per_layer) {
+    const std::string k = kind;
+    static const char* const lay[5] = {"w1", "wo", "ws", "w2T", "w1T"};
+    *per_layer = false;
+    for (int i = 0; i < 5; ++i) if (k == lay[i]) {
+        *per_layer = true;
+        if (layer < 0 || layer >= (int)c->packs.size()) return nullptr;
+        const WnLayerPacks& p = c->packs[layer];
+        return i == 0 ? &p.w1 : i == 1 ? &p.wo : i == 2 ? &p.ws : i == 3 ? &p.w2T : &p.w1T;
+    }
+    if (k == "wskip") return &c->wskip;
+    if (k == "wh1") return &c->wh1;
+    if (k == "wh2") return &c->wh2;
+    if (k == "wh2T") return &c->wh2T;
+    if (k == "wh1T") return &c->wh1T;
+    if (k == "wcT") return &c->wcT;
+    return nullptr;
+}
+extern "C" int wn_test_pack_info(wn_ctx* c, const char* kind, int32_t layer, int32_t out[4]) {
+    if (!c || !kind || !out) return WN_E_ARG;
+    bool per_layer;
+    const PackedW* w = find_pack(c, kind, layer, &per_layer);
+    if (!w) WN_FAIL(c, WN_E_ARG, "wn_test_pack_info: %s '%s' (layer %d)", per_layer ? "bad layer of pack" : "unknown pack", kind, layer);
+    if (!c->packed) WN_FAIL(c, WN_E_STATE, "wn_test_pack_info: wn_pack_weights has not run yet");
+    out[0] = w->M; out[1] = w->K; out[2] = w->kil; out[3] = w->gate_interleave;
+    return WN_OK;
+}
+extern "C" int wn_test_pack_copy(wn_ctx* c, const char* kind, int32_t layer, float* out, int64_t n) {
+    if (!c || !kind || !out) return WN_E_ARG;
+    bool per_layer;
+    const PackedW* w = find_pack(c, kind, layer, &per_layer);
+    if (!w) WN_FAIL(c, WN_E_ARG, "wn_test_pack_copy: %s '%s' (layer %d)", per_layer ? "bad layer of pack" : "unknown pack", kind, layer);
+    const int64_t len = (int64_t)w->M * w->K;
+    if (n < len) WN_FAIL(c, WN_E_ARG, "wn_test_pack_copy('%s'): out holds %lld floats, the pack has %lld", kind, (long long)n, (long long)len);
+    if (!c->packed) WN_FAIL(c, WN_E_STATE, "wn_test_pack_copy: wn_pack_weights has not run yet");
+    WN_HIP(c, hipDeviceSynchronize());          // (the pack launch may still run on the caller's stream)
+    hipLaunchKernelGGL(wn_bf16_to_f32, dim3(cdiv(len, 256)), dim3(256), 0, (hipStream_t)0, w->dev.get(), out, len);
+    WN_LAUNCH_CHECK(c);
+    WN_HIP(c, hipDeviceSynchronize());
     return WN_OK;
 }
 

@@ -136,6 +136,8 @@ def load_library():
         'wn_synth_check': (ctypes.c_int, [vp]),
         'wn_synth_last_path': (ctypes.c_int, [vp]),
         'wn_test_gemm8p_mask': (ctypes.c_int, [vp]),
+        'wn_test_pack_info': (ctypes.c_int, [vp, ctypes.c_char_p, i32, ctypes.POINTER(i32)]),
+        'wn_test_pack_copy': (ctypes.c_int, [vp, ctypes.c_char_p, i32, vp, i64]),
         'wn_test_pipe_layout': (ctypes.c_int, [i32, i32, i32, vp, i32, vp, i32, vp, vp]),
         'wn_test_device_resources': (ctypes.c_int, [ctypes.POINTER(i64)]),
         'wn_synth_pipe_dtype': (ctypes.c_int, [vp, i32]),
@@ -683,6 +685,20 @@ class Engine:
         import torch
         out = torch.empty(rows, cols, dtype=torch.float32, device='cuda')
         self._ok(self.lib.wn_debug_copy(self.h, name.encode(), int(layer), _ptr(out), ctypes.c_int64(rows * cols), _stream()))
+        return out
+
+    def pack_info(self, kind, layer=0):
+        """(M, K, kil, gate_interleave) of one fragment-ordered operand pack (wn_test_pack_info; tests only)."""
+        out = (ctypes.c_int32 * 4)()
+        self._ok(self.lib.wn_test_pack_info(self.h, kind.encode(), int(layer), out))
+        return tuple(int(v) for v in out)
+
+    def pack_copy(self, kind, layer=0):
+        """One operand pack in storage order, bf16 -> fp32, flat [M * K] (wn_test_pack_copy; tests only, synchronises)."""
+        import torch
+        M, K, _, _ = self.pack_info(kind, layer)
+        out = torch.empty(M * K, dtype=torch.float32, device='cuda')
+        self._ok(self.lib.wn_test_pack_copy(self.h, kind.encode(), int(layer), _ptr(out), ctypes.c_int64(M * K)))
         return out
 
     def sample(self, y_hat, noise, out):

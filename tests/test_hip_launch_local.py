@@ -16,7 +16,8 @@ Weight-gradient tensors are sums over all rows, where a worst-case bound is usel
 reference, in the test, per tensor: the same contraction of the same downloaded buffers in float32 with one running accumulator over
 128-row blocks in row order, against float64 (floored at 2^-24, the final rounding of any float32 result: WGRAD_YARD_FLOOR below).  The
 device gets 8 x that rel-L2 (different summation tree, float atomics between splits) and never more than 1e-5 (a condition, not a measurement: one wrong row in 22 000, all rows agreeing in sign, is 4.5e-5).  A
-tensor whose reference is all zeros (the top layer's W_out) must be exact zeros.  The upsample-net gradients: float64 backward of
+tensor whose reference is all zeros (the top layer's W_out) must be exact zeros.  With weight normalisation the tensors compared are the
+effective-kernel gradients the launches wrote (wn_debug_copy 'DEFF'), not the d v / d g of the flat buffer (those: test_hip_weightnorm.py).  The upsample-net gradients: float64 backward of
 O.upsample from the device's DC, yardstick = the float32 backward.
 
 Per launch kind and layer the test prints the largest err / bound, the rel-L2 and where the worst element is (the small sweep engines:
@@ -39,6 +40,7 @@ import pytest
 import torch
 
 import launch_ref as LR
+import wnorm_ref as WR
 from hip_util import SMALL, download_grads, dropout_mask_rows, make_hp, oracle_cfg, synth_batch, upload_params
 from oracle import wavenet_oracle as O
 from test_hip_bench_geometry import C5, PAPER
@@ -260,7 +262,16 @@ def check_step(tag, eng, cfg, params, B, T, lengths, seed, x_in, y_or, c_in, gra
     W = LR.Weights(params, cfg, rounded=True)
     rep = Report(tag, B, T, detail)
     p = float(cfg.wavenet_dropout)
-    g_dev = download_grads(eng, grads_flat) if wgrads else {}
+    g_dev, eff_params = {}, params
+    if wgrads and not cfg.wavenet_weight_normalization:
+        g_dev = download_grads(eng, grads_flat)
+    elif wgrads:
+        # weight normalisation: the flat buffer holds d v, d g (tests/test_hip_weightnorm.py maps them back).  What the GEMMs wrote are the gradients
+        # of the EFFECTIVE tensors, the context's 'DEFF' (effective layout); the device's own effective parameters feed the gin / upsample references
+        lay, n_eff = WR.effective_layout(eng.layout)
+        deff, peff = (eng.debug_copy(nm, 0, 1, n_eff).cpu().view(-1) for nm in ('DEFF', 'PARAMS'))
+        g_dev = {k: deff[off:off + int(np.prod(shape))].view(*shape).clone() for k, (shape, off) in lay.items()}
+        eff_params = {k: peff[off:off + int(np.prod(shape))].view(*shape).clone() for k, (shape, off) in lay.items()}
     check_forward(tag, eng, cfg, params, B, T, seed, x_in, c_in, g=g, chain_layers=chain_layers, x_checks=False, rep=rep)      # (X0 / X_next / XD: in the loop below)
 
     def dl(name, l, ch):
@@ -355,14 +366,14 @@ def check_step(tag, eng, cfg, params, B, T, lengths, seed, x_in, y_or, c_in, gra
         tensors('input wg', 0, LR.ref_wgrads_input(W, x_in, GX_up, True))
         if g is not None:
             ids = g.long() if cfg.use_speaker_embedding else None
-            gvec = params['gc_embedding'][ids] if ids is not None else g
-            r64 = LR.ref_wgrads_gin(params, cfg, gvec, ids, colsums, torch.float64)
-            r32 = LR.ref_wgrads_gin(params, cfg, gvec, ids, colsums32, torch.float32)      # yardstick: float32 column sums (128-row blocks in row order) through the float32 contraction
+            gvec = eff_params['gc_embedding'][ids] if ids is not None else g
+            r64 = LR.ref_wgrads_gin(eff_params, cfg, gvec, ids, colsums, torch.float64)
+            r32 = LR.ref_wgrads_gin(eff_params, cfg, gvec, ids, colsums32, torch.float32)      # yardstick: float32 column sums (128-row blocks in row order) through the float32 contraction
             tensors('gin wg', 0, {k: (r64[k], float((r32[k].double() - r64[k]).norm()) / max(float(r64[k].norm()), 1e-300)) for k in r64})
         if want_dc:      # upsample net: float64 backward of O.upsample from the device's DC; yardstick = the float32 backward
             up = {}
             for dt in (torch.float64, torch.float32):
-                leaf = {k: v.to(dt).clone().requires_grad_(True) for k, v in params.items() if k.startswith('local_conditioning')}
+                leaf = {k: v.to(dt).clone().requires_grad_(True) for k, v in eff_params.items() if k.startswith('local_conditioning')}
                 out = O.upsample(leaf, cfg, c_in.to(dt))
                 out.backward(DC.permute(0, 2, 1).to(dt))
                 up[dt] = {k: v.grad.double() for k, v in leaf.items()}
@@ -372,7 +383,7 @@ def check_step(tag, eng, cfg, params, B, T, lengths, seed, x_in, y_or, c_in, gra
 
 
 # ------------------------------------------------------------------------------------------------------------------ small configurations
-SMALL_CONFIGS = ['paper_width_drop', 'wide', 'mol_2d', 'gauss_subpixel', 'mol_2d_legacy_drop', 'mol_gin_embed', 'mol_nobias', 'softmax_c1', 'mol_weightnorm']
+SMALL_CONFIGS = ['paper_width_drop', 'wide', 'mol_2d', 'gauss_subpixel', 'mol_2d_legacy_drop', 'mol_gin_embed', 'mol_nobias', 'softmax_c1', 'mol_weightnorm', 'gauss_weightnorm_gin_nobias']
 
 
 @pytest.mark.parametrize('name', SMALL_CONFIGS)
@@ -388,8 +399,7 @@ def test_launch_local_geometry_sweep(name):
         quant = cfg.input_type == 'mulaw-quantize'
         x_in = r['y_or'] if quant else r['x_or'].view(B, T)
         try:
-            check_step('%s B=%d T=%d' % (name, B, T), eng, cfg, r['params'], B, T, lengths, r['seed'], x_in, r['y_or'], r['c'], grads, g=r['g'],
-                       wgrads=not cfg.wavenet_weight_normalization)      # (v / g gradients stay with the end-to-end test)
+            check_step('%s B=%d T=%d' % (name, B, T), eng, cfg, r['params'], B, T, lengths, r['seed'], x_in, r['y_or'], r['c'], grads, g=r['g'])
         finally:
             eng.close()
 

@@ -46,6 +46,10 @@ def test_library_loads_and_exports_every_declared_symbol():
     for sym in sorted(declared):
         assert hasattr(lib, sym), 'symbol %s declared in include/wavenet_mi355.h is not exported' % sym
     assert set(_ext.exported_symbols()) <= declared | {'wn_debug_copy'}
+    for sym in ('wn_test_pack_info', 'wn_test_pack_copy'):      # the read hooks of the operand packs: declared, exported and bound
+        assert sym in declared and sym in _ext.exported_symbols() and hasattr(lib, sym), sym
+    for name in ('PARAMS', 'DEFF', 'B1SUM', 'SKIPB'):           # ... and the weight-path names of wn_debug_copy are documented where it is declared
+        assert '"%s"' % name in header, name
     # host-only entry points work without a GPU
     assert abs(_ext.learning_rate('exponential', 1e-3, 200000) - 5e-4) < 1e-9
     assert abs(_ext.learning_rate('noam', 1e-3, 0) - max(1e-3 * 4000 ** 0.5 * 4000 ** -1.5, 1e-4)) < 1e-9
