@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Build libwavenet_mi355.so for gfx950 with hipcc (cross-compiles without a GPU).
 
-    python tacotron-2_amd/csrc/build.py [--force]
+    python tacotron-2_amd/csrc/build.py [--force | --sanitize | --ablate | --pipe-svc]
 
 One hipcc invocation per translation unit (in parallel), then one link.  The .so is written next to
 the sources (git-ignored, but it travels to the GPU box with the gpurun snapshot).
@@ -93,13 +93,40 @@ def sanitizer_runtime():
     return p if os.path.isabs(p) and os.path.exists(p) else None
 
 
+# diagnostic builds: option -> (translation unit, define, object suffix, library)
+DIAGNOSTIC = {
+    # WN_ABLATE skips whole launch classes of the training step (wn_train.hip; results are wrong by construction)
+    '--ablate': ('wn_train.hip', '-DWN_ABLATE_BUILD', '.ablate.o', 'libwavenet_mi355_ablate.so'),
+    # the synthesis pipeline with its service-time stamps compiled in (tools/pipe_svc_trace.py)
+    '--pipe-svc': ('wn_synth_pipe.hip', '-DWN_PIPE_SVC_BUILD', '.pipesvc.o', 'libwavenet_mi355_pipesvc.so'),
+}
+
+
+def build_diagnostic(opt, verbose=True):
+    """One translation unit rebuilt with its diagnostic define into an object and a library of their own, linked with the regular
+    objects of the other translation units (the build_sanitized pattern).  The product objects and libwavenet_mi355.so are only ever
+    written by build(); a tool selects the diagnostic library through WN_MI355_TEST_LIB."""
+    unit, define, suffix, libname = DIAGNOSTIC[opt]
+    build(verbose=verbose)
+    src, obj, lib = os.path.join(HERE, unit), os.path.join(HERE, unit.replace('.hip', suffix)), os.path.join(HERE, libname)
+    newest = max([_mtime(src)] + [_mtime(os.path.join(HERE, h)) for h in HEADERS] + [_mtime(__file__)])
+    if _mtime(obj) <= newest:
+        r = subprocess.run(['hipcc'] + FLAGS + [define, '-c', src, '-o', obj], capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError('hipcc (%s) failed for %s:\n%s\n%s' % (opt, unit, r.stdout, r.stderr))
+    others = [os.path.join(HERE, s.replace('.hip', '.o')) for s in SOURCES if s != unit]
+    if _mtime(lib) < max(_mtime(o) for o in others + [obj]):
+        r = subprocess.run(['hipcc', '--offload-arch=gfx950', '-shared', '-fPIC', '-o', lib, obj] + others, capture_output=True, text=True)
+        if r.returncode != 0:
+            raise RuntimeError('link (%s) failed:\n%s\n%s' % (opt, r.stdout, r.stderr))
+    return lib
+
+
 if __name__ == '__main__':
-    if '--pipe-svc' in sys.argv:      # diagnostic build: the synthesis pipeline with its service-time stamps compiled in (tools/pipe_svc_trace.py)
-        FLAGS.append('-DWN_PIPE_SVC_BUILD')
-    if '--ablate' in sys.argv:        # diagnostic build: WN_ABLATE skips whole launch classes of the training step (wn_train.hip; results are wrong by construction)
-        FLAGS.append('-DWN_ABLATE_BUILD')
-        o = os.path.join(HERE, 'wn_train.o')
-        if os.path.exists(o):
-            os.remove(o)
-    print(build_sanitized() if '--sanitize' in sys.argv else build(force='--force' in sys.argv or '--pipe-svc' in sys.argv))
+    diag = [o for o in DIAGNOSTIC if o in sys.argv]
+    if diag:
+        for o in diag:
+            print(build_diagnostic(o))
+    else:
+        print(build_sanitized() if '--sanitize' in sys.argv else build(force='--force' in sys.argv))
     print('build mode: ' + ', '.join('%s %s' % kv for kv in sorted(LAST_BUILD.items())))

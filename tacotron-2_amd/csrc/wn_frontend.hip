@@ -305,101 +305,12 @@ __global__ void wn_up_bwd_input_generic(const float* __restrict__ out, const flo
     din[idx] = a;
 }
 
-// dpre = dout * act'(out);  dK[kf][j], dbias.  One workgroup per (b, f) row; thread x owns phase j = x % s of the stride-s
-// output grid (to = j + s*q), so its kernel taps are fixed and accumulate in registers; one LDS atomic per thread and
-// tap at the end, one global atomic per workgroup and tap.  (The v0 kernel did an LDS atomic per ELEMENT and tap on ~30
-// addresses: 290 us on the last upsample layer.)
 #define WN_UP_MAXTAP 27
-__global__ __launch_bounds__(256) void wn_up_bwd_params(const float* __restrict__ in, const float* __restrict__ out, const float* __restrict__ dout,
-                                 float* __restrict__ dK, float* __restrict__ dbias, int B, int C, int Tin, int s, int fk,
-                                 int type, int act, float alpha) {
-    extern __shared__ float sh[];          // [nk + nb]
-    const int nk = (type == 1) ? fk * s : fk * 3 * s;
-    const int nb = (type == 1) ? 1 : s;
-    for (int i = threadIdx.x; i < nk + nb; i += blockDim.x) sh[i] = 0.0f;
-    __syncthreads();
-    const int Tout = Tin * s;
-    const int b = blockIdx.x / C, f = blockIdx.x % C;
-    const int groups = blockDim.x / s;                 // (threads beyond groups*s idle)
-    const int j = threadIdx.x % s, q0 = threadIdx.x / s;
-    const int pf = (fk - 1) / 2;
-    const int ntap = (type == 1) ? fk : fk * 3;
-    float dk[WN_UP_MAXTAP], db = 0.0f;
-#pragma unroll
-    for (int i = 0; i < WN_UP_MAXTAP; ++i) dk[i] = 0.0f;
-    if (q0 < groups) {
-        const float* inb = in + (int64_t)b * C * Tin;
-        const int64_t rowo = ((int64_t)b * C + f) * Tout;
-        for (int t = q0; t < Tin; t += groups) {
-            const int64_t o = rowo + (int64_t)t * s + j;
-            const float dp = dout[o] * act_grad(out[o], act, alpha);
-            db += dp;
-            if (type == 1) {
-#pragma unroll
-                for (int kf = 0; kf < 9; ++kf) {
-                    if (kf < fk) { const int fs = f - kf + pf; if (fs >= 0 && fs < C) dk[kf] += inb[(int64_t)fs * Tin + t] * dp; }
-                }
-            } else {
-#pragma unroll
-                for (int kf = 0; kf < 9; ++kf) {
-                    if (kf < fk) {
-                        const int fs = f + kf - pf;
-                        if (fs >= 0 && fs < C) {
-#pragma unroll
-                            for (int kt = 0; kt < 3; ++kt) { const int tsrc = t + kt - 1; if (tsrc >= 0 && tsrc < Tin) dk[kf * 3 + kt] += inb[(int64_t)fs * Tin + tsrc] * dp; }
-                        }
-                    }
-                }
-            }
-        }
-        if (type == 1) atomicAdd(&sh[nk], db); else atomicAdd(&sh[nk + j], db);
-#pragma unroll
-        for (int i = 0; i < WN_UP_MAXTAP; ++i) if (i < ntap) atomicAdd(&sh[i * s + j], dk[i]);
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < nk; i += blockDim.x) if (sh[i] != 0.0f) unsafeAtomicAdd(&dK[i], sh[i]);
-    for (int i = threadIdx.x; i < nb; i += blockDim.x) if (sh[nk + i] != 0.0f) unsafeAtomicAdd(&dbias[i], sh[nk + i]);
-}
-
-// din[b][f'][t]: a group of GL lanes (GL = power of two <= 64, >= min(s, 64)) per input element; the lanes stride over the s
-// output phases j (contiguous in memory: coalesced), then shuffle-reduce.  (One thread per element walked fk*3*s strided
-// addresses: 1.4 ms for the s = 25 SubPixel layer of hparams.py.)
-__global__ __launch_bounds__(256) void wn_up_bwd_input(const float* __restrict__ out, const float* __restrict__ dout, float* __restrict__ din,
-                                const float* __restrict__ K, int B, int C, int Tin, int s, int fk, int type, int act, float alpha, int GL) {
-    const int Tout = Tin * s;
-    const int lj = threadIdx.x & (GL - 1);
-    const int64_t idx = (int64_t)blockIdx.x * (blockDim.x / GL) + threadIdx.x / GL;
-    const bool live = idx < (int64_t)B * C * Tin;
-    float a = 0.0f;
-    if (live) {
-        const int t = (int)(idx % Tin); const int64_t bf = idx / Tin;
-        const int f = (int)(bf % C), b = (int)(bf / C);
-        const int pf = (fk - 1) / 2;
-        const float* ob = out + (int64_t)b * C * Tout; const float* db = dout + (int64_t)b * C * Tout;
-        if (type == 0) {
-            for (int j = lj; j < s; j += GL) a += db[(int64_t)f * Tout + t * s + j];
-        } else if (type == 1) {
-            for (int kf = 0; kf < fk; ++kf) {
-                const int fo = f + kf - pf; if (fo < 0 || fo >= C) continue;
-                for (int j = lj; j < s; j += GL) { const int64_t o = (int64_t)fo * Tout + t * s + j; a += K[kf * s + j] * db[o] * act_grad(ob[o], act, alpha); }
-            }
-        } else {
-            for (int kf = 0; kf < fk; ++kf) {
-                const int fo = f - kf + pf; if (fo < 0 || fo >= C) continue;
-                for (int kt = 0; kt < 3; ++kt) {
-                    const int tt = t - kt + 1; if (tt < 0 || tt >= Tin) continue;
-                    for (int j = lj; j < s; j += GL) { const int64_t o = (int64_t)fo * Tout + tt * s + j; a += K[(kf * 3 + kt) * s + j] * db[o] * act_grad(ob[o], act, alpha); }
-                }
-            }
-        }
-    }
-    for (int o = GL >> 1; o > 0; o >>= 1) a += __shfl_down(a, o, GL);
-    if (live && lj == 0) din[idx] = a;
-}
-
-// ---- round-2 replacements for types 1 / 2: no float atomics anywhere (bit-reproducible gradients), enough workgroups to fill the part.
-// Stage 1: workgroup (row = (b, f), time slice y) accumulates its taps in registers exactly like wn_up_bwd_params, folds the
-// threads of one phase j in a FIXED order through LDS and writes ne = nk + nb partial sums to part[block][e].
+// ---- types 1 / 2 ('2D' / 'SubPixel'): no float atomics anywhere (bit-reproducible gradients), enough workgroups to fill the part.
+// dpre = dout * act'(out);  dK[kf][j], dbias.
+// Stage 1: workgroup (row = (b, f), time slice y); thread x owns phase j = x % s of the stride-s output grid (to = j + s*q), so its
+// kernel taps are fixed and accumulate in registers; the threads of one phase j are folded in a FIXED order through LDS and
+// ne = nk + nb partial sums go to part[block][e].
 // Stage 2 (wn_up_bwd_params_reduce): one workgroup per element sums the blocks in a fixed order and STORES dK / dbias.
 __global__ __launch_bounds__(256) void wn_up_bwd_params2(const float* __restrict__ in, const float* __restrict__ out, const float* __restrict__ dout,
                                  float* __restrict__ part, int B, int C, int Tin, int s, int fk, int type, int act, float alpha, int tchunk) {
@@ -572,43 +483,27 @@ int wn_upsample_bwd(wn_ctx* c, const float* dc_final, float* grads, hipStream_t 
         }
         const int nk = (type == 1) ? fk * s : fk * 3 * s, nb = (type == 1) ? 1 : s;
         if ((size_t)(nk + nb) * 4 > 60000) WN_FAIL(c, WN_E_UNSUPPORTED, "upsample scale %d too large for the LDS partials", s);
-        const int64_t n = (int64_t)B * C * Tout;
         if (s > 256) WN_FAIL(c, WN_E_UNSUPPORTED, "upsample scale %d > 256", s);
-        (void)n;
-        static const bool v1 = getenv("WN_UP_BWD_V1") != nullptr;          // A/B switch: the round-1 kernels (float atomics)
-        if (v1) {
-        hipLaunchKernelGGL(wn_up_bwd_params, dim3(B * C), dim3(256), (nk + nb) * 4, st, in, c->CUP[i], dout,
-                           grads + c->up_k[i], grads + c->up_b[i], B, C, Tin, s, fk, type, c->cfg.upsample_activation, c->cfg.leaky_alpha);
+        const int rows = B * C, groups = 256 / s;
+        int Y = std::max(1, std::min(cdiv(2048, rows), cdiv(Tin, groups)));
+        const int tchunk = cdiv(Tin, Y); Y = cdiv(Tin, tchunk);
+        const int ne = nk + nb, nblk = rows * Y;
+        if ((int64_t)nblk * ne > c->uppart_floats) WN_FAIL(c, WN_E_STATE, "upsample partial buffer too small (%d x %d)", nblk, ne);
+        if ((type == 1 ? fk : fk * 3) > WN_UP_MAXTAP) WN_FAIL(c, WN_E_UNSUPPORTED, "freq_axis_kernel_size %d too large", fk);
+        hipLaunchKernelGGL(wn_up_bwd_params2, dim3(rows, Y), dim3(256), 0, st, in, c->CUP[i], dout, c->UPPART, B, C, Tin, s, fk, type,
+                           c->cfg.upsample_activation, c->cfg.leaky_alpha, tchunk);
         WN_LAUNCH_CHECK(c);
-        } else {
-            const int rows = B * C, groups = 256 / s;
-            int Y = std::max(1, std::min(cdiv(2048, rows), cdiv(Tin, groups)));
-            const int tchunk = cdiv(Tin, Y); Y = cdiv(Tin, tchunk);
-            const int ne = nk + nb, nblk = rows * Y;
-            if ((int64_t)nblk * ne > c->uppart_floats) WN_FAIL(c, WN_E_STATE, "upsample partial buffer too small (%d x %d)", nblk, ne);
-            if ((type == 1 ? fk : fk * 3) > WN_UP_MAXTAP) WN_FAIL(c, WN_E_UNSUPPORTED, "freq_axis_kernel_size %d too large", fk);
-            hipLaunchKernelGGL(wn_up_bwd_params2, dim3(rows, Y), dim3(256), 0, st, in, c->CUP[i], dout, c->UPPART, B, C, Tin, s, fk, type,
-                               c->cfg.upsample_activation, c->cfg.leaky_alpha, tchunk);
-            WN_LAUNCH_CHECK(c);
-            hipLaunchKernelGGL(wn_up_bwd_params_reduce, dim3(ne), dim3(256), 0, st, c->UPPART, nblk, ne, nk, grads + c->up_k[i], grads + c->up_b[i]);
-            WN_LAUNCH_CHECK(c);
-        }
+        hipLaunchKernelGGL(wn_up_bwd_params_reduce, dim3(ne), dim3(256), 0, st, c->UPPART, nblk, ne, nk, grads + c->up_k[i], grads + c->up_b[i]);
+        WN_LAUNCH_CHECK(c);
         if (i > 0) {
             float* din = c->DCUP[i & 1];
-            const int64_t ni = (int64_t)B * C * Tin;
-            if (v1) {
-            int GL = 1; while (GL < s && GL < 64) GL <<= 1;
-            hipLaunchKernelGGL(wn_up_bwd_input, dim3(cdiv(ni, 256 / GL)), dim3(256), 0, st, c->CUP[i], dout, din, c->params_dev + c->up_k[i],
-                               B, C, Tin, s, fk, type, c->cfg.upsample_activation, c->cfg.leaky_alpha, GL);
-            } else {
-                const int halo = (type == 2) ? 1 : 0;
-                int TB = std::min(256, 8192 / (fk * s) - 2 * halo);
-                if (TB < 1) WN_FAIL(c, WN_E_UNSUPPORTED, "upsample scale %d x freq kernel %d too large for the LDS stage", s, fk);
-                TB = std::min(TB, Tin);
-                const size_t lds = ((size_t)fk * (TB + 2 * halo) * s + nk) * 4;
-                hipLaunchKernelGGL(wn_up_bwd_input2, dim3(cdiv(Tin, TB), B * C), dim3(256), lds, st, c->CUP[i], dout, din, c->params_dev + c->up_k[i],
-                                   B, C, Tin, s, fk, type, c->cfg.upsample_activation, c->cfg.leaky_alpha, TB);
-            }
+            const int halo = (type == 2) ? 1 : 0;
+            int TB = std::min(256, 8192 / (fk * s) - 2 * halo);
+            if (TB < 1) WN_FAIL(c, WN_E_UNSUPPORTED, "upsample scale %d x freq kernel %d too large for the LDS stage", s, fk);
+            TB = std::min(TB, Tin);
+            const size_t lds = ((size_t)fk * (TB + 2 * halo) * s + nk) * 4;
+            hipLaunchKernelGGL(wn_up_bwd_input2, dim3(cdiv(Tin, TB), B * C), dim3(256), lds, st, c->CUP[i], dout, din, c->params_dev + c->up_k[i],
+                               B, C, Tin, s, fk, type, c->cfg.upsample_activation, c->cfg.leaky_alpha, TB);
             WN_LAUNCH_CHECK(c);
             dout = din;
         }

@@ -25,7 +25,8 @@ struct SrcSeg {
     int32_t col0;         // first channel of the segment
     int32_t nk;           // channels (multiple of 16)
     int32_t shift;        // time shift: source row t + shift, zero outside [0,T)
-    int32_t dropout;      // 1: apply the layer's dropout mask while staging
+    int32_t pad_;         // never read: keeps the segment at 32 bytes, i.e. every kernel-argument offset of GemmArgs where the register
+                          // audit and the step time were taken (profiles/retire_isa_audit.md)
 };
 
 struct EpiArgs {
@@ -93,22 +94,6 @@ __device__ __forceinline__ bool drop_keep(uint32_t key_lo, uint32_t key_hi, uint
     uint32_t w = wn_drop_word(key_lo, key_hi, e >> 1);
     uint32_t bits = (e & 1u) ? (w >> 16) : (w & 0xffffu);
     return bits >= thresh16;
-}
-
-// apply dropout to 8 consecutive bf16 elements starting at flat element index e0 (e0 % 8 == 0)
-__device__ __forceinline__ uint4 drop8(uint4 v, uint32_t key_lo, uint32_t key_hi, uint32_t thresh16, float ks, uint32_t e0) {
-    uint32_t in[4] = {v.x, v.y, v.z, v.w};
-    uint32_t out[4], wq[4];
-    wn_drop_quad(key_lo, key_hi, e0 >> 2, wq[0], wq[1]); wn_drop_quad(key_lo, key_hi, (e0 >> 2) + 1, wq[2], wq[3]);
-#pragma unroll
-    for (int p = 0; p < 4; ++p) {
-        const uint32_t w = wq[p];
-        float lo = bf2f((bf16_t)(in[p] & 0xffffu)), hi = bf2f((bf16_t)(in[p] >> 16));
-        lo = ((w & 0xffffu) >= thresh16) ? lo * ks : 0.0f;
-        hi = ((w >> 16) >= thresh16) ? hi * ks : 0.0f;
-        out[p] = pack_bf2(lo, hi);
-    }
-    return make_uint4(out[0], out[1], out[2], out[3]);
 }
 
 // Fused epilogues, shared by both main loops.  acc[i][j][r]: time t = t0w + j*32 + (lane&31);
@@ -287,9 +272,6 @@ __global__ __launch_bounds__(WM * WN * 64) void wn_gemm_tile_kernel(const GemmAr
             if (c16 * 8 < kc && t < T && ts >= 0 && ts < T) {
                 const int64_t r = rowbase + ts;
                 v = *reinterpret_cast<const uint4*>(base + r * s.ld + col + c16 * 8);
-                if (s.dropout)
-                    v = drop8(v, a.key_lo, a.key_hi, a.thresh16, a.keep_scale,
-                              (uint32_t)(r * a.drop_ld + col + c16 * 8));
             }
             st[p] = v;
         }

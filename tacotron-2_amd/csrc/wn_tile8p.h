@@ -450,7 +450,6 @@ static inline bool wn_gemm8p_fits(const GemmArgs& a, int M, int64_t rows_total) 
     if (M % 256 != 0 || a.e.M_valid != M || !a.zero || a.taps != 3 || a.nrep != 1 || a.nseg < 3 || a.nseg > 4) return false;
     if (a.seg[0].nk % 64 != 0 || a.seg[0].nk != a.seg[1].nk || a.seg[0].nk != a.seg[2].nk) return false;
     for (int s = 0; s < a.nseg; ++s) {
-        if (a.seg[s].dropout) return false;
         if (s >= 3 && (a.seg[s].shift != 0 || a.seg[s].nk % 16 != 0)) return false;
         if (s >= 3 && s + 1 < a.nseg && a.seg[s].nk % 64 != 0) return false;
         if (rows_total * a.seg[s].ld * 2 >= (int64_t)1 << 31) return false;

@@ -8,7 +8,7 @@ int wn_first_conv_grad(wn_ctx* c, const bf16_t* g0, float* grads, hipStream_t st
 int wn_upsample_bwd(wn_ctx* c, const float* dc_final, float* grads, hipStream_t st);
 int wn_loss_fwd_bwd(wn_ctx* c, float* loss_out, hipStream_t st);
 
-// Ablation switches of the DIAGNOSTIC build only (csrc/build.py --ablate defines WN_ABLATE_BUILD; the product library has none of this):
+// Ablation switches of the DIAGNOSTIC build only (csrc/build.py --ablate defines WN_ABLATE_BUILD and writes libwavenet_mi355_ablate.so; the product library has none of this):
 // WN_ABLATE bit 0 skips the d c_up GEMM, bit 1 the d W_cin launch, bit 2 every out-conv launch, bit 3 every d z launch.  Results are
 // WRONG by construction; the step time says what that launch class costs the LIVE two-stream step, i.e. the most any fusion / speed-up of
 // it could return ("measure it rather than price it").
@@ -34,8 +34,8 @@ static void base_args(wn_ctx* c, GemmArgs& a, const PackedW& w, int b0 = 0, int 
     a.e.scale = 1.0f; a.e.GH = c->GH; a.e.M_valid = w.M_valid;
 }
 
-static SrcSeg seg(const bf16_t* base, int ld, int col0, int nk, int shift, int drop) {
-    SrcSeg s; s.base = base; s.ld = ld; s.col0 = col0; s.nk = nk; s.shift = shift; s.dropout = drop; return s;
+static SrcSeg seg(const bf16_t* base, int ld, int col0, int nk, int shift) {
+    SrcSeg s{}; s.base = base; s.ld = ld; s.col0 = col0; s.nk = nk; s.shift = shift; return s;
 }
 
 static void prof_mark(wn_ctx* c, hipStream_t st) {
@@ -170,11 +170,6 @@ extern "C" int wn_profile_result(wn_ctx* c, double* total_ms, int64_t* launches)
 static void wgrad_common(wn_ctx* c, WgBatchArgs& w, int ng, int B, int T) {
     memset(&w, 0, sizeof w); w.ngroups = ng; w.B = B; w.T = T;
 }
-// multi-A weight-gradient workgroups (wn_wgrad.h): WN_WGRAD_MULTI=0 restores one A tile per workgroup (A/B switch)
-static bool wgrad_multi() {
-    static const int v = [] { const char* e = getenv("WN_WGRAD_MULTI"); return e ? atoi(e) : 1; }();
-    return v != 0;
-}
 // d W_dil of the layers [l0, l0 + ng): the three taps of one 128-channel block of the layer input share ONE workgroup and ONE staged
 // d z tile (A = xd(t-2d) | xd(t-d) | xd(t), B = d z); the conditioning kernel's gradient is its own (single-A) launch, wgrad_cin_args.
 static void wgrad_taps_args(wn_ctx* c, WgBatchArgs& w, int l0, int ng, int B, int T) {
@@ -203,7 +198,7 @@ static void wgrad_cin_args(wn_ctx* c, WgBatchArgs& w, int l0, int ng, int B, int
         q.out_off = c->lay[l].cin_k; q.bias_off = c->lbias ? c->lay[l].dil_b : -1; q.bias2_off = c->lbias ? c->lay[l].cin_b : 0; q.has_bias2 = c->lbias ? 1 : 0; q.scale = 1.0f;
     }
 }
-static bool wgrad_taps_ok(wn_ctx* c) { return wgrad_multi() && c->R % 128 == 0 && c->G % 256 == 0; }
+static bool wgrad_taps_ok(wn_ctx* c) { return c->R % 128 == 0 && c->G % 256 == 0; }
 static void wgrad_w1_args(wn_ctx* c, WgBatchArgs& w, int l0, int ng, int B, int T) {
     const int64_t NT = c->NT; const int R = c->R, G = c->G, C = c->C;
     wgrad_common(c, w, ng, B, T);
@@ -246,7 +241,7 @@ static void wgrad_skipout_args(wn_ctx* c, WgBatchArgs& w, int l0, int ng, int B,
     w.nseg = 1; w.seg_base[0] = c->U + (size_t)l0 * NT * GH; w.seg_gstride[0] = NT * GH; w.seg_ld[0] = GH; w.seg_nk[0] = GH;
     w.Bm = c->DSKIP; w.b_gstride = 0; w.ldb = S; w.N = S + R; w.ldw = S;
     w.Bm_hi = c->GXall + (size_t)(l0 + 1) * NT * R; w.b_gstride_hi = NT * R; w.ldb_hi = R; w.split_n = S; w.ldw_hi = R;
-    if (wgrad_multi() && GH % 256 == 0) {      // both 128-channel halves of a 256-channel block of u_l share the staged [d skip | d h] tile
+    if (GH % 256 == 0) {      // both 128-channel halves of a 256-channel block of u_l share the staged [d skip | d h] tile
         w.na = 2; w.hblocks = GH / 256; w.a_colstep = 256;
         for (int x = 0; x < 2; ++x) { w.a_seg[x] = 0; w.a_col0[x] = 128 * x; w.a_mrow[x] = 128 * x; }
     }
@@ -266,7 +261,7 @@ static void wgrad_head1_args(wn_ctx* c, WgBatchArgs& w, int B, int T) {
     wgrad_common(c, w, 1, B, T);
     w.nseg = 1; w.seg_base[0] = c->R1; w.seg_gstride[0] = 0; w.seg_ld[0] = S; w.seg_nk[0] = S;
     w.Bm = c->DPRE1; w.b_gstride = 0; w.ldb = S; w.N = S; w.ldw = S;
-    if (wgrad_multi() && S % 256 == 0) {
+    if (S % 256 == 0) {
         w.na = 2; w.hblocks = S / 256; w.a_colstep = 256;
         for (int x = 0; x < 2; ++x) { w.a_seg[x] = 0; w.a_col0[x] = 128 * x; w.a_mrow[x] = 128 * x; }
     }
@@ -284,31 +279,77 @@ static void wgrad_head2_args(wn_ctx* c, WgBatchArgs& w, int B, int T) {
     q.out_off = c->fin2_k; q.bias_off = -1; q.bias2_off = 0; q.has_bias2 = 0; q.scale = 1.0f;      // (the bias row of this launch sums H2: unused)
 }
 static bool wgrad_heads_ok(wn_ctx* c) {
-    static const int v = [] { const char* e = getenv("WN_WGRAD_HEADS"); return e ? atoi(e) : 1; }();      // A/B switch (0: round-1 kernel)
-    if (!v || c->S % 8 != 0 || c->O > 128) return false;
+    if (c->S % 8 != 0 || c->O > 128) return false;      // (else: the per-layer kernel wn_wgrad_kernel, wgrad_v1_head*_args)
     WgBatchArgs w; wgrad_head1_args(c, w, 1, c->maxT); if (!wn_wgrad_v2_ok(w)) return false;
     wgrad_head2_args(c, w, 1, c->maxT); return wn_wgrad_v2_ok(w);
+}
+// ---- per-layer descriptors of wn_wgrad_kernel (float atomics): narrow models (N % 256 != 0) and the softmax head (O > 128) ----------
+static void wgrad_v1_common(wn_ctx* c, WgArgs& w) {
+    memset(&w, 0, sizeof w); w.ones_row = 1; w.scale = 1.0f; w.B = c->fB; w.T = c->fT;
+}
+// d [W_dil; W_cin], d biases of layer l:  A = [xd(t-2d) | xd(t-d) | xd(t) | c(t)],  B = d z
+static void wgrad_v1_w1_args(wn_ctx* c, WgArgs& w, float* grads, int l) {
+    const int64_t NT = c->NT; const int R = c->R, G = c->G, C = c->C, d = c->dil[l];
+    const bf16_t* XDl = c->XD + (size_t)l * NT * R;
+    wgrad_v1_common(c, w);
+    w.nseg = 4;
+    w.seg[0] = seg(XDl, R, 0, R, -2 * d); w.seg[1] = seg(XDl, R, 0, R, -d); w.seg[2] = seg(XDl, R, 0, R, 0);
+    w.seg[3] = seg(c->cbt, C, 0, C, 0);
+    w.Bm = c->DZ + (size_t)l * NT * G; w.ldb = G; w.N = G;
+    w.out = grads + c->lay[l].dil_k; w.ldw = G; w.bias_out = c->lbias ? grads + c->lay[l].dil_b : nullptr; w.bias_out2 = c->lbias ? grads + c->lay[l].cin_b : nullptr;
+}
+// d W_skip (scaled by the legacy factor c_l), d skip bias of layer l:  A = u_l,  B = d skip
+static void wgrad_v1_skip_args(wn_ctx* c, WgArgs& w, float* grads, int l) {
+    const int GH = c->GH, S = c->S;
+    wgrad_v1_common(c, w);
+    w.nseg = 1; w.seg[0] = seg(c->U + (size_t)l * c->NT * GH, GH, 0, GH, 0);
+    w.Bm = c->DSKIP; w.ldb = S; w.N = S;
+    w.out = grads + c->lay[l].skip_k; w.ldw = S; w.bias_out = c->lbias ? grads + c->lay[l].skip_b : nullptr;
+    w.scale = c->skip_scale[l];
+}
+// d W_out, d out bias of layer l < L - 1:  A = u_l,  B = rho * dL/dh_{l+1}
+static void wgrad_v1_out_args(wn_ctx* c, WgArgs& w, float* grads, int l) {
+    const int GH = c->GH, R = c->R;
+    wgrad_v1_common(c, w);
+    w.nseg = 1; w.seg[0] = seg(c->U + (size_t)l * c->NT * GH, GH, 0, GH, 0);
+    w.Bm = c->GXall + (size_t)(l + 1) * c->NT * R; w.ldb = R; w.N = R;
+    w.out = grads + c->lay[l].out_k; w.ldw = R; w.bias_out = c->lbias ? grads + c->lay[l].out_b : nullptr;
+}
+static void wgrad_v1_head1_args(wn_ctx* c, WgArgs& w, float* grads) {      // d final_convolution_1 = R1^T d pre1, + bias
+    const int S = c->S;
+    wgrad_v1_common(c, w);
+    w.nseg = 1; w.seg[0] = seg(c->R1, S, 0, S, 0);
+    w.Bm = c->DPRE1; w.ldb = S; w.N = S;
+    w.out = grads + c->fin1_k; w.ldw = S; w.bias_out = grads + c->fin1_b;
+}
+static void wgrad_v1_head2_args(wn_ctx* c, WgArgs& w, float* grads) {      // d final_convolution_2 = H2^T dY, + bias
+    const int S = c->S, O = c->O, ldDY = (O + 15) / 16 * 16;
+    wgrad_v1_common(c, w);
+    w.nseg = 1; w.seg[0] = seg(c->H2, S, 0, S, 0);
+    w.Bm = c->DY; w.ldb = ldDY; w.N = O;
+    w.out = grads + c->fin2_k; w.ldw = O; w.bias_out = grads + c->fin2_b;
 }
 // bytes of split-K partials the grouped launches can need for any batch <= max_batch at max_time
 size_t wn_wgrad_partial_need(wn_ctx* c) {
     size_t need = 0;
+    auto plan = [&need](WgBatchArgs& w) { if (wn_wgrad_v2_ok(w)) { wn_wgrad_plan(w); need = std::max(need, wn_wgrad_partial_bytes(w)); } };
     for (int ng = 1; ng <= min(WN_MAX_GROUPS, c->L); ++ng)          // any bucket size (wn_plan_buckets) up to all layers at once
     for (int B = 1; B <= c->maxB; ++B) {
         WgBatchArgs w;
-        wgrad_w1_args(c, w, 0, ng, B, c->maxT); if (wn_wgrad_v2_ok(w)) { wn_wgrad_plan(w); need = std::max(need, wn_wgrad_partial_bytes(w)); }
+        wgrad_w1_args(c, w, 0, ng, B, c->maxT); plan(w);
         if (wgrad_taps_ok(c)) {
-            wgrad_taps_args(c, w, 0, ng, B, c->maxT); if (wn_wgrad_v2_ok(w)) { wn_wgrad_plan(w); need = std::max(need, wn_wgrad_partial_bytes(w)); }
-            wgrad_cin_args(c, w, 0, ng, B, c->maxT); if (wn_wgrad_v2_ok(w)) { wn_wgrad_plan(w); need = std::max(need, wn_wgrad_partial_bytes(w)); }
+            wgrad_taps_args(c, w, 0, ng, B, c->maxT); plan(w);
+            wgrad_cin_args(c, w, 0, ng, B, c->maxT); plan(w);
         }
-        wgrad_skip_args(c, w, 0, ng, B, c->maxT); if (wn_wgrad_v2_ok(w)) { wn_wgrad_plan(w); need = std::max(need, wn_wgrad_partial_bytes(w)); }
-        wgrad_out_args(c, w, 0, ng, B, c->maxT); if (wn_wgrad_v2_ok(w)) { wn_wgrad_plan(w); need = std::max(need, wn_wgrad_partial_bytes(w)); }
-        wgrad_skipout_args(c, w, 0, ng, B, c->maxT); if (wn_wgrad_v2_ok(w)) { wn_wgrad_plan(w); need = std::max(need, wn_wgrad_partial_bytes(w)); }
+        wgrad_skip_args(c, w, 0, ng, B, c->maxT); plan(w);
+        wgrad_out_args(c, w, 0, ng, B, c->maxT); plan(w);
+        wgrad_skipout_args(c, w, 0, ng, B, c->maxT); plan(w);
     }
     if (wgrad_heads_ok(c))      // (the head launches share the stream of the stack launches: one buffer serves both)
         for (int B = 1; B <= c->maxB; ++B) {
             WgBatchArgs w;
-            wgrad_head1_args(c, w, B, c->maxT); wn_wgrad_plan(w); need = std::max(need, wn_wgrad_partial_bytes(w));
-            wgrad_head2_args(c, w, B, c->maxT); wn_wgrad_plan(w); need = std::max(need, wn_wgrad_partial_bytes(w));
+            wgrad_head1_args(c, w, B, c->maxT); plan(w);
+            wgrad_head2_args(c, w, B, c->maxT); plan(w);
         }
     return need + (1 << 20);
 }
@@ -346,10 +387,10 @@ static void mk_gate(wn_ctx* c, int l, int b0, int nb, GemmArgs& a) {
     const bf16_t* XDl = (c->feval ? c->X : c->XD) + (size_t)l * NT * R;      // dropout already applied by the producer (wn_eval_fwd: none, the layer input itself)
     base_args(c, a, c->packs[l].w1, b0, nb);
     a.nseg = 4;
-    a.seg[0] = seg(XDl, R, 0, R, -2 * d, 0);
-    a.seg[1] = seg(XDl, R, 0, R, -d, 0);
-    a.seg[2] = seg(XDl, R, 0, R, 0, 0);
-    a.seg[3] = seg(c->cbt, C, 0, C, 0, 0);
+    a.seg[0] = seg(XDl, R, 0, R, -2 * d);
+    a.seg[1] = seg(XDl, R, 0, R, -d);
+    a.seg[2] = seg(XDl, R, 0, R, 0);
+    a.seg[3] = seg(c->cbt, C, 0, C, 0);
     a.taps = c->packs[l].w1.kil ? 3 : 0; a.kil = c->packs[l].w1.kil;
     if (c->gin > 0) { a.e.bias = c->gbias + (size_t)l * c->fB * G; a.e.bias_bstride = G; }      // + W_g^T g + b_g per utterance
     else a.e.bias = c->b1sum + (size_t)l * G;
@@ -360,7 +401,7 @@ static void mk_out(wn_ctx* c, int l, int b0, int nb, GemmArgs& o) {
     const int R = c->R, GH = c->GH;
     const int64_t NT = c->NT;
     base_args(c, o, c->packs[l].wo, b0, nb);
-    o.nseg = 1; o.seg[0] = seg(c->U + (size_t)l * NT * GH, GH, 0, GH, 0, 0);
+    o.nseg = 1; o.seg[0] = seg(c->U + (size_t)l * NT * GH, GH, 0, GH, 0);
     o.e.bias = c->params_dev + c->lay[l].out_b;
     o.e.in0 = c->X + (size_t)l * NT * R; o.e.ld_in0 = R;
     o.e.scale = c->res_scale;
@@ -395,19 +436,19 @@ static int fwd_tail(wn_ctx* c, int b0, int nb, hipStream_t st) {
     int rc;
     {   // skip sum over all layers as one contraction, + ReLU (wavenet.py:716-719 first activation)
         GemmArgs a; base_args(c, a, c->wskip, b0, nb);
-        a.nseg = 1; a.seg[0] = seg(c->U, GH, 0, GH, 0, 0); a.nrep = L; a.rep_stride = NT * GH;
+        a.nseg = 1; a.seg[0] = seg(c->U, GH, 0, GH, 0); a.nrep = L; a.rep_stride = NT * GH;
         a.e.bias = c->skip_bias_total; a.e.relu = 1; a.e.out0 = c->R1; a.e.ld_out0 = S;
         if ((rc = wn_launch_gemm<EPI_STORE_BF16>(c, a, c->wskip.M, st))) return rc;
     }
     {   // final_convolution_1 + ReLU
         GemmArgs a; base_args(c, a, c->wh1, b0, nb);
-        a.nseg = 1; a.seg[0] = seg(c->R1, S, 0, S, 0, 0);
+        a.nseg = 1; a.seg[0] = seg(c->R1, S, 0, S, 0);
         a.e.bias = c->params_dev + c->fin1_b; a.e.relu = 1; a.e.out0 = c->H2; a.e.ld_out0 = S;
         if ((rc = wn_launch_gemm<EPI_STORE_BF16>(c, a, c->wh1.M, st))) return rc;
     }
     {   // final_convolution_2 -> y_hat [B,O,T] fp32
         GemmArgs a; base_args(c, a, c->wh2, b0, nb);
-        a.nseg = 1; a.seg[0] = seg(c->H2, S, 0, S, 0, 0);
+        a.nseg = 1; a.seg[0] = seg(c->H2, S, 0, S, 0);
         a.e.bias = c->params_dev + c->fin2_b; a.e.out0 = c->YHAT; a.e.M_valid = c->O;
         if ((rc = wn_launch_gemm<EPI_STORE_F32_BOT>(c, a, c->wh2.M, st))) return rc;
     }
@@ -491,14 +532,14 @@ static int bwd_head(wn_ctx* c, int b0, int nb, hipStream_t st, int part) {
     int rc;
     {   // d pre1 = (W2 dY) * (H2 > 0)
         GemmArgs a; base_args(c, a, c->wh2T, b0, nb);
-        a.nseg = 1; a.seg[0] = seg(c->DY, ldDY, 0, c->wh2T.K, 0, 0);
+        a.nseg = 1; a.seg[0] = seg(c->DY, ldDY, 0, c->wh2T.K, 0);
         a.e.in0 = c->H2; a.e.ld_in0 = S; a.e.out0 = c->DPRE1; a.e.ld_out0 = S;
         if ((rc = wn_launch_gemm<EPI_MASK_STORE>(c, a, c->wh2T.M, st))) return rc;
         WN_HIP(c, hipEventRecord(c->ev_head[part], st));
     }
     {   // d skip = (W1 dpre1) * (skips > 0)
         GemmArgs a; base_args(c, a, c->wh1T, b0, nb);
-        a.nseg = 1; a.seg[0] = seg(c->DPRE1, S, 0, S, 0, 0);
+        a.nseg = 1; a.seg[0] = seg(c->DPRE1, S, 0, S, 0);
         a.e.in0 = c->R1; a.e.ld_in0 = S; a.e.out0 = c->DSKIP; a.e.ld_out0 = S;
         if ((rc = wn_launch_gemm<EPI_MASK_STORE>(c, a, c->wh1T.M, st))) return rc;
     }
@@ -510,8 +551,8 @@ static void mk_dgate(wn_ctx* c, int l, int b0, int nb, GemmArgs& a) {
     const int64_t NT = c->NT;
     base_args(c, a, c->packs[l].w2T, b0, nb);
     a.nseg = 2;
-    a.seg[0] = seg(c->GXall + (size_t)(l + 1) * NT * R, R, 0, R, 0, 0);
-    a.seg[1] = seg(c->DSKIP, S, 0, S, 0, 0);
+    a.seg[0] = seg(c->GXall + (size_t)(l + 1) * NT * R, R, 0, R, 0);
+    a.seg[1] = seg(c->DSKIP, S, 0, S, 0);
     a.e.in0 = c->TS + (size_t)l * NT * (G / 2); a.e.in1 = c->U + (size_t)l * NT * (G / 2); a.e.ld_in0 = G / 2; a.e.out0 = c->DZ + (size_t)l * NT * G; a.e.ld_out0 = G;
 }
 // d h_l = dropout-mask * conv^T(dz) + residual path   (modules.py:484, 517-520)   (MFMA-bound)
@@ -523,9 +564,9 @@ static void mk_dx(wn_ctx* c, int l, int b0, int nb, GemmArgs& a) {
     const bool top = (l == c->L - 1);
     base_args(c, a, c->packs[l].w1T, b0, nb);
     a.nseg = 3;
-    a.seg[0] = seg(DZl, G, 0, G, 2 * d, 0);
-    a.seg[1] = seg(DZl, G, 0, G, d, 0);
-    a.seg[2] = seg(DZl, G, 0, G, 0, 0);
+    a.seg[0] = seg(DZl, G, 0, G, 2 * d);
+    a.seg[1] = seg(DZl, G, 0, G, d);
+    a.seg[2] = seg(DZl, G, 0, G, 0);
     a.taps = c->packs[l].w1T.kil ? 3 : 0; a.kil = c->packs[l].w1T.kil;
     set_dropout(c, l, a.key_lo, a.key_hi, a.thresh16, a.keep_scale, a.drop_ld);
     if (!(c->cfg.dropout > 0.0f)) a.thresh16 = 0;
@@ -666,11 +707,112 @@ static int stack_wgrads(wn_ctx* c, float* grads, int l0, int ng, bool fused, hip
     return WN_OK;
 }
 
+// the same three gradients of ONE layer on the per-layer kernel (narrow channel counts: N % 256 != 0)
+static int stack_wgrads_narrow(wn_ctx* c, float* grads, int l, hipStream_t st) {
+    int rc;
+    WgArgs w;
+    wgrad_v1_w1_args(c, w, grads, l);
+    if ((rc = launch_wgrad(c, w, st))) return rc;
+    wgrad_v1_skip_args(c, w, grads, l);
+    if ((rc = launch_wgrad(c, w, st))) return rc;
+    if (l != c->L - 1) {      // the top layer's residual branch is dead: zero gradient
+        wgrad_v1_out_args(c, w, grads, l);
+        if ((rc = launch_wgrad(c, w, st))) return rc;
+    }
+    return WN_OK;
+}
+
+// ---- the phases of the backward schedule, in the order wn_bwd_eff enqueues them -------------------------------
+struct WgradPath {
+    bool grouped;      // stack weight gradients on the grouped LDS-DMA kernel (else per layer: stack_wgrads_narrow)
+    bool fused;        // d W_skip and d W_out of a bucket in one launch
+    bool heads_v2;     // head weight gradients on the grouped kernel too
+    int nearly;        // buckets whose weight gradients run under the chain
+};
+static WgradPath wgrad_path(wn_ctx* c) {
+    WgradPath p;
+    WgBatchArgs w; wgrad_w1_args(c, w, 0, 1, c->fB, c->fT); p.grouped = wn_wgrad_v2_ok(w);
+    wgrad_skipout_args(c, w, 0, 1, c->fB, c->fT); p.fused = wn_wgrad_v2_ok(w) && c->S % 8 == 0;     // N = S + R (256 for the 128-channel default hparams)
+    if (!p.fused) { wgrad_skip_args(c, w, 0, 1, c->fB, c->fT); p.grouped = p.grouped && wn_wgrad_v2_ok(w);
+                    wgrad_out_args(c, w, 0, 1, c->fB, c->fT); p.grouped = p.grouped && wn_wgrad_v2_ok(w); }
+    p.heads_v2 = wgrad_heads_ok(c);
+    p.nearly = p.grouped ? c->nbuckets_early : 0;       // (per-layer v1 kernels: everything after the chain, as one piece)
+    return p;
+}
+// d final_convolution_2 = H2^T dY: both operands exist since the forward / loss -- starts now, under the chain (low priority)
+static int head2_wgrad(wn_ctx* c, float* grads, const WgradPath& p, hipStream_t wst) {
+    int rc;
+    if (p.heads_v2) {
+        const int O = c->O, ldDY = (O + 15) / 16 * 16;
+        WgBatchArgs w; wgrad_head2_args(c, w, c->fB, c->fT); w.grads = grads;
+        if ((rc = launch_wgrad_batch(c, w, wst))) return rc;
+        return wn_colsum2(c, c->DY, ldDY, ldDY, O, nullptr, (int64_t)c->fB * c->fT, grads + c->fin2_b, nullptr, 1, wst);
+    }
+    WgArgs w; wgrad_v1_head2_args(c, w, grads);
+    return launch_wgrad(c, w, wst);
+}
+// d final_convolution_1 = R1^T dpre1 over the whole batch (wavenet.py:136-149) needs d pre1 of every part, the first thing each chain
+// stream computes (enqueued after the chain in host order, gated only by those events)
+static int head1_wgrad(wn_ctx* c, float* grads, const WgradPath& p, hipStream_t wst) {
+    for (int pk = 0; pk < c->parts; ++pk) WN_HIP(c, hipStreamWaitEvent(wst, c->ev_head[pk], 0));
+    if (p.heads_v2) {
+        WgBatchArgs w; wgrad_head1_args(c, w, c->fB, c->fT); w.grads = grads;
+        return launch_wgrad_batch(c, w, wst);
+    }
+    WgArgs w; wgrad_v1_head1_args(c, w, grads);
+    return launch_wgrad(c, w, wst);
+}
+// st -> wst: everything enqueued on st so far happens before what wst gets next
+static int wst_after(wn_ctx* c, hipStream_t st, hipStream_t wst) {
+    WN_HIP(c, hipEventRecord(c->ev_w0, st));
+    WN_HIP(c, hipStreamWaitEvent(wst, c->ev_w0, 0));
+    return WN_OK;
+}
+// weight gradients of the early buckets, each kind for all layers of a bucket in one grouped launch (wn_wgrad.h), each bucket as soon
+// as every chain stream has passed its lowest layer; without early buckets the weight-gradient stream waits for the whole chain
+static int early_buckets(wn_ctx* c, float* grads, const WgradPath& p, hipStream_t st, hipStream_t wst) {
+    int rc;
+    if (p.nearly == 0) return wst_after(c, st, wst);
+    for (int k = 0; k < p.nearly; ++k) {
+        for (int pk = 0; pk < c->parts; ++pk) WN_HIP(c, hipStreamWaitEvent(wst, c->ev_chain[pk][k], 0));
+        for (int l0 = c->bucket_lo[k]; l0 < c->bucket_hi[k]; l0 += WN_MAX_GROUPS)
+            if ((rc = stack_wgrads(c, grads, l0, min(WN_MAX_GROUPS, c->bucket_hi[k] - l0), p.fused, wst))) return rc;
+        WN_HIP(c, hipEventRecord(c->ev_bucket[k], wst));
+    }
+    return WN_OK;
+}
+// the layers below the early buckets (all layers when there are none), on the weight-gradient stream
+static int low_layer_wgrads(wn_ctx* c, float* grads, const WgradPath& p, hipStream_t wst) {
+    const int L = c->L;
+    int rc;
+    if (p.grouped) {
+        const int hi = p.nearly > 0 ? c->bucket_lo[p.nearly - 1] : L;
+        for (int l0 = 0; l0 < hi; l0 += WN_MAX_GROUPS)
+            if ((rc = stack_wgrads(c, grads, l0, min(WN_MAX_GROUPS, hi - l0), p.fused, wst))) return rc;
+        return WN_OK;
+    }
+    for (int l = L - 1; l >= 0; --l)
+        if ((rc = stack_wgrads_narrow(c, grads, l, wst))) return rc;
+    return WN_OK;
+}
+// everything small or latency-bound: global-conditioning / input-conv / upsample-net gradients, the d c_up GEMM
+static int small_grads(wn_ctx* c, float* grads, hipStream_t side) {
+    int rc;
+    if ((rc = wn_gin_bwd(c, grads, side))) return rc;     // d W_g, d b_g, d embedding table (modules.py:499-508)
+    if ((rc = wn_first_conv_grad(c, c->GXall, grads, side))) return rc;      // GXall[0] = dL/dh_0
+    if (c->cfg.upsample_type != WN_UP_NEAREST) {
+        // d c_up[b][cc][t] = sum_l W_cin_l dz_l  as one contraction over all layers
+        GemmArgs a; base_args(c, a, c->wcT);
+        a.nseg = 1; a.seg[0] = seg(c->DZ, c->G, 0, c->G, 0); a.nrep = c->L; a.rep_stride = c->NT * c->G;
+        a.e.out0 = c->DC; a.e.M_valid = c->C;
+        if (!(wn_ablate() & 1)) if ((rc = wn_launch_gemm<EPI_STORE_F32_BOT>(c, a, c->wcT.M, side))) return rc;
+        if ((rc = wn_upsample_bwd(c, c->DC, grads, side))) return rc;
+    }
+    return WN_OK;
+}
+
 static int wn_bwd_eff(wn_ctx* c, float* grads, hipStream_t st) {
     if (!c->have_loss) WN_FAIL(c, WN_E_STATE, "wn_train_bwd needs a forward that computed the loss (loss_out != NULL)");
-    const int L = c->L, R = c->R, G = c->G, GH = c->GH, S = c->S, C = c->C, O = c->O;
-    const int64_t NT = c->NT;
-    const int ldDY = (O + 15) / 16 * 16;
     int rc;
     if ((rc = buckets_setup(c))) return rc;
     WN_HIP(c, hipMemsetAsync(grads, 0, (size_t)c->n_params * 4, st));
@@ -681,125 +823,28 @@ static int wn_bwd_eff(wn_ctx* c, float* grads, hipStream_t st) {
         c->have_bwd = true;
         return WN_OK;
     }
-    const int64_t rows = (int64_t)c->fB * c->fT;
-    WN_HIP(c, hipMemsetAsync(c->GXall + (size_t)L * NT * R, 0, (size_t)rows * R * 2, st));   // top layer: residual branch is dead
-    bool grouped, fused;
-    { WgBatchArgs w; wgrad_w1_args(c, w, 0, 1, c->fB, c->fT); grouped = wn_wgrad_v2_ok(w);
-      wgrad_skipout_args(c, w, 0, 1, c->fB, c->fT); fused = wn_wgrad_v2_ok(w) && c->S % 8 == 0;     // N = S + R (256 for the 128-channel default hparams)
-      if (!fused) { wgrad_skip_args(c, w, 0, 1, c->fB, c->fT); grouped = grouped && wn_wgrad_v2_ok(w);
-                    wgrad_out_args(c, w, 0, 1, c->fB, c->fT); grouped = grouped && wn_wgrad_v2_ok(w); } }
-    const int nearly = grouped ? c->nbuckets_early : 0;       // (per-layer v1 kernels: everything after the chain, as one piece)
-    c->nearly_live = nearly;                                  // wn_bwd_wait_bucket: which pieces have their own event in THIS backward
-    // ---- weight-gradient stream: head weight gradients first (their operands exist since the forward / loss), then one bucket of
-    // stack weight gradients whenever both chain streams have passed its lowest layer
-    WN_HIP(c, hipEventRecord(c->ev_w0, st));
+    WN_HIP(c, hipMemsetAsync(c->GXall + (size_t)c->L * c->NT * c->R, 0, (size_t)c->fB * c->fT * c->R * 2, st));   // top layer: residual branch is dead
+    const WgradPath p = wgrad_path(c);
+    c->nearly_live = p.nearly;                                // wn_bwd_wait_bucket: which pieces have their own event in THIS backward
     static const bool serial = getenv("WN_SERIAL") != nullptr;      // profiling aid: every kernel on the caller's stream (with WN_BATCH_PARTS=1: exclusive kernel times)
-    hipStream_t wst = serial ? st : c->st3;
-    WN_HIP(c, hipStreamWaitEvent(wst, c->ev_w0, 0));
-    const bool heads_v2 = wgrad_heads_ok(c);
-    if (heads_v2) {   // d final_convolution_2 = H2^T dY: both operands exist since the forward / loss -- starts now, under the chain (low priority)
-        WgBatchArgs w; wgrad_head2_args(c, w, c->fB, c->fT); w.grads = grads;
-        if ((rc = launch_wgrad_batch(c, w, wst))) return rc;
-        if ((rc = wn_colsum2(c, c->DY, ldDY, ldDY, O, nullptr, rows, grads + c->fin2_b, nullptr, 1, wst))) return rc;
-    } else {
-        WgArgs w; memset(&w, 0, sizeof w);
-        w.nseg = 1; w.seg[0] = seg(c->H2, S, 0, S, 0, 0); w.ones_row = 1;
-        w.Bm = c->DY; w.ldb = ldDY; w.colb0 = 0; w.N = O;
-        w.out = grads + c->fin2_k; w.ldw = O; w.bias_out = grads + c->fin2_b; w.scale = 1.0f; w.B = c->fB; w.T = c->fT;
-        if ((rc = launch_wgrad(c, w, wst))) return rc;
-    }
-    // ---- the serial chain, per batch part (two streams)
+    hipStream_t wst = serial ? st : c->st3;                   // weight-gradient stream (low priority)
+    if ((rc = wst_after(c, st, wst))) return rc;
+    if ((rc = head2_wgrad(c, grads, p, wst))) return rc;
+    // the serial chain, per batch part (two streams)
     if ((rc = for_each_part(c, st, [&](int b0, int nb, hipStream_t s, bool, int part) { return bwd_part(c, b0, nb, s, part); }))) return rc;
-    // ---- head weight gradients over the whole batch (wavenet.py:136-149): d final_convolution_1 = R1^T dpre1 needs d pre1 of every
-    // part, the first thing each chain stream computes (enqueued after the chain in host order, gated only by those events)
-    for (int pk = 0; pk < c->parts; ++pk) WN_HIP(c, hipStreamWaitEvent(wst, c->ev_head[pk], 0));
-    if (heads_v2) {
-        WgBatchArgs w; wgrad_head1_args(c, w, c->fB, c->fT); w.grads = grads;
-        if ((rc = launch_wgrad_batch(c, w, wst))) return rc;
-    } else {
-        WgArgs w; memset(&w, 0, sizeof w);
-        w.nseg = 1; w.seg[0] = seg(c->R1, S, 0, S, 0, 0); w.ones_row = 1;
-        w.Bm = c->DPRE1; w.ldb = S; w.N = S;
-        w.out = grads + c->fin1_k; w.ldw = S; w.bias_out = grads + c->fin1_b; w.scale = 1.0f; w.B = c->fB; w.T = c->fT;
-        if ((rc = launch_wgrad(c, w, wst))) return rc;
-    }
-    {   // the stack weight gradients below need the chain (all of it, or up to the first bucket's lowest layer)
-        if (nearly > 0) {
-            for (int pk = 0; pk < c->parts; ++pk) WN_HIP(c, hipStreamWaitEvent(wst, c->ev_chain[pk][0], 0));
-        } else {
-            WN_HIP(c, hipEventRecord(c->ev_w0, st));
-            WN_HIP(c, hipStreamWaitEvent(wst, c->ev_w0, 0));
-        }
-    }
-    // ---- weight gradients of the stack, each kind for all layers of a bucket in one grouped launch (wn_wgrad.h)
-    for (int k = 0; k < nearly; ++k) {
-        if (k > 0) {
-            for (int pk = 0; pk < c->parts; ++pk) WN_HIP(c, hipStreamWaitEvent(wst, c->ev_chain[pk][k], 0));
-        }
-        for (int l0 = c->bucket_lo[k]; l0 < c->bucket_hi[k]; l0 += WN_MAX_GROUPS)
-            if ((rc = stack_wgrads(c, grads, l0, min(WN_MAX_GROUPS, c->bucket_hi[k] - l0), fused, wst))) return rc;
-        WN_HIP(c, hipEventRecord(c->ev_bucket[k], wst));
-    }
-    // ---- after the chain: the lowest layers' weight gradients (weight-gradient stream), and on the second stream everything small
-    // or latency-bound (global-conditioning / input-conv / upsample-net gradients, the d c_up GEMM); disjoint regions of `grads`
-    WN_HIP(c, hipEventRecord(c->ev_w0, st));
-    WN_HIP(c, hipStreamWaitEvent(wst, c->ev_w0, 0));
+    if ((rc = head1_wgrad(c, grads, p, wst))) return rc;
+    if ((rc = early_buckets(c, grads, p, st, wst))) return rc;
+    // after the chain: the lowest layers' weight gradients (weight-gradient stream) beside the small gradients (second stream);
+    // disjoint regions of `grads`
+    if ((rc = wst_after(c, st, wst))) return rc;
     hipStream_t side = st;
     if (c->parts >= 2) {
         WN_HIP(c, hipEventRecord(c->ev_fork, st));
         WN_HIP(c, hipStreamWaitEvent(c->st2, c->ev_fork, 0));
         side = c->st2;
     }
-    if (grouped) {
-        const int hi = nearly > 0 ? c->bucket_lo[nearly - 1] : L;
-        for (int l0 = 0; l0 < hi; l0 += WN_MAX_GROUPS)
-            if ((rc = stack_wgrads(c, grads, l0, min(WN_MAX_GROUPS, hi - l0), fused, wst))) return rc;
-    }
-    for (int l = L - 1; !grouped && l >= 0; --l) {      // narrow channel counts (N % 256 != 0): per-layer v1 kernels
-        const int d = c->dil[l];
-        const bf16_t* Ul = c->U + (size_t)l * NT * GH;
-        const bf16_t* XDl = c->XD + (size_t)l * NT * R;
-        const bf16_t* gxu = c->GXall + (size_t)(l + 1) * NT * R;
-        {
-            WgArgs w; memset(&w, 0, sizeof w);
-            w.nseg = 4;
-            w.seg[0] = seg(XDl, R, 0, R, -2 * d, 0); w.seg[1] = seg(XDl, R, 0, R, -d, 0); w.seg[2] = seg(XDl, R, 0, R, 0, 0);
-            w.seg[3] = seg(c->cbt, C, 0, C, 0, 0);
-            w.ones_row = 1;
-            w.Bm = c->DZ + (size_t)l * NT * G; w.ldb = G; w.N = G;
-            w.out = grads + c->lay[l].dil_k; w.ldw = G; w.bias_out = c->lbias ? grads + c->lay[l].dil_b : nullptr; w.bias_out2 = c->lbias ? grads + c->lay[l].cin_b : nullptr;
-            w.scale = 1.0f; w.B = c->fB; w.T = c->fT;
-            if ((rc = launch_wgrad(c, w, wst))) return rc;
-        }
-        {
-            WgArgs w; memset(&w, 0, sizeof w);
-            w.nseg = 1; w.seg[0] = seg(Ul, GH, 0, GH, 0, 0); w.ones_row = 1;
-            w.Bm = c->DSKIP; w.ldb = S; w.N = S;
-            w.out = grads + c->lay[l].skip_k; w.ldw = S; w.bias_out = c->lbias ? grads + c->lay[l].skip_b : nullptr;
-            w.scale = c->skip_scale[l]; w.B = c->fB; w.T = c->fT;
-            if ((rc = launch_wgrad(c, w, wst))) return rc;
-        }
-        if (l != L - 1) {
-            WgArgs w; memset(&w, 0, sizeof w);
-            w.nseg = 1; w.seg[0] = seg(Ul, GH, 0, GH, 0, 0); w.ones_row = 1;
-            w.Bm = gxu; w.ldb = R; w.N = R;
-            w.out = grads + c->lay[l].out_k; w.ldw = R; w.bias_out = c->lbias ? grads + c->lay[l].out_b : nullptr;
-            w.scale = 1.0f; w.B = c->fB; w.T = c->fT;
-            if ((rc = launch_wgrad(c, w, wst))) return rc;
-        }
-    }
-    if ((rc = wn_gin_bwd(c, grads, side))) return rc;     // d W_g, d b_g, d embedding table (modules.py:499-508)
-    const bf16_t* gx_up = c->GXall;
-    // gx_up now holds dL/dh_0
-    if ((rc = wn_first_conv_grad(c, gx_up, grads, side))) return rc;
-    if (c->cfg.upsample_type != WN_UP_NEAREST) {
-        // d c_up[b][cc][t] = sum_l W_cin_l dz_l  as one contraction over all layers
-        GemmArgs a; base_args(c, a, c->wcT);
-        a.nseg = 1; a.seg[0] = seg(c->DZ, G, 0, G, 0, 0); a.nrep = L; a.rep_stride = NT * G;
-        a.e.out0 = c->DC; a.e.M_valid = C;
-        if (!(wn_ablate() & 1)) if ((rc = wn_launch_gemm<EPI_STORE_F32_BOT>(c, a, c->wcT.M, side))) return rc;
-        if ((rc = wn_upsample_bwd(c, c->DC, grads, side))) return rc;
-    }
+    if ((rc = low_layer_wgrads(c, grads, p, wst))) return rc;
+    if ((rc = small_grads(c, grads, side))) return rc;
     if (side != st) {
         WN_HIP(c, hipEventRecord(c->ev_join, side));
         WN_HIP(c, hipStreamWaitEvent(st, c->ev_join, 0));

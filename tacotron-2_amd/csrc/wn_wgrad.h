@@ -4,9 +4,8 @@
 
 // ================================================================================================
 // Weight-gradient kernel:  dW[m][n] (+)= scale * sum_t A[t][m] * Bm[t][n]     (contraction over TIME)
-//   A[t][m]  : concatenation of source segments (dilated taps of the layer input with the dropout mask
-//              re-generated, conditioning, gate output ...) plus an optional all-ones column whose row of
-//              dW is the bias gradient;
+//   A[t][m]  : concatenation of source segments (dilated taps of the dropped layer input XD, conditioning,
+//              gate output ...) plus an optional all-ones column whose row of dW is the bias gradient;
 //   Bm[t][n] : dz / d_skip / d_out ... [rows][ldb] bf16.
 // Both operands have the contraction index as their ROW index, so the MFMA fragments (8 consecutive k per
 // lane) are column gathers from the [t][c] LDS tiles (ds_read_u16, bank-conflict free with the 272-B
@@ -21,7 +20,6 @@ struct WgArgs {
     float* bias_out; float* bias_out2;
     float scale;
     int32_t B, T, slab, slabs_per_utt;
-    uint32_t key_lo, key_hi, thresh16; float keep_scale; int32_t drop_ld;
 };
 
 #define WG_STRIDE 136   // halfs per LDS row: 128 columns + 8 pad (272 B)
@@ -44,12 +42,12 @@ __global__ __launch_bounds__(256) void wn_wgrad_kernel(const WgArgs a) {
     // A column group -> (segment, channel)
     const int mcol = mblk * 128 + c16 * 8;
     int a_kind = 2;                      // 0 data, 1 ones column, 2 zero
-    const bf16_t* a_base = nullptr; int a_ld = 0, a_shift = 0, a_drop = 0, a_col = 0;
+    const bf16_t* a_base = nullptr; int a_ld = 0, a_shift = 0, a_col = 0;
     {
         int m0 = 0;
         for (int s = 0; s < a.nseg; ++s) {
             if (mcol >= m0 && mcol < m0 + a.seg[s].nk) {
-                a_kind = 0; a_base = a.seg[s].base; a_ld = a.seg[s].ld; a_shift = a.seg[s].shift; a_drop = a.seg[s].dropout;
+                a_kind = 0; a_base = a.seg[s].base; a_ld = a.seg[s].ld; a_shift = a.seg[s].shift;
                 a_col = a.seg[s].col0 + (mcol - m0);
             }
             m0 += a.seg[s].nk;
@@ -79,7 +77,6 @@ __global__ __launch_bounds__(256) void wn_wgrad_kernel(const WgArgs a) {
                     if (ts >= 0 && ts < T) {
                         const int64_t r = rowbase + ts;
                         va = *reinterpret_cast<const uint4*>(a_base + r * a_ld + a_col);
-                        if (a_drop) va = drop8(va, a.key_lo, a.key_hi, a.thresh16, a.keep_scale, (uint32_t)(r * a.drop_ld + a_col));
                     }
                 } else if (a_kind == 1) va.x = 0x3f80u;      // bf16 1.0 in column 0 of the group
                 if (b_ok) vb = *reinterpret_cast<const uint4*>(a.Bm + (rowbase + t) * a.ldb + a.colb0 + ncol);

@@ -12,7 +12,9 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.normpath(os.path.join(_HERE, '..', '..', 'csrc', 'libwavenet_mi355.so'))
-if os.environ.get('WN_MI355_TEST_LIB'):      # test hook: the ASAN / UBSAN build of the host side (csrc/build.py --sanitize), never the product
+# test / tool hook: another build of the library -- the ASAN / UBSAN build of the host side (csrc/build.py --sanitize), a diagnostic build
+# (--ablate, --pipe-svc) or an earlier build for an A/B; never set by the product
+if os.environ.get('WN_MI355_TEST_LIB'):
     LIB_PATH = os.environ['WN_MI355_TEST_LIB']
 
 WN_ABI_VERSION = 4

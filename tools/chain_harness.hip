@@ -138,7 +138,7 @@ int main(int argc, char** argv) {
     bf16_t* W1[NL]; bf16_t* Wo[NL];
     for (int l = 0; l < NL; ++l) { W1[l] = dev_bf16_random((size_t)G * (3 * R + C), 0.03f); Wo[l] = dev_bf16_random((size_t)R * GH, 0.05f); }
     float* bias; CK(hipMalloc(&bias, 8192)); CK(hipMemset(bias, 0, 8192));
-    auto mkseg = [](const bf16_t* b, int ld, int nk, int shift) { SrcSeg s; s.base = b; s.ld = ld; s.col0 = 0; s.nk = nk; s.shift = shift; s.dropout = 0; return s; };
+    auto mkseg = [](const bf16_t* b, int ld, int nk, int shift) { SrcSeg s; s.base = b; s.ld = ld; s.col0 = 0; s.nk = nk; s.shift = shift; return s; };
     auto mk_gate = [&](int l, int b0, int nb) {
         GemmArgs a; memset(&a, 0, sizeof a); a.Apk = W1[l]; a.ksteps_total = (3 * R + C) / 16; a.nrep = 1; a.B = nb; a.T = T; a.b0 = b0; a.zero = zero; a.e.scale = 1.0f; a.e.GH = GH; a.e.M_valid = G;
         const bf16_t* x = XD + (size_t)l * NT * R; const int d = dil[l];

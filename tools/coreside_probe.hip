@@ -76,7 +76,7 @@ int main(int argc, char** argv) {
     bf16_t *A32, *A64; { auto p = pack_frag(W, M, K, R, 32); CK(hipMalloc(&A32, p.size() * 2)); CK(hipMemcpy(A32, p.data(), p.size() * 2, hipMemcpyHostToDevice)); }
     { auto p = pack_frag(W, M, K, R, 64); CK(hipMalloc(&A64, p.size() * 2)); CK(hipMemcpy(A64, p.data(), p.size() * 2, hipMemcpyHostToDevice)); }
     bf16_t *TS, *U; CK(hipMalloc(&TS, NT_ * GH * 2)); CK(hipMalloc(&U, NT_ * GH * 2));
-    auto mkseg = [](const bf16_t* b, int ld, int col0, int nk, int shift) { SrcSeg s; s.base = b; s.ld = ld; s.col0 = col0; s.nk = nk; s.shift = shift; s.dropout = 0; return s; };
+    auto mkseg = [](const bf16_t* b, int ld, int col0, int nk, int shift) { SrcSeg s; s.base = b; s.ld = ld; s.col0 = col0; s.nk = nk; s.shift = shift; return s; };
     GemmArgs g; memset(&g, 0, sizeof g); g.ksteps_total = K / 16; g.nrep = 1; g.B = B / 2; g.b0 = 0; g.T = T; g.zero = zero; g.taps = 3; g.e.scale = 1.0f; g.e.GH = GH; g.nseg = 4;
     g.seg[0] = mkseg(XD, R, 0, R, -2 * d); g.seg[1] = mkseg(XD, R, 0, R, -d); g.seg[2] = mkseg(XD, R, 0, R, 0); g.seg[3] = mkseg(cbt, C, 0, C, 0);
     g.e.bias = bias; g.e.out0 = TS; g.e.ld_out0 = GH; g.e.out1 = U; g.e.ld_out1 = GH; g.e.M_valid = M;

@@ -16,6 +16,6 @@ done
 [ -f $OUT/pipe_batch_scaling_ab.txt ] && grep -v amdgpu.ids $OUT/pipe_batch_scaling_ab.txt | cut -c1-300
 wait $CK; sort $OUT/clocks.txt | uniq -c | head -8
 if [ -n "$3" ]; then
-  python tacotron-2_amd/csrc/build.py --pipe-svc > /dev/null 2>&1
+  python tacotron-2_amd/csrc/build.py --pipe-svc > /dev/null 2>&1      # libwavenet_mi355_pipesvc.so: pipe_svc_trace.py selects it through WN_MI355_TEST_LIB
   timeout 300 python tools/pipe_svc_trace.py $3 > $OUT/pipe_svc_trace.txt 2>&1; grep -v amdgpu.ids $OUT/pipe_svc_trace.txt
 fi

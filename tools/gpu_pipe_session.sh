@@ -15,7 +15,7 @@ for v in ${PIPE_AB:-}; do     # A/B arms of the c2 scaling table: PIPE_AB="WN_PI
 done
 [ -f $OUT/pipe_batch_scaling_ab.txt ] && grep -v amdgpu.ids $OUT/pipe_batch_scaling_ab.txt | cut -c1-300
 if [ -n "$1" ]; then
-  python tacotron-2_amd/csrc/build.py --pipe-svc > /dev/null 2>&1
+  python tacotron-2_amd/csrc/build.py --pipe-svc > /dev/null 2>&1      # libwavenet_mi355_pipesvc.so: pipe_svc_trace.py selects it through WN_MI355_TEST_LIB
   timeout 300 python tools/pipe_svc_trace.py "$@" > $OUT/pipe_svc_trace.txt 2>&1; cat $OUT/pipe_svc_trace.txt
   WN_PIPE_BATCHPRE=0 timeout 300 python tools/pipe_svc_trace.py "$@" > $OUT/pipe_svc_trace_per_stream_form.txt 2>&1; cat $OUT/pipe_svc_trace_per_stream_form.txt
 fi

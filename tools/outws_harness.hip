@@ -28,7 +28,7 @@ int main() {
     auto alloc = [&](size_t n) { bf16_t* p; CK(hipMalloc(&p, n * 2)); CK(hipMemset(p, 0, n * 2)); return p; };
     bf16_t* O0[2] = {alloc((size_t)NT * R), alloc((size_t)NT * R)}; bf16_t* O1[2] = {alloc((size_t)NT * R), alloc((size_t)NT * R)};
     bf16_t* TS = alloc((size_t)NT * GH); bf16_t* UG = alloc((size_t)NT * GH);
-    auto mkseg = [](const bf16_t* b, int ld, int nk, int shift) { SrcSeg s; s.base = b; s.ld = ld; s.col0 = 0; s.nk = nk; s.shift = shift; s.dropout = 0; return s; };
+    auto mkseg = [](const bf16_t* b, int ld, int nk, int shift) { SrcSeg s; s.base = b; s.ld = ld; s.col0 = 0; s.nk = nk; s.shift = shift; return s; };
     auto mk_out = [&](int set, int b0, int nb, bool drop) {
         GemmArgs a; memset(&a, 0, sizeof a); a.Apk = Wo; a.ksteps_total = GH / 16; a.nrep = 1; a.B = nb; a.T = T; a.b0 = b0; a.zero = zero; a.e.scale = 0.70710678f; a.e.GH = GH; a.e.M_valid = R;
         a.nseg = 1; a.seg[0] = mkseg(U, GH, GH, 0);

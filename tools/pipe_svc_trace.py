@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Where a layer CU's service time per stream goes (WN_PIPE_SVC_TRACE=1; stderr) at a few batch sizes, C2 model.  Needs the diagnostic build of the
-library (the stamp sites are compiled out of the product: they cost SGPRs):
-    python tacotron-2_amd/csrc/build.py --pipe-svc && python tools/pipe_svc_trace.py [B ...] ; python tacotron-2_amd/csrc/build.py --force"""
+library (the stamp sites are compiled out of the product: they cost SGPRs), a library of its own that this tool selects through WN_MI355_TEST_LIB:
+    python tacotron-2_amd/csrc/build.py --pipe-svc && python tools/pipe_svc_trace.py [B ...]"""
 import os
 import sys
 import time
@@ -10,6 +10,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for p in (ROOT, os.path.join(ROOT, 'tacotron-2_amd')):
     sys.path.insert(0, p)
 os.environ['WN_PIPE_SVC_TRACE'] = '1'
+os.environ.setdefault('WN_MI355_TEST_LIB', os.path.join(ROOT, 'tacotron-2_amd', 'csrc', 'libwavenet_mi355_pipesvc.so'))
+if not os.path.exists(os.environ['WN_MI355_TEST_LIB']):
+    sys.exit('pipe_svc_trace: %s is missing: python tacotron-2_amd/csrc/build.py --pipe-svc' % os.environ['WN_MI355_TEST_LIB'])
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 

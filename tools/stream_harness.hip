@@ -92,7 +92,7 @@ int main(int argc, char** argv) {
     auto base = [&](GemmArgs& a, const bf16_t* Apk, int K, int nb, int b0) {
         memset(&a, 0, sizeof a); a.Apk = Apk; a.ksteps_total = K / 16; a.nrep = 1; a.B = nb; a.b0 = b0; a.T = T; a.zero = zero; a.e.scale = 1.0f;
     };
-    auto mkseg = [](const bf16_t* b, int ld, int col0, int nk, int shift) { SrcSeg s; s.base = b; s.ld = ld; s.col0 = col0; s.nk = nk; s.shift = shift; s.dropout = 0; return s; };
+    auto mkseg = [](const bf16_t* b, int ld, int col0, int nk, int shift) { SrcSeg s; s.base = b; s.ld = ld; s.col0 = col0; s.nk = nk; s.shift = shift; return s; };
     auto report = [&](const char* what, const char* kern, float ms, double bytes) { printf("%-34s %-38s %7.1f us  %5.2f TB/s\n", what, kern, ms * 1e3, bytes / ms / 1e9); };
     {
         hipFuncAttributes fa; int nb = -1;

@@ -36,7 +36,7 @@ int main(int argc, char** argv) {
         const int64_t NT_ = (int64_t)B * T;
         bf16_t* XD = dev_bf16_random((size_t)L * NT_ * R, 1.0f); bf16_t* cbt = dev_bf16_random(NT_ * C, 1.0f);
         bf16_t* DZ = dev_bf16_random((size_t)L * NT_ * G, 1.0f); bf16_t* U = dev_bf16_random((size_t)L * NT_ * GH, 1.0f); bf16_t* DS = dev_bf16_random(NT_ * S, 1.0f);
-        auto mkseg = [](const bf16_t* b, int ld, int col0, int nk, int shift) { SrcSeg s; s.base = b; s.ld = ld; s.col0 = col0; s.nk = nk; s.shift = shift; s.dropout = 0; return s; };
+        auto mkseg = [](const bf16_t* b, int ld, int col0, int nk, int shift) { SrcSeg s; s.base = b; s.ld = ld; s.col0 = col0; s.nk = nk; s.shift = shift; return s; };
         for (int which = 0; which < 2; ++which) {
             const int K = which == 0 ? 3 * R + C : GH, N = which == 0 ? G : S;
             const char* name = which == 0 ? "W1  " : "skip";

@@ -170,7 +170,7 @@ __global__ __launch_bounds__(512, 4) void wn_out_ws_kernel(const GemmArgs a) {
 
 // does this EPI_STORE_BF16 launch take the streaming kernel?  (out conv of the paper-width stack; everything else: tile engine)
 static inline bool wn_out_ws_fits(const GemmArgs& a, int M) {
-    return M == 256 && a.e.M_valid == 256 && a.nseg == 1 && a.nrep == 1 && a.taps == 0 && a.seg[0].nk == 256 && a.seg[0].shift == 0 && !a.seg[0].dropout &&
+    return M == 256 && a.e.M_valid == 256 && a.nseg == 1 && a.nrep == 1 && a.taps == 0 && a.seg[0].nk == 256 && a.seg[0].shift == 0 &&
            a.seg[0].ld == 256 && a.e.in0 && a.e.ld_in0 == 256 && a.e.ld_out0 == 256 && (!a.e.out1 || a.e.ld_out1 == 256) && a.zero && a.ksteps_total == 16 &&
            (!a.e.out1 || a.drop_ld == 256);
 }

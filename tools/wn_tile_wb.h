@@ -238,11 +238,11 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN / 2) void wn_gemm_wb_kernel(c
     if (a.kprof && tid == 0) atomicMax(a.kprof + 1, (unsigned long long)wall_clock64());
 }
 
-// Does this launch fit?  One unshifted source tensor of exactly K = NKC * 64 channels, M a multiple of the tile, no dropout on the source.
+// Does this launch fit?  One unshifted source tensor of exactly K = NKC * 64 channels, M a multiple of the tile.
 template <int WM, int WN, int NKC>
 static inline bool wn_gemm_wb_fits(const GemmArgs& a, int M) {
     using Cfg = WbCfg<WM, WN, NKC>;
-    return M % Cfg::MTILE == 0 && a.e.M_valid == M && a.zero && a.nseg == 1 && a.nrep == 1 && a.taps == 0 && a.seg[0].shift == 0 && !a.seg[0].dropout
+    return M % Cfg::MTILE == 0 && a.e.M_valid == M && a.zero && a.nseg == 1 && a.nrep == 1 && a.taps == 0 && a.seg[0].shift == 0
            && a.seg[0].nk == Cfg::K && a.ksteps_total == Cfg::K / 16;
 }
 template <int WM, int WN, int NKC, int EPI>
