@@ -573,6 +573,55 @@ int  wn_stats_set_tensors(wn_stats* h, const int64_t* offsets, const int64_t* co
 /* flat: device float; out: device double [nt, 4] */
 int  wn_stats_tensors(wn_stats* h, const float* flat, double* out, void* stream);
 
+/* ---- pitch check: F0 and voicing of a signal, and of a generated signal against a recording ----------------------------------------
+ * A handle of its own, independent of the model context, like the mel analysis, the output stage and the reconstruction check: what an 80-band mel
+ * cannot resolve -- pitch drift, octave jumps, voicing that flickers -- read off the waveforms themselves.  The estimator is YIN (de Cheveigne &
+ * Kawahara 2002, steps 2 ... 5) on frames aligned with the mel frames: a signal of n samples has F = 1 + n / hop frames, and with L = window + tau_max
+ * frame f covers the signal indices [f hop - L / 2, f hop - L / 2 + L), zeros outside [0, n): x_0 ... x_{L-1}.
+ *   d(tau)  = sum_{j = 0 ... window-1} (x_j - x_{j+tau})^2    tau = 1 ... tau_max; float32, one accumulator, j ascending, e = x_j - x_{j+tau}; acc = fma(e, e, acc)
+ *   c(tau)  = sum_{k = 1 ... tau} d(k)                         float32, tau ascending
+ *   d'(0)   = 1;  d'(tau) = c(tau) > 0 ? (d(tau) tau) / c(tau) : 1
+ * The direct form of d on purpose: all terms are non-negative, so every d'(tau) is within (window + tau_max + 8) 2^-24, relative, of its exact value; the
+ * energy-minus-autocorrelation form has no such bound.  Pick over tau in [tau_min, tau_max - 1]: the first tau with d'(tau) < threshold, then walk while
+ * tau + 1 <= tau_max - 1 and d'(tau + 1) < d'(tau).  If there is one the frame is voiced: with a = d'(tau - 1), b = d'(tau), c = d'(tau + 1), den = a - 2 b + c,
+ * delta = den > 0 ? 0.5 (a - c) / den : 0,  f0 = sample_rate / (tau + delta),  ap = b.  Otherwise it is unvoiced: f0 = 0, ap = min d' over the range.  No
+ * energy gate, no smoothing, no octave post-processing; digital silence is unvoiced with ap = 1.  Cells of frames >= a row's F keep the caller's bytes.
+ * A frame's results depend on that row's samples alone -- not on B, the row's index, ld, F_max, which outputs are asked for, or the run -- bit for bit.
+ * wn_pitch_compare: a reference track a against a generated track b over the first frames[b] frames of row b, a frame being voiced when its f0 > 0; one
+ * float32 row of 9: frames, voiced_a, voiced_b, both, vuv_error (share of frames whose voiced flags differ), gpe (share of both-voiced frames with
+ * |f_b / f_a - 1| > 0.2), f0_rmse_cents and f0_bias_cents (over the both-voiced frames, of 1200 log2(f_b / f_a) in double), f0_fine_rmse_cents (the same
+ * RMSE over the both-voiced frames that are not gross); an empty denominator gives 0.  Sums are doubles added in frame order, no atomics.
+ * The handle holds no device memory (a tile's signal span and its d' table live in LDS): creation touches no device, no call allocates or synchronises,
+ * lengths and frames travel as kernel arguments (the host arrays are free when the call returns).
+ * Validation before any device call: WN_E_ARG for a null pointer, a foreign abi_version, sample_rate < 1, hop < 1, window < 1, tau_min < 2,
+ * tau_max <= tau_min + 1, threshold outside (0, 1], max_batch < 1, a negative size, B < 1; WN_E_UNSUPPORTED when one tile's span, 7 hop + window + tau_max
+ * floats, and its table, 8 (tau_max + 1), exceed the 64 KiB of LDS the kernel is built for; WN_E_SHAPE for B > max_batch, F_max beyond the frames of
+ * max_samples or below a row's, lengths[b] > ld or > max_samples, frames[b] > pitch or beyond the frames of max_samples. */
+typedef struct wn_pitch_config {
+    int32_t abi_version;   /* = WN_ABI_VERSION */
+    int32_t sample_rate;   /* Hz */
+    int32_t hop;           /* samples between frames: the mel analysis' hop_size */
+    int32_t window;        /* W: terms of the difference function */
+    int32_t tau_min;       /* >= 2: sample_rate / the highest f0 */
+    int32_t tau_max;       /* > tau_min + 1: ceil(sample_rate / the lowest f0) */
+    float   threshold;     /* in (0, 1]: a lag whose d' falls below it is a candidate */
+    int32_t max_batch;     /* rows per call, >= 1 */
+    int64_t max_samples;   /* samples per row */
+} wn_pitch_config;
+typedef struct wn_pitch wn_pitch;
+int  wn_pitch_create(const wn_pitch_config* cfg, wn_pitch** out);
+void wn_pitch_destroy(wn_pitch* h);
+const char* wn_pitch_last_error(const wn_pitch* h);   /* NULL: text of the last failed create or host hook */
+/* 1 + n_samples / hop; WN_E_ARG for a NULL handle or n_samples < 0 (host only) */
+int64_t wn_pitch_num_frames(const wn_pitch* h, int64_t n_samples);
+/* frames one workgroup takes (8): tests place row lengths around its multiples */
+int  wn_pitch_frame_tile(const wn_pitch* h);
+/* wav: device float [B, ld], row b holds lengths[b] <= ld samples (HOST int32 [B], as wn_mel_run); f0: device float [B, F_max]; ap: device float
+ * [B, F_max] or NULL; dprime: device float [B, F_max, tau_max + 1] or NULL */
+int  wn_pitch_run(wn_pitch* h, const float* wav, int64_t ld, const int32_t* lengths, int32_t B, int32_t F_max, float* f0, float* ap, float* dprime, void* stream);
+/* f0_a, f0_b: device float [B, pitch]; frames: HOST int32 [B]; table: device float [B, 9] */
+int  wn_pitch_compare(wn_pitch* h, const float* f0_a, const float* f0_b, int64_t pitch, const int32_t* frames, int32_t B, float* table, void* stream);
+
 /* ---- introspection ------------------------------------------------------------------------------ */
 int64_t wn_workspace_bytes(const wn_ctx* ctx);
 /* name of the kernel that dominates training time (bench.py's roofline line names it) */
@@ -665,6 +714,11 @@ int wn_test_melcmp_host(const wn_melcmp_config* cfg, const float* a, int32_t a_c
  * max_tensors limit applies; otherwise validated as the device calls. */
 int wn_test_stats_hist_host(const float* x, int64_t pitch, const int32_t* lengths, int32_t B, int32_t T, int64_t* bucket, double* summary);
 int wn_test_stats_tensors_host(const float* flat, const int64_t* offsets, const int64_t* counts, int32_t nt, double* out);
+/* the pitch check on the host (no handle, no GPU): the arguments of wn_pitch_run / wn_pitch_compare with every pointer in HOST memory, evaluated by the very
+ * functions the kernels inline (csrc/wn_pitch.h), in the device's order: the same bits (the comparison's log2 in double is each side's library's).
+ * Validated as a create followed by a run; the comparison hook has no max_batch / max_samples limit. */
+int wn_test_pitch_host(const wn_pitch_config* cfg, const float* wav, int64_t ld, const int32_t* lengths, int32_t B, int32_t F_max, float* f0, float* ap, float* dprime);
+int wn_test_pitch_compare_host(const float* f0_a, const float* f0_b, int64_t pitch, const int32_t* frames, int32_t B, float* table);
 #endif /* WN_NO_TEST_HOOKS */
 
 #ifdef __cplusplus

@@ -103,6 +103,14 @@ MI355 = dict(
                                        # wavs/reconstruction.tsv, one log line, two scalars beside the eval loss.  The wavs, map.txt and plots are byte-identical either way
     mi355_reconstruction_alarm_db=6.0, # a frame whose level-compensated mean |difference| exceeds this counts as alarmed.  A guess: nobody has a trained checkpoint of this tree,
                                        # so what a good model scores is unknown; set it from the clean score of your own model
+    mi355_pitch_check=False,           # True: where ground-truth audio exists -- the item eval_step generates next to its target, synthesize.py --wavs_dir next to the
+                                       # recordings (all three routes) -- F0 and voicing of both are estimated on the device (YIN, csrc/wn_pitch.hip) and compared: three
+                                       # scalars beside the eval loss, one row per utterance appended to wavs/pitch.tsv, one log line.  False: nothing of it runs and every
+                                       # file is byte-identical to a run without the key
+    mi355_pitch_fmin=60.0,             # lowest f0 searched, Hz: tau_max = ceil(sample_rate / fmin)
+    mi355_pitch_fmax=500.0,            # highest f0 searched, Hz: tau_min = max(2, sample_rate // fmax)
+    mi355_pitch_threshold=0.15,        # YIN's absolute threshold on the normalised difference: a frame with no lag below it is unvoiced
+    mi355_pitch_window=1024,           # terms of the difference function (46 ms at 22.05 kHz: 2.8 periods of 60 Hz)
     mi355_steps_per_graph=0,       # synthesis path: 0 = the persistent dataflow pipeline (real time at 22.05 kHz) whenever the model fits it, else the
                                    # launch-per-layer path with 32 steps per hipGraph replay; N > 0 = that path with N steps per replay
     mi355_synthetic_data=False,    # train on LJSpeech-shaped synthetic tensors (no dataset on disk)

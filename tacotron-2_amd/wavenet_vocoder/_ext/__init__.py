@@ -78,6 +78,11 @@ class WnStatsConfig(ctypes.Structure):
     _fields_ = [('abi_version', ctypes.c_int32), ('max_rows', ctypes.c_int32), ('max_time', ctypes.c_int32), ('max_tensors', ctypes.c_int32)]
 
 
+class WnPitchConfig(ctypes.Structure):
+    _fields_ = [('abi_version', ctypes.c_int32), ('sample_rate', ctypes.c_int32), ('hop', ctypes.c_int32), ('window', ctypes.c_int32), ('tau_min', ctypes.c_int32),
+                ('tau_max', ctypes.c_int32), ('threshold', ctypes.c_float), ('max_batch', ctypes.c_int32), ('max_samples', ctypes.c_int64)]
+
+
 class WnFoldRow(ctypes.Structure):
     """wn_fold_row: one row of a folded run, in mel frames of utterance `utt`."""
     _fields_ = [('utt', ctypes.c_int32), ('first', ctypes.c_int32), ('frames', ctypes.c_int32), ('keep', ctypes.c_int32), ('fade', ctypes.c_int32)]
@@ -212,6 +217,15 @@ def load_library():
         'wn_stats_tensors': (ctypes.c_int, [vp, vp, vp, vp]),
         'wn_test_stats_hist_host': (ctypes.c_int, [vp, i64, vp, i32, i32, vp, vp]),
         'wn_test_stats_tensors_host': (ctypes.c_int, [vp, vp, vp, i32, vp]),
+        'wn_pitch_create': (ctypes.c_int, [ctypes.POINTER(WnPitchConfig), ctypes.POINTER(vp)]),
+        'wn_pitch_destroy': (None, [vp]),
+        'wn_pitch_last_error': (ctypes.c_char_p, [vp]),
+        'wn_pitch_num_frames': (i64, [vp, i64]),
+        'wn_pitch_frame_tile': (ctypes.c_int, [vp]),
+        'wn_pitch_run': (ctypes.c_int, [vp, vp, i64, ctypes.POINTER(i32), i32, i32, vp, vp, vp, vp]),
+        'wn_pitch_compare': (ctypes.c_int, [vp, vp, vp, i64, ctypes.POINTER(i32), i32, vp, vp]),
+        'wn_test_pitch_host': (ctypes.c_int, [ctypes.POINTER(WnPitchConfig), vp, i64, ctypes.POINTER(i32), i32, i32, vp, vp, vp]),
+        'wn_test_pitch_compare_host': (ctypes.c_int, [vp, vp, i64, ctypes.POINTER(i32), i32, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)            # AttributeError here == ABI symbol missing
@@ -1131,6 +1145,163 @@ class MelCompare:
     def close(self):
         if getattr(self, 'h', None):
             self.lib.wn_melcmp_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---- pitch check (csrc/wn_pitch.hip)
+PITCH_COLUMNS = ('frames', 'voiced_a', 'voiced_b', 'both', 'vuv_error', 'gpe', 'f0_rmse_cents', 'f0_bias_cents', 'f0_fine_rmse_cents')      # table[b][j]
+PITCH_GEOMETRY = ('sample_rate', 'hop', 'window', 'tau_min', 'tau_max', 'threshold')
+
+
+def pitch_geometry(hp):
+    """hparams -> the estimator's geometry: the mel analysis' hop, the lags of mi355_pitch_fmax ... mi355_pitch_fmin, window and threshold as given."""
+    import math
+    from datasets.audio import get_hop_size
+    sr = int(hp.sample_rate)
+    return dict(sample_rate=sr, hop=int(get_hop_size(hp)), window=int(getattr(hp, 'mi355_pitch_window', 1024)),
+                tau_min=max(2, sr // int(float(getattr(hp, 'mi355_pitch_fmax', 500.0)))), tau_max=int(math.ceil(sr / float(getattr(hp, 'mi355_pitch_fmin', 60.0)))),
+                threshold=float(getattr(hp, 'mi355_pitch_threshold', 0.15)))
+
+
+def pitch_config(spec, max_batch, max_samples):
+    """wn_pitch_config.  spec: hparams, or a dict with the keys PITCH_GEOMETRY."""
+    geo = dict(spec) if isinstance(spec, dict) else pitch_geometry(spec)
+    if set(geo) != set(PITCH_GEOMETRY):
+        raise ValueError('pitch geometry must have exactly the keys %r (got %r)' % (PITCH_GEOMETRY, sorted(geo)))
+    cfg = WnPitchConfig()
+    cfg.abi_version = WN_ABI_VERSION
+    for k in PITCH_GEOMETRY[:5]:
+        setattr(cfg, k, int(geo[k]))
+    cfg.threshold = float(geo['threshold'])
+    cfg.max_batch, cfg.max_samples = int(max_batch), int(max_samples)
+    return cfg
+
+
+def _pitch_rows(wav, lengths):
+    if wav.ndim != 2:
+        raise ValueError('wav must be [B, ld]')
+    lens = [int(n) for n in lengths]
+    if len(lens) != int(wav.shape[0]):
+        raise ValueError('one length per row of wav (%d lengths for %d rows)' % (len(lens), int(wav.shape[0])))
+    return lens
+
+
+def pitch_host(spec, wav, lengths, frames=None, return_dprime=False, fill=np.nan):
+    """wn_test_pitch_host: the estimator on the host (no handle, no GPU), in the device's order.  wav: numpy float32 [B, ld].  Returns a dict: f0 and ap
+    float32 [B, F_max] (F_max = frames or the frames of the longest row) and, with return_dprime, dprime float32 [B, F_max, tau_max + 1]; cells of frames
+    beyond a row's keep `fill`."""
+    wav = np.ascontiguousarray(wav, dtype=np.float32)
+    lens = _pitch_rows(wav, lengths)
+    B = len(lens)
+    cfg = pitch_config(spec, max(B, 1), max(lens + [0]))
+    F = int(frames) if frames is not None else max([1 + max(n, 0) // max(cfg.hop, 1) for n in lens] + [1])
+    cfg.max_samples = max(int(cfg.max_samples), (F - 1) * max(int(cfg.hop), 1))          # the hook's capacity is the call's own: any F_max >= the rows' frames is taken
+    f0, ap = np.full((B, F), fill, np.float32), np.full((B, F), fill, np.float32)
+    dp = np.full((B, F, cfg.tau_max + 1), fill, np.float32) if return_dprime else None
+    vp = ctypes.c_void_p
+    rc = load_library().wn_test_pitch_host(ctypes.byref(cfg), wav.ctypes.data_as(vp), int(wav.shape[1]), (ctypes.c_int32 * max(B, 1))(*lens), B, F, f0.ctypes.data_as(vp),
+                                           ap.ctypes.data_as(vp), dp.ctypes.data_as(vp) if return_dprime else None)
+    if rc != 0:
+        raise WnError(rc, (load_library().wn_pitch_last_error(None) or b'').decode())
+    res = {'f0': f0, 'ap': ap}
+    if return_dprime:
+        res['dprime'] = dp
+    return res
+
+
+def pitch_compare_host(f0_a, f0_b, frames):
+    """wn_test_pitch_compare_host: reference track a against generated track b, numpy float32 [B, pitch] each -> float32 [B, 9], columns PITCH_COLUMNS."""
+    a, b = np.ascontiguousarray(f0_a, dtype=np.float32), np.ascontiguousarray(f0_b, dtype=np.float32)
+    fr = [int(f) for f in frames]
+    if a.ndim != 2 or a.shape != b.shape or len(fr) != int(a.shape[0]):
+        raise ValueError('f0_a and f0_b must be [B, pitch] alike, with one frame count per row')
+    B = len(fr)
+    table = np.full((B, len(PITCH_COLUMNS)), np.nan, np.float32)
+    vp = ctypes.c_void_p
+    rc = load_library().wn_test_pitch_compare_host(a.ctypes.data_as(vp), b.ctypes.data_as(vp), int(a.shape[1]), (ctypes.c_int32 * max(B, 1))(*fr), B, table.ctypes.data_as(vp))
+    if rc != 0:
+        raise WnError(rc, (load_library().wn_pitch_last_error(None) or b'').decode())
+    return table
+
+
+class PitchTracker:
+    """One wn_pitch: F0 and voicing per mel-aligned frame of a ragged batch on the current device (csrc/wn_pitch.hip), and the comparison of two tracks,
+    asynchronously.  spec: hparams (pitch_geometry) or a dict with the keys PITCH_GEOMETRY."""
+
+    def __init__(self, spec, rows, max_samples):
+        self.lib = load_library()
+        self.cfg = pitch_config(spec, rows, max_samples)
+        h = ctypes.c_void_p()
+        rc = self.lib.wn_pitch_create(ctypes.byref(self.cfg), ctypes.byref(h))
+        if rc != 0:
+            raise WnError(rc, (self.lib.wn_pitch_last_error(None) or b'').decode())
+        self.h = h
+        self.rows, self.max_samples = int(rows), int(max_samples)
+        self.hop, self.tau_max, self.sample_rate = int(self.cfg.hop), int(self.cfg.tau_max), int(self.cfg.sample_rate)
+
+    def _ok(self, rc):
+        if rc != 0:
+            raise WnError(rc, (self.lib.wn_pitch_last_error(self.h) or b'').decode())
+
+    def num_frames(self, n):
+        r = int(self.lib.wn_pitch_num_frames(self.h, int(n)))
+        if r < 0:
+            raise WnError(r, 'wn_pitch_num_frames(%d)' % n)
+        return r
+
+    @property
+    def frame_tile(self):
+        return int(self.lib.wn_pitch_frame_tile(self.h))
+
+    def run(self, wav, lengths, return_dprime=False, frames=None, out=None):
+        """wav float32 [B, ld] on the device, lengths: B ints (host).  Returns (f0, ap), float32 [B, F_max] each on the device (F_max = frames or the
+        frames of the longest row), and with return_dprime also dprime float32 [B, F_max, tau_max + 1].  out: a tuple of ready tensors to write into
+        instead (cells of frames beyond a row's keep their bytes; fresh tensors are zero there)."""
+        import torch
+        _check(wav, torch.float32, 'wav')
+        lens = _pitch_rows(wav, lengths)
+        B = len(lens)
+        F = int(frames) if frames is not None else max(1 + n // self.hop for n in lens)
+        if out is None:
+            out = (torch.zeros(B, F, dtype=torch.float32, device=wav.device), torch.zeros(B, F, dtype=torch.float32, device=wav.device)) + (
+                (torch.zeros(B, F, self.tau_max + 1, dtype=torch.float32, device=wav.device),) if return_dprime else ())
+        shapes = [(B, F), (B, F)] + ([(B, F, self.tau_max + 1)] if return_dprime else [])
+        if len(out) != len(shapes):
+            raise ValueError('out must hold %d tensors' % len(shapes))
+        for t, s in zip(out, shapes):
+            _check(t, torch.float32, 'out')
+            if tuple(t.shape) != s:
+                raise ValueError('out must be %r (got %r)' % (s, tuple(t.shape)))
+        self._ok(self.lib.wn_pitch_run(self.h, _ptr(wav), int(wav.shape[1]), (ctypes.c_int32 * B)(*lens), B, F, _ptr(out[0]), _ptr(out[1]),
+                                       _ptr(out[2]) if return_dprime else None, _stream()))
+        return tuple(out)
+
+    def compare(self, f0_a, f0_b, frames, out=None):
+        """Reference track f0_a against generated track f0_b, float32 [B, pitch] each on the device; frames: B ints (host) -> float32 [B, 9] on the
+        device, columns PITCH_COLUMNS."""
+        import torch
+        _check(f0_a, torch.float32, 'f0_a'); _check(f0_b, torch.float32, 'f0_b')
+        fr = [int(f) for f in frames]
+        if f0_a.dim() != 2 or tuple(f0_a.shape) != tuple(f0_b.shape) or len(fr) != int(f0_a.shape[0]):
+            raise ValueError('f0_a and f0_b must be [B, pitch] alike, with one frame count per row')
+        B = len(fr)
+        if out is None:
+            out = torch.zeros(B, len(PITCH_COLUMNS), dtype=torch.float32, device=f0_a.device)
+        _check(out, torch.float32, 'out')
+        if tuple(out.shape) != (B, len(PITCH_COLUMNS)):
+            raise ValueError('out must be %r' % ((B, len(PITCH_COLUMNS)),))
+        self._ok(self.lib.wn_pitch_compare(self.h, _ptr(f0_a), _ptr(f0_b), int(f0_a.shape[1]), (ctypes.c_int32 * B)(*fr), B, _ptr(out), _stream()))
+        return out
+
+    def close(self):
+        if getattr(self, 'h', None):
+            self.lib.wn_pitch_destroy(self.h)
             self.h = None
 
     def __del__(self):

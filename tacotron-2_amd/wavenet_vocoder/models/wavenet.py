@@ -793,6 +793,12 @@ class WaveNet(object):
         from wavenet_vocoder.reconstruction import ReconstructionCheck
         return ReconstructionCheck(self._hparams, rows, max_samples, preemphasis=preemphasis, alarm_db=alarm_db)
 
+    def pitch_check(self, rows, max_samples):
+        """A PitchCheck (wavenet_vocoder/pitch.py) for up to `rows` utterances of up to `max_samples` samples: F0 and voicing of generated audio against
+        a recording in the same domain, per utterance, on the device; the geometry comes from the hparams (mi355_pitch_*)."""
+        from wavenet_vocoder.pitch import PitchCheck
+        return PitchCheck(self._hparams, rows, max_samples)
+
     def train_stats(self):
         """The model's _ext.TrainStats (csrc/wn_stats.hip), built at the first call: histograms of up to max_batch rows of max_time samples and the
         per-tensor statistics of a flat buffer in the engine's layout (``grads``, ``params``, the Adam slots)."""

@@ -91,9 +91,16 @@ def analyse_wavs(paths, hparams, batch=32):
     return mels
 
 
+def pitch_references(paths, hparams):
+    """The recordings as the pitch check takes them (mi355_pitch_check): pre-emphasised as preprocessing does it, so that they stand beside the
+    model-domain output; the estimator is scale-invariant, so the rescale is left out."""
+    from datasets import audio
+    return [audio.preemphasis(audio.load_wav(p, sr=hparams.sample_rate), hparams.preemphasis, hparams.preemphasize).astype(np.float32) for p in paths]
+
+
 def run_wav_synthesis(args, checkpoint_path, output_dir, hparams):
     """--wavs_dir: analysis then synthesis.  Writes wavs/wavenet-audio-<basename>.wav (mel_frames * hop samples), the analysed mel next to
-    it as wavs/mel-<basename>.npy, and wavs/map.txt rows ``recording|mel|wav``."""
+    it as wavs/mel-<basename>.npy, and wavs/map.txt rows ``recording|mel|wav``; with mi355_pitch_check also one row per utterance in wavs/pitch.tsv."""
     plot_dir, wav_dir = os.path.join(output_dir, 'plots'), os.path.join(output_dir, 'wavs')
     log(hparams_debug_string())
     if hparams.gin_channels > 0:
@@ -114,6 +121,8 @@ def run_wav_synthesis(args, checkpoint_path, output_dir, hparams):
             mel_paths = [os.path.join(wav_dir, 'mel-{}.npy'.format(n)) for n in names]
             for mp, mel in zip(mel_paths, mels):
                 np.save(mp, mel, allow_pickle=False)
+            if bool(getattr(hparams, 'mi355_pitch_check', False)):
+                synth.pitch_references = pitch_references(batch, hparams)
             wavs = synth.synthesize(mels, None, names, wav_dir, plot_dir)
             for p, mp, wav in zip(batch, mel_paths, wavs):
                 index.write('|'.join([p, mp, wav]) + '\n')

@@ -40,6 +40,8 @@ class Synthesizer(object):
         self._capacity = (0, 0)
         self._post_stages = {}
         self._recon = None
+        self._pitch_chk = None
+        self.pitch_references = None      # mi355_pitch_check: the recordings of the next synthesize() call (run_wav_synthesis sets them)
 
     def _output_mode(self):
         """(device, k): whether the written wavs come from the device output stage (mi355_output_stage), and the de-emphasis coefficient they get
@@ -95,6 +97,41 @@ class Synthesizer(object):
         log(reconstruction.log_line(basenames, table))
         return table
 
+    def _pitch(self, decoded, generated_wavs, basenames, out_dir):
+        """mi355_pitch_check with recordings at hand (self.pitch_references: one model-domain signal per utterance of the call): F0 and voicing of every
+        generated utterance against its recording (WaveNet.pitch_check), one row each appended to <out_dir>/pitch.tsv and one log line.  decoded /
+        generated_wavs as _reconstruction takes them.  Reads results only; a failure logs one line and never fails the run."""
+        refs, self.pitch_references = getattr(self, 'pitch_references', None), None
+        if refs is None or not bool(getattr(self._hparams, 'mi355_pitch_check', False)):
+            return None
+        try:
+            from wavenet_vocoder import pitch
+            if len(refs) != len(basenames):
+                raise ValueError('{} recordings for {} utterances'.format(len(refs), len(basenames)))
+            dev = self.model.device
+            glen = [int(decoded.shape[1])] * len(refs) if decoded is not None else [len(w) for w in generated_wavs]
+            n = [min(len(r), g) for r, g in zip(refs, glen)]
+            ref = np.zeros((len(n), max(max(n), 1)), np.float32)
+            for b, r in enumerate(refs):
+                ref[b, :n[b]] = np.asarray(r, np.float32)[:n[b]]
+            if decoded is None:
+                host = np.zeros_like(ref)
+                for b, w in enumerate(generated_wavs):
+                    host[b, :n[b]] = np.asarray(w, np.float32)[:n[b]]
+                decoded = torch.from_numpy(host).to(dev)
+            chk = getattr(self, '_pitch_chk', None)
+            if chk is None or chk.rows < len(n) or chk.max_samples < max(n):
+                if chk is not None:
+                    chk.close()
+                chk = self._pitch_chk = self.model.pitch_check(max(len(n), chk.rows if chk else 0), max(max(n), chk.max_samples if chk else 0))
+            table = chk.score(decoded, torch.from_numpy(ref).to(dev), n)
+            pitch.append_tsv(os.path.join(out_dir, 'pitch.tsv'), basenames, table)
+            log(pitch.log_line(basenames, table))
+            return table
+        except Exception as e:
+            log('pitch check skipped: {}'.format(e))
+            return None
+
     def _ensure_capacity(self, batch, time_steps):
         if batch <= self._capacity[0] and time_steps <= self._capacity[1]:
             return
@@ -145,11 +182,13 @@ class Synthesizer(object):
         if nfold > 0 and not self.synth_debug:
             generated_wavs, upsampled_features, pcm, decoded = self._synthesize_folded(c_batch, frames, speaker_ids, min(nfold, 32), log_dir is not None)
             self._reconstruction(decoded, generated_wavs, cond, frames, basenames, out_dir)
+            self._pitch(decoded, generated_wavs, basenames, out_dir)
             return self._write(generated_wavs, upsampled_features, mel_spectrograms, basenames, out_dir, log_dir, pcm)
         nslots = int(getattr(hparams, 'mi355_synthesis_slots', 0))
         if nslots > 0 and not self.synth_debug:
             generated_wavs, upsampled_features, pcm, decoded = self._synthesize_slots(c_batch, frames, speaker_ids, min(nslots, 32), log_dir is not None)
             self._reconstruction(decoded, generated_wavs, cond, frames, basenames, out_dir)
+            self._pitch(decoded, generated_wavs, basenames, out_dir)
             return self._write(generated_wavs, upsampled_features, mel_spectrograms, basenames, out_dir, log_dir, pcm)
         self._ensure_capacity(len(c_batch), maxlen * hop)
         dev = self.model.device
@@ -173,6 +212,7 @@ class Synthesizer(object):
         upsampled_features = [f[:, :length] for f, length in zip(feats, audio_lengths)]
         if not self.synth_debug:
             self._reconstruction(self.model.tower_y_hat[0] if device else None, generated_wavs, cond, frames, basenames, out_dir)
+            self._pitch(self.model.tower_y_hat[0] if device else None, generated_wavs, basenames, out_dir)
         return self._write(generated_wavs, upsampled_features, mel_spectrograms, basenames, out_dir, log_dir, pcm)
 
     def _synthesize_folded(self, c_batch, lengths, speaker_ids, nrows, want_features):
@@ -191,7 +231,8 @@ class Synthesizer(object):
         wavs, ups = [], []
         device, k = self._output_mode()
         pcm = [] if device else None
-        check = device and bool(getattr(hparams, 'mi355_reconstruction_check', False))
+        check = device and (bool(getattr(hparams, 'mi355_reconstruction_check', False)) or
+                            (bool(getattr(hparams, 'mi355_pitch_check', False)) and getattr(self, 'pitch_references', None) is not None))
         decoded = torch.zeros(len(lengths), max(lengths) * hop, device=self.model.device) if check else None      # out_wav of every group, kept on the device
         ids = None if not self.global_conditions else np.asarray(speaker_ids).reshape(-1)
         for grp, plan in zip(groups, plans):

@@ -247,6 +247,11 @@ def eval_step(model, batch, step, plot_dir, wav_dir, scalars, hparams, model_nam
             row.update(_reconstruction_scalars(model, hparams))
         except Exception as e:      # like the plotting: never kills a training run
             log('reconstruction check skipped: {}'.format(e))
+    if bool(getattr(hparams, 'mi355_pitch_check', False)):
+        try:
+            row.update(_pitch_scalars(model))
+        except Exception as e:      # likewise
+            log('pitch check skipped: {}'.format(e))
     scalars.write(json.dumps(row) + '\n'); scalars.flush()
     return loss
 
@@ -269,6 +274,23 @@ def _reconstruction_scalars(model, hparams):
     log('Eval reconstruction: bias {:+.2f} dB, l1c {:.2f} dB, mcd {:.2f} dB over {} frames (worst frame {} at {:.2f} dB)'.format(t[0], t[4], t[3], frames, int(t[7]), t[6]))
     return {'Wavenet_eval_model/eval_stats/wavenet_eval_reconstruction_l1c_db': float(t[4]),
             'Wavenet_eval_model/eval_stats/wavenet_eval_reconstruction_mcd_db': float(t[3])}
+
+
+def _pitch_scalars(model):
+    """The generated item of eval_step next to its target on the device (WaveNet.pitch_check): F0 and voicing of both, compared.  Both are decoded
+    model-domain signals (the target is the preprocessed, pre-emphasised recording), so they stand side by side as they are."""
+    from wavenet_vocoder import pitch
+    gen = model.tower_y_hat[0].float().reshape(1, -1).contiguous()
+    ref = model.tower_y_target[0].float().reshape(1, -1).contiguous()
+    n = min(int(gen.shape[1]), int(ref.shape[1]))
+    chk = model.pitch_check(1, n)
+    try:
+        t = chk.score(gen, ref, [n])[0]
+    finally:
+        chk.close()
+    log('Eval pitch: V/UV error {:.3f}, gross pitch error {:.3f}, F0 RMSE {:.1f} cents (bias {:+.1f}) over {} frames, {} voiced in both'.format(
+        t[4], t[5], t[6], t[7], int(t[0]), int(t[3])))
+    return pitch.scalars(t)
 
 
 def add_train_stats(model, batch, step, tensorboard_dir, hparams):
