@@ -219,6 +219,29 @@ int wn_synthesize(wn_ctx* ctx, const float* c, int32_t B, int32_t Tc, const floa
 int wn_noise_per_step(const wn_ctx* ctx);
 /* The device noise stream of wn_synthesize(noise = NULL, seed): fills float [T, B, noise_per_step]. */
 int wn_fill_noise(wn_ctx* ctx, float* noise, int32_t B, int32_t T, uint64_t seed, void* stream);
+/* ---- wide synthesis: more than 32 utterances in one launch-per-layer run -----------------------------------------------------------
+ * wn_synthesize for any 0 < B <= cfg.max_batch, for offline work (vocoding an evaluation set, GTA outputs, a data set) where samples per
+ * second count and latency does not.  Always the launch-per-layer path (wn_synth_last_path() = 1): streams are the N dimension of 32-wide MFMA
+ * tiles, a launch has ceil(B / 32) tiles of workgroups, and a step stays 2 L + 3 dependent launches whatever B is.  The arithmetic of a stream
+ * is that of wn_synthesize(steps_per_graph > 0): its bits depend neither on its tile nor on B, and B = 1 ... 32 IS that run, bit for bit.
+ * Same contract as wn_synthesize (layouts, noise == NULL => wn_fill_noise(B, T, seed) of the full B, the context's temperature pair, global
+ * conditioning from wn_set_global_condition(B), test_inputs, it ends an open stream / slot session, wn_get_upsampled_features returns
+ * [B, cin, T] afterwards) except:
+ *   - 0 < B <= max_batch and B * T <= max_batch * max_time, else WN_E_SHAPE;
+ *   - steps_per_graph <= 0 means 32 (there is no pipeline to select);
+ *   - WN_E_UNSUPPORTED on compute_dtype = WN_COMPUTE_F32; WN_E_STATE before wn_pack_weights.
+ * wn_synthesize, streams, slot sessions and folded runs keep their limit of 32 streams.
+ * State: its own queues, per-step scratch and captured graph (a wide run never evicts the graph of the <= 32 path), sized for
+ * 32 * ceil(B / 32) streams.  A training context grows it to the largest B seen; an inference-only context (which may now have
+ * max_batch > 32: the pipeline, the streaming state and the slot tables are then sized for 32, the wide state for max_batch, and only when
+ * max_batch > 32) sizes it at wn_create and wn_synthesize_wide never allocates there.
+ * Memory (computed from the layouts, not measured): the queues hold sum_l 4 d_l rows of R bf16 per stream -- the paper model (24 layers in 2
+ * stacks, d <= 2 048, R = 256): 32 760 rows x 256 x 2 B = 16.8 MB per stream, 17 GB at 1 024 streams; the upsampled conditioning is about 0.5 KB per
+ * stream-sample (cin bf16 rows + the fp32 levels of the upsample net): 54 GB for 1 024 streams x 5 s at 22 050 Hz.  There is no chunked
+ * run that would bound the latter: cut long utterances, or lower B. */
+int wn_synthesize_wide(wn_ctx* ctx, const float* c, int32_t B, int32_t Tc, const float* noise,
+                       uint64_t seed, const void* test_inputs, void* out_samples, float* out_raw,
+                       int32_t steps_per_graph, void* stream);
 /* ---- sampling temperature: tempered noise for every head, path and slot ---------------------------------------------------------
  * All samplers consume noise in a form where temperature is a change of the NOISE ENTRY, not of the sampler:
  *   select   (Gumbel-max choice of a mixture component / a class)  argmax(logit_i - log(-log u_i))     u' = exp(-(-ln u)^tau)        (the Gumbel term x tau)

@@ -271,18 +271,20 @@ extern "C" int wn_create(const wn_config* cfg, wn_ctx** out) {
         rc = [&]() -> int { WN_HIP(c, c->wg_partial.reserve(need / 4)); return WN_OK; }();
     }
     if (rc == WN_OK && c->inference) {
-        // pre-size every synthesis buffer for (max_batch, max_time): wn_synthesize never allocates on this context
-        if (c->maxB > 32) { c->err = "inference_only: max_batch must be <= 32 streams"; rc = WN_E_SHAPE; }
+        // pre-size every synthesis buffer for (max_batch, max_time): wn_synthesize never allocates on this context.  The pipeline, the streaming state and the
+        // slot tables serve at most 32 streams and are sized for nb = min(32, max_batch); a larger max_batch adds the state of wn_synthesize_wide for all of it
+        const int nb = std::min(32, c->maxB);
         if (rc == WN_OK) rc = wn_noise_reserve(c, c->maxB, c->maxT);
         // the persistent pipeline when the model fits it, pre-sized for the LARGEST eligible run of <= max_batch streams (it was
         // sized for max_batch or else 8, so a batch between 8 and a non-eligible max_batch was eligible by wn_synth_pipe_eligible and then
         // failed to grow); else the launch-per-layer graph path
         if (rc == WN_OK) {
-            int pb = c->maxB;
+            int pb = nb;
             while (pb > 0 && !wn_pipe_eligible(c, pb)) --pb;
             c->pipe_cap = pb;
-            rc = c->cfg.compute_dtype == WN_COMPUTE_F32 ? wn_synth_f32_reserve(c, c->maxB) : pb > 0 ? wn_pipe_reserve(c, pb, c->maxT) : wn_synth_reserve(c);
+            rc = c->cfg.compute_dtype == WN_COMPUTE_F32 ? wn_synth_f32_reserve(c, nb) : pb > 0 ? wn_pipe_reserve(c, pb, c->maxT) : wn_synth_reserve(c);
         }
+        if (rc == WN_OK && c->maxB > 32 && c->cfg.compute_dtype != WN_COMPUTE_F32) rc = wn_synth_wide_reserve(c, c->maxB);
         if (rc == WN_OK) rc = stream_alloc(c);      // the streaming state too: wn_synth_stream_* never allocate here
         if (rc == WN_OK && c->cfg.compute_dtype != WN_COMPUTE_F32) rc = wn_slots_alloc(c);      // ... nor do wn_synth_slots_* and wn_synthesize_folded
     }
@@ -459,6 +461,31 @@ extern "C" int wn_synthesize(wn_ctx* c, const float* cc, int32_t B, int32_t Tc, 
         noise = c->noise_buf;
     }
     return wn_synth_impl(c, cc, B, Tc, noise, seed, test_inputs, out_samples, out_raw, steps_per_graph, (hipStream_t)stream);
+}
+
+// The launch-per-layer run of wn_synthesize(steps_per_graph > 0) for any 0 < B <= max_batch: ceil(B / 32) tiles of streams per launch (wn_synth.hip).
+extern "C" int wn_synthesize_wide(wn_ctx* c, const float* cc, int32_t B, int32_t Tc, const float* noise, uint64_t seed,
+                                  const void* test_inputs, void* out_samples, float* out_raw, int32_t steps_per_graph, void* stream) {
+    if (!c || !cc || !out_samples) return WN_E_ARG;
+    WnRange range("wn_synthesize_wide");
+    if (c->cfg.compute_dtype == WN_COMPUTE_F32) WN_FAIL(c, WN_E_UNSUPPORTED, "wn_synthesize_wide: wide runs are not built for the fp32 validation mode (compute_dtype = WN_COMPUTE_F32)");
+    if (!c->packed) WN_FAIL(c, WN_E_STATE, "wn_pack_weights must be called before wn_synthesize_wide");
+    if (B <= 0 || B > c->maxB) WN_FAIL(c, WN_E_SHAPE, "wide synthesis batch %d outside (0, max_batch = %d]", B, c->maxB);
+    if (Tc <= 0) WN_FAIL(c, WN_E_SHAPE, "Tc must be positive");
+    const int64_t T64 = (int64_t)Tc * c->hop;
+    if (T64 * B > c->NT) WN_FAIL(c, WN_E_SHAPE, "synthesis B*T = %d*%lld exceeds the workspace (max_batch*max_time = %lld)", B, (long long)T64, (long long)c->NT);
+    c->strm.open = false; c->slots.open = false;            // (ends an open stream / slot session, as wn_synthesize does)
+    int rc = wn_pipe_check(c, false);
+    if (rc) return rc;
+    const int T = (int)T64;      // (<= NT / B: the kernels index [T][B][nps], [B][O][T] and the queues in 64 bits, so no further shape is refused)
+    const bool tempered = c->tau_scale != 1.0f || c->tau_select != 1.0f;
+    if (!noise || tempered) {
+        if ((rc = wn_noise_reserve(c, B, T))) return rc;
+        if ((rc = noise ? wn_temper_noise_impl(c, noise, c->noise_buf, B, T, c->tau_scale, c->tau_select, (hipStream_t)stream)
+                        : wn_fill_noise_impl(c, c->noise_buf, B, T, seed, c->tau_scale, c->tau_select, (hipStream_t)stream))) return rc;
+        noise = c->noise_buf;
+    }
+    return wn_synth_impl(c, cc, B, Tc, noise, seed, test_inputs, out_samples, out_raw, steps_per_graph, (hipStream_t)stream, true);
 }
 
 extern "C" int wn_fill_noise(wn_ctx* c, float* noise, int32_t B, int32_t T, uint64_t seed, void* stream) {
@@ -728,7 +755,7 @@ static int stream_alloc(wn_ctx* c) {
     auto& S = c->strm;
     for (auto& q : S.pend) WN_HIP(c, q.reserve((size_t)c->C * (c->NT / c->hop + 1)));
     WN_HIP(c, S.carry.reserve(32));
-    if (c->gin > 0) WN_HIP(c, S.gbias.reserve((size_t)c->L * c->maxB * c->G));
+    if (c->gin > 0) WN_HIP(c, S.gbias.reserve((size_t)c->L * std::min(32, c->maxB) * c->G));      // (a stream has at most 32 streams)
     return WN_OK;
 }
 

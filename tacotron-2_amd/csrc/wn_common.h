@@ -243,7 +243,8 @@ struct wn_ctx {
     // lazy per-path states, each defined (and deleted) in its own translation unit.  Declared LAST: members are destroyed in reverse order, so the private
     // streams these states own are synchronised and destroyed before any buffer above that their work may still read is freed.
     std::unique_ptr<F32State, WnStateDelete> f32;         // fp32-forward state (wn_f32.hip), built by the first forward of a cfg.compute_dtype = WN_COMPUTE_F32 context
-    std::unique_ptr<Synth, WnStateDelete> synth;          // launch-per-layer synthesis (wn_synth.hip)
+    std::unique_ptr<Synth, WnStateDelete> synth;          // launch-per-layer synthesis (wn_synth.hip): runs of <= 32 streams, streams, slot sessions
+    std::unique_ptr<Synth, WnStateDelete> wide;           // the same for wide runs (wn_synthesize_wide): queues and scratch of 32 * ceil(B / 32) streams, its own runner
     std::unique_ptr<SynthF32, WnStateDelete> synth32;     // fp32 synthesis (wn_synth_f32.hip; cfg.compute_dtype = WN_COMPUTE_F32)
     std::unique_ptr<Pipe, WnStateDelete> pipe;            // persistent synthesis pipeline (wn_synth_pipe.hip)
 };
@@ -298,7 +299,7 @@ int wn_fwd_impl(wn_ctx* ctx, hipStream_t st, float* loss_out, float* y_hat_out, 
 int wn_bwd_impl(wn_ctx* ctx, float* grads, hipStream_t st);
 int wn_optim_impl(wn_ctx* ctx, float* p, const float* g, float* m, float* v, float* ema, float lr, int64_t step, hipStream_t st);
 int wn_synth_impl(wn_ctx* ctx, const float* c, int B, int Tc, const float* noise, uint64_t seed,
-                  const void* test_inputs, void* out_samples, float* out_raw, int steps_per_graph, hipStream_t st);
+                  const void* test_inputs, void* out_samples, float* out_raw, int steps_per_graph, hipStream_t st, bool wide = false);
 // T samples of a span (conditioning already upsampled into cbt / CUP) on one of the three paths: the only way into each of them
 int wn_synth_span(wn_ctx* ctx, int B, int T, const WnSpan& sp, const float* noise, const void* test_inputs, void* out_samples, float* out_raw,
                   int steps_per_graph, hipStream_t st);
@@ -320,6 +321,9 @@ int wn_synth_f32_reserve(wn_ctx* ctx, int B);
 bool wn_pipe_eligible(const wn_ctx* ctx, int B);
 int wn_pipe_reserve(wn_ctx* ctx, int B, int T);            // size every pipeline buffer for (B, T) (no-op when already large enough)
 int wn_synth_reserve(wn_ctx* ctx);                        // state of the launch-per-layer graph path
+int wn_synth_wide_reserve(wn_ctx* ctx, int B);            // ... of its wide runs, for B streams
+int wn_synth_wide_span(wn_ctx* ctx, int B, int T, const WnSpan& sp, const float* noise, const void* test_inputs, void* out_samples, float* out_raw,
+                       int steps_per_graph, hipStream_t st);      // a whole utterance (sp.t0 == 0) of any B on the wide owner
 int wn_pipe_check(wn_ctx* ctx, bool wait);                // pending abort flag of the last pipeline run -> WN_E_HIP
 int wn_noise_reserve(wn_ctx* ctx, int B, int T);
 int wn_fill_noise_impl(wn_ctx* ctx, float* noise, int B, int T, uint64_t seed, float tau_scale, float tau_select, hipStream_t st);

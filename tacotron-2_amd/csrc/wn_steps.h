@@ -63,14 +63,16 @@ struct WnStepRunner {
 __device__ __forceinline__ void wn_queue_store(bf16_t* q, float v) { *q = f2bf(v); }
 __device__ __forceinline__ void wn_queue_store(float* q, float v) { *q = v; }
 
-// initial input (silence, wavenet.py:433-445) -> queue 0 slot 0; t = 0
+// initial input (silence, wavenet.py:433-445) -> queue 0 slot 0; t = 0.  One block per tile of 32 streams (blockIdx.y): stream b = 32 * tile + n; the
+// sampler of tile k > 0 keeps its own copy of the time index in t_dev[1 + k] (wn_synth_sample), tile 0 the one every other kernel reads
 template <class Q>
 __global__ void wn_synth_init(const float* __restrict__ Wf, const float* __restrict__ bf_, int R, int mode, int start_id, Q* __restrict__ ring0, int B, int32_t* t_dev) {
-    for (int o = threadIdx.x; o < B * R; o += blockDim.x) {
+    const int tile = blockIdx.y, nb = min(32, B - 32 * tile);
+    for (int o = threadIdx.x; o < nb * R; o += blockDim.x) {
         const int n = o / R, r = o - n * R;
-        wn_queue_store(ring0 + (size_t)n * R + r, (mode == 2) ? Wf[(size_t)start_id * R + r] + bf_[r] : bf_[r]);      // x = 0 for raw / mulaw
+        wn_queue_store(ring0 + ((size_t)32 * tile + n) * R + r, (mode == 2) ? Wf[(size_t)start_id * R + r] + bf_[r] : bf_[r]);      // x = 0 for raw / mulaw
     }
-    if (threadIdx.x == 0) { t_dev[0] = 0; t_dev[1] = 0; }
+    if (threadIdx.x == 0) { if (tile == 0) { t_dev[0] = 0; t_dev[1] = 0; } else t_dev[1 + tile] = 0; }
 }
 
 // A span that begins an utterance (t0 == 0) zeroes the queues (wavenet.py:815-816: `SB` streams per queue row) and starts from silence; any other one
@@ -79,7 +81,7 @@ template <class Q>
 static int wn_span_start(wn_ctx* c, const std::vector<DevBuf<Q>>& ring, const std::vector<int>& mask, int SB, int B, int32_t* t_dev, int t0, hipStream_t st) {
     if (t0 != 0) { WN_HIP(c, hipMemsetD32Async((hipDeviceptr_t)(t_dev + 1), t0, 1, st)); return WN_OK; }
     for (int l = 0; l < c->L; ++l) WN_HIP(c, hipMemsetAsync(ring[l], 0, (size_t)(mask[l] + 1) * SB * c->R * sizeof(Q), st));
-    hipLaunchKernelGGL(wn_synth_init<Q>, dim3(1), dim3(256), 0, st, c->params_dev + c->first.dil_k, c->params_dev + c->first.dil_b, c->R, wn_sample_mode(c), 127, ring[0], B, t_dev);
+    hipLaunchKernelGGL(wn_synth_init<Q>, dim3(1, (B + 31) / 32), dim3(256), 0, st, c->params_dev + c->first.dil_k, c->params_dev + c->first.dil_b, c->R, wn_sample_mode(c), 127, ring[0], B, t_dev);
     WN_LAUNCH_CHECK(c);
     return WN_OK;
 }

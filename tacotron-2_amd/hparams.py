@@ -89,6 +89,9 @@ MI355 = dict(
     mi355_synthesis_fold_rows=0,       # N > 0: Synthesizer.synthesize generates through WaveNet.folded: every utterance is cut into overlapping segments that run side by
                                        # side as up to min(N, 32) rows of one batch and are cross-faded back (groups of utterances whose rows fit 32); 0: off.
                                        # Not with mi355_synthesis_slots.  Segments start cold: the waveform is not the one-shot run's after the first seam
+    mi355_synthesis_wide_rows=0,       # N > 0: Synthesizer.synthesize generates through WaveNet.wide: launch-per-layer runs of up to N utterances, N may exceed 32
+                                       # (offline throughput: an evaluation set, GTA outputs); longest first, every run padded to its own longest.  0: off.
+                                       # Not with mi355_synthesis_slots or mi355_synthesis_fold_rows
     mi355_synthesis_fold_warm=4,       # mel frames a segment generates and discards before the part it contributes (50 ms at hop 275)
     mi355_synthesis_fold_fade=2,       # mel frames of cross-fade between consecutive segments (25 ms); equal power
     mi355_synthesis_fold_min_frames=40,    # no segment contributes fewer new frames than this (~0.5 s): shorter utterances stay one row, i.e. the one-shot run.

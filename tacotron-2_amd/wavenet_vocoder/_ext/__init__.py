@@ -132,6 +132,7 @@ def load_library():
         'wn_optim_step': (ctypes.c_int, [vp, vp, vp, vp, vp, vp, f32, i64, vp]),
         'wn_learning_rate': (f32, [i32, f32, i64, f32, i64, f32]),
         'wn_synthesize': (ctypes.c_int, [vp, vp, i32, i32, vp, u64, vp, vp, vp, i32, vp]),
+        'wn_synthesize_wide': (ctypes.c_int, [vp, vp, i32, i32, vp, u64, vp, vp, vp, i32, vp]),
         'wn_noise_per_step': (ctypes.c_int, [vp]),
         'wn_fill_noise': (ctypes.c_int, [vp, vp, i32, i32, u64, vp]),
         'wn_synth_set_temperature': (ctypes.c_int, [vp, f32, f32]),
@@ -426,6 +427,13 @@ class Engine:
         B, Tc = int(c.shape[0]), int(c.shape[-1])
         self._ok(self.lib.wn_synthesize(self.h, _ptr(c), B, Tc, _ptr(noise), ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), _ptr(test_inputs),
                                         _ptr(out_samples), _ptr(out_raw), int(steps_per_graph), _stream()))
+
+    def synthesize_wide(self, c, noise, out_samples, out_raw=None, test_inputs=None, steps_per_graph=0, seed=0):
+        """synthesize() for any B <= max_batch (wn_synthesize_wide): always the launch-per-layer path, ceil(B / 32) tiles of streams per
+        launch; steps_per_graph <= 0 means 32.  A stream's samples do not depend on B: B <= 32 is synthesize(steps_per_graph > 0) bit for bit."""
+        B, Tc = int(c.shape[0]), int(c.shape[-1])
+        self._ok(self.lib.wn_synthesize_wide(self.h, _ptr(c), B, Tc, _ptr(noise), ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), _ptr(test_inputs),
+                                             _ptr(out_samples), _ptr(out_raw), int(steps_per_graph), _stream()))
 
     # ---- streaming synthesis (wn_synth_stream_*): the samples of one synthesize() over the concatenated frames, push by push
     def stream_lookahead(self):

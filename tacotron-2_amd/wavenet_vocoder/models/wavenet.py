@@ -189,6 +189,39 @@ def slot_plan(lengths, B, tick_frames):
         yield opens, frames, final
 
 
+def wide_plan(frames, rows, max_cells):
+    """Cut utterances of `frames` mel frames into the runs of WaveNet.wide (no GPU): sorted by length (stable, longest first), then cut greedily into
+    runs of at most `rows` utterances whose rows_in_run x longest_frames stays within `max_cells`; every run is padded to its own longest utterance
+    only.  Returns (runs, perm): runs = lists of input indices, perm[i] = the position of utterance i in the concatenation of the runs.  An
+    utterance longer than max_cells fits no run: ValueError naming it.  Sorting never pads more than cutting the input order into runs of `rows`:
+    the k-th run's longest is the smallest possible, and a cut forced by max_cells only shortens what a run is padded to."""
+    rows, max_cells = int(rows), int(max_cells)
+    if rows <= 0 or max_cells <= 0:
+        raise ValueError('wide_plan: rows and max_cells must be positive')
+    frames = [int(f) for f in frames]
+    for i, f in enumerate(frames):
+        if f <= 0:
+            raise ValueError('wide_plan: utterance {} has no frame'.format(i))
+        if f > max_cells:
+            raise ValueError('wide_plan: utterance {} ({} frames) fits no run of at most {} cells'.format(i, f, max_cells))
+    order = sorted(range(len(frames)), key=lambda i: -frames[i])
+    runs = []
+    for i in order:
+        if runs and len(runs[-1]) < rows and (len(runs[-1]) + 1) * frames[runs[-1][0]] <= max_cells:
+            runs[-1].append(i)
+        else:
+            runs.append([i])
+    perm = [0] * len(frames)
+    for k, i in enumerate(order):
+        perm[i] = k
+    return runs, perm
+
+
+def wide_padded_cells(frames, runs):
+    """Cells a plan generates and throws away: every run is padded to its longest utterance."""
+    return sum(len(r) * max(int(frames[i]) for i in r) - sum(int(frames[i]) for i in r) for r in runs)
+
+
 class SlotSession(object):
     """B slots served by one pipeline configuration (WaveNet.slots): every slot is idle or carries ONE utterance with its own start, seed and
     global condition; utterances are opened, fed mel frames, finished and replaced independently, and a slot's samples are bit-identical to a
@@ -778,6 +811,94 @@ class WaveNet(object):
         self.engine.upsampled_features(feats)
         info = {'plan': plan, 'rows': out_rows, 'raw': out_raw, 'features': feats, 'seed': seed}
         return (wavs, info) if post is None else (wavs, info, posts)
+
+    def wide(self, c_list, g=None, rows=64, temperature=None, mixture_temperature=None, noise=None, test_inputs=None, return_raw=False, post=None, check=True):
+        """Wide generation for offline work: the utterances of c_list ([cin, F_u] mel frames each, any lengths: the layout folded([c]) takes) in launch-per-layer
+        runs of up to `rows` utterances -- `rows` may exceed 32 (Engine.synthesize_wide) -- planned by wide_plan: longest first, every run padded to its own
+        longest utterance.  A stream's samples are those of incremental() on the launch-per-layer path with the same noise; they do not depend on the run's
+        width.  Returns (samples, info): one model-domain tensor [F_u * hop] per utterance in input order (floats, or class ids of the softmax head), and
+        info = {'plan': (runs, perm), 'seeds': one per run, 'features': the upsampled conditioning [cin, F_u * hop] per utterance} plus 'raw' ([O, F_u * hop]
+        per utterance; return_raw) and 'post' ((float32 de-emphasised, int16 peak-normalised) per utterance through post.finish(); post: an OutputStage
+        of this model's input type with >= rows rows).  g: one speaker id / feature row per utterance.  noise: None (drawn on the device; the seed of run r
+        derives from (wavenet_random_seed, the synthesis-call counter, r), so two fresh models agree) or one tensor [T_run, n_run, noise_per_step] per run
+        of the plan; test_inputs: one model-domain tensor [F_u * hop] per utterance.  check: wait for every run and verify it.
+        Without an engine, an inference-only one is built for the largest run.  Memory: see wn_synthesize_wide (the queues take 16.8 MB per stream on the
+        paper model, the conditioning ~0.5 KB per stream-sample)."""
+        hp = self._hparams
+        pair = temperature_pair(hp, temperature, mixture_temperature)
+        hop = audio.get_hop_size(hp)
+        U = len(c_list)
+        if U < 1:
+            raise ValueError('WaveNet.wide: no utterance')
+        for c in c_list:
+            if c.dim() != 2 or int(c.shape[0]) != hp.cin_channels or int(c.shape[1]) < 1:
+                raise ValueError('WaveNet.wide: every utterance must be [cin={}, frames >= 1] (got {})'.format(hp.cin_channels, tuple(c.shape)))
+        frames = [int(c.shape[-1]) for c in c_list]
+        if g is None and self.global_conditioning_enabled():
+            raise ValueError('global conditioning is enabled (gin_channels > 0) but no g was given')
+        if test_inputs is not None and len(test_inputs) != U:
+            raise ValueError('WaveNet.wide: test_inputs needs one tensor per utterance')
+        rows = int(rows)
+        if self.engine is None:
+            runs, perm = wide_plan(frames, rows, rows * max(frames))
+            self.build(max(len(r) for r in runs), max(frames) * hop, inference_only=True)
+        else:
+            runs, perm = wide_plan(frames, min(rows, self.max_batch), self.max_batch * (self.max_time // hop))
+        if noise is not None and len(noise) != len(runs):
+            raise ValueError('WaveNet.wide: noise needs one tensor per run of the plan ({} runs)'.format(len(runs)))
+        self._ensure_packed()
+        self.engine.set_temperature(*pair)
+        dev = self.device
+        self._synth_calls = getattr(self, '_synth_calls', 0) + 1
+        base = ((int(hp.wavenet_random_seed) << 20) + self._synth_calls) << 16
+        dt = torch.float32 if self.scalar_input else torch.int32
+        spg = int(getattr(hp, 'mi355_steps_per_graph', 0))
+        gt = None
+        if self.global_conditioning_enabled():
+            gt = torch.as_tensor(g, device=dev)
+            gt = gt.reshape(U).to(torch.int32) if self.embed_speakers is not None else gt.reshape(U, hp.gin_channels).to(torch.float32)
+        samples, feats, raws, posts, seeds = [None] * U, [None] * U, [None] * U, [None] * U, []
+        for r, run in enumerate(runs):
+            n, F = len(run), frames[run[0]]
+            T = F * hop
+            cc = torch.zeros(n, hp.cin_channels, F, device=dev)
+            for k, u in enumerate(run):
+                cc[k, :, :frames[u]] = c_list[u].to(dev, torch.float32)
+            ti = None
+            if test_inputs is not None:
+                ti = torch.zeros(n, T, device=dev, dtype=dt)
+                for k, u in enumerate(run):
+                    t = test_inputs[u].reshape(-1)[:frames[u] * hop]
+                    assert t.shape[0] == frames[u] * hop, 'teacher-forcing inputs must cover the whole synthesis length'
+                    ti[k, :t.shape[0]] = t.to(dev, dt)
+            if gt is not None:
+                self._set_global(gt[torch.as_tensor(run, device=dev)], n)
+            out = torch.empty(n, T, device=dev, dtype=dt)
+            raw = torch.empty(n, hp.out_channels, T, device=dev) if return_raw else None
+            seeds.append(base + r)
+            self.engine.synthesize_wide(cc, None if noise is None else noise[r].to(dev, torch.float32).contiguous(), out, raw, ti, steps_per_graph=spg, seed=seeds[-1])
+            fe = torch.empty(n, hp.cin_channels, T, device=dev)
+            self.engine.upsampled_features(fe)
+            if check:
+                torch.cuda.synchronize()
+                self.engine.synth_check()
+            pp = post.finish(out, [frames[u] * hop for u in run]) if post is not None else None
+            for k, u in enumerate(run):
+                m = frames[u] * hop
+                samples[u], feats[u] = out[k, :m], fe[k, :, :m]
+                if raw is not None:
+                    raws[u] = raw[k, :, :m]
+                if pp is not None:
+                    posts[u] = (pp[0][k, :m], pp[1][k, :m])
+        if getattr(self, '_logged_wide', None) != (len(runs), max(len(r) for r in runs)):
+            self._logged_wide = (len(runs), max(len(r) for r in runs))
+            log('WaveNet wide synthesis: {} utterance(s) in {} run(s) of <= {} streams, path {}'.format(U, len(runs), self._logged_wide[1], self.engine.synth_path))
+        info = {'plan': (runs, perm), 'seeds': seeds, 'features': feats}
+        if return_raw:
+            info['raw'] = raws
+        if post is not None:
+            info['post'] = posts
+        return samples, info
 
     def output_stage(self, rows, **kw):
         """An _ext.OutputStage of `rows` rows for this model's samples (in_type and de-emphasis from the hparams; gain: mi355_output_gain): the post=

@@ -177,8 +177,15 @@ class Synthesizer(object):
                 raise RuntimeError('Please provide speaker ids (--speaker_id) to a globally conditioned WaveNet')
             g = torch.from_numpy(np.asarray(speaker_ids, dtype=np.int32).reshape(len(c_batch), 1))
         nfold = int(getattr(hparams, 'mi355_synthesis_fold_rows', 0))
-        if nfold > 0 and int(getattr(hparams, 'mi355_synthesis_slots', 0)) > 0:
-            raise ValueError('mi355_synthesis_fold_rows and mi355_synthesis_slots are both > 0: choose one')
+        nwide = int(getattr(hparams, 'mi355_synthesis_wide_rows', 0))
+        routes = [key for key in ('mi355_synthesis_fold_rows', 'mi355_synthesis_slots', 'mi355_synthesis_wide_rows') if int(getattr(hparams, key, 0)) > 0]
+        if len(routes) > 1:
+            raise ValueError('{} are {} > 0: choose one'.format(' and '.join(routes), 'both' if len(routes) == 2 else 'all'))
+        if nwide > 0 and not self.synth_debug:
+            generated_wavs, upsampled_features, pcm, decoded = self._synthesize_wide(c_batch, frames, speaker_ids, nwide)
+            self._reconstruction(decoded, generated_wavs, cond, frames, basenames, out_dir)
+            self._pitch(decoded, generated_wavs, basenames, out_dir)
+            return self._write(generated_wavs, upsampled_features, mel_spectrograms, basenames, out_dir, log_dir, pcm)
         if nfold > 0 and not self.synth_debug:
             generated_wavs, upsampled_features, pcm, decoded = self._synthesize_folded(c_batch, frames, speaker_ids, min(nfold, 32), log_dir is not None)
             self._reconstruction(decoded, generated_wavs, cond, frames, basenames, out_dir)
@@ -253,6 +260,36 @@ class Synthesizer(object):
                 ups += [np.zeros((hparams.cin_channels, 0), np.float32) for _ in grp]
             wavs += [w.float().cpu().numpy() for w in ([y for y, _ in posts] if device else res)]
         return wavs, ups, pcm, decoded
+
+    def _synthesize_wide(self, c_batch, lengths, speaker_ids, nrows):
+        """mi355_synthesis_wide_rows > 0: the utterances of the call through WaveNet.wide, in launch-per-layer runs of at most nrows utterances (nrows may
+        exceed 32), longest first, every run padded to its own longest utterance; results in input order.  The inference-only context is built for the
+        largest run.  Seeds derive from (wavenet_random_seed, the model's synthesis-call counter, run index), so two fresh runs of the same inputs agree."""
+        from wavenet_vocoder import util as wutil
+        from wavenet_vocoder.models.wavenet import wide_plan
+        from wavenet_vocoder.util import is_mulaw, is_mulaw_quantize
+        hparams, hop = self._hparams, get_hop_size(self._hparams)
+        runs, _ = wide_plan(lengths, nrows, nrows * max(lengths))
+        self._ensure_capacity(max(len(r) for r in runs), max(lengths) * hop)
+        m = self.model
+        dev = m.device
+        cl = [torch.from_numpy(np.ascontiguousarray(c_batch[u, :lengths[u]].T)) for u in range(len(lengths))]
+        ids = None if not self.global_conditions else [int(v) for v in np.asarray(speaker_ids).reshape(-1)]
+        samples, info = m.wide(cl, g=ids, rows=nrows, check=True)
+        device, k = self._output_mode()
+        rows = torch.zeros(len(lengths), max(lengths) * hop, device=dev)      # every utterance decoded, one row each
+        for u, out in enumerate(samples):
+            if is_mulaw_quantize(hparams.input_type):
+                out = wutil.inv_mulaw_quantize(out)
+            elif is_mulaw(hparams.input_type):
+                out = wutil.inv_mulaw(out)
+            rows[u, :out.shape[0]] = out.float()
+        ups = [f.cpu().numpy() for f in info['features']]
+        if device:
+            wavs, pcm = self._finish_device(rows, [n * hop for n in lengths], k)
+            return wavs, ups, pcm, rows
+        host = rows.cpu().numpy()
+        return [host[u, :n * hop] for u, n in enumerate(lengths)], ups, None, None
 
     def _synthesize_slots(self, c_batch, lengths, speaker_ids, nslots, want_features):
         """mi355_synthesis_slots > 0: all utterances of the call through ONE slot session (WaveNet.slots): no utterance is padded to the longest of its
