@@ -230,15 +230,16 @@ int wn_fill_noise(wn_ctx* ctx, float* noise, int32_t B, int32_t T, uint64_t seed
  *   - 0 < B <= max_batch and B * T <= max_batch * max_time, else WN_E_SHAPE;
  *   - steps_per_graph <= 0 means 32 (there is no pipeline to select);
  *   - WN_E_UNSUPPORTED on compute_dtype = WN_COMPUTE_F32; WN_E_STATE before wn_pack_weights.
- * wn_synthesize, streams, slot sessions and folded runs keep their limit of 32 streams.
+ * wn_synthesize, streams, the slot sessions of wn_synth_slots_begin and folded runs keep their limit of 32 streams (wide slot sessions:
+ * wn_synth_wide_slots_begin below).
  * State: its own queues, per-step scratch and captured graph (a wide run never evicts the graph of the <= 32 path), sized for
  * 32 * ceil(B / 32) streams.  A training context grows it to the largest B seen; an inference-only context (which may now have
  * max_batch > 32: the pipeline, the streaming state and the slot tables are then sized for 32, the wide state for max_batch, and only when
  * max_batch > 32) sizes it at wn_create and wn_synthesize_wide never allocates there.
  * Memory (computed from the layouts, not measured): the queues hold sum_l 4 d_l rows of R bf16 per stream -- the paper model (24 layers in 2
  * stacks, d <= 2 048, R = 256): 32 760 rows x 256 x 2 B = 16.8 MB per stream, 17 GB at 1 024 streams; the upsampled conditioning is about 0.5 KB per
- * stream-sample (cin bf16 rows + the fp32 levels of the upsample net): 54 GB for 1 024 streams x 5 s at 22 050 Hz.  There is no chunked
- * run that would bound the latter: cut long utterances, or lower B. */
+ * stream-sample (cin bf16 rows + the fp32 levels of the upsample net): 54 GB for 1 024 streams x 5 s at 22 050 Hz.  The run that bounds
+ * the latter is the wide slot session (wn_synth_wide_slots_begin): its conditioning is upsampled push by push. */
 int wn_synthesize_wide(wn_ctx* ctx, const float* c, int32_t B, int32_t Tc, const float* noise,
                        uint64_t seed, const void* test_inputs, void* out_samples, float* out_raw,
                        int32_t steps_per_graph, void* stream);
@@ -365,6 +366,27 @@ int wn_synth_slots_push(wn_ctx* ctx, const float* c, int32_t Tn, const int32_t* 
 int wn_synth_slot_abandon(wn_ctx* ctx, int32_t slot);              /* drop a live utterance (host only, no device work); the slot is idle */
 int wn_synth_slot_frames_done(const wn_ctx* ctx, int32_t slot);    /* frames generated so far, -1 idle; WN_E_ARG / WN_E_STATE */
 int wn_synth_slots_end(wn_ctx* ctx);
+/* ---- wide slot sessions: more than 32 slots on the launch-per-layer path -------------------------------------------------------
+ * The same kind of session for any 0 < B <= max_batch: continuous batching at the width of wn_synthesize_wide.  Always the launch-per-layer path
+ * (wn_synth_last_path() = 1) on the wide owner -- the queues, runner and captured graph of wn_synthesize_wide, ceil(B / 32) tiles of 32 slots per
+ * launch; steps_per_graph <= 0 means 32.  Every other call of the session is shared, with host arrays of B entries: wn_synth_slot_open,
+ * wn_synth_set_slot_temperature, wn_synth_slots_push, wn_synth_slot_abandon, wn_synth_slot_frames_done, wn_synth_slots_end.
+ * Contract: that of the slot sessions above, restated for width.  A slot's out_samples / out_raw depend only on the slot's own frames, noise,
+ * teacher forcing, condition and temperature pair -- not on B, the slot's tile, how the frames were cut into pushes, when the slot was opened, what the
+ * other slots (or whole other tiles) do or what occupied it before.  They are bit-identical to wn_synthesize(steps_per_graph > 0) of <= 32 streams with
+ * the utterance in row slot & 31, and to wn_synthesize_wide with the utterance in row slot; for device noise the column is
+ * wn_fill_noise(B = 1, T, seed_slot) tempered by the slot's pair.  A tile without a live slot runs as dummy steps that store nothing.
+ * Errors: as above, and WN_E_SHAPE for B outside (0, max_batch] (an inference-only context: the width its wide state was sized for),
+ * WN_E_UNSUPPORTED on WN_COMPUTE_F32, WN_E_STATE before wn_pack_weights.  One session at a time per context, narrow or wide: either begin ends the
+ * other's, as wn_synthesize, wn_synthesize_wide, wn_pack_weights, wn_synth_pipe_dtype and wn_synth_stream_begin do.  A rejected push leaves every slot
+ * as it was.  The session tables are sized for the session's B: a training context grows them at begin; an inference-only context with
+ * max_batch > 32 sizes them for max_batch at wn_create and never allocates in these calls.  A push never synchronises.
+ * Memory (computed from the layouts, not measured): the queues are those of wn_synthesize_wide (16.8 MB per slot on the paper model).  The
+ * conditioning is upsampled per push: the tables of the push (cin bf16 rows + fp32 rows) and the upsample workspace hold at most max_batch x max_time
+ * stream-samples (about 0.5 KB each), where max_time need only cover ONE push (a slot generates at most max_time samples per push), not the
+ * utterance: 1 024 slots x 8 frames of 256 samples = 2.1 M stream-samples, about 1 GB, whatever the utterances' lengths.  The pending mel windows are
+ * 2 x B x cin x capw floats, capw = max_time / hop + lookahead + 1 frames per slot. */
+int wn_synth_wide_slots_begin(wn_ctx* ctx, int32_t B, int32_t steps_per_graph, void* stream);
 
 /* ---- folded synthesis: ONE utterance generated as overlapping segments that run side by side (WaveRNN's fold_with_overlap / xfade_and_unfold) ----
  * Streams and slots spend the width of a run on more utterances; a folded run spends it on one.  The utterances are cut into rows; row r generates

@@ -272,7 +272,8 @@ extern "C" int wn_create(const wn_config* cfg, wn_ctx** out) {
     }
     if (rc == WN_OK && c->inference) {
         // pre-size every synthesis buffer for (max_batch, max_time): wn_synthesize never allocates on this context.  The pipeline, the streaming state and the
-        // slot tables serve at most 32 streams and are sized for nb = min(32, max_batch); a larger max_batch adds the state of wn_synthesize_wide for all of it
+        // narrow slot sessions serve at most 32 streams and are sized for nb = min(32, max_batch); a larger max_batch adds the state of wn_synthesize_wide and
+        // the tables of a wide slot session (wn_synth_wide_slots_begin) for all of it
         const int nb = std::min(32, c->maxB);
         if (rc == WN_OK) rc = wn_noise_reserve(c, c->maxB, c->maxT);
         // the persistent pipeline when the model fits it, pre-sized for the LARGEST eligible run of <= max_batch streams (it was
@@ -286,7 +287,7 @@ extern "C" int wn_create(const wn_config* cfg, wn_ctx** out) {
         }
         if (rc == WN_OK && c->maxB > 32 && c->cfg.compute_dtype != WN_COMPUTE_F32) rc = wn_synth_wide_reserve(c, c->maxB);
         if (rc == WN_OK) rc = stream_alloc(c);      // the streaming state too: wn_synth_stream_* never allocate here
-        if (rc == WN_OK && c->cfg.compute_dtype != WN_COMPUTE_F32) rc = wn_slots_alloc(c);      // ... nor do wn_synth_slots_* and wn_synthesize_folded
+        if (rc == WN_OK && c->cfg.compute_dtype != WN_COMPUTE_F32) rc = wn_slots_alloc(c, c->maxB > 32 ? c->maxB : nb);      // ... nor do wn_synth_slots_*, wn_synth_wide_slots_begin and wn_synthesize_folded
     }
     if (rc != WN_OK) { g_create_err = c->err; wn_destroy(c); return rc; }
     *out = c;
@@ -853,18 +854,32 @@ extern "C" int wn_synth_stream_end(wn_ctx* c) {
 // ---- synthesis slots: utterances join and leave a running batch -------------------------------------------------------------------
 // One session = B slots on one path / pipeline configuration.  What a stream keeps once (time index, pending window, seed, carried input, bias row) a
 // session keeps per slot; a push runs max_b n_out[b] steps in which every slot takes part, the ones that have nothing (more) to generate as dummies.
-int wn_slots_alloc(wn_ctx* c) {
+// the host arrays of one push, one entry per slot (st0 / snl padded to whole tiles); sized with the tables, so that a push allocates nothing
+struct wn_ctx::WnSlots::PushHost {
+    std::vector<WnPushPlan> pl; std::vector<int64_t> w, first, cnt; std::vector<int> nb; std::vector<uint8_t> rebuilt, grouped; std::vector<float> ts, tsel;
+    std::vector<uint64_t> seed; std::vector<int32_t> st0, snl; std::vector<uint32_t> fresh;
+    explicit PushHost(int n) : pl(n), w(n), first(n), cnt(n), nb(n), rebuilt(n), grouped(n), ts(n), tsel(n), seed(n), st0(32 * ((n + 31) / 32)), snl(st0.size()), fresh(st0.size() / 32) {}
+};
+int wn_slots_alloc(wn_ctx* c, int nslots) {
     auto& S = c->slots;
     int l = 0, r = 0; wn_synth_stream_lookahead(&c->cfg, &l, &r);
     S.capw = c->maxT / c->hop + l + r + 1;
-    const int nb = std::min(32, c->maxB);
-    for (auto& q : S.pend) WN_HIP(c, q.reserve((size_t)nb * c->C * S.capw));
-    WN_HIP(c, S.gwin.reserve((size_t)nb * c->C * S.capw));
+    nslots = std::max(nslots, std::min(32, c->maxB));      // (never fewer than a narrow session may ask for: its begin does not grow them)
+    if (nslots > S.cap_slots) {      // the tables that hold one entry or region per slot (a training context grows them at begin; inference-only: sized once, at wn_create)
+        if (c->inference && S.cap_slots > 0) WN_FAIL(c, WN_E_SHAPE, "slot session: %d slots exceed the %d this inference-only context was sized for", nslots, S.cap_slots);
+        if (S.cap_slots > 0) WN_HIP(c, hipDeviceSynchronize());      // (growing: nothing may still read the old tables)
+        const int nb = std::min(32, nslots);
+        for (auto& q : S.pend) WN_HIP(c, q.grow((size_t)nslots * c->C * S.capw));
+        WN_HIP(c, S.gwin.grow((size_t)nb * c->C * S.capw));      // (a conditioning group has at most 32 members)
+        WN_HIP(c, S.tdev.grow((size_t)((nslots + 31) / 32) * WN_SL_STRIDE));
+        if (c->gin > 0) WN_HIP(c, S.gbias.grow((size_t)c->L * nslots * c->G));
+        S.s.assign(nslots, wn_ctx::WnSlots::Slot());
+        S.ph = std::make_shared<wn_ctx::WnSlots::PushHost>(nslots);
+        S.cap_slots = nslots;
+    }
     WN_HIP(c, S.cbt.reserve((size_t)c->NT * c->C));
     WN_HIP(c, S.feat.reserve((size_t)c->NT * c->C));
     WN_HIP(c, S.carry.reserve(32));
-    WN_HIP(c, S.tdev.reserve(128));
-    if (c->gin > 0) WN_HIP(c, S.gbias.reserve((size_t)c->L * nb * c->G));
     // folded synthesis: whole utterances of up to max_batch x max_time samples in all, the rows' samples / teacher-forcing inputs, the fade tables
     WN_HIP(c, S.fwin.reserve((size_t)c->C * (c->NT / c->hop + 1)));
     WN_HIP(c, S.frow.reserve((size_t)c->NT));
@@ -873,26 +888,37 @@ int wn_slots_alloc(wn_ctx* c) {
     return WN_OK;
 }
 
-extern "C" int wn_synth_slots_begin(wn_ctx* c, int32_t B, int32_t steps_per_graph, void* stream) {
-    if (!c) return WN_E_ARG;
-    WnRange range("wn_synth_slots_begin");
+// both begins: `wide` opens the session on the wide owner of the launch-per-layer path (any B <= max_batch), else on the path of wn_synthesize(steps_per_graph) for B <= 32
+static int slots_begin(wn_ctx* c, const char* who, int B, int steps_per_graph, hipStream_t st, bool wide) {
     auto& S = c->slots;
-    S.open = false; c->strm.open = false;                 // a slot session and a stream exclude one another
-    if (c->cfg.compute_dtype == WN_COMPUTE_F32) WN_FAIL(c, WN_E_UNSUPPORTED, "wn_synth_slots_begin: slot sessions are not built for the fp32 validation mode (compute_dtype = WN_COMPUTE_F32)");
-    if (!c->packed) WN_FAIL(c, WN_E_STATE, "wn_pack_weights must be called before wn_synth_slots_begin");
-    if (B <= 0 || B > 32 || B > c->maxB) WN_FAIL(c, WN_E_SHAPE, "slot count %d outside (0, min(32, max_batch = %d)]", B, c->maxB);
+    S.open = false; c->strm.open = false;                 // a slot session and a stream exclude one another; one session at a time, narrow or wide
+    if (c->cfg.compute_dtype == WN_COMPUTE_F32) WN_FAIL(c, WN_E_UNSUPPORTED, "%s: slot sessions are not built for the fp32 validation mode (compute_dtype = WN_COMPUTE_F32)", who);
+    if (!c->packed) WN_FAIL(c, WN_E_STATE, "wn_pack_weights must be called before %s", who);
+    if (wide) { if (B <= 0 || B > c->maxB) WN_FAIL(c, WN_E_SHAPE, "wide slot count %d outside (0, max_batch = %d]", B, c->maxB); }
+    else if (B <= 0 || B > 32 || B > c->maxB) WN_FAIL(c, WN_E_SHAPE, "slot count %d outside (0, min(32, max_batch = %d)]", B, c->maxB);
     int rc = wn_pipe_check(c, false);
     if (rc) return rc;
-    const int path = wn_synth_takes_pipe(c, B, steps_per_graph) ? 2 : 1;
+    const int path = !wide && wn_synth_takes_pipe(c, B, steps_per_graph) ? 2 : 1;
     if ((rc = wn_noise_reserve(c, B, c->maxT))) return rc;
-    if ((rc = path == 2 ? wn_pipe_reserve(c, B, c->maxT) : wn_synth_reserve(c))) return rc;
-    if ((rc = wn_slots_alloc(c))) return rc;
+    if ((rc = wide ? wn_synth_wide_reserve(c, B) : path == 2 ? wn_pipe_reserve(c, B, c->maxT) : wn_synth_reserve(c))) return rc;
+    if ((rc = wn_slots_alloc(c, B))) return rc;
     wn_synth_stream_lookahead(&c->cfg, &S.left, &S.right);
-    WN_HIP(c, hipMemsetAsync(S.tdev, 0, 128 * 4, (hipStream_t)stream));
-    S.B = B; S.spg = steps_per_graph; S.path = path; S.poisoned = false; S.first_run = true;
+    WN_HIP(c, hipMemsetAsync(S.tdev, 0, (size_t)((B + 31) / 32) * WN_SL_STRIDE * 4, st));
+    S.B = B; S.spg = steps_per_graph; S.path = path; S.wide = wide; S.poisoned = false; S.first_run = true;
     for (auto& s : S.s) s = wn_ctx::WnSlots::Slot();
     S.open = true;
     return WN_OK;
+}
+extern "C" int wn_synth_slots_begin(wn_ctx* c, int32_t B, int32_t steps_per_graph, void* stream) {
+    if (!c) return WN_E_ARG;
+    WnRange range("wn_synth_slots_begin");
+    return slots_begin(c, "wn_synth_slots_begin", B, steps_per_graph, (hipStream_t)stream, false);
+}
+// The same session for any 0 < B <= max_batch, always on the launch-per-layer path: ceil(B / 32) tiles of slots per launch on the wide owner (wn_synth.hip)
+extern "C" int wn_synth_wide_slots_begin(wn_ctx* c, int32_t B, int32_t steps_per_graph, void* stream) {
+    if (!c) return WN_E_ARG;
+    WnRange range("wn_synth_wide_slots_begin");
+    return slots_begin(c, "wn_synth_wide_slots_begin", B, steps_per_graph, (hipStream_t)stream, true);
 }
 
 static int slots_usable(wn_ctx* c, const char* who) {
@@ -950,20 +976,23 @@ extern "C" int wn_synth_slots_end(wn_ctx* c) {
     return WN_OK;
 }
 
-// every rebuilt slot's pending window in ONE launch: [C][w] dense = the kept columns of its previous window + its leading frames of the pushed block
+// every rebuilt slot's pending window of a tile of 32 slots (b0 + blockIdx.y) in ONE launch: [C][w] dense = the kept columns of its previous window + its
+// leading frames of the pushed block
 struct WnSlotWin { int32_t prev_cols[32], drop[32], keep[32], w[32], cur[32]; };
 __global__ void wn_slots_window_kernel(const float* __restrict__ p0, const float* __restrict__ p1, float* __restrict__ q0, float* __restrict__ q1, int64_t region,
-                                       const float* __restrict__ cnew, int Tn, int C, WnSlotWin p) {
-    const int b = blockIdx.y, w = p.w[b];
+                                       const float* __restrict__ cnew, int Tn, int C, WnSlotWin p, int b0) {
+    const int k = blockIdx.y, w = p.w[k];
+    const int64_t b = (int64_t)b0 + k;
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (w <= 0 || i >= (int64_t)C * w) return;
     const int64_t row = i / w, col = i - row * w;
-    const float* prev = (p.cur[b] ? p1 : p0) + region * b;
-    float* win = (p.cur[b] ? q0 : q1) + region * b;
-    win[i] = col < p.keep[b] ? prev[row * p.prev_cols[b] + p.drop[b] + col] : cnew[((int64_t)b * C + row) * Tn + (col - p.keep[b])];
+    const float* prev = (p.cur[k] ? p1 : p0) + region * b;
+    float* win = (p.cur[k] ? q0 : q1) + region * b;
+    win[i] = col < p.keep[k] ? prev[row * p.prev_cols[k] + p.drop[k] + col] : cnew[(b * C + row) * Tn + (col - p.keep[k])];
 }
 // the windows of a group of slots side by side [g][C][w] (the upsample net takes a batch of equal width), and back: the rows of every member's span out of
-// the group's upsampled conditioning into the session's table cbt [B][n_max][C] (bf16) / feat [B][C][n_max] (fp32)
+// the group's upsampled conditioning into the session's table cbt [B][n_max][C] (bf16) / feat [B][C][n_max] (fp32).  slot[]: the members' slots of the
+// SESSION (any tile), so a group needs no slot base
 struct WnSlotGrp { int32_t slot[32], cur[32], off[32], n[32]; };
 __global__ void wn_slots_gather_kernel(const float* __restrict__ p0, const float* __restrict__ p1, int64_t region, float* __restrict__ gwin, int64_t cw, WnSlotGrp p) {
     const int g = blockIdx.y;
@@ -991,11 +1020,12 @@ extern "C" int wn_synth_slots_push(wn_ctx* c, const float* cc, int32_t Tn, const
     if ((rc = wn_pipe_check(c, false))) return rc;       // a failed earlier push surfaces here at the latest (and poisons the session)
     if (S.poisoned) WN_FAIL(c, WN_E_STATE, "wn_synth_slots_push: a pipeline run of this session failed; begin a new session");
     const int B = S.B, hop = c->hop, C = c->C;
-    // ---- plan (host only: a rejected push leaves every slot as it was)
-    WnPushPlan pl[32] = {}; int64_t w[32]; int nb[32]; int n_max = 0;
+    // ---- plan (host only: a rejected push leaves every slot as it was).  The arrays of a push hold one entry per slot and belong to the session.
+    auto& H = *S.ph;
+    WnPushPlan* const pl = H.pl.data(); int64_t* const w = H.w.data(); int* const nb = H.nb.data(); int n_max = 0;
     for (int b = 0; b < B; ++b) {
         const auto& s = S.s[b];
-        nb[b] = 0; w[b] = 0;
+        nb[b] = 0; w[b] = 0; pl[b] = WnPushPlan();
         if (frames[b] < 0 || frames[b] > Tn) WN_FAIL(c, WN_E_ARG, "wn_synth_slots_push: frames[%d] = %d outside [0, Tn = %d]", b, frames[b], Tn);
         if (!s.live) { if (frames[b] > 0) WN_FAIL(c, WN_E_STATE, "wn_synth_slots_push: %d frames for slot %d, which is idle (wn_synth_slot_open first)", frames[b], b); continue; }
         char who[40]; snprintf(who, sizeof who, "wn_synth_slots_push: slot %d", b);
@@ -1010,24 +1040,27 @@ extern "C" int wn_synth_slots_push(wn_ctx* c, const float* cc, int32_t Tn, const
     const int64_t region = (int64_t)C * S.capw;
     S.poisoned = true;                                    // (the state advances only once everything is enqueued; a failure after the first enqueue poisons the session)
     // ---- pending windows of the slots that received frames or dropped generated ones
-    bool rebuilt[32] = {};
-    {
+    uint8_t* const rebuilt = H.rebuilt.data();
+    for (int b0 = 0; b0 < B; b0 += 32) {      // (the parameters travel by value: one launch per tile of 32 slots that has a window to rebuild)
+        const int nbt = std::min(32, B - b0);
         WnSlotWin p; memset(&p, 0, sizeof p); int64_t wmax = 0;
-        for (int b = 0; b < B; ++b) {
+        for (int k = 0; k < nbt; ++k) {
+            const int b = b0 + k;
             const WnUtt& u = S.s[b].u; const int64_t wstart = pl[b].wstart;
+            rebuilt[b] = 0;
             if (!S.s[b].live || w[b] <= 0 || (frames[b] == 0 && wstart == u.pend_first)) continue;
-            p.prev_cols[b] = (int)(u.pushed - u.pend_first); p.drop[b] = (int)(wstart - u.pend_first); p.keep[b] = (int)(u.pushed - wstart); p.w[b] = (int)w[b]; p.cur[b] = u.cur;
-            rebuilt[b] = true; wmax = std::max(wmax, w[b]);
+            p.prev_cols[k] = (int)(u.pushed - u.pend_first); p.drop[k] = (int)(wstart - u.pend_first); p.keep[k] = (int)(u.pushed - wstart); p.w[k] = (int)w[b]; p.cur[k] = u.cur;
+            rebuilt[b] = 1; wmax = std::max(wmax, w[b]);
         }
         if (wmax > 0) {
-            hipLaunchKernelGGL(wn_slots_window_kernel, dim3(cdiv(C * wmax, 256), B), dim3(256), 0, st, S.pend[0], S.pend[1], S.pend[0], S.pend[1], region, cc, Tn, C, p);
+            hipLaunchKernelGGL(wn_slots_window_kernel, dim3(cdiv(C * wmax, 256), nbt), dim3(256), 0, st, S.pend[0], S.pend[1], S.pend[0], S.pend[1], region, cc, Tn, C, p, b0);
             WN_LAUNCH_CHECK(c);
         }
     }
     if (n_max > 0) {
         // ---- conditioning (wavenet.py:781-803): slots of equal window width are upsampled as one batch; every window starts at its utterance's own frame
         // max(0, done - left) and ends at its own last pushed frame, so an edge is either the utterance's own or outside what the lookahead lets a span read
-        bool grouped[32] = {};
+        uint8_t* const grouped = H.grouped.data(); memset(grouped, 0, (size_t)B);
         for (int b0 = 0; b0 < B; ++b0) {
             if (nb[b0] <= 0 || grouped[b0]) continue;
             const int64_t gw = w[b0];
@@ -1035,7 +1068,7 @@ extern "C" int wn_synth_slots_push(wn_ctx* c, const float* cc, int32_t Tn, const
             WnSlotGrp g; memset(&g, 0, sizeof g); int ng = 0; int nmaxg = 0;
             for (int b = b0; b < B && ng < gcap; ++b) {
                 if (nb[b] <= 0 || grouped[b] || w[b] != gw) continue;
-                grouped[b] = true;
+                grouped[b] = 1;
                 g.slot[ng] = b; g.cur[ng] = S.s[b].u.cur ^ (rebuilt[b] ? 1 : 0); g.off[ng] = (int)((S.s[b].u.done - pl[b].wstart) * hop); g.n[ng] = nb[b]; nmaxg = std::max(nmaxg, nb[b]); ++ng;
             }
             hipLaunchKernelGGL(wn_slots_gather_kernel, dim3(cdiv(C * gw, 256), ng), dim3(256), 0, st, S.pend[0], S.pend[1], region, S.gwin, C * gw, g);
@@ -1045,10 +1078,10 @@ extern "C" int wn_synth_slots_push(wn_ctx* c, const float* cc, int32_t Tn, const
                                (int64_t)n_max, g);
             WN_LAUNCH_CHECK(c);
         }
-        float ts[32], tsel[32]; bool tempered = false;      // every slot's own pair; rows of slots that do not generate are ignored
+        float* const ts = H.ts.data(); float* const tsel = H.tsel.data(); bool tempered = false;      // every slot's own pair; rows of slots that do not generate are ignored
         for (int b = 0; b < B; ++b) { ts[b] = S.s[b].tau_scale; tsel[b] = S.s[b].tau_select; tempered |= nb[b] > 0 && (ts[b] != 1.0f || tsel[b] != 1.0f); }
         if (!noise) {      // every generating slot's own one-stream noise, continued at its sample done * hop
-            uint64_t seed[32]; int64_t first[32], cnt[32]; const int nps = wn_noise_per_step(c);
+            uint64_t* const seed = H.seed.data(); int64_t* const first = H.first.data(); int64_t* const cnt = H.cnt.data(); const int nps = wn_noise_per_step(c);
             for (int b = 0; b < B; ++b) { seed[b] = S.s[b].seed; first[b] = S.s[b].u.done * hop * nps; cnt[b] = (int64_t)nb[b] * nps; }
             if ((rc = wn_fill_noise_slots(c, c->noise_buf, B, seed, first, cnt, ts, tsel, st))) return rc;
             noise = c->noise_buf;
@@ -1056,12 +1089,15 @@ extern "C" int wn_synth_slots_push(wn_ctx* c, const float* cc, int32_t Tn, const
             if ((rc = wn_temper_noise_cols(c, noise, c->noise_buf, B, n_max, ts, tsel, st))) return rc;
             noise = c->noise_buf;
         }
-        int32_t st0[32], snl[32]; uint32_t fresh = 0;
-        for (int b = 0; b < 32; ++b) { st0[b] = b < B ? (int)(S.s[b].u.done * hop) : 0; snl[b] = b < B ? nb[b] : 0; if (b < B && nb[b] > 0 && S.s[b].u.done == 0) fresh |= 1u << b; }
+        int32_t* const st0 = H.st0.data(); int32_t* const snl = H.snl.data(); uint32_t* const fresh = H.fresh.data();      // (padded to whole tiles of 32)
+        const int Bp = 32 * ((B + 31) / 32);
+        for (int k = 0; 32 * k < Bp; ++k) fresh[k] = 0;
+        for (int b = 0; b < Bp; ++b) { st0[b] = b < B ? (int)(S.s[b].u.done * hop) : 0; snl[b] = b < B ? nb[b] : 0; if (b < B && nb[b] > 0 && S.s[b].u.done == 0) fresh[b >> 5] |= 1u << (b & 31); }
         WnSpan sp;
         sp.t0 = 0; sp.Tcb = n_max; sp.cbt_off = 0; sp.carry = S.carry; sp.gbias = S.gbias;
         sp.st0 = st0; sp.snl = snl; sp.out_pitch = out_pitch; sp.cbt = S.cbt; sp.reslice = S.first_run; sp.tdev = S.tdev; sp.fresh = fresh;
-        rc = S.path == 2 ? wn_pipe_span(c, B, n_max, sp, noise, test_inputs, out_samples, out_raw, st)
+        rc = S.wide ? wn_synth_wide_span(c, B, n_max, sp, noise, test_inputs, out_samples, out_raw, S.spg, st)
+           : S.path == 2 ? wn_pipe_span(c, B, n_max, sp, noise, test_inputs, out_samples, out_raw, st)
                          : wn_synth_span(c, B, n_max, sp, noise, test_inputs, out_samples, out_raw, S.spg, st);
         if (rc) return rc;
         S.first_run = false;

@@ -222,16 +222,21 @@ struct wn_ctx {
     // synthesis slots (wn_synth_slots_*): B slots served by one pipeline configuration; every slot is idle or carries ONE utterance with its own
     // time origin, seed, global condition and pending window of mel frames ([C][pushed - pend_first] dense, in the slot's region of pend[cur]).
     // Everything the session needs is sized by slots_alloc (wn_create on inference-only contexts): nothing is allocated by a push.
+    // A wide session (wn_synth_wide_slots_begin: `wide`, any B <= max_batch, the wide owner of the launch-per-layer path) is the same state with tables of
+    // cap_slots >= B entries; the per-slot host records and the host arrays of a push live here too, so that a push allocates nothing on the host either.
     struct WnSlots {
-        bool open = false, poisoned = false; int path = 0, B = 0, spg = 0, left = 0, right = 0, capw = 0; bool first_run = true;
-        struct Slot { bool live = false; uint64_t seed = 0; WnUtt u; float tau_scale = 1.0f, tau_select = 1.0f; } s[32];      // (the pair: copied from the context at wn_synth_slot_open)
-        DevBuf<float> pend[2];                    // [32 regions][C * capw] pending frames of every slot (ping-pong per slot)
+        bool open = false, poisoned = false, wide = false; int path = 0, B = 0, spg = 0, left = 0, right = 0, capw = 0, cap_slots = 0; bool first_run = true;
+        struct Slot { bool live = false; uint64_t seed = 0; WnUtt u; float tau_scale = 1.0f, tau_select = 1.0f; };      // (the pair: copied from the context at wn_synth_slot_open)
+        std::vector<Slot> s;                      // [cap_slots]
+        struct PushHost;                          // host arrays of one push, cap_slots long (wn_api.hip)
+        std::shared_ptr<PushHost> ph;
+        DevBuf<float> pend[2];                    // [cap_slots regions][C * capw] pending frames of every slot (ping-pong per slot)
         DevBuf<float> gwin;                       // [group][C][w]: the windows of the slots upsampled together (equal window width)
         DevBuf<bf16_t> cbt;                       // [B][n_max][C]: the conditioning rows every slot's steps of this push read
         DevBuf<float> feat;                       // [B][C][n_max] fp32: the same rows as wn_get_upsampled_features returns them
         DevBuf<float> gbias;                      // [L][B][G] gate-bias row of every slot (gin > 0), written at wn_synth_slot_open
         DevBuf<int32_t> carry;                    // [32] the pipeline's carried next input per slot
-        DevBuf<int32_t> tdev;                     // launch-per-layer path: [0..31] absolute index of every slot's next sample, [32..63] samples it generates in this push, [64] push-local step
+        DevBuf<int32_t> tdev;                     // launch-per-layer path, one block of WN_SL_STRIDE per tile of 32 slots: [0..31] absolute index of every slot's next sample, [32..63] samples it generates in this push, [64] push-local step
         int64_t feat_pitch = 0; int feat_B = 0;
         // folded synthesis (wn_synthesize_folded, wn_fold.hip) runs ONE slot-form span on the tables above; its own scratch, sized with them:
         DevBuf<float> fwin;                       // [group][C][F]: the whole utterances of equal length that are upsampled together
@@ -244,7 +249,7 @@ struct wn_ctx {
     // streams these states own are synchronised and destroyed before any buffer above that their work may still read is freed.
     std::unique_ptr<F32State, WnStateDelete> f32;         // fp32-forward state (wn_f32.hip), built by the first forward of a cfg.compute_dtype = WN_COMPUTE_F32 context
     std::unique_ptr<Synth, WnStateDelete> synth;          // launch-per-layer synthesis (wn_synth.hip): runs of <= 32 streams, streams, slot sessions
-    std::unique_ptr<Synth, WnStateDelete> wide;           // the same for wide runs (wn_synthesize_wide): queues and scratch of 32 * ceil(B / 32) streams, its own runner
+    std::unique_ptr<Synth, WnStateDelete> wide;           // the same for wide runs (wn_synthesize_wide) and wide slot sessions: queues and scratch of 32 * ceil(B / 32) streams, its own runner
     std::unique_ptr<SynthF32, WnStateDelete> synth32;     // fp32 synthesis (wn_synth_f32.hip; cfg.compute_dtype = WN_COMPUTE_F32)
     std::unique_ptr<Pipe, WnStateDelete> pipe;            // persistent synthesis pipeline (wn_synth_pipe.hip)
 };
@@ -256,8 +261,10 @@ struct wn_ctx {
 // own table [B][Tcb][C]; reslice: first run of the session (the pipeline builds its weight images)
 // A whole utterance (wn_synthesize) is the span t0 = 0, cbt_off = 0, Tcb = T, carry = nullptr, gbias = ctx->gbias with `whole` set: not a push, so a
 // failed run of it poisons no stream or session that is opened afterwards (wn_pipe_check)
+// st0 / snl hold one entry per stream, padded with zeros to a multiple of 32; fresh one mask per tile of 32 streams (bit n: stream 32 * tile + n starts an utterance)
+#define WN_SL_STRIDE 128      // entries of one tile's block of the session table tdev (wn_synth.hip)
 struct WnSpan { int t0, Tcb, cbt_off; int32_t* carry; const float* gbias; bool whole = false;
-                const int32_t* st0 = nullptr; const int32_t* snl = nullptr; int out_pitch = 0; const bf16_t* cbt = nullptr; bool reslice = false; int32_t* tdev = nullptr; uint32_t fresh = 0; };
+                const int32_t* st0 = nullptr; const int32_t* snl = nullptr; int out_pitch = 0; const bf16_t* cbt = nullptr; bool reslice = false; int32_t* tdev = nullptr; const uint32_t* fresh = nullptr; };
 
 extern std::string g_create_err;
 
@@ -312,11 +319,11 @@ int wn_pipe_span(wn_ctx* ctx, int B, int T, const WnSpan& sp, const float* noise
 int wn_fill_noise_span(wn_ctx* ctx, float* noise, int64_t first, int64_t n, uint64_t seed, float tau_scale, float tau_select, hipStream_t st);   // elements [first, first + n) of the flat stream
 // column b of noise [n_max][B][nps] = elements [first[b], first[b] + cnt[b]) of the ONE-stream noise of seed[b] (wn_fill_noise(B = 1)), every b with cnt[b] > 0 in one launch
 int wn_fill_noise_slots(wn_ctx* ctx, float* noise, int B, const uint64_t* seed, const int64_t* first, const int64_t* cnt, const float* tau_scale, const float* tau_select, hipStream_t st);
-// caller noise in [T][B][nps] tempered into out (in == out allowed): one pair, or column b by ITS pair (tau_scale[b], tau_select[b]), B <= 32
+// caller noise in [T][B][nps] tempered into out (in == out allowed): one pair, or column b by ITS pair (tau_scale[b], tau_select[b])
 int wn_temper_noise_impl(wn_ctx* ctx, const float* in, float* out, int B, int T, float tau_scale, float tau_select, hipStream_t st);
 int wn_temper_noise_cols(wn_ctx* ctx, const float* in, float* out, int B, int T, const float* tau_scale, const float* tau_select, hipStream_t st);
 int wn_gbias_row(wn_ctx* ctx, const void* g_dev, float* table, int B, int slot, hipStream_t st);      // one slot's gate-bias row into table [L][B][G]
-int wn_slots_alloc(wn_ctx* ctx);                           // tables of a slot session / a folded run, sized for (max_batch, max_time) (wn_create on inference-only contexts)
+int wn_slots_alloc(wn_ctx* ctx, int nslots);               // tables of a slot session of nslots slots / a folded run, sized for (nslots, max_time) (wn_create on inference-only contexts; a training context grows them)
 int wn_synth_f32_reserve(wn_ctx* ctx, int B);
 bool wn_pipe_eligible(const wn_ctx* ctx, int B);
 int wn_pipe_reserve(wn_ctx* ctx, int B, int T);            // size every pipeline buffer for (B, T) (no-op when already large enough)

@@ -229,7 +229,7 @@ extern "C" int wn_synthesize_folded(wn_ctx* c, const float* cc, const int32_t* u
     const int path = wn_synth_takes_pipe(c, n_rows, steps_per_graph) ? 2 : 1;
     if ((rc = wn_noise_reserve(c, n_rows, (int)n_max))) return rc;
     if ((rc = path == 2 ? wn_pipe_reserve(c, n_rows, c->maxT) : wn_synth_reserve(c))) return rc;
-    if ((rc = wn_slots_alloc(c))) return rc;
+    if ((rc = wn_slots_alloc(c, std::min(32, c->maxB)))) return rc;
     // ---- fade tables: one per distinct fade length (sum of the fades <= n_rows x n_max <= what fw holds)
     WnUnfold uf; memset(&uf, 0, sizeof uf);
     {
@@ -302,7 +302,8 @@ extern "C" int wn_synthesize_folded(wn_ctx* c, const float* cc, const int32_t* u
         WnSpan sp;
         sp.t0 = 0; sp.Tcb = (int)n_max; sp.cbt_off = 0; sp.carry = S.carry; sp.gbias = S.gbias; sp.whole = true;
         sp.st0 = st0; sp.snl = snl; sp.out_pitch = (int)pitch; sp.cbt = S.cbt; sp.reslice = true; sp.tdev = S.tdev;
-        sp.fresh = n_rows == 32 ? 0xffffffffu : ((1u << n_rows) - 1u);
+        const uint32_t fresh = n_rows == 32 ? 0xffffffffu : ((1u << n_rows) - 1u);
+        sp.fresh = &fresh;
         rc = path == 2 ? wn_pipe_span(c, n_rows, (int)n_max, sp, noise, ti_rows, row_buf, out_raw, st)
                        : wn_synth_span(c, n_rows, (int)n_max, sp, noise, ti_rows, row_buf, out_raw, steps_per_graph, st);
         if (rc) return rc;

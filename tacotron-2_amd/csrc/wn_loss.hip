@@ -509,16 +509,16 @@ int wn_fill_noise_span(wn_ctx* c, float* noise, int64_t first, int64_t n, uint64
 // Slot sessions: every slot draws from ITS OWN one-stream noise (seed_b, element t_local * nps + j: exactly wn_fill_noise(B = 1, seed_b)), written into column b of
 // the push's [n_max][B][nps] buffer.  Thread (x, b) evaluates one whole Philox group of slot b's stream -- Box-Muller pairs follow the one-stream numbering, not
 // the batch layout -- and keeps the elements of the span [first_b, first_b + cnt_b).  Slots that generate nothing (cnt 0) leave their column as it is.
-// Every slot's entries are tempered by the slot's own pair.
+// Every slot's entries are tempered by the slot's own pair.  One launch serves a tile of <= 32 slots, the columns b0 + blockIdx.y (the parameters travel by value).
 struct WnNoiseSlots { uint32_t k0[32], k1[32]; int64_t first[32], cnt[32]; float tau_scale[32], tau_select[32]; };
-__global__ void wn_noise_slots_kernel(float* __restrict__ out, int B, int nps, int mode, WnNoiseSlots p) {
-    const int b = blockIdx.y;
-    const int64_t first = p.first[b], n = p.cnt[b];
+__global__ void wn_noise_slots_kernel(float* __restrict__ out, int B, int nps, int mode, WnNoiseSlots p, int b0) {
+    const int i = blockIdx.y, b = b0 + i;
+    const int64_t first = p.first[i], n = p.cnt[i];
     const int64_t g = first / 4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (n <= 0 || g * 4 >= first + n) return;
     float v[4];
-    wn_noise_group(g, p.k0[b], p.k1[b], mode == 1, v);
-    const float ts = p.tau_scale[b], tsel = p.tau_select[b];
+    wn_noise_group(g, p.k0[i], p.k1[i], mode == 1, v);
+    const float ts = p.tau_scale[i], tsel = p.tau_select[i];
     for (int j = 0; j < 4; ++j) {
         const int64_t e = g * 4 + j;
         if (e < first || e >= first + n) continue;
@@ -527,15 +527,19 @@ __global__ void wn_noise_slots_kernel(float* __restrict__ out, int B, int nps, i
     }
 }
 int wn_fill_noise_slots(wn_ctx* c, float* noise, int B, const uint64_t* seed, const int64_t* first, const int64_t* cnt, const float* tau_scale, const float* tau_select, hipStream_t st) {
-    WnNoiseSlots p; memset(&p, 0, sizeof p);
-    int64_t groups = 0;
-    for (int b = 0; b < B; ++b) {
-        p.k0[b] = (uint32_t)seed[b]; p.k1[b] = (uint32_t)(seed[b] >> 32); p.first[b] = first[b]; p.cnt[b] = cnt[b]; p.tau_scale[b] = tau_scale[b]; p.tau_select[b] = tau_select[b];
-        if (cnt[b] > 0) groups = std::max<int64_t>(groups, (first[b] + cnt[b] + 3) / 4 - first[b] / 4);
+    for (int b0 = 0; b0 < B; b0 += 32) {
+        const int nbt = std::min(32, B - b0);
+        WnNoiseSlots p; memset(&p, 0, sizeof p);
+        int64_t groups = 0;
+        for (int i = 0; i < nbt; ++i) {
+            const int b = b0 + i;
+            p.k0[i] = (uint32_t)seed[b]; p.k1[i] = (uint32_t)(seed[b] >> 32); p.first[i] = first[b]; p.cnt[i] = cnt[b]; p.tau_scale[i] = tau_scale[b]; p.tau_select[i] = tau_select[b];
+            if (cnt[b] > 0) groups = std::max<int64_t>(groups, (first[b] + cnt[b] + 3) / 4 - first[b] / 4);
+        }
+        if (groups == 0) continue;
+        hipLaunchKernelGGL(wn_noise_slots_kernel, dim3(cdiv(groups, 256), nbt), dim3(256), 0, st, noise, B, wn_noise_per_step(c), wn_sample_mode(c), p, b0);
+        WN_LAUNCH_CHECK(c);
     }
-    if (groups == 0) return WN_OK;
-    hipLaunchKernelGGL(wn_noise_slots_kernel, dim3(cdiv(groups, 256), B), dim3(256), 0, st, noise, B, wn_noise_per_step(c), wn_sample_mode(c), p);
-    WN_LAUNCH_CHECK(c);
     return WN_OK;
 }
 
@@ -573,8 +577,26 @@ int wn_temper_noise_impl(wn_ctx* c, const float* in, float* out, int B, int T, f
     p.tau_scale[0] = tau_scale; p.tau_select[0] = tau_select;
     return temper_launch(c, in, out, (int64_t)B * T * wn_noise_per_step(c), B, 0, p, st);
 }
+// more than 32 columns: the columns b0 .. b0 + nbt - 1 of every sample, one launch per tile of 32 (its pairs travel by value); element by element
+__global__ void wn_temper_tile_kernel(const float* in, float* out, int64_t T, int mode, int nps, int B, int b0, int nbt, WnTauCols p) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= T * nbt * nps) return;
+    const int64_t s = i / nps, t = s / nbt; const int q = (int)(i - s * nps), n = (int)(s - t * nbt);
+    const int64_t e = (t * B + b0 + n) * nps + q;
+    out[e] = wn_temper_entry(in[e], mode, nps, q, p.tau_scale[n], p.tau_select[n]);
+}
 int wn_temper_noise_cols(wn_ctx* c, const float* in, float* out, int B, int T, const float* tau_scale, const float* tau_select, hipStream_t st) {
     WnTauCols p; memset(&p, 0, sizeof p);
-    for (int b = 0; b < B && b < 32; ++b) { p.tau_scale[b] = tau_scale[b]; p.tau_select[b] = tau_select[b]; }
-    return temper_launch(c, in, out, (int64_t)B * T * wn_noise_per_step(c), B, 1, p, st);
+    if (B <= 32) {
+        for (int b = 0; b < B; ++b) { p.tau_scale[b] = tau_scale[b]; p.tau_select[b] = tau_select[b]; }
+        return temper_launch(c, in, out, (int64_t)B * T * wn_noise_per_step(c), B, 1, p, st);
+    }
+    const int nps = wn_noise_per_step(c);
+    for (int b0 = 0; b0 < B && T > 0; b0 += 32) {
+        const int nbt = std::min(32, B - b0);
+        for (int i = 0; i < nbt; ++i) { p.tau_scale[i] = tau_scale[b0 + i]; p.tau_select[i] = tau_select[b0 + i]; }
+        hipLaunchKernelGGL(wn_temper_tile_kernel, dim3(cdiv((int64_t)T * nbt * nps, 256)), dim3(256), 0, st, in, out, (int64_t)T, wn_sample_mode(c), nps, B, b0, nbt, p);
+        WN_LAUNCH_CHECK(c);
+    }
+    return WN_OK;
 }

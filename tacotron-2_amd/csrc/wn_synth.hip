@@ -6,7 +6,7 @@
 //     which is exactly the reference's zero-initialised queue (wavenet.py:815-816);
 //   * per step and layer two tiny MFMA contractions replace ~20 TF ops: streams are the N dimension
 //     of v_mfma_f32_32x32x16_bf16 (32 per tile; blockIdx.y is the tile: stream b = 32 * tile + (lane & 31), queue rows [slot][SB][R] with
-//     SB = 32 * tiles -- one tile for wn_synthesize, streams and slot sessions, ceil(B / 32) for wn_synthesize_wide), weights are the same fragment-ordered bf16 packs the
+//     SB = 32 * tiles -- one tile for wn_synthesize, streams and the slot sessions of up to 32 slots, ceil(B / 32) for wn_synthesize_wide and wide slot sessions), weights are the same fragment-ordered bf16 packs the
 //     training kernels use (one coalesced 1-KiB load per wave and k-step, L2-resident), the 4 waves of
 //     a workgroup split K and reduce through LDS;
 //   * the whole step (2L+3 kernels) is captured once into a hipGraph of `steps_per_graph` steps; all
@@ -16,7 +16,7 @@
 #include "wn_steps.h"
 #include <stdlib.h>
 
-// One owner of this kind serves the runs of up to 32 streams (wn_ctx::synth: SB = 32, one tile), a second one the wide runs (wn_ctx::wide: SB = 32 * tiles),
+// One owner of this kind serves the runs of up to 32 streams (wn_ctx::synth: SB = 32, one tile), a second one the wide runs and wide slot sessions (wn_ctx::wide: SB = 32 * tiles),
 // each with its own runner, so that neither evicts the other's captured graph.
 struct Synth {
     int B = 0, T = 0;
@@ -30,13 +30,17 @@ struct Synth {
     DevBuf<int32_t> t_dev;         // [0] absolute time index of the next step, [1] first sample of the running span (0 for wn_synthesize; a stream push: its t0),
                                    // [1 + k] the sampler's own copy of [0] for tile k > 0
     WnStepRunner run;              // the ctx-owned stream the steps run on, the step graph and its key
-    // slot sessions: sl != nullptr while a push of a session is enqueued -- [0..31] absolute index of every stream's next sample, [32..63] samples it generates
-    // in this push, [64] push-local step.  A stream whose count is used up (or an idle slot) is a dummy for the rest of the push: its operand columns are
-    // zero, nothing of it is stored.  Values live in device memory, so captured graphs stay valid across pushes.
+    // slot sessions: sl != nullptr while a push of a session is enqueued -- one block of WN_SL_STRIDE entries per tile of 32 streams (tile k: sl + k * WN_SL_STRIDE),
+    // in it [0..31] absolute index of every stream's next sample, [32..63] samples it generates in this push, [64] push-local step.  A stream whose count is
+    // used up (or an idle slot) is a dummy for the rest of the push: its operand columns are zero, nothing of it is stored; a tile without a live slot runs
+    // as dummies only.  Values live in device memory, so captured graphs stay valid across pushes.
     const int32_t* sl = nullptr;
 };
 #define WN_SL_N 32
 #define WN_SL_STEP 64
+// The block of this workgroup's tile.  Every tile keeps and advances its OWN push-local step (the hazard wn_synth_sample documents for t_dev: a block of
+// tile k may start after tile 0's sampler stored the incremented step), so no kernel reads another tile's block.  ONE: tile 0, a compile-time fact.
+template <bool ONE> __device__ __forceinline__ const int32_t* wn_sl_tile(const int32_t* sl) { return (ONE || !sl) ? sl : sl + (size_t)blockIdx.y * WN_SL_STRIDE; }
 
 __device__ __forceinline__ f32x16_t zero16() { f32x16_t z; for (int i = 0; i < 16; ++i) z[i] = 0.0f; return z; }
 
@@ -53,14 +57,16 @@ __device__ __forceinline__ float acc_at(const float* red, int wave_stride, int n
 // one L2 round trip per pass instead of one per k-step).  C5 width (G = 1024, K = 1616): 834 -> see profiles/ (DESIGN 3.4).
 #define WN_SYN_MAXK 8
 // ---- stage A: z = [W_dil | W_cin] [x(t-2d); x(t-d); x(t); c_t] + b  -> tanh * sigmoid -> u    (modules.py:273-303, 494-510)
-// ONE: the launch has one tile of queue rows of 32 streams (every run of <= 32 streams, every slot session): tile index and row stride are compile-time
+// ONE: the launch has one tile of queue rows of 32 streams (every run of <= 32 streams, every slot session of <= 32 slots): tile index, row stride and the
+// tile's block of the session table are compile-time
 // constants of the same kernel, which then is the kernel of before the tile index (measured: profiles/wide_timing.json -> existing_path)
 template <int NW, bool ONE>
 __global__ __launch_bounds__(NW * 64) void wn_synth_gate(const bf16_t* __restrict__ Apk, int ksteps, const bf16_t* __restrict__ ring, int mask,
                                                      int d, int R, const bf16_t* __restrict__ cbt, int C, int Tcb, int B,
                                                      const float* __restrict__ bias, int bias_bstride, int GH, bf16_t* __restrict__ ucur,
-                                                     const int32_t* __restrict__ t_dev, int kil, const int32_t* __restrict__ sl, int SBa) {
+                                                     const int32_t* __restrict__ t_dev, int kil, const int32_t* __restrict__ sla, int SBa) {
     __shared__ float red[NW * 2 * 64 * 16];
+    const int32_t* const sl = wn_sl_tile<ONE>(sla);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n = lane & 31, h = lane >> 5;
     const int SB = ONE ? 32 : SBa, b0 = ONE ? 0 : 32 * (int)blockIdx.y, b = b0 + n;      // streams per queue row; the tile's first stream, this lane's stream
@@ -126,8 +132,9 @@ __global__ __launch_bounds__(NW * 64) void wn_synth_out(const bf16_t* __restrict
                                                     const bf16_t* __restrict__ ring_cur, int mask_cur,
                                                     bf16_t* __restrict__ ring_next, int mask_next,
                                                     float* __restrict__ skip_acc, int first_layer, int B,
-                                                    const int32_t* __restrict__ t_dev, const int32_t* __restrict__ sl, int SBa) {
+                                                    const int32_t* __restrict__ t_dev, const int32_t* __restrict__ sla, int SBa) {
     __shared__ float red[NW * 64 * 16];
+    const int32_t* const sl = wn_sl_tile<ONE>(sla);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int t0_ = sl ? 0 : *t_dev;
     const int n = lane & 31, h = lane >> 5;
@@ -245,7 +252,8 @@ __global__ __launch_bounds__(256) void wn_synth_sample(const float* __restrict__
                                                        const float* __restrict__ noise, const void* __restrict__ test_inputs,
                                                        void* __restrict__ out_samples, float* __restrict__ out_raw,
                                                        const float* __restrict__ Wf, const float* __restrict__ bf_, int R,
-                                                       bf16_t* __restrict__ ring0, int mask0, int B, int T, int32_t* __restrict__ t_dev, int32_t* __restrict__ sl, int SBa) {
+                                                       bf16_t* __restrict__ ring0, int mask0, int B, int T, int32_t* __restrict__ t_dev, int32_t* __restrict__ sla, int SBa) {
+    int32_t* const sl = const_cast<int32_t*>(wn_sl_tile<ONE>(sla));
     __shared__ float nxt_f[32];
     __shared__ int nxt_i[32];
     __shared__ int t_n[32];
@@ -287,14 +295,15 @@ __global__ __launch_bounds__(256) void wn_synth_sample(const float* __restrict__
 
 // a push of a slot session: the samples every stream generates, the push-local step, and for the slots opened with this push (bit n of `fresh`) the
 // input of their first step (silence) in ring 0 at THEIR index 0.  Nothing is cleared: a tap is valid iff t_n - k d >= 0, rows of an earlier occupant are unreachable.
+// One launch serves ONE tile: its B <= 32 slots are the streams b0 .. b0 + B - 1 of the queue rows, `sl` is the tile's block, `fresh` and `cnt` are the tile's.
 struct WnSlCounts { int32_t n[32]; };
 __global__ void wn_synth_slots_setup(const float* __restrict__ Wf, const float* __restrict__ bf_, int R, int mode, int start_id, bf16_t* __restrict__ ring0, int B,
-                                     int32_t* __restrict__ sl, WnSlCounts cnt, uint32_t fresh) {
+                                     int32_t* __restrict__ sl, WnSlCounts cnt, uint32_t fresh, int b0) {
     for (int o = threadIdx.x; o < B * R; o += blockDim.x) {
         const int n = o / R, r = o - n * R;
         if (!((fresh >> n) & 1u)) continue;
         const float v = (mode == 2) ? Wf[(size_t)start_id * R + r] + bf_[r] : bf_[r];
-        ring0[((size_t)n) * R + r] = f2bf(v);
+        ring0[((size_t)b0 + n) * R + r] = f2bf(v);
     }
     if (threadIdx.x < 32) { sl[WN_SL_N + threadIdx.x] = threadIdx.x < B ? cnt.n[threadIdx.x] : 0; if ((fresh >> threadIdx.x) & 1u) sl[threadIdx.x] = 0; }
     if (threadIdx.x == 0) sl[WN_SL_STEP] = 0;
@@ -305,7 +314,7 @@ void WnStateDelete::operator()(Synth* s) const { delete s; }
 static int enqueue_step(wn_ctx* c, Synth* s, const bf16_t* cbt, int Tcb, const float* gbias, const float* noise, const void* test_inputs, void* out_samples,
                         float* out_raw, hipStream_t st) {
     const int L = c->L, R = c->R, GH = c->GH, S = c->S, C = c->C, B = s->B, T = s->T, SB = s->SB;
-    const unsigned tiles = (unsigned)((B + 31) / 32);      // grid.y: 32 streams each (a run of <= 32 streams, a slot session: one)
+    const unsigned tiles = (unsigned)((B + 31) / 32);      // grid.y: 32 streams each (a run or a slot session of <= 32 streams: one)
     const bool one = tiles == 1 && SB == 32;
     for (int l = 0; l < L; ++l) {
         // waves per block by the K of the launch: every wave should get its k-steps in ONE pass of <= WN_SYN_MAXK loads
@@ -423,10 +432,13 @@ static int synth_span_on(wn_ctx* c, Synth* s, int SB, int B, int T, const WnSpan
     hipStream_t st = s->run.st;
     s->B = B; s->T = sp.st0 ? sp.out_pitch : T; s->sl = nullptr;      // (T of the kernels: the row pitch of the outputs)
     if (sp.st0) {
-        WnSlCounts cnt; for (int i = 0; i < 32; ++i) cnt.n[i] = i < B ? sp.snl[i] : 0;
-        hipLaunchKernelGGL(wn_synth_slots_setup, dim3(1), dim3(256), 0, st, c->params_dev + c->first.dil_k, c->params_dev + c->first.dil_b, c->R, wn_sample_mode(c), 127,
-                           s->ring[0], B, sp.tdev, cnt, sp.fresh);
-        WN_LAUNCH_CHECK(c);
+        for (int k = 0; 32 * k < B; ++k) {      // one small launch per tile and push (the counts travel by value: 1 024 of them would not fit the kernel arguments)
+            const int b0 = 32 * k, nbt = std::min(32, B - b0);
+            WnSlCounts cnt; for (int i = 0; i < 32; ++i) cnt.n[i] = i < nbt ? sp.snl[b0 + i] : 0;
+            hipLaunchKernelGGL(wn_synth_slots_setup, dim3(1), dim3(256), 0, st, c->params_dev + c->first.dil_k, c->params_dev + c->first.dil_b, c->R, wn_sample_mode(c), 127,
+                               s->ring[0], nbt, sp.tdev + (size_t)k * WN_SL_STRIDE, cnt, sp.fresh[k], b0);
+            WN_LAUNCH_CHECK(c);
+        }
         s->sl = sp.tdev;
     } else if ((rc = wn_span_start(c, s->ring, s->mask, SB, B, s->t_dev, sp.t0, st))) return rc;
     const bf16_t* cbt = (sp.cbt ? sp.cbt : c->cbt) + (size_t)sp.cbt_off * c->C;
@@ -442,8 +454,8 @@ int wn_synth_span(wn_ctx* c, int B, int T, const WnSpan& sp, const float* noise,
     if (rc) return rc;
     return synth_span_on(c, c->synth.get(), 32, B, T, sp, noise, test_inputs, out_samples, out_raw, steps_per_graph, caller_st);
 }
-// A whole utterance of any B on the wide owner: the same steps with ceil(B / 32) tiles and queue rows of 32 * tiles streams.  (The key of the captured
-// graph carries B, which fixes both.)
+// A whole utterance, or a push of a wide slot session (sp.st0), of any B on the wide owner: the same steps with ceil(B / 32) tiles and queue rows of
+// 32 * tiles streams.  (The key of the captured graph carries B, which fixes both.)
 int wn_synth_wide_span(wn_ctx* c, int B, int T, const WnSpan& sp, const float* noise, const void* test_inputs, void* out_samples, float* out_raw,
                        int steps_per_graph, hipStream_t caller_st) {
     int rc = wn_synth_wide_reserve(c, B);

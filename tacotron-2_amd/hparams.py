@@ -92,6 +92,9 @@ MI355 = dict(
     mi355_synthesis_wide_rows=0,       # N > 0: Synthesizer.synthesize generates through WaveNet.wide: launch-per-layer runs of up to N utterances, N may exceed 32
                                        # (offline throughput: an evaluation set, GTA outputs); longest first, every run padded to its own longest.  0: off.
                                        # Not with mi355_synthesis_slots or mi355_synthesis_fold_rows
+    mi355_synthesis_wide_slots=0,      # N > 0: Synthesizer.synthesize sends all utterances of a call through ONE wide slot session (WaveNet.wide_slots) of
+                                       # min(N, utterances) slots, N may exceed 32: continuous batching on the launch-per-layer path, conditioning memory bounded by one
+                                       # push (tick = mi355_synthesis_chunk_frames or 8 frames).  0: off.  Not with the three route keys above
     mi355_synthesis_fold_warm=4,       # mel frames a segment generates and discards before the part it contributes (50 ms at hop 275)
     mi355_synthesis_fold_fade=2,       # mel frames of cross-fade between consecutive segments (25 ms); equal power
     mi355_synthesis_fold_min_frames=40,    # no segment contributes fewer new frames than this (~0.5 s): shorter utterances stay one row, i.e. the one-shot run.

@@ -158,6 +158,7 @@ def load_library():
         'wn_synth_stream_push': (ctypes.c_int, [vp, vp, i32, i32, vp, vp, vp, vp, ctypes.POINTER(i32), vp]),
         'wn_synth_stream_end': (ctypes.c_int, [vp]),
         'wn_synth_slots_begin': (ctypes.c_int, [vp, i32, i32, vp]),
+        'wn_synth_wide_slots_begin': (ctypes.c_int, [vp, i32, i32, vp]),
         'wn_synth_slot_open': (ctypes.c_int, [vp, i32, u64, vp, vp]),
         'wn_synth_slots_push': (ctypes.c_int, [vp, vp, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), vp, vp, vp, vp, i32, ctypes.POINTER(i32), vp]),
         'wn_synth_slot_abandon': (ctypes.c_int, [vp, i32]),
@@ -472,6 +473,13 @@ class Engine:
         """Open a session of B idle slots (path as synthesize(steps_per_graph) would take for B, kept for the session)."""
         self._slots_B = None
         self._ok(self.lib.wn_synth_slots_begin(self.h, int(B), int(steps_per_graph), _stream()))
+        self._slots_B = int(B)
+
+    def wide_slots_begin(self, B, steps_per_graph=0):
+        """Open a session of B idle slots for any B <= max_batch (wn_synth_wide_slots_begin): always the launch-per-layer path, ceil(B / 32) tiles of
+        slots per launch; steps_per_graph <= 0 means 32.  Every other slot call serves it as it serves slots_begin's session."""
+        self._slots_B = None
+        self._ok(self.lib.wn_synth_wide_slots_begin(self.h, int(B), int(steps_per_graph), _stream()))
         self._slots_B = int(B)
 
     def slot_open(self, slot, seed=0, g=None):

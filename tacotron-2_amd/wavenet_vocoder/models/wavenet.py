@@ -226,16 +226,17 @@ class SlotSession(object):
     """B slots served by one pipeline configuration (WaveNet.slots): every slot is idle or carries ONE utterance with its own start, seed and
     global condition; utterances are opened, fed mel frames, finished and replaced independently, and a slot's samples are bit-identical to a
     one-shot run of that utterance in the same batch row.  push() returns the samples whose conditioning is now complete, per slot, as device
-    tensors (asynchronous: nothing waits for the GPU)."""
+    tensors (asynchronous: nothing waits for the GPU).  wide: the session of WaveNet.wide_slots -- any B <= the engine's max_batch on the
+    launch-per-layer path (Engine.wide_slots_begin); everything else is the same."""
 
-    def __init__(self, model, batch, steps_per_graph=0):
-        self.model, self.B = model, int(batch)
+    def __init__(self, model, batch, steps_per_graph=0, wide=False):
+        self.model, self.B, self.wide = model, int(batch), bool(wide)
         self.lookahead = model.engine.stream_lookahead()
         self.hop = model.engine.hop
         self.done, self.pushed = [None] * self.B, [0] * self.B          # frames per live slot (None: idle)
         self._post_restart = set()                                      # slots opened since their last push: an output stage starts them from y[-1] = 0
         model._ensure_packed()
-        model.engine.slots_begin(self.B, steps_per_graph=steps_per_graph)
+        (model.engine.wide_slots_begin if self.wide else model.engine.slots_begin)(self.B, steps_per_graph=steps_per_graph)
         self.closed = False
 
     def open(self, slot, g=None, seed=None, temperature=None, mixture_temperature=None):
@@ -963,6 +964,15 @@ class WaveNet(object):
             raise RuntimeError('WaveNet.slots: call build() / initialize() first')
         spg = int(getattr(hp, 'mi355_steps_per_graph', 0)) if steps_per_graph is None else int(steps_per_graph)
         return SlotSession(self, batch, steps_per_graph=spg)
+
+    def wide_slots(self, batch, steps_per_graph=None):
+        """Open a SlotSession of any `batch` <= the engine's max_batch slots on the launch-per-layer path (Engine.wide_slots_begin): continuous
+        batching at the width of WaveNet.wide.  The conditioning is upsampled push by push, so the engine's max_time need only cover one push."""
+        hp = self._hparams
+        if self.engine is None:
+            raise RuntimeError('WaveNet.wide_slots: call build() / initialize() first')
+        spg = int(getattr(hp, 'mi355_steps_per_graph', 0)) if steps_per_graph is None else int(steps_per_graph)
+        return SlotSession(self, batch, steps_per_graph=spg, wide=True)
 
     def stream(self, batch, g=None, seed=None, steps_per_graph=None, temperature=None, mixture_temperature=None):
         """Open a SynthesisStream of `batch` utterances (<= 32, the model's engine must have been built for them).  seed None: derived as

@@ -178,7 +178,8 @@ class Synthesizer(object):
             g = torch.from_numpy(np.asarray(speaker_ids, dtype=np.int32).reshape(len(c_batch), 1))
         nfold = int(getattr(hparams, 'mi355_synthesis_fold_rows', 0))
         nwide = int(getattr(hparams, 'mi355_synthesis_wide_rows', 0))
-        routes = [key for key in ('mi355_synthesis_fold_rows', 'mi355_synthesis_slots', 'mi355_synthesis_wide_rows') if int(getattr(hparams, key, 0)) > 0]
+        routes = [key for key in ('mi355_synthesis_fold_rows', 'mi355_synthesis_slots', 'mi355_synthesis_wide_rows', 'mi355_synthesis_wide_slots')
+                  if int(getattr(hparams, key, 0)) > 0]
         if len(routes) > 1:
             raise ValueError('{} are {} > 0: choose one'.format(' and '.join(routes), 'both' if len(routes) == 2 else 'all'))
         if nwide > 0 and not self.synth_debug:
@@ -191,9 +192,10 @@ class Synthesizer(object):
             self._reconstruction(decoded, generated_wavs, cond, frames, basenames, out_dir)
             self._pitch(decoded, generated_wavs, basenames, out_dir)
             return self._write(generated_wavs, upsampled_features, mel_spectrograms, basenames, out_dir, log_dir, pcm)
-        nslots = int(getattr(hparams, 'mi355_synthesis_slots', 0))
-        if nslots > 0 and not self.synth_debug:
-            generated_wavs, upsampled_features, pcm, decoded = self._synthesize_slots(c_batch, frames, speaker_ids, min(nslots, 32), log_dir is not None)
+        nslots, nwslots = int(getattr(hparams, 'mi355_synthesis_slots', 0)), int(getattr(hparams, 'mi355_synthesis_wide_slots', 0))
+        if (nslots > 0 or nwslots > 0) and not self.synth_debug:
+            generated_wavs, upsampled_features, pcm, decoded = self._synthesize_slots(c_batch, frames, speaker_ids, nwslots if nwslots > 0 else min(nslots, 32),
+                                                                                      log_dir is not None, wide=nwslots > 0)
             self._reconstruction(decoded, generated_wavs, cond, frames, basenames, out_dir)
             self._pitch(decoded, generated_wavs, basenames, out_dir)
             return self._write(generated_wavs, upsampled_features, mel_spectrograms, basenames, out_dir, log_dir, pcm)
@@ -291,10 +293,11 @@ class Synthesizer(object):
         host = rows.cpu().numpy()
         return [host[u, :n * hop] for u, n in enumerate(lengths)], ups, None, None
 
-    def _synthesize_slots(self, c_batch, lengths, speaker_ids, nslots, want_features):
+    def _synthesize_slots(self, c_batch, lengths, speaker_ids, nslots, want_features, wide=False):
         """mi355_synthesis_slots > 0: all utterances of the call through ONE slot session (WaveNet.slots): no utterance is padded to the longest of its
         batch, a slot that finishes takes the next utterance at the next push.  Seeds derive from (wavenet_random_seed, the model's synthesis-call
-        counter, utterance index), so two fresh runs of the same inputs agree, whatever the tick."""
+        counter, utterance index), so two fresh runs of the same inputs agree, whatever the tick.  wide (mi355_synthesis_wide_slots > 0): the same
+        through ONE wide session (WaveNet.wide_slots) of nslots slots, which may exceed 32."""
         from wavenet_vocoder.models.wavenet import slot_plan, temperature_pair
         from wavenet_vocoder import util as wutil
         from wavenet_vocoder.util import is_mulaw, is_mulaw_quantize
@@ -309,7 +312,7 @@ class Synthesizer(object):
             self._ensure_capacity(B, (tick + right) * hop)
         m._synth_calls = getattr(m, '_synth_calls', 0) + 1
         base = ((int(hparams.wavenet_random_seed) << 20) + m._synth_calls) << 20
-        sess = m.slots(B)
+        sess = m.wide_slots(B) if wide else m.slots(B)
         pair = temperature_pair(hparams)                  # every utterance is opened at the hparams temperature (SlotSession.open)
         if pair != (1.0, 1.0) and getattr(self, '_logged_temperature', None) != pair:
             self._logged_temperature = pair

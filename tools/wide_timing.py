@@ -47,7 +47,7 @@ def _params(hp, eng):
 
 
 def _tolerate_missing_wide_symbol():
-    """the parent build has no wn_synthesize_wide: the binding resolves every name at load time, so give it a stub (these arms never call it)"""
+    """a parent build may lack wn_synthesize_wide / wn_synth_wide_slots_begin: the binding resolves every name at load time, so give it a stub (these arms never call it)"""
     import ctypes
     base = ctypes.CDLL
 
@@ -56,7 +56,7 @@ def _tolerate_missing_wide_symbol():
             try:
                 return base.__getattr__(self, name)
             except AttributeError:
-                if name != 'wn_synthesize_wide':
+                if name not in ('wn_synthesize_wide', 'wn_synth_wide_slots_begin'):
                     raise
                 return ctypes.CFUNCTYPE(ctypes.c_int)(lambda *x: -4)
     ctypes.CDLL = Lib
@@ -70,6 +70,8 @@ def _summary(us, B):
 
 
 def arm_wide(a):
+    if os.environ.get('WN_MI355_TEST_LIB'):
+        _tolerate_missing_wide_symbol()
     import torch
     from wavenet_vocoder import _ext
     hp = _hp(a.model)
@@ -179,6 +181,24 @@ def measure_wide(a, model, streams, yard=True):
     return res
 
 
+def measure_wide_vs_parent(a, model, streams):
+    """wn_synthesize_wide itself, --parent-lib against this build: children alternate (parent, this, parent, this), --repeats runs each; accepted when the
+    median of this build lies inside the parent's own p05 ... p95 of the session"""
+    out = {'frames': a.frames, 'model': model, 'summary': {}}
+    for B in streams:
+        us = {'parent': [], 'this': []}
+        for r in range(2):
+            for k, lib in (('parent', a.parent_lib), ('this', None)):
+                us[k] += _child('wide', a, model, B, a.repeats, lib=lib)['us_per_step']
+        pv = us['parent']
+        row = {'this': us['this'], 'this_median': float(np.median(us['this'])), 'parent': pv, 'parent_median': float(np.median(pv)),
+               'parent_p05': float(np.percentile(pv, 5)), 'parent_p95': float(np.percentile(pv, 95))}
+        row['within'] = bool(row['parent_p05'] <= row['this_median'] <= row['parent_p95'])
+        out['summary']['%s_%d.us_per_step' % (model, B)] = row
+        print('wide %s B=%d: parent %.2f [%.2f, %.2f], this %.2f us per step' % (model, B, row['parent_median'], row['parent_p05'], row['parent_p95'], row['this_median']), flush=True)
+    return out
+
+
 def measure_existing(a):
     libs = [('this', None)] + ([('parent', a.parent_lib)] if a.parent_lib else [])
     runs = {k: [] for k, _ in libs}
@@ -225,6 +245,8 @@ def main():
     for part in a.only.split(','):
         if part == 'existing':
             res['existing_path'] = measure_existing(a)
+        elif part == 'wide_vs_parent':
+            res['wide_vs_parent'] = measure_wide_vs_parent(a, 'paper', streams)
         elif part == 'c5':
             res['c5_width'] = measure_wide(a, 'c5', [b for b in (32, 256)], yard=False)
         else:
