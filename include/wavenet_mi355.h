@@ -667,6 +667,44 @@ int  wn_pitch_run(wn_pitch* h, const float* wav, int64_t ld, const int32_t* leng
 /* f0_a, f0_b: device float [B, pitch]; frames: HOST int32 [B]; table: device float [B, 9] */
 int  wn_pitch_compare(wn_pitch* h, const float* f0_a, const float* f0_b, int64_t pitch, const int32_t* frames, int32_t B, float* table, void* stream);
 
+/* ---- spectral denoiser (csrc/wn_denoise.hip) ----------------------------------------------------
+ * The bias denoiser of sampled vocoders on decoded float samples: STFT with a periodic Hann window of n_fft at hop (frames as wn_mel: F = 1 + n / hop,
+ * frame f centred on f hop, zeros outside [0, n)), |X| of every bin lowered by strength x profile[bin] and clamped at zero with the phase kept, inverse
+ * transform, synthesis window, overlap-add divided by the window-square sum of the covering frames (ascending f).  The profile is the mean |X| per bin
+ * over the frames of some signal whose window lies wholly inside it -- fitted on the device (wn_denoise_fit) or given (wn_denoise_set_profile).  A
+ * handle of its own, independent of wn_ctx.  All device memory -- both tables, the profile, two frame workspaces of max_batch x frames(max_samples) x
+ * n_fft floats, the partial sums of fit -- is reserved by wn_denoise_create; fit and run allocate nothing and never synchronise; lengths travel as
+ * kernel arguments (the host arrays are free when the call returns); no atomics, every sum in an order that depends only on (n_fft, hop) and the
+ * sample's own row, so a row's output bits do not depend on the batch, the row index or the pitches.
+ * Validation before any device call, in this order.  WN_E_ARG: a null pointer, a foreign abi_version, a negative size, B < 1, strength negative or not
+ * finite, a negative or non-finite profile entry.  WN_E_STATE: run / get_profile before any profile was fitted or set.  WN_E_SHAPE: n_fft odd or below 8,
+ * hop outside [1, n_fft / 4], B > max_batch, lengths[b] above a pitch or above max_samples, fit with no frame wholly inside any row.  WN_E_UNSUPPORTED:
+ * n_fft not a multiple of 32 or above 4096 (the inverse product runs in whole 32-column groups; the span of a 32-frame tile, 31 hop + n_fft floats, must
+ * fit the LDS): (1024, 256), (2048, 512) and (4096, 1024) are admitted. */
+typedef struct wn_denoise_config {
+    int32_t abi_version;   /* = WN_ABI_VERSION */
+    int32_t n_fft;         /* window and transform length */
+    int32_t hop;           /* samples between frames, 1 ... n_fft / 4 */
+    int32_t max_batch;     /* rows per call; 0: geometry-only handle (validation, num_frames, a host copy of a set profile): no device is touched */
+    int64_t max_samples;   /* samples per row */
+} wn_denoise_config;
+typedef struct wn_denoise wn_denoise;
+int  wn_denoise_create(const wn_denoise_config* cfg, wn_denoise** out);
+void wn_denoise_destroy(wn_denoise* h);
+const char* wn_denoise_last_error(const wn_denoise* h);   /* NULL: text of the last failed create or host hook */
+/* 1 + n / hop; WN_E_ARG for a NULL handle or n < 0 (host only) */
+int64_t wn_denoise_num_frames(const wn_denoise* h, int64_t n);
+/* wav: device float [B, ld], row b holds lengths[b] <= ld samples (HOST int32 [B]).  Sets the handle's profile: per (row, tile of 32 frames) partial sums in
+ * float32, frames ascending, then (row, tile) ascending in double, divided by the frame count and rounded to float32 */
+int  wn_denoise_fit(wn_denoise* h, const float* wav, int64_t ld, const int32_t* lengths, int32_t B, void* stream);
+/* profile: HOST float [1 + n_fft / 2]; its values travel as kernel arguments: the array is free when the call returns, nothing synchronises */
+int  wn_denoise_set_profile(wn_denoise* h, const float* profile, void* stream);
+/* profile: HOST float [1 + n_fft / 2].  SYNCHRONISES the stream: the only call of the handle that does */
+int  wn_denoise_get_profile(wn_denoise* h, float* profile, void* stream);
+/* in: device float [B, in_pitch]; out: device float [B, out_pitch], in == out allowed.  Elements of an out row beyond lengths[b] keep the caller's bytes;
+ * lengths[b] = 0 writes nothing */
+int  wn_denoise_run(wn_denoise* h, const float* in, int64_t in_pitch, const int32_t* lengths, int32_t B, float strength, float* out, int64_t out_pitch, void* stream);
+
 /* ---- introspection ------------------------------------------------------------------------------ */
 int64_t wn_workspace_bytes(const wn_ctx* ctx);
 /* name of the kernel that dominates training time (bench.py's roofline line names it) */
@@ -764,6 +802,13 @@ int wn_test_stats_tensors_host(const float* flat, const int64_t* offsets, const 
  * Validated as a create followed by a run; the comparison hook has no max_batch / max_samples limit. */
 int wn_test_pitch_host(const wn_pitch_config* cfg, const float* wav, int64_t ld, const int32_t* lengths, int32_t B, int32_t F_max, float* f0, float* ap, float* dprime);
 int wn_test_pitch_compare_host(const float* f0_a, const float* f0_b, int64_t pitch, const int32_t* frames, int32_t B, float* table);
+/* the spectral denoiser on the host (no handle, no GPU): fit and run in plain C++ float32 on HOST arrays, with the device's tables, packed spectrum and orders
+ * of summation (csrc/wn_denoise.h); the matrix instruction's rounding inside a product is the device's own, so the two sides agree to float32 roundoff, not
+ * bit for bit.  fit_wav != NULL: profile [1 + n_fft / 2] is fitted from fit_wav [fit_B, fit_ld] / fit_lengths and written; fit_wav == NULL: profile is read.
+ * in != NULL: rows of in [B, in_pitch] -> out [B, out_pitch] at `strength` (in == out allowed, elements beyond lengths[b] untouched); in == NULL: fit only.
+ * cfg->max_batch / max_samples are not limits here; otherwise validated as a create followed by the device calls. */
+int wn_test_denoise_host(const wn_denoise_config* cfg, const float* fit_wav, int64_t fit_ld, const int32_t* fit_lengths, int32_t fit_B, float* profile,
+                         const float* in, int64_t in_pitch, const int32_t* lengths, int32_t B, float strength, float* out, int64_t out_pitch);
 #endif /* WN_NO_TEST_HOOKS */
 
 #ifdef __cplusplus

@@ -104,6 +104,14 @@ MI355 = dict(
     mi355_output_stage='host',         # 'host': audio.inv_preemphasis + save_wavenet_wav on numpy; 'device': decode, de-emphasis, peak normalisation and the int16
                                        # cast on the device (csrc/wn_post.hip, OutputStage.finish) on every synthesis route; the same files without de-emphasis
     mi355_output_gain=1.0,             # gain of the playable chunks of streams and slot sessions (WaveNet.output_stage): PCM = y * gain * 32767, clamped
+    mi355_output_denoise=0.0,          # strength of the spectral bias denoiser (csrc/wn_denoise.hip) between the decode and the output stage of every route of
+                                       # Synthesizer.synthesize and on eval_step's item: strength x the model's noise profile is subtracted from the magnitude of every STFT bin, the phase kept.  The
+                                       # profile is fitted once at Synthesizer.load from what the model generates on silent conditioning.  0: no handle is created, nothing of
+                                       # it runs and every file is byte-identical to a run without the key.  Not judged by ear: no trained checkpoint of this tree exists
+    mi355_output_denoise_fft=1024,     # its window and transform length (periodic Hann); a multiple of 32, at most 4096
+    mi355_output_denoise_hop=256,      # its hop, 1 ... fft / 4
+    mi355_output_denoise_profile_frames=64,    # mel frames generated from silent conditioning for the profile (0.8 s at hop 275); at least fft samples
+    mi355_output_denoise_speaker=0,    # the speaker id of that run on a globally conditioned model (one profile for all speakers)
     mi355_reconstruction_check=False,  # True: every utterance Synthesizer.synthesize generates (all three routes) and the item eval_step generates is analysed as preprocessing
                                        # analyses a recording and compared with its conditioning on the device (csrc/wn_melcmp.hip): one row per utterance appended to
                                        # wavs/reconstruction.tsv, one log line, two scalars beside the eval loss.  The wavs, map.txt and plots are byte-identical either way

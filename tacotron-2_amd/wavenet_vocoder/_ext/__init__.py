@@ -83,6 +83,10 @@ class WnPitchConfig(ctypes.Structure):
                 ('tau_max', ctypes.c_int32), ('threshold', ctypes.c_float), ('max_batch', ctypes.c_int32), ('max_samples', ctypes.c_int64)]
 
 
+class WnDenoiseConfig(ctypes.Structure):
+    _fields_ = [('abi_version', ctypes.c_int32), ('n_fft', ctypes.c_int32), ('hop', ctypes.c_int32), ('max_batch', ctypes.c_int32), ('max_samples', ctypes.c_int64)]
+
+
 class WnFoldRow(ctypes.Structure):
     """wn_fold_row: one row of a folded run, in mel frames of utterance `utt`."""
     _fields_ = [('utt', ctypes.c_int32), ('first', ctypes.c_int32), ('frames', ctypes.c_int32), ('keep', ctypes.c_int32), ('fade', ctypes.c_int32)]
@@ -228,6 +232,15 @@ def load_library():
         'wn_pitch_compare': (ctypes.c_int, [vp, vp, vp, i64, ctypes.POINTER(i32), i32, vp, vp]),
         'wn_test_pitch_host': (ctypes.c_int, [ctypes.POINTER(WnPitchConfig), vp, i64, ctypes.POINTER(i32), i32, i32, vp, vp, vp]),
         'wn_test_pitch_compare_host': (ctypes.c_int, [vp, vp, i64, ctypes.POINTER(i32), i32, vp]),
+        'wn_denoise_create': (ctypes.c_int, [ctypes.POINTER(WnDenoiseConfig), ctypes.POINTER(vp)]),
+        'wn_denoise_destroy': (None, [vp]),
+        'wn_denoise_last_error': (ctypes.c_char_p, [vp]),
+        'wn_denoise_num_frames': (i64, [vp, i64]),
+        'wn_denoise_fit': (ctypes.c_int, [vp, vp, i64, ctypes.POINTER(i32), i32, vp]),
+        'wn_denoise_set_profile': (ctypes.c_int, [vp, vp, vp]),
+        'wn_denoise_get_profile': (ctypes.c_int, [vp, vp, vp]),
+        'wn_denoise_run': (ctypes.c_int, [vp, vp, i64, ctypes.POINTER(i32), i32, f32, vp, i64, vp]),
+        'wn_test_denoise_host': (ctypes.c_int, [ctypes.POINTER(WnDenoiseConfig), vp, i64, ctypes.POINTER(i32), i32, vp, vp, i64, ctypes.POINTER(i32), i32, f32, vp, i64]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)            # AttributeError here == ABI symbol missing
@@ -1318,6 +1331,127 @@ class PitchTracker:
     def close(self):
         if getattr(self, 'h', None):
             self.lib.wn_pitch_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---- spectral denoiser (csrc/wn_denoise.hip)
+def denoise_config(n_fft, hop, max_batch=0, max_samples=0):
+    cfg = WnDenoiseConfig()
+    cfg.abi_version = WN_ABI_VERSION
+    cfg.n_fft, cfg.hop, cfg.max_batch, cfg.max_samples = int(n_fft), int(hop), int(max_batch), int(max_samples)
+    return cfg
+
+
+def denoise_geometry(hp):
+    """hparams -> (n_fft, hop) of the output denoiser (mi355_output_denoise_fft / mi355_output_denoise_hop)."""
+    return int(getattr(hp, 'mi355_output_denoise_fft', 1024)), int(getattr(hp, 'mi355_output_denoise_hop', 256))
+
+
+def denoise_host(n_fft, hop, wav=None, lengths=None, strength=0.0, profile=None, fit_wav=None, fit_lengths=None):
+    """wn_test_denoise_host: fit and / or run in plain C++ float32 on numpy arrays (no handle, no GPU).  fit_wav [B', ld'] with fit_lengths: the profile is
+    fitted from it, else `profile` [1 + n_fft / 2] is used.  wav [B, ld] with lengths: returns (out, profile), out a copy of wav with the first lengths[b]
+    samples of every row denoised; wav None: returns (None, profile)."""
+    vp = ctypes.c_void_p
+    cfg = denoise_config(n_fft, hop)
+    nb = 1 + max(int(n_fft), 0) // 2
+    fw = fl = None
+    fB = fld = 0
+    if fit_wav is not None:
+        fw = np.ascontiguousarray(fit_wav, dtype=np.float32)
+        fls = _pitch_rows(fw, fit_lengths)
+        fB, fld = len(fls), int(fw.shape[1])
+        fl = (ctypes.c_int32 * max(fB, 1))(*fls)
+        prof = np.zeros(nb, np.float32)
+    else:
+        prof = np.ascontiguousarray(profile, dtype=np.float32).copy()
+        if prof.shape != (nb,):
+            raise ValueError('profile must be [%d] (got %r)' % (nb, prof.shape))
+    out = x = ln = None
+    B = ld = 0
+    if wav is not None:
+        x = np.ascontiguousarray(wav, dtype=np.float32)
+        lens = _pitch_rows(x, lengths)
+        B, ld = len(lens), int(x.shape[1])
+        ln = (ctypes.c_int32 * max(B, 1))(*lens)
+        out = x.copy()
+    rc = load_library().wn_test_denoise_host(ctypes.byref(cfg), None if fw is None else fw.ctypes.data_as(vp), fld, fl, fB, prof.ctypes.data_as(vp),
+                                             None if x is None else x.ctypes.data_as(vp), ld, ln, B, float(strength), None if out is None else out.ctypes.data_as(vp), ld)
+    if rc != 0:
+        raise WnError(rc, (load_library().wn_denoise_last_error(None) or b'').decode())
+    return out, prof
+
+
+class SpectralDenoiser:
+    """One wn_denoise: the bias denoiser on a ragged batch of decoded float signals on the current device (csrc/wn_denoise.hip), asynchronously: STFT
+    (periodic Hann of n_fft at hop), every bin's magnitude lowered by strength x profile and clamped at zero with the phase kept, inverse transform and
+    overlap-add.  The profile is fitted on the device (fit) or set from numpy (profile).  rows = 0: a geometry-only handle (validation, num_frames)."""
+
+    def __init__(self, n_fft, hop, rows, max_samples):
+        self.lib = load_library()
+        self.cfg = denoise_config(n_fft, hop, rows, max_samples)
+        h = ctypes.c_void_p()
+        rc = self.lib.wn_denoise_create(ctypes.byref(self.cfg), ctypes.byref(h))
+        if rc != 0:
+            raise WnError(rc, (self.lib.wn_denoise_last_error(None) or b'').decode())
+        self.h = h
+        self.n_fft, self.hop, self.rows, self.max_samples = int(n_fft), int(hop), int(rows), int(max_samples)
+        self.bins = 1 + self.n_fft // 2
+
+    def _ok(self, rc):
+        if rc != 0:
+            raise WnError(rc, (self.lib.wn_denoise_last_error(self.h) or b'').decode())
+
+    def num_frames(self, n):
+        r = int(self.lib.wn_denoise_num_frames(self.h, int(n)))
+        if r < 0:
+            raise WnError(r, 'wn_denoise_num_frames(%d)' % n)
+        return r
+
+    def fit(self, wav, lengths):
+        """wav float32 [B, ld] on the device, lengths: B ints (host): the handle's profile becomes the mean magnitude of the frames wholly inside the rows."""
+        import torch
+        _check(wav, torch.float32, 'wav')
+        lens = _pitch_rows(wav, lengths)
+        self._ok(self.lib.wn_denoise_fit(self.h, _ptr(wav), int(wav.shape[1]), (ctypes.c_int32 * max(len(lens), 1))(*lens), len(lens), _stream()))
+
+    @property
+    def profile(self):
+        """The profile as numpy float32 [1 + n_fft / 2] (synchronises the current stream)."""
+        p = np.zeros(self.bins, np.float32)
+        self._ok(self.lib.wn_denoise_get_profile(self.h, p.ctypes.data_as(ctypes.c_void_p), _stream() if self.rows > 0 else None))
+        return p
+
+    @profile.setter
+    def profile(self, value):
+        p = np.ascontiguousarray(value, dtype=np.float32)
+        if p.shape != (self.bins,):
+            raise ValueError('profile must be [%d] (got %r)' % (self.bins, p.shape))
+        self._ok(self.lib.wn_denoise_set_profile(self.h, p.ctypes.data_as(ctypes.c_void_p), _stream() if self.rows > 0 else None))
+
+    def apply(self, wav, lengths, strength, out=None):
+        """wav float32 [B, ld] on the device -> out (fresh: a copy of wav; out=wav: in place) with the first lengths[b] samples of row b denoised at
+        `strength`; what lies beyond keeps its bytes."""
+        import torch
+        _check(wav, torch.float32, 'wav')
+        lens = _pitch_rows(wav, lengths)
+        if out is None:
+            out = wav.clone()
+        _check(out, torch.float32, 'out')
+        if out.dim() != 2 or int(out.shape[0]) != len(lens):
+            raise ValueError('out must be [B, pitch] with one row per row of wav')
+        self._ok(self.lib.wn_denoise_run(self.h, _ptr(wav), int(wav.shape[1]), (ctypes.c_int32 * max(len(lens), 1))(*lens), len(lens), float(strength), _ptr(out),
+                                         int(out.shape[1]), _stream()))
+        return out
+
+    def close(self):
+        if getattr(self, 'h', None):
+            self.lib.wn_denoise_destroy(self.h)
             self.h = None
 
     def __del__(self):

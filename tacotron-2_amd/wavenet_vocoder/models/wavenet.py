@@ -327,6 +327,60 @@ class SlotSession(object):
         self.closed = True
 
 
+def silent_conditioning_value(hp):
+    """What an all-zero signal analyses to, as synthesis hands it to the model: the level floor through the analysis' own normalisation (datasets/audio.py;
+    -max_abs_value under the default hparams: the pad value of wn_mel_run and of Synthesizer.synthesize), then clip_for_wavenet / normalize_for_wavenet."""
+    S = audio._amp_to_db(np.zeros(1), hp) - hp.ref_level_db
+    v = float(np.asarray(audio._normalize(S, hp) if hp.signal_normalization else S).reshape(-1)[0])
+    lo, hi = (-hp.max_abs_value, hp.max_abs_value) if hp.symmetric_mels else (0, hp.max_abs_value)
+    if hp.clip_for_wavenet:
+        v = min(max(v, lo), hi)
+    if hp.normalize_for_wavenet:
+        v = (v - lo) / (hi - lo)
+    return v
+
+
+class OutputDenoiser(_ext.SpectralDenoiser):
+    """WaveNet.denoiser: an _ext.SpectralDenoiser in the hparams' geometry that can fit its profile from the model's own output on silent conditioning."""
+
+    def __init__(self, model, rows, max_samples):
+        n_fft, hop = _ext.denoise_geometry(model._hparams)
+        super().__init__(n_fft, hop, rows, max_samples)
+        self.model = model
+
+    def fit_from_model(self, frames=None, seed=None, speaker=None):
+        """One utterance of `frames` mel frames (mi355_output_denoise_profile_frames) generated by WaveNet.incremental from conditioning held at
+        silent_conditioning_value, at the temperature pair every synthesis call of this model sets on its context (the hparams'), decoded, and fitted -- all
+        on the device.
+        seed: of the device noise (None: derived from wavenet_random_seed); the model's synthesis-call counter is left as it was, so the utterances
+        generated afterwards are those of a run without the fit.  speaker: the global condition (mi355_output_denoise_speaker)."""
+        m, hp = self.model, self.model._hparams
+        frames = int(frames if frames is not None else getattr(hp, 'mi355_output_denoise_profile_frames', 64))
+        speaker = int(speaker if speaker is not None else getattr(hp, 'mi355_output_denoise_speaker', 0))
+        T = frames * audio.get_hop_size(hp)
+        if T > self.max_samples:
+            raise ValueError('fit_from_model: {} frames are {} samples, the denoiser holds {}'.format(frames, T, self.max_samples))
+        if m.engine is None:
+            m.build(1, T, inference_only=True)
+        c = torch.full((1, hp.cin_channels, frames), silent_conditioning_value(hp), dtype=torch.float32, device=m.device)
+        calls = getattr(m, '_synth_calls', 0)
+        noise = None
+        if seed is not None:
+            m._ensure_packed()
+            noise = torch.empty(T, 1, m.engine.noise_per_step, device=m.device)
+            m.engine.fill_noise(noise, 1, T, int(seed))
+        try:
+            out = m.incremental(None, c=c, g=[speaker] if m.global_conditioning_enabled() else None, time_length=T, noise=noise, check=True)
+        finally:
+            m._synth_calls = calls
+        if is_mulaw_quantize(hp.input_type):
+            out = util.inv_mulaw_quantize(out)
+        elif is_mulaw(hp.input_type):
+            out = util.inv_mulaw(out)
+        self.fit(out.float().reshape(1, -1).contiguous(), [T])
+        return self
+
+
 class WaveNet(object):
     def __init__(self, hparams, init=False):
         self._hparams = hparams
@@ -920,6 +974,12 @@ class WaveNet(object):
         a recording in the same domain, per utterance, on the device; the geometry comes from the hparams (mi355_pitch_*)."""
         from wavenet_vocoder.pitch import PitchCheck
         return PitchCheck(self._hparams, rows, max_samples)
+
+    def denoiser(self, rows, max_samples):
+        """An OutputDenoiser for up to `rows` decoded utterances of up to `max_samples` samples of this model (csrc/wn_denoise.hip): the bias denoiser of
+        sampled vocoders; geometry from the hparams (mi355_output_denoise_fft / _hop).  .fit(wav, lengths) / .fit_from_model(frames, seed, speaker) set the
+        noise profile, .profile reads or sets it as numpy, .apply(wav, lengths, strength, out=None) subtracts it."""
+        return OutputDenoiser(self, rows, max_samples)
 
     def train_stats(self):
         """The model's _ext.TrainStats (csrc/wn_stats.hip), built at the first call: histograms of up to max_batch rows of max_time samples and the

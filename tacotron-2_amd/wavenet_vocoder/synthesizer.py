@@ -42,6 +42,33 @@ class Synthesizer(object):
         self._recon = None
         self._pitch_chk = None
         self.pitch_references = None      # mi355_pitch_check: the recordings of the next synthesize() call (run_wav_synthesis sets them)
+        self._denoiser = None             # mi355_output_denoise > 0: the fitted OutputDenoiser; at 0 no handle exists and nothing of it runs
+        if self._denoise_strength() > 0.0:
+            frames = int(getattr(hparams, 'mi355_output_denoise_profile_frames', 64))
+            self._ensure_capacity(1, frames * get_hop_size(hparams))
+            self._denoiser = self.model.denoiser(1, frames * get_hop_size(hparams)).fit_from_model()
+            log('Output denoiser: profile fitted on {} frames of silent conditioning, strength {:g}'.format(frames, self._denoise_strength()))
+
+    def _denoise_strength(self):
+        s = float(getattr(self._hparams, 'mi355_output_denoise', 0.0))
+        if not (s >= 0.0) or s == float('inf'):
+            raise ValueError('mi355_output_denoise must be finite and >= 0 (got {!r})'.format(s))
+        return s
+
+    def _denoise(self, rows, lengths):
+        """mi355_output_denoise > 0: the decoded float rows [B, pitch] on the device, the first lengths[b] samples of each denoised IN PLACE at the fitted
+        profile (WaveNet.denoiser; a handle that is too small is replaced by a larger one that takes the profile over).  Between the decode and the output
+        stage on every route; the checks score what this returns.  At 0 the rows come back untouched."""
+        dn = self._denoiser
+        if dn is None:
+            return rows
+        lengths = [int(n) for n in lengths]
+        if dn.rows < len(lengths) or dn.max_samples < max(lengths):
+            big = self.model.denoiser(max(len(lengths), dn.rows), max(max(lengths), dn.max_samples))
+            big.profile = dn.profile
+            dn.close()
+            dn = self._denoiser = big
+        return dn.apply(rows, lengths, self._denoise_strength(), out=rows)
 
     def _output_mode(self):
         """(device, k): whether the written wavs come from the device output stage (mi355_output_stage), and the de-emphasis coefficient they get
@@ -212,16 +239,19 @@ class Synthesizer(object):
         self.model.engine.synth_check()           # the generation is enqueued asynchronously: a pipeline hand-off timeout surfaces here
         device, k = self._output_mode()
         pcm = None
+        y_hat = self.model.tower_y_hat[0]
+        if self._denoiser is not None and not self.synth_debug:
+            y_hat = self._denoise(y_hat.float().contiguous().clone(), audio_lengths)
         if device:
-            generated_wavs, pcm = self._finish_device(self.model.tower_y_hat[0], audio_lengths, k)
+            generated_wavs, pcm = self._finish_device(y_hat, audio_lengths, k)
         else:
-            generated = self.model.tower_y_hat[0].float().cpu().numpy()
+            generated = y_hat.float().cpu().numpy()
             generated_wavs = [w[:length] for w, length in zip(generated, audio_lengths)]
         feats = self.model.tower_synth_upsampled_local_features[0].cpu().numpy()
         upsampled_features = [f[:, :length] for f, length in zip(feats, audio_lengths)]
         if not self.synth_debug:
-            self._reconstruction(self.model.tower_y_hat[0] if device else None, generated_wavs, cond, frames, basenames, out_dir)
-            self._pitch(self.model.tower_y_hat[0] if device else None, generated_wavs, basenames, out_dir)
+            self._reconstruction(y_hat if device else None, generated_wavs, cond, frames, basenames, out_dir)
+            self._pitch(y_hat if device else None, generated_wavs, basenames, out_dir)
         return self._write(generated_wavs, upsampled_features, mel_spectrograms, basenames, out_dir, log_dir, pcm)
 
     def _synthesize_folded(self, c_batch, lengths, speaker_ids, nrows, want_features):
@@ -239,28 +269,40 @@ class Synthesizer(object):
         self._ensure_capacity(max(c[0] for c in caps), max(c[1] for c in caps))
         wavs, ups = [], []
         device, k = self._output_mode()
-        pcm = [] if device else None
+        dn = self._denoiser is not None
+        staged = device and not dn          # the fold's own stage finishes every group; with the denoiser on, the rows are denoised and finished after the loop, as a whole
+        pcm = [] if staged else None
         check = device and (bool(getattr(hparams, 'mi355_reconstruction_check', False)) or
                             (bool(getattr(hparams, 'mi355_pitch_check', False)) and getattr(self, 'pitch_references', None) is not None))
-        decoded = torch.zeros(len(lengths), max(lengths) * hop, device=self.model.device) if check else None      # out_wav of every group, kept on the device
+        keep = check or dn
+        decoded = torch.zeros(len(lengths), max(lengths) * hop, device=self.model.device) if keep else None      # out_wav of every group, kept on the device
         ids = None if not self.global_conditions else np.asarray(speaker_ids).reshape(-1)
         for grp, plan in zip(groups, plans):
             cl = [torch.from_numpy(np.ascontiguousarray(c_batch[u, :lengths[u]].T)) for u in grp]
             res = self.model.folded(cl, g=None if ids is None else [int(ids[u]) for u in grp], rows=plan, check=True, return_rows=want_features,
-                                    post=self._stage(len(grp), 'raw', k) if device else None)
-            if device:          # the written waveform is the stage's: de-emphasised float32 for the plots, int16 for the file
+                                    post=self._stage(len(grp), 'raw', k) if staged else None)
+            if staged:          # the written waveform is the stage's: de-emphasised float32 for the plots, int16 for the file
                 posts = res[-1]
                 res = res[0] if len(res) == 2 else res[:2]
-                if check:
-                    for u, w in zip(grp, res[0] if want_features else res):
-                        decoded[u, :w.shape[0]] = w
                 pcm += [q.cpu().numpy() for _, q in posts]
+            if keep:
+                for u, w in zip(grp, res[0] if want_features else res):
+                    decoded[u, :w.shape[0]] = w
             if want_features:
                 res, info = res
                 ups += [f.cpu().numpy() for f in unfold_features(plan, info['features'], hop)]
             else:
                 ups += [np.zeros((hparams.cin_channels, 0), np.float32) for _ in grp]
-            wavs += [w.float().cpu().numpy() for w in ([y for y, _ in posts] if device else res)]
+            if not dn:
+                wavs += [w.float().cpu().numpy() for w in ([y for y, _ in posts] if staged else res)]
+        if dn:          # decode (the fold's), denoise, output stage
+            n = [f * hop for f in lengths]
+            decoded = self._denoise(decoded, n)
+            if device:
+                wavs, pcm = self._finish_device(decoded, n, k)
+            else:
+                host = decoded.cpu().numpy()
+                wavs, decoded = [host[u, :n[u]] for u in range(len(n))], None
         return wavs, ups, pcm, decoded
 
     def _synthesize_wide(self, c_batch, lengths, speaker_ids, nrows):
@@ -287,6 +329,7 @@ class Synthesizer(object):
                 out = wutil.inv_mulaw(out)
             rows[u, :out.shape[0]] = out.float()
         ups = [f.cpu().numpy() for f in info['features']]
+        rows = self._denoise(rows, [n * hop for n in lengths])
         if device:
             wavs, pcm = self._finish_device(rows, [n * hop for n in lengths], k)
             return wavs, ups, pcm, rows
@@ -359,7 +402,9 @@ class Synthesizer(object):
             for u, n in enumerate(lengths):
                 if chunks[u]:
                     rows[u, :n * hop] = torch.cat(chunks[u])
+            rows = self._denoise(rows, [n * hop for n in lengths])
             wavs, pcm = self._finish_device(rows, [n * hop for n in lengths], k)
+        host_rows = torch.zeros(len(lengths), max(lengths) * hop, device=dev) if (self._denoiser is not None and not device) else None
         for u, n in enumerate(lengths):
             if not device:
                 out = torch.cat(chunks[u]) if chunks[u] else torch.zeros(0, device=dev)
@@ -368,8 +413,14 @@ class Synthesizer(object):
                     out = wutil.inv_mulaw_quantize(out)
                 elif is_mulaw(hparams.input_type):
                     out = wutil.inv_mulaw(out)
-                wavs.append(out.float().cpu().numpy())
+                if host_rows is not None:
+                    host_rows[u, :n * hop] = out.float()
+                else:
+                    wavs.append(out.float().cpu().numpy())
             ups.append(torch.cat(feats[u], 1).cpu().numpy() if feats[u] else np.zeros((hparams.cin_channels, 0), np.float32))
+        if host_rows is not None:          # the decoded utterances of the call denoised together, in one call
+            host = self._denoise(host_rows, [n * hop for n in lengths]).cpu().numpy()
+            wavs = [host[u, :n * hop] for u, n in enumerate(lengths)]
         return wavs, ups, pcm, rows      # rows: every utterance's decoded chunks, kept on the device until it finished (None on the host path)
 
     def _write(self, generated_wavs, upsampled_features, mel_spectrograms, basenames, out_dir, log_dir, pcm=None):

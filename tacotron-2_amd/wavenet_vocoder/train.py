@@ -223,6 +223,12 @@ def eval_step(model, batch, step, plot_dir, wav_dir, scalars, hparams, model_nam
     x, y, lengths, c, g = batch
     model.initialize(y, c, g, lengths)
     torch.cuda.synchronize()
+    if float(getattr(hparams, 'mi355_output_denoise', 0.0)) > 0.0:
+        try:
+            _denoise_eval_item(model, hparams)
+            torch.cuda.synchronize()
+        except Exception as e:      # like the checks below: never kills a training run
+            log('output denoiser skipped: {}'.format(e))
     y_hat = model.tower_y_hat[0].cpu().numpy()
     y_target = model.tower_y_target[0].float().cpu().numpy()
     loss = float(model.eval_loss.item())
@@ -254,6 +260,28 @@ def eval_step(model, batch, step, plot_dir, wav_dir, scalars, hparams, model_nam
             log('pitch check skipped: {}'.format(e))
     scalars.write(json.dumps(row) + '\n'); scalars.flush()
     return loss
+
+
+def _denoise_eval_item(model, hparams):
+    """mi355_output_denoise > 0: the generated item of eval_step goes through the chain synthesis applies -- decode (initialize's), denoise, write -- so the
+    wav, the plots and the two checks below are those of the denoised signal.  The denoiser belongs to the model and is fitted ONCE, at the first eval step
+    that needs it (WaveNet.denoiser(...).fit_from_model(): the profile of the weights of that step); a longer item later takes a larger handle that
+    keeps the profile."""
+    from datasets.audio import get_hop_size
+    strength = float(hparams.mi355_output_denoise)
+    wav = model.tower_y_hat[0].float().reshape(1, -1).contiguous()
+    n = int(wav.shape[1])
+    dn = getattr(model, '_eval_denoiser', None)
+    if dn is None or dn.max_samples < n:
+        frames = int(getattr(hparams, 'mi355_output_denoise_profile_frames', 64))
+        big = model.denoiser(1, max(n, frames * get_hop_size(hparams), dn.max_samples if dn is not None else 0))
+        if dn is None:          # no longer than the training context holds
+            big.fit_from_model(frames=min(frames, int(getattr(model, 'max_time', frames * get_hop_size(hparams))) // get_hop_size(hparams)))
+        else:
+            big.profile = dn.profile
+            dn.close()
+        dn = model._eval_denoiser = big
+    model.tower_y_hat[0] = dn.apply(wav, [n], strength, out=wav).reshape(model.tower_y_hat[0].shape)
 
 
 def _reconstruction_scalars(model, hparams):
