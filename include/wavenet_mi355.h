@@ -705,6 +705,51 @@ int  wn_denoise_get_profile(wn_denoise* h, float* profile, void* stream);
  * lengths[b] = 0 writes nothing */
 int  wn_denoise_run(wn_denoise* h, const float* in, int64_t in_pitch, const int32_t* lengths, int32_t B, float strength, float* out, int64_t out_pitch, void* stream);
 
+/* ---- streaming spectral denoiser (csrc/wn_denoise_stream.hip) -----------------------------------
+ * The denoiser above on rows that arrive push by push (the playable chunks of streams and slot sessions): a row's emitted samples, concatenated over its
+ * pushes, are BIT-IDENTICAL to wn_denoise_run of the whole row, however the row is cut.  A handle of its own, independent of wn_ctx and of wn_denoise.
+ * With H = n_fft / 2, S the samples a row was given since its restart and E those it has emitted, the emit rule depends on (n_fft, hop, S, final) alone:
+ *   E = S when final;  otherwise E = max(0, (floor((S - H) / hop) + 1) hop - H)   (floor towards -inf; 0 for S < H)
+ * so S - n_fft < E <= S - n_fft + hop whenever E > 0: the lag is below n_fft samples.  Frame f is analysed once f hop + H <= S, or when the row is final
+ * (zeros beyond the end, F = 1 + S / hop frames, as wn_denoise_run pads).  Per row the handle keeps the input tail (the < n_fft decoded samples the next
+ * frame still needs, double-buffered: a push reads one half and writes the other) and a ring of R = ceil(n_fft / hop) + (max_push + H) / hop + 2 windowed
+ * frames: those that still cover unemitted samples and those one push can add.  A push is two launches per group of 64 rows: the tile kernel (one
+ * workgroup per row and 32 new frames: stages tail + decoded new samples in LDS, the forward product, shrink and inverse product of wn_denoise_run in the
+ * same instruction order, frames into the ring, the new tail) and the gather kernel (out[E_old ... E_new) from the ring, frames ascending, one division).
+ * All device memory is reserved by create; a push allocates nothing, uses no atomics and never synchronises; the row counters live on the host and travel
+ * as kernel arguments.  Calls on one handle belong on one stream at a time.
+ * Validation before any device call, as wn_denoise's.  WN_E_ARG: a null pointer, a foreign abi_version, a negative size, in_type outside 0 ... 2, B < 1,
+ * a negative n[b] or pitch, strength negative or not finite, a bad profile entry.  WN_E_STATE: a push before any profile; a push (n[b] > 0 or final[b])
+ * on a row that ended without restart[b].  WN_E_SHAPE: the geometry rules of wn_denoise, B > max_rows, n[b] > max_push or > in_pitch, out_pitch below some
+ * n_out[b], a row beyond 2^31 - 1 samples since its restart.  WN_E_UNSUPPORTED: the geometry limits of wn_denoise, and a reserve (tables, tails, rings and
+ * the tiles' spectrum rows: max_rows x (2 n_fft + R n_fft + 32 ceil(((max_push + H) / hop + 2) / 32) n_fft) floats) above 4 GiB. */
+typedef struct wn_denoise_stream_config {
+    int32_t abi_version;   /* = WN_ABI_VERSION */
+    int32_t n_fft;         /* as wn_denoise_config */
+    int32_t hop;
+    int32_t max_rows;      /* rows of carried state; 0: geometry-only handle (validation, ready, the counters of a push): no device is touched */
+    int32_t max_push;      /* most samples per row in one push, >= 1 */
+    int32_t in_type;       /* as wn_post_config: 0 float waveform, 1 float mu-law, 2 int32 class ids; decoded while staging (wn_post_decode) */
+} wn_denoise_stream_config;
+typedef struct wn_denoise_stream wn_denoise_stream;
+int  wn_denoise_stream_create(const wn_denoise_stream_config* cfg, wn_denoise_stream** out);
+void wn_denoise_stream_destroy(wn_denoise_stream* h);
+const char* wn_denoise_stream_last_error(const wn_denoise_stream* h);   /* NULL: text of the last failed create or host hook */
+/* profile: HOST float [1 + n_fft / 2], as wn_denoise_set_profile (kernel arguments, nothing synchronises) */
+int  wn_denoise_stream_set_profile(wn_denoise_stream* h, const float* profile, void* stream);
+/* the fitted or set profile of a wn_denoise of the same n_fft (WN_E_SHAPE otherwise; WN_E_STATE if it has none), copied device to device on `stream`
+ * behind the fit enqueued there: nothing synchronises */
+int  wn_denoise_stream_take_profile(wn_denoise_stream* h, const wn_denoise* src, void* stream);
+/* E of the rule above (host only); WN_E_ARG for a NULL handle or S < 0 */
+int64_t wn_denoise_stream_ready(const wn_denoise_stream* h, int64_t S, int32_t final);
+/* in: device [B, in_pitch] elements of in_type, row b's next n[b] samples (never read beyond n[b]; NULL allowed when every n[b] is 0); out: device float
+ * [B, out_pitch], row b receives n_out[b] samples, elements beyond keep the caller's bytes.  n, restart, final (either may be NULL: none), n_out: HOST
+ * int32 [B]; n_out is computed from the counters and written before the call returns.  restart[b]: row b starts at S = E = 0 before it consumes its
+ * samples (a slot reopened inherits nothing).  final[b]: the row's utterance ends, everything left is flushed, and its next push must restart it.  A row
+ * with n[b] = 0 that is neither restarted nor final is left alone.  A failed call changes no row. */
+int  wn_denoise_stream_push(wn_denoise_stream* h, const void* in, int64_t in_pitch, const int32_t* n, const int32_t* restart, const int32_t* final, int32_t B,
+                            float strength, float* out, int64_t out_pitch, int32_t* n_out, void* stream);
+
 /* ---- introspection ------------------------------------------------------------------------------ */
 int64_t wn_workspace_bytes(const wn_ctx* ctx);
 /* name of the kernel that dominates training time (bench.py's roofline line names it) */
@@ -809,6 +854,13 @@ int wn_test_pitch_compare_host(const float* f0_a, const float* f0_b, int64_t pit
  * cfg->max_batch / max_samples are not limits here; otherwise validated as a create followed by the device calls. */
 int wn_test_denoise_host(const wn_denoise_config* cfg, const float* fit_wav, int64_t fit_ld, const int32_t* fit_lengths, int32_t fit_B, float* profile,
                          const float* in, int64_t in_pitch, const int32_t* lengths, int32_t B, float strength, float* out, int64_t out_pitch);
+/* the streaming denoiser on the host (no handle, no GPU): P pushes of B rows through the same state machine (counters, input tail, frame ring of R slots,
+ * emit rule; csrc/wn_denoise_stream.h) in plain C++ float32 with the arithmetic of wn_test_denoise_host, so a row's concatenated output equals
+ * wn_test_denoise_host of the whole row bit for bit.  Every pointer in HOST memory: in [P, B, in_pitch] elements of cfg->in_type, push p reads
+ * n[p][b] of row b; out [P, B, out_pitch] receives n_out[p][b]; n, restart, final (either may be NULL), n_out: int32 [P, B].  profile [1 + n_fft / 2].
+ * cfg->max_rows is not a limit here; otherwise validated as a create followed by the pushes (the first failing push ends the run with its code). */
+int wn_test_denoise_stream_host(const wn_denoise_stream_config* cfg, const float* profile, float strength, const void* in, int64_t in_pitch, const int32_t* n,
+                                const int32_t* restart, const int32_t* final, int32_t P, int32_t B, float* out, int64_t out_pitch, int32_t* n_out);
 #endif /* WN_NO_TEST_HOOKS */
 
 #ifdef __cplusplus

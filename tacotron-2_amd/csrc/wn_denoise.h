@@ -136,8 +136,9 @@ static inline int64_t wn_denoise_fit_frames(int64_t n, int64_t n_fft, int64_t ho
 // ---- host: the operation in plain float32 on the tables above, in the device's order: fused multiply-adds ascending in the device's interleaved chains
 // (the forward sum in two, tap pair (j >> 1) & 1; the inverse sum in four, packed column pair (c >> 1) & 3), joined as the kernels join them
 // X of one frame, packed: spec[2 k], spec[2 k + 1] = re, im of bin k (spec[1] = Re X[H]); spec holds 2 n_fft floats (the second half is scratch).
-// Reads wav[s] for 0 <= s < n only.
-static inline void dn_host_analyse(const DnTables& t, int hop, const float* wav, int64_t n, int64_t f, float* spec) {
+// Reads wav[s] for 0 <= s < n only.  dn_host_analyse_at: wav holds the samples from `base` on (sample s at wav[s - base]; the streaming form keeps only a
+// row's tail) and every sample the frame needs below n lies at or above base.
+static inline void dn_host_analyse_at(const DnTables& t, int hop, const float* wav, int64_t base, int64_t n, int64_t f, float* spec) {
 #pragma clang fp contract(off)
     const int N = t.n_fft, H = N / 2;
     const int64_t s0 = f * hop - H;
@@ -145,7 +146,7 @@ static inline void dn_host_analyse(const DnTables& t, int hop, const float* wav,
     for (int j = 0; j < N; ++j) {
         const int64_t s = s0 + j;
         if (s < 0 || s >= n) continue;      // a zero sample adds exactly nothing
-        const float x = wav[s];
+        const float x = wav[s - base];
         const float* row = &t.fb[(size_t)j * t.ldb];
         float* acc = spec + ((j >> 1) & 1) * N;
         for (int k = 0; k < H; ++k) {
@@ -155,6 +156,24 @@ static inline void dn_host_analyse(const DnTables& t, int hop, const float* wav,
         }
     }
     for (int c = 0; c < N; ++c) spec[c] = spec[c] + spec[N + c];
+}
+static inline void dn_host_analyse(const DnTables& t, int hop, const float* wav, int64_t n, int64_t f, float* spec) { dn_host_analyse_at(t, hop, wav, 0, n, f, spec); }
+// one analysed frame (spec, packed; shrunk in place) -> its windowed frame y [n_fft]; ch: 4 n_fft floats of scratch (the four chains of the inverse sum)
+static inline void dn_host_synth_frame(const DnTables& t, const float* profile, float strength, float* spec, float* ch, float* y) {
+#pragma clang fp contract(off)
+    const int N = t.n_fft, H = N / 2;
+    float d;
+    dn_shrink(spec[0], 0.0f, strength * profile[0], &spec[0], &d);
+    dn_shrink(spec[1], 0.0f, strength * profile[H], &spec[1], &d);
+    for (int k = 1; k < H; ++k) dn_shrink(spec[2 * k], spec[2 * k + 1], strength * profile[k], &spec[2 * k], &spec[2 * k + 1]);
+    for (size_t e = 0; e < (size_t)4 * N; ++e) ch[e] = 0.0f;
+    for (int c = 0; c < N; ++c) {
+        const float v = spec[c];
+        const float* row = &t.ib[(size_t)c * N];
+        float* acc = &ch[(size_t)((c >> 1) & 3) * N];
+        for (int j = 0; j < N; ++j) acc[j] = __builtin_fmaf(v, row[j], acc[j]);
+    }
+    for (int j = 0; j < N; ++j) y[j] = (ch[j] + ch[N + j]) + (ch[2 * (size_t)N + j] + ch[3 * (size_t)N + j]);
 }
 // the mean magnitude of the wholly-inside frames of B rows -> profile [H + 1]; returns the number of frames (0: nothing written)
 static inline int64_t wn_denoise_host_fit(const DnTables& t, int hop, const float* wav, int64_t ld, const int32_t* lengths, int32_t B, float* profile) {
@@ -193,19 +212,7 @@ static inline void wn_denoise_host_run(const DnTables& t, int hop, const float* 
         fr.assign((size_t)F * N, 0.0f);
         for (int64_t f = 0; f < F; ++f) {
             dn_host_analyse(t, hop, in + b * in_pitch, n, f, spec.data());
-            float d;
-            dn_shrink(spec[0], 0.0f, strength * profile[0], &spec[0], &d);
-            dn_shrink(spec[1], 0.0f, strength * profile[H], &spec[1], &d);
-            for (int k = 1; k < H; ++k) dn_shrink(spec[2 * k], spec[2 * k + 1], strength * profile[k], &spec[2 * k], &spec[2 * k + 1]);
-            float* y = &fr[(size_t)f * N];
-            for (size_t e = 0; e < ch.size(); ++e) ch[e] = 0.0f;
-            for (int c = 0; c < N; ++c) {
-                const float v = spec[c];
-                const float* row = &t.ib[(size_t)c * N];
-                float* acc = &ch[(size_t)((c >> 1) & 3) * N];
-                for (int j = 0; j < N; ++j) acc[j] = __builtin_fmaf(v, row[j], acc[j]);
-            }
-            for (int j = 0; j < N; ++j) y[j] = (ch[j] + ch[N + j]) + (ch[2 * (size_t)N + j] + ch[3 * (size_t)N + j]);
+            dn_host_synth_frame(t, profile, strength, spec.data(), ch.data(), &fr[(size_t)f * N]);
         }
         for (int64_t i = 0; i < n; ++i) {
             const int64_t f_lo = i >= H ? (i - H) / hop + 1 : 0, f_hi = (i + H) / hop < F - 1 ? (i + H) / hop : F - 1;
@@ -215,3 +222,7 @@ static inline void wn_denoise_host_run(const DnTables& t, int hop, const float* 
         }
     }
 }
+
+// library-internal (not part of the C ABI): where a handle's profile lives -- the device array of a handle with rows, the host copy of a geometry-only
+// one; WN_E_STATE before any profile.  wn_denoise_stream_take_profile reads it.
+extern "C" int wn_denoise_profile_source(const wn_denoise* h, int32_t* n_fft, const float** device_profile, const float** host_profile);

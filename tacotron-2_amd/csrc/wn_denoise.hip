@@ -15,8 +15,7 @@
 // lane per bin adds its 32 frames in ascending order (float32) and stores the (row, tile) partial; a second kernel adds the partials over (row, tile)
 // ascending in double, divides by the frame count and rounds to float32 (the wn_stats pattern).
 // No atomics, no sum split across workgroups, every order a function of (n_fft, hop) and the sample's own row; nothing allocated or synchronised by fit / run.
-#include "wn_denoise.h"
-#include "wn_common.h"
+#include "wn_denoise_dev.h"
 
 struct wn_denoise {
     wn_denoise_config cfg;
@@ -64,45 +63,13 @@ __global__ __launch_bounds__(DN_THREADS) void wn_denoise_tile_kernel(const DnArg
     float* patch = lds + a.sig_floats + wave * (DN_TILE * DN_PATCH);
     const float* sp = sig + l31 * hop + lh;      // A operand, taps k / k + 1: lane l holds frame l % 32, tap k + l / 32; largest index 31 hop + n_fft - 1
     for (int g = wave; g < a.G; g += 4) {        // (wave-uniform; no workgroup barrier inside)
-        f32x16_t rc[2], ic[2];      // two chains per sum (MFMA steps alternate between them), joined once: half the length of every rounding chain
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { rc[0][r] = 0.0f; rc[1][r] = 0.0f; ic[0][r] = 0.0f; ic[1][r] = 0.0f; }
-        const float* bp = a.fb + (size_t)lh * a.ldb + g * 64 + l31;      // B operand: lane l holds fb[k + l / 32][column l % 32]
-        float nre[4], nim[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { nre[u] = bp[(size_t)(2 * u) * a.ldb]; nim[u] = bp[(size_t)(2 * u) * a.ldb + 32]; }
-        for (int k0 = 0; k0 < N; k0 += 8) {      // n_fft is a multiple of 32: whole bodies of 8 taps, the next body's table loads in flight
-            float bre[4], bim[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) { bre[u] = nre[u]; bim[u] = nim[u]; }
-            if (k0 + 8 < N) {
-#pragma unroll
-                for (int u = 0; u < 4; ++u) { nre[u] = bp[(size_t)(k0 + 8 + 2 * u) * a.ldb]; nim[u] = bp[(size_t)(k0 + 8 + 2 * u) * a.ldb + 32]; }
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const float av = sp[k0 + 2 * u];
-                rc[u & 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bre[u], rc[u & 1], 0, 0, 0);
-                ic[u & 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bim[u], ic[u & 1], 0, 0, 0);
-            }
-        }
         f32x16_t re, im;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) { re[r] = __fadd_rn(rc[0][r], rc[1][r]); im[r] = __fadd_rn(ic[0][r], ic[1][r]); }
+        dn_forward_group(sp, a.fb + (size_t)lh * a.ldb + g * 64 + l31, a.ldb, N, &re, &im);      // wn_denoise_dev.h
         // accumulator register r of lane l is (frame 8 (r / 4) + 4 (l / 32) + r % 4, bin 32 g + l % 32); bin 0's "im" is Re X[H]
         const int bin = g * 32 + l31;
         const bool live = bin < H;
         if (!FIT) {
-            const float t = live ? __fmul_rn(a.strength, a.prof[bin]) : 0.0f, tH = __fmul_rn(a.strength, a.prof[H]);
-            float* y = Y + dn_spec_slot(live ? bin : 0, 0);
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int fr = (r >> 2) * 8 + lh * 4 + (r & 3);
-                float yr, yi, d;
-                if (bin == 0) { dn_shrink(re[r], 0.0f, t, &yr, &d); dn_shrink(im[r], 0.0f, tH, &yi, &d); }
-                else dn_shrink(re[r], im[r], t, &yr, &yi);
-                if (live) { y[(size_t)fr * N] = yr; y[(size_t)fr * N + 4] = yi; }
-            }
+            dn_shrink_group(re, im, Y, a.prof, a.strength, g, N, l31, lh);
         } else {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
@@ -130,19 +97,10 @@ __global__ __launch_bounds__(DN_THREADS) void wn_denoise_tile_kernel(const DnArg
     float* out = a.frames + row * a.ws_row + (int64_t)f0 * N;
     const float* yp = Y + (size_t)l31 * N + lh * 4;      // lane l: frame l % 32, (re | im) of four consecutive bins
     for (int jg = wave; jg < N / 32; jg += 4) {
-        f32x16_t acc[4];      // four chains (one per bin of a body of four), joined pairwise once
+        f32x16_t y;
+        dn_inverse_group(yp, a.ib + (size_t)lh * N + jg * 32 + l31, N, &y);
 #pragma unroll
-        for (int u = 0; u < 4; ++u)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[u][r] = 0.0f;
-        const float* bq = a.ib + (size_t)lh * N + jg * 32 + l31;      // B operand: lane l holds ib[packed column c + l / 32][sample 32 jg + l % 32]
-        for (int kb = 0; kb < N; kb += 8) {
-            const f32x4_t a4 = *(const f32x4_t*)(yp + kb);
-#pragma unroll
-            for (int u = 0; u < 4; ++u) acc[u] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[u], bq[(size_t)(kb + 2 * u) * N], acc[u], 0, 0, 0);
-        }
-#pragma unroll
-        for (int r = 0; r < 16; ++r) out[(size_t)((r >> 2) * 8 + lh * 4 + (r & 3)) * N + jg * 32 + l31] = __fadd_rn(__fadd_rn(acc[0][r], acc[1][r]), __fadd_rn(acc[2][r], acc[3][r]));
+        for (int r = 0; r < 16; ++r) out[(size_t)dn_acc_frame(r, lh) * N + jg * 32 + l31] = y[r];
     }
 }
 
@@ -324,6 +282,16 @@ extern "C" int wn_denoise_run(wn_denoise* d, const float* in, int64_t in_pitch, 
         hipLaunchKernelGGL(wn_denoise_gather_kernel, dim3(cdiv(n_max, DN_THREADS), nb), dim3(DN_THREADS), 0, st, g);
         WN_LAUNCH_CHECK(d);
     }
+    return WN_OK;
+}
+
+// the fitted or set profile where it lives (wn_denoise.h): the streaming handle copies it device to device on its own stream, nothing synchronises
+extern "C" int wn_denoise_profile_source(const wn_denoise* d, int32_t* n_fft, const float** device_profile, const float** host_profile) {
+    if (!d || !n_fft || !device_profile || !host_profile) return WN_E_ARG;
+    if (!d->have_profile) return WN_E_STATE;
+    *n_fft = d->cfg.n_fft;
+    *device_profile = d->cfg.max_batch > 0 ? (const float*)d->prof : nullptr;
+    *host_profile = d->cfg.max_batch == 0 ? d->prof_host.data() : nullptr;
     return WN_OK;
 }
 

@@ -87,6 +87,11 @@ class WnDenoiseConfig(ctypes.Structure):
     _fields_ = [('abi_version', ctypes.c_int32), ('n_fft', ctypes.c_int32), ('hop', ctypes.c_int32), ('max_batch', ctypes.c_int32), ('max_samples', ctypes.c_int64)]
 
 
+class WnDenoiseStreamConfig(ctypes.Structure):
+    _fields_ = [('abi_version', ctypes.c_int32), ('n_fft', ctypes.c_int32), ('hop', ctypes.c_int32), ('max_rows', ctypes.c_int32), ('max_push', ctypes.c_int32),
+                ('in_type', ctypes.c_int32)]
+
+
 class WnFoldRow(ctypes.Structure):
     """wn_fold_row: one row of a folded run, in mel frames of utterance `utt`."""
     _fields_ = [('utt', ctypes.c_int32), ('first', ctypes.c_int32), ('frames', ctypes.c_int32), ('keep', ctypes.c_int32), ('fade', ctypes.c_int32)]
@@ -241,6 +246,14 @@ def load_library():
         'wn_denoise_get_profile': (ctypes.c_int, [vp, vp, vp]),
         'wn_denoise_run': (ctypes.c_int, [vp, vp, i64, ctypes.POINTER(i32), i32, f32, vp, i64, vp]),
         'wn_test_denoise_host': (ctypes.c_int, [ctypes.POINTER(WnDenoiseConfig), vp, i64, ctypes.POINTER(i32), i32, vp, vp, i64, ctypes.POINTER(i32), i32, f32, vp, i64]),
+        'wn_denoise_stream_create': (ctypes.c_int, [ctypes.POINTER(WnDenoiseStreamConfig), ctypes.POINTER(vp)]),
+        'wn_denoise_stream_destroy': (None, [vp]),
+        'wn_denoise_stream_last_error': (ctypes.c_char_p, [vp]),
+        'wn_denoise_stream_set_profile': (ctypes.c_int, [vp, vp, vp]),
+        'wn_denoise_stream_take_profile': (ctypes.c_int, [vp, vp, vp]),
+        'wn_denoise_stream_ready': (i64, [vp, i64, i32]),
+        'wn_denoise_stream_push': (ctypes.c_int, [vp, vp, i64, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32), i32, f32, vp, i64, ctypes.POINTER(i32), vp]),
+        'wn_test_denoise_stream_host': (ctypes.c_int, [ctypes.POINTER(WnDenoiseStreamConfig), vp, f32, vp, i64, vp, vp, vp, i32, i32, vp, i64, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)            # AttributeError here == ABI symbol missing
@@ -1452,6 +1465,138 @@ class SpectralDenoiser:
     def close(self):
         if getattr(self, 'h', None):
             self.lib.wn_denoise_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---- streaming spectral denoiser (csrc/wn_denoise_stream.hip)
+def denoise_stream_config(n_fft, hop, max_rows=0, max_push=1, in_type=0):
+    cfg = WnDenoiseStreamConfig()
+    cfg.abi_version = WN_ABI_VERSION
+    cfg.n_fft, cfg.hop, cfg.max_rows, cfg.max_push = int(n_fft), int(hop), int(max_rows), int(max_push)
+    cfg.in_type = INPUT_TYPES[in_type] if in_type in INPUT_TYPES else int(in_type)
+    return cfg
+
+
+def denoise_stream_ready(n_fft, hop, S, final=False):
+    """The emit rule in Python (what wn_denoise_stream_ready computes): samples emitted of a row that was given S since its restart."""
+    S, H = int(S), int(n_fft) // 2
+    if final:
+        return S
+    return max(0, ((S - H) // int(hop) + 1) * int(hop) - H)
+
+
+def denoise_stream_host(n_fft, hop, pushes, profile, strength, in_type=0, max_push=None):
+    """wn_test_denoise_stream_host: the streaming state machine in plain C++ float32 on numpy arrays (no handle, no GPU).  pushes: a list of
+    (block [B, pitch] float32 / int32, n [B], restart [B] or None, final [B] or None).  Returns a list of (out [B, out_pitch] float32, n_out [B]) per push:
+    out rows hold n_out[b] samples, what lies beyond keeps the fill it was given (`nan`)."""
+    vp = ctypes.c_void_p
+    P = len(pushes)
+    B = len(pushes[0][1])
+    dt = np.int32 if (INPUT_TYPES[in_type] if in_type in INPUT_TYPES else int(in_type)) == 2 else np.float32
+    ipitch = max([1] + [int(np.asarray(p[0]).reshape(B, -1).shape[1]) for p in pushes])
+    n = np.zeros((P, B), np.int32); rs = np.zeros((P, B), np.int32); fin = np.zeros((P, B), np.int32)
+    blk = np.zeros((P, B, ipitch), dt)
+    if dt == np.float32:
+        blk[:] = np.nan
+    for p, (x, nn, r, f) in enumerate(pushes):
+        x = np.asarray(x, dtype=dt).reshape(B, -1)
+        blk[p, :, :x.shape[1]] = x
+        n[p] = nn
+        if r is not None:
+            rs[p] = np.asarray(r, np.int32)
+        if f is not None:
+            fin[p] = np.asarray(f, np.int32)
+    cfg = denoise_stream_config(n_fft, hop, 0, max(1, int(n.max()) if max_push is None else int(max_push)), in_type)
+    opitch = int(n.max()) + int(n_fft) + 3
+    out = np.full((P, B, opitch), np.nan, np.float32)
+    n_out = np.full((P, B), -1, np.int32)
+    prof = np.ascontiguousarray(profile, dtype=np.float32)
+    rc = load_library().wn_test_denoise_stream_host(ctypes.byref(cfg), prof.ctypes.data_as(vp), float(strength), blk.ctypes.data_as(vp), ipitch, n.ctypes.data_as(vp),
+                                                    rs.ctypes.data_as(vp), fin.ctypes.data_as(vp), P, B, out.ctypes.data_as(vp), opitch, n_out.ctypes.data_as(vp))
+    if rc != 0:
+        raise WnError(rc, (load_library().wn_denoise_stream_last_error(None) or b'').decode())
+    return [(out[p], n_out[p]) for p in range(P)]
+
+
+class DenoiseStream:
+    """One wn_denoise_stream: the spectral denoiser on rows that arrive push by push on the current device (csrc/wn_denoise_stream.hip), asynchronously.  A
+    row's emitted samples, concatenated, are bit-identical to SpectralDenoiser.apply on the whole row; they lag the samples given by less than n_fft (ready()).
+    rows = 0: a geometry-only handle.  Use one handle from one stream at a time."""
+
+    def __init__(self, n_fft, hop, rows, max_push, in_type=0):
+        self.lib = load_library()
+        self.cfg = denoise_stream_config(n_fft, hop, rows, max_push, in_type)
+        h = ctypes.c_void_p()
+        rc = self.lib.wn_denoise_stream_create(ctypes.byref(self.cfg), ctypes.byref(h))
+        if rc != 0:
+            raise WnError(rc, (self.lib.wn_denoise_stream_last_error(None) or b'').decode())
+        self.h = h
+        self.n_fft, self.hop, self.rows, self.max_push, self.in_type = int(n_fft), int(hop), int(rows), int(max_push), int(self.cfg.in_type)
+        self.bins = 1 + self.n_fft // 2
+
+    def _ok(self, rc):
+        if rc != 0:
+            raise WnError(rc, (self.lib.wn_denoise_stream_last_error(self.h) or b'').decode())
+
+    def ready(self, S, final=False):
+        r = int(self.lib.wn_denoise_stream_ready(self.h, int(S), int(bool(final))))
+        if r < 0:
+            raise WnError(r, 'wn_denoise_stream_ready(%d)' % S)
+        return r
+
+    def set_profile(self, value):
+        p = np.ascontiguousarray(value, dtype=np.float32)
+        if p.shape != (self.bins,):
+            raise ValueError('profile must be [%d] (got %r)' % (self.bins, p.shape))
+        self._ok(self.lib.wn_denoise_stream_set_profile(self.h, p.ctypes.data_as(ctypes.c_void_p), _stream() if self.rows > 0 else None))
+
+    def take_profile(self, source):
+        """The fitted or set profile of a SpectralDenoiser of the same n_fft, device to device on the current stream (nothing synchronises)."""
+        self._ok(self.lib.wn_denoise_stream_take_profile(self.h, source.h, _stream() if self.rows > 0 else None))
+
+    def push(self, samples, n=None, restart=None, final=None, strength=0.0, out=None):
+        """samples [B, pitch] on the device (float32, or int32 class ids with in_type 2), n: B ints (None: the whole pitch), restart / final: B flags
+        (None: none; True: all).  Returns (out float32 [B, max(n) + n_fft] on the device, contiguous, n_out: B ints): row b's next n_out[b] denoised samples, zeros
+        beyond.  out: a float32 [B, pitch'] tensor to write into instead (elements beyond n_out[b] keep their bytes)."""
+        import torch
+        _check(samples, torch.int32 if self.in_type == 2 else torch.float32, 'samples')
+        if samples.dim() == 1:
+            samples = samples.reshape(1, -1)
+        if samples.dim() != 2:
+            raise ValueError('samples must be [B, pitch]')
+        B, pitch = int(samples.shape[0]), int(samples.shape[1])
+        n = [pitch] * B if n is None else [int(v) for v in n]
+        if len(n) != B:
+            raise ValueError('one length per row of samples (%d lengths for %d rows)' % (len(n), B))
+
+        def flags(v, name):
+            if v is None:
+                return None
+            f = [1] * B if v is True else [int(bool(x)) for x in v]
+            if len(f) != B:
+                raise ValueError('one %s flag per row' % name)
+            return (ctypes.c_int32 * B)(*f)
+        rs, fin = flags(restart, 'restart'), flags(final, 'final')
+        if out is None:
+            out = torch.zeros(B, max(max(n), 0) + self.n_fft, dtype=torch.float32, device=samples.device)      # a push emits at most n + (S - E) < n + n_fft samples
+        _check(out, torch.float32, 'out')
+        if out.dim() != 2 or int(out.shape[0]) != B:
+            raise ValueError('out must be [B, pitch] with one row per row of samples')
+        opitch = int(out.shape[1])
+        n_out = (ctypes.c_int32 * B)()
+        self._ok(self.lib.wn_denoise_stream_push(self.h, _ptr(samples), pitch, (ctypes.c_int32 * B)(*n), rs, fin, B, float(strength), _ptr(out), opitch, n_out, _stream()))
+        n_out = [int(v) for v in n_out]
+        return out, n_out
+
+    def close(self):
+        if getattr(self, 'h', None):
+            self.lib.wn_denoise_stream_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -94,6 +94,25 @@ def _post_push(post, post_output, out, n, restart):
     return post.push(out, n=n, restart=restart, pcm=post_output != 'float', float_out=post_output != 'pcm')
 
 
+def _denoise_post_check(post):
+    """denoise= hands the output stage decoded samples: refuse any other stage before anything is generated"""
+    if post is not None and getattr(post, 'in_type', None) != 0:
+        raise ValueError("denoise= decodes the samples itself: post must be an OutputStage with in_type='raw' (model.output_stage(rows, in_type='raw')), got in_type {!r}".format(
+            getattr(post, 'in_type', None)))
+
+
+def _denoise_push(model, ds, strength, out, n, restart, final, post, post_output):
+    """One DenoiseStream.push of a synthesis push, followed by the output stage when there is one: out [B, pitch] model-domain samples, n / restart / final
+    per row.  Returns (chunk, n_out): what the denoiser emitted for every row (n_out[b] samples, lagging the row's samples by less than n_fft), as the
+    float32 chunk [B, pitch'] it produced (post None) or as what post_output names from post.push on it."""
+    if strength is None:
+        strength = float(getattr(model._hparams, 'mi355_output_denoise', 0.0))
+    y, n_out = ds.push(out, n=n, restart=restart, final=final, strength=float(strength))
+    if post is None:
+        return y, n_out
+    return _post_push(post, post_output, y, n_out, restart), n_out
+
+
 class SynthesisStream(object):
     """Generation of B utterances chunk by chunk as their mel frames arrive (WaveNet.stream): the samples are bit-identical to one
     WaveNet.incremental-style run over the concatenated frames with the same seed.  push() returns the samples whose conditioning is now
@@ -113,13 +132,19 @@ class SynthesisStream(object):
         model.engine.stream_begin(self.B, seed=seed, steps_per_graph=steps_per_graph)
         self.closed = False
 
-    def push(self, c_frames=None, final=False, noise=None, test_inputs=None, return_raw=False, post=None, post_output='pcm'):
+    def push(self, c_frames=None, final=False, noise=None, test_inputs=None, return_raw=False, post=None, post_output='pcm', denoise=None, denoise_strength=None):
         """c_frames [B, cin, Tn] (None or Tn = 0: no new frames); noise [n, B, noise_per_step] / test_inputs [B, n] of the span this push
         generates (its length follows from stream_schedule and the lookahead).  post: an OutputStage (WaveNet.output_stage) of >= B rows: the
         playable chunk [B, n] -- decoded, de-emphasised, int16 at the stage's gain (post_output 'float': float32; 'both': (int16, float32)) -- is
-        returned as a last element beside the samples; the stage's filter runs on from push to push, restarted at the stream's first one."""
+        returned as a last element beside the samples; the stage's filter runs on from push to push, restarted at the stream's first one.
+        denoise: an _ext.DenoiseStream (WaveNet.stream_denoiser) of >= B rows and max_push >= n: the samples of this push are decoded and denoised by it
+        (strength denoise_strength; None: mi355_output_denoise) and what it emits goes to post, which must then be an OutputStage with in_type='raw'.  The
+        playable chunk is the denoised one: it lags the samples by S - E < n_fft (DenoiseStream.ready) and the final push returns the flushed rest; without
+        post it is the denoised float32 chunk.  The generated samples are the same with or without denoise."""
         if self.closed:
             raise RuntimeError('SynthesisStream: the stream is closed')
+        if denoise is not None:
+            _denoise_post_check(post)
         m = self.model
         cc = None
         if c_frames is not None and int(c_frames.shape[-1]) > 0:
@@ -141,13 +166,18 @@ class SynthesisStream(object):
         if final:
             self.closed = True
         chunk = None
-        if post is not None:
+        if denoise is not None:
+            chunk, n_out = _denoise_push(m, denoise, denoise_strength, out, [n] * self.B, None if getattr(self, '_post_started', False) else True, [final] * self.B,
+                                         post, post_output)
+            self._post_started = True
+            chunk = tuple(t[:, :n_out[0]] for t in chunk) if isinstance(chunk, tuple) else chunk[:, :n_out[0]]      # (every row has the same S: the same n_out)
+        elif post is not None:
             chunk = _post_push(post, post_output, out, [n] * self.B, None if getattr(self, '_post_started', False) else True)
             self._post_started = True
             chunk = tuple(t[:, :n] for t in chunk) if isinstance(chunk, tuple) else chunk[:, :n]
         out = out[:, :n]
         res = (out, raw[:, :, :n]) if return_raw else (out,)
-        if post is not None:
+        if chunk is not None:
             res = res + (chunk,)
         return res if len(res) > 1 else res[0]
 
@@ -261,13 +291,18 @@ class SlotSession(object):
         self.done[slot], self.pushed[slot] = 0, 0
         self._post_restart.add(int(slot))
 
-    def push(self, items, return_raw=False, post=None, post_output='pcm'):
+    def push(self, items, return_raw=False, post=None, post_output='pcm', denoise=None, denoise_strength=None):
         """items {slot: frames [cin, Tn]} or {slot: (frames, final)}: append the frames to the slots' utterances (final: the utterance ends, the slot
         is idle afterwards).  Returns {slot: samples [n]} (or (samples, raw [O, n]) with return_raw) for every slot named.  post: an OutputStage of
         >= B rows (row = slot): every slot's playable chunk [n] (SynthesisStream.push) follows as a last element; a slot's filter runs on from push
-        to push and starts afresh at the first push after its open()."""
+        to push and starts afresh at the first push after its open().  denoise: an _ext.DenoiseStream (WaveNet.stream_denoiser) of >= B rows
+        (row = slot), as SynthesisStream.push: a slot's chunk is then the denoised one (its length is what the denoiser emitted, the slot's final push
+        returns the flushed rest), a slot opened anew restarts its row in the denoiser together with its row in post, and an abandoned slot's row is
+        restarted at the next open."""
         if self.closed:
             raise RuntimeError('SlotSession: the session is closed')
+        if denoise is not None:
+            _denoise_post_check(post)
         m, hp = self.model, self.model._hparams
         frames, final, blocks = [0] * self.B, [False] * self.B, {}
         for b, it in items.items():
@@ -295,9 +330,13 @@ class SlotSession(object):
         raw = torch.empty(self.B, hp.out_channels, pitch, device=m.device) if return_raw else None
         got = m.engine.slots_push(cc, frames, final, out, raw)
         assert got == n, (got, n)
-        chunk = None
-        if post is not None:
-            chunk = _post_push(post, post_output, out, n, [int(b in self._post_restart and b in items) for b in range(self.B)])
+        chunk, nc = None, n      # nc: the length of every slot's chunk
+        if post is not None or denoise is not None:
+            restart = [int(b in self._post_restart and b in items) for b in range(self.B)]
+            if denoise is not None:
+                chunk, nc = _denoise_push(m, denoise, denoise_strength, out, n, restart, [int(f) for f in final], post, post_output)
+            else:
+                chunk = _post_push(post, post_output, out, n, restart)
             self._post_restart -= set(items)
         res = {}
         for b in items:
@@ -306,8 +345,8 @@ class SlotSession(object):
             if final[b]:
                 self.done[b] = None
             r = (out[b, :n[b]], raw[b, :, :n[b]]) if return_raw else (out[b, :n[b]],)
-            if post is not None:
-                r = r + (tuple(t[b, :n[b]] for t in chunk) if isinstance(chunk, tuple) else chunk[b, :n[b]],)
+            if chunk is not None:
+                r = r + (tuple(t[b, :nc[b]] for t in chunk) if isinstance(chunk, tuple) else chunk[b, :nc[b]],)
             res[b] = r if len(r) > 1 else r[0]
         return res
 
@@ -980,6 +1019,17 @@ class WaveNet(object):
         sampled vocoders; geometry from the hparams (mi355_output_denoise_fft / _hop).  .fit(wav, lengths) / .fit_from_model(frames, seed, speaker) set the
         noise profile, .profile reads or sets it as numpy, .apply(wav, lengths, strength, out=None) subtracts it."""
         return OutputDenoiser(self, rows, max_samples)
+
+    def stream_denoiser(self, rows, max_push, source=None):
+        """An _ext.DenoiseStream of `rows` rows for pushes of up to `max_push` samples per row (csrc/wn_denoise_stream.hip): the denoise= argument of
+        SynthesisStream.push / SlotSession.push.  Geometry from the hparams (mi355_output_denoise_fft / _hop), in_type from hparams.input_type (it decodes
+        the model's samples itself).  source: a fitted OutputDenoiser (WaveNet.denoiser) whose profile it takes, device to device; None: set one with
+        .set_profile(numpy) or .take_profile(denoiser) before the first push."""
+        n_fft, hop = _ext.denoise_geometry(self._hparams)
+        ds = _ext.DenoiseStream(n_fft, hop, rows, max_push, self._hparams.input_type)
+        if source is not None:
+            ds.take_profile(source)
+        return ds
 
     def train_stats(self):
         """The model's _ext.TrainStats (csrc/wn_stats.hip), built at the first call: histograms of up to max_batch rows of max_time samples and the
