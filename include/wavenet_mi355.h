@@ -750,6 +750,57 @@ int64_t wn_denoise_stream_ready(const wn_denoise_stream* h, int64_t S, int32_t f
 int  wn_denoise_stream_push(wn_denoise_stream* h, const void* in, int64_t in_pitch, const int32_t* n, const int32_t* restart, const int32_t* final, int32_t B,
                             float strength, float* out, int64_t out_pitch, int32_t* n_out, void* stream);
 
+/* ---- sample-rate conversion (csrc/wn_resample.hip) ----------------------------------------------
+ * Rows of float32 samples from sr_in to sr_out by the rational factor L / M (g = gcd(sr_in, sr_out), L = sr_out / g, M = sr_in / g), whole rows (wn_resample_run)
+ * or push by push (wn_resample_push: row = slot, the playable chunks of streams and slot sessions).  A handle of its own, independent of wn_ctx.
+ * The filter is a Kaiser-windowed sinc in closed form, h(t) = rolloff sinc(rolloff t) I0(beta sqrt(1 - (t / zeros)^2)) / I0(beta) for |t| < zeros, else 0; with
+ * s = min(1, L / M), output m of a row of n samples is
+ *   y[m] = s sum_k x[k] h(s (m M / L - k)),  x = 0 outside [0, n),  m < n_out = ceil(n L / M)                        (the last sample computed, not zero-filled)
+ * evaluated in polyphase form: W = ceil(zeros max(L, M) / L), T = 2 W taps, k0 = floor(m M / L), p = (m M) mod L,
+ *   y[m] = sum_{j < T} C[p][j] x[k0 - W + 1 + j],  C[p][j] = s h(s (p / L + W - 1 - j))
+ * C [L][T] is evaluated in double on the host EXACTLY at the polyphase positions and rounded once to float32 (no interpolation from a sampled table: the
+ * result differs from resampy's kaiser_best, whose design values zeros = 64, beta = 14.769656459379492, rolloff = 0.9475937167399596 are the usual choice,
+ * by that table's interpolation error).  One float32 accumulator per output from 0, T fmaf in ascending j, taps outside the row read 0.0f and are never
+ * skipped: an output's bits depend on (L, M, zeros, beta, rolloff), m and the row's samples alone -- not on the batch, the row index, the pitches or how the
+ * row was cut into pushes -- and equal the plain loop of wn_test_resample_host.  sr_in == sr_out (L = M = 1) does not filter: W = 0 and the bits are copied.
+ * Streaming: S inputs given to a row since its restart, E outputs emitted.  Final: E = ceil(S L / M).  Otherwise E = max(0, ceil((S - W) L / M)): the lag is at
+ * most W inputs (177, about 8 ms, for 22 050 -> 8 000 Hz).  Per row the handle keeps the counters on the host and at most 2 W - 1 inputs on the device,
+ * double-buffered.  All device memory (the table, the tails) is reserved by create; no call allocates, uses atomics or synchronises.  Calls on one handle
+ * belong on one stream at a time.
+ * Validation before any device call.  WN_E_ARG: a null pointer, a foreign abi_version, negative max_rows / max_in / lengths / pitches, B < 1, sr_in or sr_out
+ * below 1, zeros < 1, rolloff outside (0, 1], beta negative or not finite.  WN_E_SHAPE: B > max_rows, a row longer than max_in or its pitch, out_pitch below
+ * some row's outputs, a row beyond 2^31 - 1 samples since its restart.  WN_E_STATE: a push (n[b] > 0 or final[b]) on a row that ended without restart[b].
+ * WN_E_UNSUPPORTED: a table L x T above 4 Mi floats (22 050 -> 8 000 needs 56 640), more than 12 288 inputs under a block of 64 outputs, beta above 256. */
+typedef struct wn_resample_config {
+    int32_t abi_version;   /* = WN_ABI_VERSION */
+    int32_t max_rows;      /* rows of one call and of carried state; 0: geometry-only handle (validation, num_out, ready, taps): no device is touched */
+    int32_t max_in;        /* most input samples per row in one call; >= 1 when max_rows > 0 (0 on a geometry-only handle or in a hook: no limit) */
+    int32_t sr_in;         /* >= 1 */
+    int32_t sr_out;        /* >= 1 */
+    int32_t zeros;         /* zero crossings of the prototype on each side, >= 1 */
+    double  beta;          /* Kaiser window shape, finite, 0 ... 256 */
+    double  rolloff;       /* cutoff as a share of the lower Nyquist frequency, in (0, 1] */
+} wn_resample_config;
+typedef struct wn_resample wn_resample;
+int  wn_resample_create(const wn_resample_config* cfg, wn_resample** out);
+void wn_resample_destroy(wn_resample* h);
+const char* wn_resample_last_error(const wn_resample* h);   /* NULL: text of the last failed create or host hook */
+/* ceil(n L / M) and E of the rule above (host only); WN_E_ARG for a NULL handle or an n / S outside [0, 2^31 - 1] */
+int64_t wn_resample_num_out(const wn_resample* h, int64_t n);
+int64_t wn_resample_ready(const wn_resample* h, int64_t S, int32_t final);
+/* the plan: any of L, M, W may be NULL */
+int  wn_resample_taps(const wn_resample* h, int32_t* L, int32_t* M, int32_t* W);
+/* whole ragged rows.  in: device float [B, in_pitch], row b holds lengths[b] samples (HOST int32 [B]); out: device float [B, out_pitch], row b receives
+ * ceil(lengths[b] L / M) samples, elements beyond keep the caller's bytes.  Neither reads nor writes the carried state of a push. */
+int  wn_resample_run(wn_resample* h, const float* in, int64_t in_pitch, const int32_t* lengths, int32_t B, float* out, int64_t out_pitch, void* stream);
+/* in: device float [B, in_pitch], row b's next n[b] samples (never read beyond n[b]; NULL allowed when every n[b] is 0); out: device float [B, out_pitch], row b
+ * receives n_out[b] samples, elements beyond keep the caller's bytes.  n, restart, final (either may be NULL: none), n_out: HOST int32 [B]; n_out is computed
+ * from the counters and written before the call returns.  restart[b]: row b starts at S = E = 0 before it consumes its samples.  final[b]: the row ends,
+ * everything left is flushed, and its next push must restart it.  A row with n[b] = 0 that is neither restarted nor final is left alone.  A failed call
+ * changes no row. */
+int  wn_resample_push(wn_resample* h, const float* in, int64_t in_pitch, const int32_t* n, const int32_t* restart, const int32_t* final, int32_t B, float* out,
+                      int64_t out_pitch, int32_t* n_out, void* stream);
+
 /* ---- introspection ------------------------------------------------------------------------------ */
 int64_t wn_workspace_bytes(const wn_ctx* ctx);
 /* name of the kernel that dominates training time (bench.py's roofline line names it) */
@@ -861,6 +912,14 @@ int wn_test_denoise_host(const wn_denoise_config* cfg, const float* fit_wav, int
  * cfg->max_rows is not a limit here; otherwise validated as a create followed by the pushes (the first failing push ends the run with its code). */
 int wn_test_denoise_stream_host(const wn_denoise_stream_config* cfg, const float* profile, float strength, const void* in, int64_t in_pitch, const int32_t* n,
                                 const int32_t* restart, const int32_t* final, int32_t P, int32_t B, float* out, int64_t out_pitch, int32_t* n_out);
+/* sample-rate conversion on the host (no handle, no GPU): P pushes of B rows through the state machine of wn_resample_push (counters, carried inputs, emit
+ * rule; csrc/wn_resample.h) as a plain loop of fmaf -- the device's bits.  Every pointer in HOST memory: in [P, B, in_pitch] float, push p reads n[p][b] of
+ * row b; out [P, B, out_pitch] receives n_out[p][b]; n, restart, final (either may be NULL), n_out: int32 [P, B].  A whole row is one push with final set.
+ * cfg->max_rows is not a limit here and max_in = 0 means none; otherwise validated as a create followed by the pushes (the first failing push ends the run
+ * with its code).  wn_test_resample_table: the float32 table C [L][T] of a configuration into table [cap]; WN_E_ARG when cap is below L x T. */
+int wn_test_resample_host(const wn_resample_config* cfg, const float* in, int64_t in_pitch, const int32_t* n, const int32_t* restart, const int32_t* final, int32_t P,
+                          int32_t B, float* out, int64_t out_pitch, int32_t* n_out);
+int wn_test_resample_table(const wn_resample_config* cfg, float* table, int64_t cap);
 #endif /* WN_NO_TEST_HOOKS */
 
 #ifdef __cplusplus

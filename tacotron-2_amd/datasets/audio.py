@@ -9,10 +9,15 @@ from scipy.io import wavfile
 
 def load_wav(path, sr):
     """Reference audio.py:9-10 (librosa.core.load) on scipy: float32 in [-1, 1), channels averaged.  int16 / 32768, int32 / 2^31, uint8 as
-    (x - 128) / 128, float as is.  The reference resamples to sr; no resampler here matches librosa's, so another rate is an error."""
+    (x - 128) / 128, float as is.  The reference resamples to sr; no resampler here matches librosa's, so another rate is an error.
+    (mi355_resample_input=True takes another road: read_wav, then resample_signals.)"""
     rate, x = wavfile.read(path)
     if rate != sr:
         raise ValueError('%s: sample rate %d, expected %d (resample the file first: no resampler here matches librosa\'s)' % (path, rate, sr))
+    return _as_float_mono(path, x)
+
+
+def _as_float_mono(path, x):
     if x.dtype == np.int16:
         y = x.astype(np.float32) / 32768.0
     elif x.dtype == np.int32:
@@ -26,6 +31,56 @@ def load_wav(path, sr):
     if y.ndim == 2:
         y = y.mean(axis=1, dtype=np.float32)
     return y
+
+
+def read_wav(path):
+    """(sample rate, float32 signal in [-1, 1), channels averaged) of a wav file at whatever rate it has: the conversions of load_wav."""
+    rate, x = wavfile.read(path)
+    return int(rate), _as_float_mono(path, x)
+
+
+RESAMPLE_BATCH = 20
+
+
+def resample_host(x, sr_in, sr_out, **design):
+    """One signal from sr_in to sr_out on the host: the plain float32 loop of wn_test_resample_host (csrc/wn_resample.h), BIT-IDENTICAL to the device's
+    _ext.Resampler -- the fallback where no GPU exists.  A Kaiser-windowed sinc in closed form with resampy's published kaiser_best design values (zeros,
+    beta, rolloff in **design), evaluated exactly at the polyphase positions: close to, not equal to, what librosa's load(sr=...) returned; the length is
+    librosa's ceil(n sr_out / sr_in), the last sample computed."""
+    from wavenet_vocoder import _ext
+    return _ext.resample_rows_host([x], sr_in, sr_out, **design)[0]
+
+
+def resample_signals(signals, sr_in, sr_out, device=None):
+    """float32 signals from sr_in to sr_out: in batches of RESAMPLE_BATCH through ONE _ext.Resampler on the GPU when there is one (device None: ask torch),
+    else resample_host one by one; the bits are the same either way.  sr_in == sr_out returns the signals as they are."""
+    signals = [np.ascontiguousarray(s, dtype=np.float32) for s in signals]
+    if int(sr_in) == int(sr_out) or not signals:
+        return signals
+    if device is None:
+        import torch
+        device = torch.cuda.is_available()
+    if not device:
+        return [resample_host(s, sr_in, sr_out) for s in signals]
+    import torch
+    from wavenet_vocoder import _ext
+    order = sorted(range(len(signals)), key=lambda i: len(signals[i]))      # neighbours in length share a batch
+    rs = _ext.Resampler(sr_in, sr_out, min(RESAMPLE_BATCH, len(signals)), max(1, max(len(s) for s in signals)))
+    out = [None] * len(signals)
+    try:
+        for a in range(0, len(order), RESAMPLE_BATCH):
+            idx = order[a:a + RESAMPLE_BATCH]
+            lens = [len(signals[i]) for i in idx]
+            blk = np.zeros((len(idx), max(1, max(lens))), np.float32)
+            for r, i in enumerate(idx):
+                blk[r, :lens[r]] = signals[i]
+            y, n_out = rs.run(torch.from_numpy(blk).cuda(), lens)
+            y = y.cpu().numpy()
+            for r, i in enumerate(idx):
+                out[i] = y[r, :n_out[r]].copy()
+    finally:
+        rs.close()
+    return out
 
 
 def preemphasis(wav, k, preemphasize=True):

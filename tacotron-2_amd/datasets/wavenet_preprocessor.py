@@ -6,7 +6,11 @@ Split in two so that at most one process opens the GPU.  The host steps of an ut
 range check, mu-law encoding with its own silence trim -- run in worker processes (spawned: they import numpy / scipy only and never touch
 the device).  The parent then takes the mel-spectrograms of all pre-emphasised signals from ONE _ext.MelAnalyzer in batches of neighbouring
 lengths (hparams.mi355_device_mel; False: datasets.audio.melspectrogram in numpy float64, utterance by utterance) and finishes each
-utterance: length clip, right padding with the encoding's silence value, truncation to mel_frames * hop, the two files, the row."""
+utterance: length clip, right padding with the encoding's silence value, truncation to mel_frames * hop, the two files, the row.
+
+hparams.mi355_resample_input (default off: a file at another rate than sample_rate is load_wav's error) lets the folder hold wavs of any rate: the
+parent reads the off-rate files, converts them rate by rate (resample_off_rate: one _ext.Resampler per rate on the GPU, csrc/wn_resample.hip; the host
+loop with the same bits where there is none) and hands the float32 signal to the worker in place of the path's samples.  Still one process on the GPU."""
 import os
 from concurrent.futures import ProcessPoolExecutor
 from multiprocessing import get_context
@@ -19,14 +23,16 @@ from wavenet_vocoder.util import is_mulaw, is_mulaw_quantize, mulaw, mulaw_quant
 DEVICE_BATCH = 32
 
 
-def _host_steps(wav_path, hparams):
+def _host_steps(wav_path, hparams, wav=None):
     """Reference _process_utterance lines 58-108.  -> None (file missing) or (encoded audio, float32 pre-emphasised signal for the mel
-    analysis, silence value, audio dtype name, length of the signal the padding is computed from)."""
-    try:
-        wav = audio.load_wav(wav_path, sr=hparams.sample_rate)
-    except FileNotFoundError:
-        print('skipped (vanished since the folder was listed): {}'.format(wav_path))
-        return None
+    analysis, silence value, audio dtype name, length of the signal the padding is computed from).  wav: the float32 signal at
+    hparams.sample_rate where the parent has already read and converted the file (mi355_resample_input); None: load it here."""
+    if wav is None:
+        try:
+            wav = audio.load_wav(wav_path, sr=hparams.sample_rate)
+        except FileNotFoundError:
+            print('skipped (vanished since the folder was listed): {}'.format(wav_path))
+            return None
     if hparams.trim_silence:
         wav = audio.trim_silence(wav, hparams)
     if wav.size == 0:
@@ -87,6 +93,32 @@ def _mels(signals, hparams):
         analyzer.close()
 
 
+def _wav_rate(path):
+    """the sample rate in the file's header (memory-mapped: the samples are not read); None for a file that has vanished"""
+    from scipy.io import wavfile
+    try:
+        return int(wavfile.read(path, mmap=True)[0])
+    except FileNotFoundError:
+        return None
+
+
+def resample_off_rate(paths, hparams):
+    """mi355_resample_input: {path: float32 signal at hparams.sample_rate} for the files of `paths` at another rate, read here and converted rate by rate
+    (audio.resample_signals: one handle per rate on the GPU, the host loop with the same bits without one).  Files at sample_rate are not in the result:
+    they never pass through the resampler."""
+    by_rate = {}
+    for p in paths:
+        rate = _wav_rate(p)
+        if rate is not None and rate != int(hparams.sample_rate):
+            by_rate.setdefault(rate, []).append(p)
+    converted = {}
+    for rate in sorted(by_rate):
+        signals = [audio.read_wav(p)[1] for p in by_rate[rate]]
+        for p, y in zip(by_rate[rate], audio.resample_signals(signals, rate, int(hparams.sample_rate))):
+            converted[p] = y
+    return converted
+
+
 def build_from_path(hparams, input_dir, mel_dir, wav_dir, n_jobs=12, tqdm=lambda x: x):
     """Preprocess every *.wav of input_dir (sorted by name: two runs write the same map.txt).  Returns the map.txt rows
     (audio_filename, mel_filename, mel_filename, '<no_g>', time_steps, mel_frames) of the utterances that were kept."""
@@ -94,12 +126,13 @@ def build_from_path(hparams, input_dir, mel_dir, wav_dir, n_jobs=12, tqdm=lambda
         raise NotImplementedError('use_lws: the lws package is not available')
     names = sorted(f for f in os.listdir(input_dir) if f.endswith('.wav'))
     paths = [os.path.join(input_dir, f) for f in names]
+    converted = resample_off_rate(paths, hparams) if getattr(hparams, 'mi355_resample_input', False) else {}      # (the parent: still one process on the GPU)
     if n_jobs and n_jobs > 1 and len(paths) > 1:
         with ProcessPoolExecutor(max_workers=min(n_jobs, len(paths)), mp_context=get_context('spawn')) as executor:
-            futures = [executor.submit(_host_steps, p, hparams) for p in paths]
+            futures = [executor.submit(_host_steps, p, hparams, converted.get(p)) for p in paths]
             hosts = [f.result() for f in tqdm(futures)]
     else:
-        hosts = [_host_steps(p, hparams) for p in tqdm(paths)]
+        hosts = [_host_steps(p, hparams, converted.get(p)) for p in tqdm(paths)]
     kept = [(f[:-len('.wav')], h) for f, h in zip(names, hosts) if h is not None]
     if not kept:
         return []

@@ -141,6 +141,13 @@ MI355 = dict(
                                      # for synthesis (csrc/wn_synth_f32.hip: fp32 weights and queues like WaveNet.incremental; far from real time)
     mi355_device_mel=False,         # mel analysis on the GPU (csrc/wn_mel.hip).  wavenet_preprocess.py turns it on unless --hparams says otherwise (False: the
                                      # numpy float64 path, datasets.audio.melspectrogram); synthesize.py --wavs_dir always analyses on the device
+    mi355_resample_input=False,     # True: wavenet_preprocess.py and synthesize.py --wavs_dir accept wavs of any sample rate: the parent converts the off-rate files to
+                                     # sample_rate (csrc/wn_resample.hip in batches, one handle per rate; datasets.audio.resample_host with the same bits where no GPU
+                                     # exists) before the host steps.  A Kaiser-windowed sinc with resampy's kaiser_best design values: close to librosa's load(sr=...),
+                                     # not equal to it.  False: a file at another rate is an error, as before; files at sample_rate never pass through the resampler
+    mi355_output_sample_rate=0,     # N > 0: the wavs Synthesizer writes are converted to N Hz after the de-emphasis and before the peak normalisation and the int16
+                                     # cast, on both mi355_output_stage settings and every route; the checks keep seeing the model-rate signal.  0: no handle is created,
+                                     # nothing of it runs and every file is byte-identical to a run without the key
 )
 
 

@@ -92,6 +92,11 @@ class WnDenoiseStreamConfig(ctypes.Structure):
                 ('in_type', ctypes.c_int32)]
 
 
+class WnResampleConfig(ctypes.Structure):
+    _fields_ = [('abi_version', ctypes.c_int32), ('max_rows', ctypes.c_int32), ('max_in', ctypes.c_int32), ('sr_in', ctypes.c_int32), ('sr_out', ctypes.c_int32),
+                ('zeros', ctypes.c_int32), ('beta', ctypes.c_double), ('rolloff', ctypes.c_double)]
+
+
 class WnFoldRow(ctypes.Structure):
     """wn_fold_row: one row of a folded run, in mel frames of utterance `utt`."""
     _fields_ = [('utt', ctypes.c_int32), ('first', ctypes.c_int32), ('frames', ctypes.c_int32), ('keep', ctypes.c_int32), ('fade', ctypes.c_int32)]
@@ -254,6 +259,16 @@ def load_library():
         'wn_denoise_stream_ready': (i64, [vp, i64, i32]),
         'wn_denoise_stream_push': (ctypes.c_int, [vp, vp, i64, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32), i32, f32, vp, i64, ctypes.POINTER(i32), vp]),
         'wn_test_denoise_stream_host': (ctypes.c_int, [ctypes.POINTER(WnDenoiseStreamConfig), vp, f32, vp, i64, vp, vp, vp, i32, i32, vp, i64, vp]),
+        'wn_resample_create': (ctypes.c_int, [ctypes.POINTER(WnResampleConfig), ctypes.POINTER(vp)]),
+        'wn_resample_destroy': (None, [vp]),
+        'wn_resample_last_error': (ctypes.c_char_p, [vp]),
+        'wn_resample_num_out': (i64, [vp, i64]),
+        'wn_resample_ready': (i64, [vp, i64, i32]),
+        'wn_resample_taps': (ctypes.c_int, [vp, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32)]),
+        'wn_resample_run': (ctypes.c_int, [vp, vp, i64, ctypes.POINTER(i32), i32, vp, i64, vp]),
+        'wn_resample_push': (ctypes.c_int, [vp, vp, i64, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32), i32, vp, i64, ctypes.POINTER(i32), vp]),
+        'wn_test_resample_host': (ctypes.c_int, [ctypes.POINTER(WnResampleConfig), vp, i64, vp, vp, vp, i32, i32, vp, i64, vp]),
+        'wn_test_resample_table': (ctypes.c_int, [ctypes.POINTER(WnResampleConfig), vp, i64]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)            # AttributeError here == ABI symbol missing
@@ -1598,6 +1613,174 @@ class DenoiseStream:
         if getattr(self, 'h', None):
             self.lib.wn_denoise_stream_destroy(self.h)
             self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---- sample-rate conversion (csrc/wn_resample.hip)
+RESAMPLE_ZEROS, RESAMPLE_BETA, RESAMPLE_ROLLOFF = 64, 14.769656459379492, 0.9475937167399596      # resampy's published kaiser_best design values
+
+
+def resample_config(sr_in, sr_out, max_rows=0, max_in=0, zeros=RESAMPLE_ZEROS, beta=RESAMPLE_BETA, rolloff=RESAMPLE_ROLLOFF):
+    cfg = WnResampleConfig()
+    cfg.abi_version = WN_ABI_VERSION
+    cfg.max_rows, cfg.max_in, cfg.sr_in, cfg.sr_out, cfg.zeros = int(max_rows), int(max_in), int(sr_in), int(sr_out), int(zeros)
+    cfg.beta, cfg.rolloff = float(beta), float(rolloff)
+    return cfg
+
+
+def resample_table(sr_in, sr_out, zeros=RESAMPLE_ZEROS, beta=RESAMPLE_BETA, rolloff=RESAMPLE_ROLLOFF):
+    """wn_test_resample_table: the float32 coefficient table C [L, T] of a configuration, as the device holds it ([0, 0] for sr_in == sr_out)."""
+    rs = Resampler(sr_in, sr_out, 0, 0, zeros, beta, rolloff)
+    C = np.zeros((rs.L, 2 * rs.W), np.float32)
+    rc = rs.lib.wn_test_resample_table(ctypes.byref(rs.cfg), C.ctypes.data_as(ctypes.c_void_p), C.size)
+    if rc != 0:
+        raise WnError(rc, (rs.lib.wn_resample_last_error(None) or b'').decode())
+    return C
+
+
+def resample_host(pushes, sr_in, sr_out, zeros=RESAMPLE_ZEROS, beta=RESAMPLE_BETA, rolloff=RESAMPLE_ROLLOFF, max_in=0):
+    """wn_test_resample_host: the state machine of Resampler.push as a plain float32 loop on numpy arrays (no handle, no GPU), bit-identical to the device.
+    pushes: a list of (block [B, pitch] float32, n [B], restart [B] or None, final [B] or None).  Returns a list of (out [B, out_pitch] float32, n_out [B]) per
+    push: out rows hold n_out[b] samples, what lies beyond keeps the fill it was given (`nan`)."""
+    vp = ctypes.c_void_p
+    P = len(pushes)
+    B = len(pushes[0][1])
+    ipitch = max([1] + [int(np.asarray(p[0]).reshape(B, -1).shape[1]) for p in pushes])
+    n = np.zeros((P, B), np.int32); rs = np.zeros((P, B), np.int32); fin = np.zeros((P, B), np.int32)
+    blk = np.full((P, B, ipitch), np.nan, np.float32)
+    for p, (x, nn, r, f) in enumerate(pushes):
+        x = np.asarray(x, dtype=np.float32).reshape(B, -1)
+        blk[p, :, :x.shape[1]] = x
+        n[p] = nn
+        if r is not None:
+            rs[p] = np.asarray(r, np.int32)
+        if f is not None:
+            fin[p] = np.asarray(f, np.int32)
+    cfg = resample_config(sr_in, sr_out, 0, max_in, zeros, beta, rolloff)
+    lib = load_library()
+    geo = Resampler(sr_in, sr_out, 0, max_in, zeros, beta, rolloff)
+    opitch = geo.num_out(max(0, int(n.max())) + 2 * geo.W) + 3      # a push emits the outputs of at most n + 2 W - 1 inputs
+    out = np.full((P, B, opitch), np.nan, np.float32)
+    n_out = np.full((P, B), -1, np.int32)
+    rc = lib.wn_test_resample_host(ctypes.byref(cfg), blk.ctypes.data_as(vp), ipitch, n.ctypes.data_as(vp), rs.ctypes.data_as(vp), fin.ctypes.data_as(vp), P, B,
+                                   out.ctypes.data_as(vp), opitch, n_out.ctypes.data_as(vp))
+    if rc != 0:
+        raise WnError(rc, (lib.wn_resample_last_error(None) or b'').decode())
+    return [(out[p], n_out[p]) for p in range(P)]
+
+
+def resample_rows_host(rows, sr_in, sr_out, zeros=RESAMPLE_ZEROS, beta=RESAMPLE_BETA, rolloff=RESAMPLE_ROLLOFF):
+    """Whole rows through wn_test_resample_host (one final push): a list of 1-D float32 arrays in, a list of float32 arrays of ceil(n L / M) samples out."""
+    rows = [np.ascontiguousarray(r, dtype=np.float32).reshape(-1) for r in rows]
+    blk = np.zeros((len(rows), max([1] + [len(r) for r in rows])), np.float32)
+    for b, r in enumerate(rows):
+        blk[b, :len(r)] = r
+    (out, n_out), = resample_host([(blk, [len(r) for r in rows], None, [1] * len(rows))], sr_in, sr_out, zeros, beta, rolloff)
+    return [out[b, :n_out[b]].copy() for b in range(len(rows))]
+
+
+class Resampler:
+    """One wn_resample: rows of float32 samples from sr_in to sr_out on the current device (csrc/wn_resample.hip), asynchronously: whole ragged rows (run) or
+    push by push with carried state (push; row = slot).  A row's pushed outputs, concatenated, are bit-identical to run on the whole row and to resample_host;
+    they lag the inputs by at most W samples (ready()).  rows = 0: a geometry-only handle (num_out, ready, L / M / W) that needs no GPU.  Use one handle from one
+    stream at a time."""
+
+    def __init__(self, sr_in, sr_out, rows, max_in, zeros=RESAMPLE_ZEROS, beta=RESAMPLE_BETA, rolloff=RESAMPLE_ROLLOFF):
+        self.lib = load_library()
+        self.cfg = resample_config(sr_in, sr_out, rows, max_in, zeros, beta, rolloff)
+        h = ctypes.c_void_p()
+        rc = self.lib.wn_resample_create(ctypes.byref(self.cfg), ctypes.byref(h))
+        if rc != 0:
+            raise WnError(rc, (self.lib.wn_resample_last_error(None) or b'').decode())
+        self.h = h
+        self.sr_in, self.sr_out, self.rows, self.max_in = int(sr_in), int(sr_out), int(rows), int(max_in)
+        L, M, W = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+        self._ok(self.lib.wn_resample_taps(self.h, ctypes.byref(L), ctypes.byref(M), ctypes.byref(W)))
+        self.L, self.M, self.W = int(L.value), int(M.value), int(W.value)
+
+    def _ok(self, rc):
+        if rc != 0:
+            raise WnError(rc, (self.lib.wn_resample_last_error(self.h) or b'').decode())
+
+    def num_out(self, n):
+        r = int(self.lib.wn_resample_num_out(self.h, int(n)))
+        if r < 0:
+            raise WnError(r, 'wn_resample_num_out(%d)' % n)
+        return r
+
+    def ready(self, S, final=False):
+        r = int(self.lib.wn_resample_ready(self.h, int(S), int(bool(final))))
+        if r < 0:
+            raise WnError(r, 'wn_resample_ready(%d)' % S)
+        return r
+
+    @staticmethod
+    def _rows(samples, n, what):
+        import torch
+        _check(samples, torch.float32, 'samples')
+        if samples.dim() == 1:
+            samples = samples.reshape(1, -1)
+        if samples.dim() != 2:
+            raise ValueError('samples must be [B, pitch]')
+        B, pitch = int(samples.shape[0]), int(samples.shape[1])
+        n = [pitch] * B if n is None else [int(v) for v in n]
+        if len(n) != B:
+            raise ValueError('one %s per row of samples (%d for %d rows)' % (what, len(n), B))
+        return samples, n, B, pitch
+
+    @staticmethod
+    def _out(out, B):
+        import torch
+        _check(out, torch.float32, 'out')
+        if out.dim() != 2 or int(out.shape[0]) != B:
+            raise ValueError('out must be [B, pitch] with one row per row of samples')
+        return int(out.shape[1])
+
+    def run(self, samples, lengths=None, out=None):
+        """samples [B, pitch] float32 on the device, lengths: B ints (None: the whole pitch).  Returns (out float32 [B, num_out(max(lengths))] on the device,
+        n_out: B ints): row b holds num_out(lengths[b]) samples, zeros beyond.  out: a float32 [B, pitch'] tensor to write into instead (elements beyond a
+        row's outputs keep their bytes).  Carried state is neither read nor written."""
+        import torch
+        samples, n, B, pitch = self._rows(samples, lengths, 'length')
+        if out is None:
+            out = torch.zeros(B, max(1, self.num_out(max(max(n), 0))), dtype=torch.float32, device=samples.device)
+        opitch = self._out(out, B)
+        self._ok(self.lib.wn_resample_run(self.h, _ptr(samples), pitch, (ctypes.c_int32 * B)(*n), B, _ptr(out), opitch, _stream()))
+        return out, [self.num_out(v) for v in n]
+
+    def push(self, samples, n=None, restart=None, final=None, out=None):
+        """samples [B, pitch] float32 on the device, n: B ints (None: the whole pitch), restart / final: B flags (None: none; True: all).  Returns (out float32
+        [B, pitch'] on the device, n_out: B ints): row b's next n_out[b] samples at sr_out, zeros beyond (with out given: its bytes kept)."""
+        import torch
+        samples, n, B, pitch = self._rows(samples, n, 'count')
+
+        def flags(v, name):
+            if v is None:
+                return None
+            f = [1] * B if v is True else [int(bool(x)) for x in v]
+            if len(f) != B:
+                raise ValueError('one %s flag per row' % name)
+            return (ctypes.c_int32 * B)(*f)
+        rs, fin = flags(restart, 'restart'), flags(final, 'final')
+        if out is None:
+            out = torch.zeros(B, self.num_out(max(max(n), 0) + 2 * self.W) + 1, dtype=torch.float32, device=samples.device)      # a push emits the outputs of at most n + 2 W - 1 inputs
+        opitch = self._out(out, B)
+        n_out = (ctypes.c_int32 * B)()
+        self._ok(self.lib.wn_resample_push(self.h, _ptr(samples), pitch, (ctypes.c_int32 * B)(*n), rs, fin, B, _ptr(out), opitch, n_out, _stream()))
+        return out, [int(v) for v in n_out]
+
+    def close(self):
+        if getattr(self, 'h', None):
+            self.lib.wn_resample_destroy(self.h)
+            self.h = None
+        if getattr(self, 'tail', None) is not None:      # (WaveNet.output_resampler's int16 stage)
+            self.tail.close()
+            self.tail = None
 
     def __del__(self):
         try:

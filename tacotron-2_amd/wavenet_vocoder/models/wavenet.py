@@ -113,6 +113,29 @@ def _denoise_push(model, ds, strength, out, n, restart, final, post, post_output
     return _post_push(post, post_output, y, n_out, restart), n_out
 
 
+def _resample_push(rs, out, n, restart, final, post, post_output, denoise, model, strength):
+    """The playable chunk of a synthesis push at the output rate: the float32 chain at the model rate (denoise if given, then post's decode and de-emphasis),
+    then one Resampler.push (rs: WaveNet.output_resampler; row = row of the push, restarted and ended with it), then what post_output names: the float32
+    chunk, its int16 cast at rs.tail's gain, or both as (pcm, float).  Returns (chunk, n_out): n_out[b] samples of row b at the output rate."""
+    if post_output not in ('pcm', 'float', 'both'):
+        raise ValueError("post_output must be 'pcm', 'float' or 'both' (got {!r})".format(post_output))
+    if denoise is not None:
+        y, n_y = _denoise_push(model, denoise, strength, out, n, restart, final, post, 'float')
+    else:
+        y, n_y = _post_push(post, 'float', out, n, restart), n
+    z, n_out = rs.push(y, n=n_y, restart=restart, final=final)
+    if post_output == 'float':
+        return z, n_out
+    q = rs.tail.push(z, n=n_out, restart=restart)
+    return (q if post_output == 'pcm' else (q, z)), n_out
+
+
+def _resample_check(resample, post, denoise):
+    """resample= works on decoded float32 samples: it needs the output stage or the denoiser in front of it"""
+    if resample is not None and post is None and denoise is None:
+        raise ValueError('resample= needs post= (an OutputStage: the decode and the de-emphasis at the model rate) or denoise= in front of it')
+
+
 class SynthesisStream(object):
     """Generation of B utterances chunk by chunk as their mel frames arrive (WaveNet.stream): the samples are bit-identical to one
     WaveNet.incremental-style run over the concatenated frames with the same seed.  push() returns the samples whose conditioning is now
@@ -132,7 +155,7 @@ class SynthesisStream(object):
         model.engine.stream_begin(self.B, seed=seed, steps_per_graph=steps_per_graph)
         self.closed = False
 
-    def push(self, c_frames=None, final=False, noise=None, test_inputs=None, return_raw=False, post=None, post_output='pcm', denoise=None, denoise_strength=None):
+    def push(self, c_frames=None, final=False, noise=None, test_inputs=None, return_raw=False, post=None, post_output='pcm', denoise=None, denoise_strength=None, resample=None):
         """c_frames [B, cin, Tn] (None or Tn = 0: no new frames); noise [n, B, noise_per_step] / test_inputs [B, n] of the span this push
         generates (its length follows from stream_schedule and the lookahead).  post: an OutputStage (WaveNet.output_stage) of >= B rows: the
         playable chunk [B, n] -- decoded, de-emphasised, int16 at the stage's gain (post_output 'float': float32; 'both': (int16, float32)) -- is
@@ -140,11 +163,15 @@ class SynthesisStream(object):
         denoise: an _ext.DenoiseStream (WaveNet.stream_denoiser) of >= B rows and max_push >= n: the samples of this push are decoded and denoised by it
         (strength denoise_strength; None: mi355_output_denoise) and what it emits goes to post, which must then be an OutputStage with in_type='raw'.  The
         playable chunk is the denoised one: it lags the samples by S - E < n_fft (DenoiseStream.ready) and the final push returns the flushed rest; without
-        post it is the denoised float32 chunk.  The generated samples are the same with or without denoise."""
+        post it is the denoised float32 chunk.  The generated samples are the same with or without denoise.
+        resample: a WaveNet.output_resampler of >= B rows, behind post and / or denoise: the playable chunk is converted to its sample rate after the
+        de-emphasis and before the int16 cast (at the resampler's tail stage), lags by at most W more input samples (Resampler.ready) and the final push
+        flushes; its length is what the resampler emitted.  The generated samples are the same with or without it."""
         if self.closed:
             raise RuntimeError('SynthesisStream: the stream is closed')
         if denoise is not None:
             _denoise_post_check(post)
+        _resample_check(resample, post, denoise)
         m = self.model
         cc = None
         if c_frames is not None and int(c_frames.shape[-1]) > 0:
@@ -166,7 +193,12 @@ class SynthesisStream(object):
         if final:
             self.closed = True
         chunk = None
-        if denoise is not None:
+        if resample is not None:
+            chunk, n_out = _resample_push(resample, out, [n] * self.B, None if getattr(self, '_post_started', False) else True, [final] * self.B, post, post_output,
+                                          denoise, m, denoise_strength)
+            self._post_started = True
+            chunk = tuple(t[:, :n_out[0]] for t in chunk) if isinstance(chunk, tuple) else chunk[:, :n_out[0]]      # (every row has the same S: the same n_out)
+        elif denoise is not None:
             chunk, n_out = _denoise_push(m, denoise, denoise_strength, out, [n] * self.B, None if getattr(self, '_post_started', False) else True, [final] * self.B,
                                          post, post_output)
             self._post_started = True
@@ -291,18 +323,20 @@ class SlotSession(object):
         self.done[slot], self.pushed[slot] = 0, 0
         self._post_restart.add(int(slot))
 
-    def push(self, items, return_raw=False, post=None, post_output='pcm', denoise=None, denoise_strength=None):
+    def push(self, items, return_raw=False, post=None, post_output='pcm', denoise=None, denoise_strength=None, resample=None):
         """items {slot: frames [cin, Tn]} or {slot: (frames, final)}: append the frames to the slots' utterances (final: the utterance ends, the slot
         is idle afterwards).  Returns {slot: samples [n]} (or (samples, raw [O, n]) with return_raw) for every slot named.  post: an OutputStage of
         >= B rows (row = slot): every slot's playable chunk [n] (SynthesisStream.push) follows as a last element; a slot's filter runs on from push
         to push and starts afresh at the first push after its open().  denoise: an _ext.DenoiseStream (WaveNet.stream_denoiser) of >= B rows
         (row = slot), as SynthesisStream.push: a slot's chunk is then the denoised one (its length is what the denoiser emitted, the slot's final push
         returns the flushed rest), a slot opened anew restarts its row in the denoiser together with its row in post, and an abandoned slot's row is
-        restarted at the next open."""
+        restarted at the next open.  resample: a WaveNet.output_resampler of >= B rows (row = slot), as SynthesisStream.push: a slot's chunk is at its
+        sample rate, a slot opened anew restarts its row there too, and the slot's final push flushes."""
         if self.closed:
             raise RuntimeError('SlotSession: the session is closed')
         if denoise is not None:
             _denoise_post_check(post)
+        _resample_check(resample, post, denoise)
         m, hp = self.model, self.model._hparams
         frames, final, blocks = [0] * self.B, [False] * self.B, {}
         for b, it in items.items():
@@ -333,7 +367,9 @@ class SlotSession(object):
         chunk, nc = None, n      # nc: the length of every slot's chunk
         if post is not None or denoise is not None:
             restart = [int(b in self._post_restart and b in items) for b in range(self.B)]
-            if denoise is not None:
+            if resample is not None:
+                chunk, nc = _resample_push(resample, out, n, restart, [int(f) for f in final], post, post_output, denoise, m, denoise_strength)
+            elif denoise is not None:
                 chunk, nc = _denoise_push(m, denoise, denoise_strength, out, n, restart, [int(f) for f in final], post, post_output)
             else:
                 chunk = _post_push(post, post_output, out, n, restart)
@@ -1030,6 +1066,15 @@ class WaveNet(object):
         if source is not None:
             ds.take_profile(source)
         return ds
+
+    def output_resampler(self, rows, max_push, sample_rate):
+        """An _ext.Resampler of `rows` rows from hparams.sample_rate to `sample_rate` for pushes (or whole rows) of up to `max_push` samples per row
+        (csrc/wn_resample.hip): the resample= argument of SynthesisStream.push / SlotSession.push, and what Synthesizer runs when
+        mi355_output_sample_rate is set.  Its .tail is a raw OutputStage without de-emphasis at mi355_output_gain: the int16 cast behind the conversion.
+        max_push counts what reaches the resampler in one call: with denoise= in front, a final push can flush up to n_fft samples more."""
+        rs = _ext.Resampler(int(self._hparams.sample_rate), int(sample_rate), rows, max_push)
+        rs.tail = self.output_stage(rows, in_type='raw', deemphasis=0.0)
+        return rs
 
     def train_stats(self):
         """The model's _ext.TrainStats (csrc/wn_stats.hip), built at the first call: histograms of up to max_batch rows of max_time samples and the

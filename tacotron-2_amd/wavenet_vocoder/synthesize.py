@@ -56,6 +56,17 @@ def run_synthesis(args, checkpoint_path, output_dir, hparams):
     log('synthesized audio waveforms at {}'.format(wav_dir))
 
 
+def load_recordings(paths, hparams):
+    """The recordings as float32 at hparams.sample_rate: audio.load_wav, which refuses another rate -- unless mi355_resample_input is on: then the off-rate
+    files are converted first (datasets.wavenet_preprocessor.resample_off_rate: one handle per rate on the device) and the others are loaded as ever."""
+    from datasets import audio
+    converted = {}
+    if getattr(hparams, 'mi355_resample_input', False):
+        from datasets.wavenet_preprocessor import resample_off_rate
+        converted = resample_off_rate(paths, hparams)
+    return [converted[p] if p in converted else audio.load_wav(p, sr=hparams.sample_rate) for p in paths]
+
+
 def analyse_wavs(paths, hparams, batch=32):
     """The conditioning mels of recordings, as preprocessing makes them (wavenet_preprocessor.py lines 71-76, 111: pre-emphasis, rescale to
     rescaling_max, melspectrogram) with every step on the device: wn_mel_peak gives max |preem_wav|, the gain rescaling_max / peak and the
@@ -63,7 +74,7 @@ def analyse_wavs(paths, hparams, batch=32):
     import torch
     from datasets import audio
     from wavenet_vocoder import _ext
-    wavs = [audio.load_wav(p, sr=hparams.sample_rate) for p in paths]
+    wavs = load_recordings(paths, hparams)
     for p, w in zip(paths, wavs):
         if w.size == 0:
             raise RuntimeError('empty recording: {}'.format(p))
@@ -95,7 +106,7 @@ def pitch_references(paths, hparams):
     """The recordings as the pitch check takes them (mi355_pitch_check): pre-emphasised as preprocessing does it, so that they stand beside the
     model-domain output; the estimator is scale-invariant, so the rescale is left out."""
     from datasets import audio
-    return [audio.preemphasis(audio.load_wav(p, sr=hparams.sample_rate), hparams.preemphasis, hparams.preemphasize).astype(np.float32) for p in paths]
+    return [audio.preemphasis(w, hparams.preemphasis, hparams.preemphasize).astype(np.float32) for w in load_recordings(paths, hparams)]
 
 
 def run_wav_synthesis(args, checkpoint_path, output_dir, hparams):

@@ -82,6 +82,31 @@ class Synthesizer(object):
         deem = bool(getattr(hparams, 'mi355_output_deemphasis', False)) and bool(hparams.preemphasize)
         return stage == 'device', (float(np.float32(hparams.preemphasis)) if deem else 0.0)
 
+    def _output_rate(self):
+        """mi355_output_sample_rate: the rate of the written wavs, or 0 (off: no handle exists and nothing of it runs)"""
+        rate = int(getattr(self._hparams, 'mi355_output_sample_rate', 0) or 0)
+        if rate < 0:
+            raise ValueError('mi355_output_sample_rate must be >= 0 (got {!r})'.format(rate))
+        return rate
+
+    def _resample_device(self, wavs, rate):
+        """De-emphasised float32 utterances at the model rate (host arrays) -> (float32, peak-normalised int16) per utterance at `rate`: one
+        Resampler.run on the device (WaveNet.output_resampler, kept; replaced by a larger one when it is too small), then its raw tail stage's finish."""
+        lens = [len(w) for w in wavs]
+        rs = getattr(self, '_resampler', None)
+        if rs is None or rs.sr_out != rate or rs.rows < len(wavs) or rs.max_in < max(lens):
+            rows, cap = max(len(wavs), rs.rows if rs else 0), max(max(lens), rs.max_in if rs else 0, 1)
+            if rs is not None:
+                rs.close()
+            rs = self._resampler = self.model.output_resampler(rows, cap, rate)
+        host = np.zeros((len(wavs), max(max(lens), 1)), np.float32)
+        for b, w in enumerate(wavs):
+            host[b, :lens[b]] = np.asarray(w, np.float32)
+        z, n_out = rs.run(torch.from_numpy(host).to(self.model.device), lens)
+        y, q = rs.tail.finish(z, n_out)
+        y, q = y.cpu().numpy(), q.cpu().numpy()
+        return [y[b, :n] for b, n in enumerate(n_out)], [q[b, :n] for b, n in enumerate(n_out)]
+
     def _stage(self, rows, in_type, k):
         """The output stage of (in_type, k) with at least `rows` rows (kept: a stage is a handle with device state)."""
         st = self._post_stages.get((in_type, k))
@@ -428,9 +453,21 @@ class Synthesizer(object):
         hparams = self._hparams
         k = self._output_mode()[1]
         audio_filenames = []
+        rate, converted = self._output_rate(), None
+        if rate > 0:      # after the de-emphasis (a filter designed at the model rate), before the peak normalisation and the int16 cast; the plots keep the model-rate signal
+            if pcm is not None:
+                converted = self._resample_device(generated_wavs, rate)[1]
+            else:
+                from datasets import audio
+                deem = [inv_preemphasis(w, k).astype(np.float32) if k != 0.0 else np.asarray(w, np.float32) for w in generated_wavs]
+                converted = audio.resample_signals(deem, hparams.sample_rate, rate)
         for i, (wav, feat, input_mel) in enumerate(zip(generated_wavs, upsampled_features, mel_spectrograms)):
             audio_filename = os.path.join(out_dir, 'wavenet-audio-{}.wav'.format(basenames[i]))
-            if pcm is not None:
+            if converted is not None and pcm is not None:
+                wavfile.write(audio_filename, rate, converted[i])
+            elif converted is not None:
+                save_wavenet_wav(converted[i], audio_filename, sr=rate, inv_preemphasize=hparams.preemphasize, k=hparams.preemphasis)
+            elif pcm is not None:
                 wavfile.write(audio_filename, hparams.sample_rate, pcm[i])
             else:
                 if k != 0.0:
