@@ -801,6 +801,39 @@ int  wn_resample_run(wn_resample* h, const float* in, int64_t in_pitch, const in
 int  wn_resample_push(wn_resample* h, const float* in, int64_t in_pitch, const int32_t* n, const int32_t* restart, const int32_t* final, int32_t B, float* out,
                       int64_t out_pitch, int32_t* n_out, void* stream);
 
+/* ---- streaming mel analysis (csrc/wn_mel_stream.hip) --------------------------------------------
+ * wn_mel_run on rows that arrive push by push (row = slot: the front end of a live vocoder).  A handle of its own; additions only, WN_ABI_VERSION unchanged.
+ * A row's frames, concatenated over its pushes, are bit-identical to wn_mel_run of the whole row with the same gain and pre-emphasis, however the row was cut:
+ * every frame's sums run in wn_mel's order (csrc/wn_mel.h) whichever tile it falls into.
+ * Geometry as wn_mel: off = (n_fft - win_size) / 2, Hl = n_fft / 2 - off, Hr = win_size - Hl; frame f reads y[f hop - Hl ... f hop + Hr), y = 0 outside the row,
+ * y[s] = gain (x[s] - preemphasis x[s - 1]) in three separately rounded operations, x[-1] = 0.
+ * Rule of readiness (beside E of wn_denoise_stream): a row that has consumed S samples since its restart has had its frames f with f hop + Hr <= S analysed,
+ * (S - Hr) / hop + 1 of them (0 for S < Hr); when the row is final, all 1 + S / hop frames, zeros beyond the end, as wn_mel_run pads.  wn_mel_stream_ready
+ * returns that count; the frames lag the samples by Hr (550 samples, about 25 ms, at the default 2048 / 1100 / 275).
+ * Per row the handle keeps, all reserved by create: the analysed-domain tail y[max(0, F hop - Hl), S) the next frame still needs (fewer than win_size samples,
+ * double-buffered on the device: a push reads one half and writes the other), the raw last sample x[S - 1] for the pre-emphasis, the gain latched at the
+ * restart, and the counters S and F on the host (they travel as kernel arguments).  No call allocates, uses atomics or synchronises; rows go in groups of 64
+ * per launch; calls on one handle belong on one stream at a time.  cfg->max_batch and cfg->max_samples are ignored.  max_rows = 0 makes a geometry-only
+ * handle: no device is touched, wn_mel_stream_ready works and wn_mel_stream_push refuses every B.
+ * Validation before any device call.  WN_E_ARG: a null pointer, a foreign abi_version, negative max_rows / n[b] / pitches, max_push < 1, B < 1, a gain that is
+ * not finite, and wn_mel's.  WN_E_STATE: a push (n[b] > 0 or final[b]) on a row that ended without restart[b].  WN_E_SHAPE: wn_mel's geometry rules,
+ * B > max_rows, n[b] > max_push or > in_pitch, out_pitch below some n_out[b], a row beyond 2^31 - 1 samples since its restart.  WN_E_UNSUPPORTED: the limits
+ * of wn_mel: num_mels > 128, n_fft > 65536, 31 hop_size + win_size floats beyond the 160 KiB LDS. */
+typedef struct wn_mel_stream wn_mel_stream;
+int  wn_mel_stream_create(const wn_mel_config* cfg, const float* mel_basis, int32_t max_rows, int32_t max_push, wn_mel_stream** out);
+void wn_mel_stream_destroy(wn_mel_stream* h);
+const char* wn_mel_stream_last_error(const wn_mel_stream* h);   /* NULL: text of the last failed create or host hook */
+/* frames analysed of a row at S (host only); WN_E_ARG for a NULL handle or an S outside [0, 2^31 - 1] */
+int64_t wn_mel_stream_ready(const wn_mel_stream* h, int64_t S, int32_t final);
+/* in: device float [B, in_pitch], row b's next n[b] samples (never read beyond n[b]; NULL allowed when every n[b] is 0); out: device float
+ * [B, out_pitch, num_mels] (channels_first = 0) or [B, num_mels, out_pitch] (1), row b receives n_out[b] frames, elements beyond keep the caller's bytes.
+ * n, restart, final, n_out: HOST int32 [B]; gain: HOST float [B]; restart, final and gain may be NULL.  n_out is computed from the counters and written before
+ * the call returns.  restart[b]: row b starts at S = F = 0 before it consumes its samples, inherits nothing, and latches gain[b] (1 with a NULL gain) for its
+ * life; gain[b] is read nowhere else.  final[b]: the row ends, its remaining frames are flushed, and its next push must restart it.  A row with n[b] = 0 that
+ * is neither restarted nor final is left alone.  A failed call changes no row. */
+int  wn_mel_stream_push(wn_mel_stream* h, const float* in, int64_t in_pitch, const int32_t* n, const int32_t* restart, const int32_t* final, const float* gain, int32_t B,
+                        float* out, int64_t out_pitch, int32_t channels_first, int32_t* n_out, void* stream);
+
 /* ---- introspection ------------------------------------------------------------------------------ */
 int64_t wn_workspace_bytes(const wn_ctx* ctx);
 /* name of the kernel that dominates training time (bench.py's roofline line names it) */
@@ -920,6 +953,12 @@ int wn_test_denoise_stream_host(const wn_denoise_stream_config* cfg, const float
 int wn_test_resample_host(const wn_resample_config* cfg, const float* in, int64_t in_pitch, const int32_t* n, const int32_t* restart, const int32_t* final, int32_t P,
                           int32_t B, float* out, int64_t out_pitch, int32_t* n_out);
 int wn_test_resample_table(const wn_resample_config* cfg, float* table, int64_t cap);
+/* the plan of wn_mel_stream_push (csrc/wn_mel_stream.h: validation, counters, the rule of readiness) over P pushes of B rows on a GEOMETRY-ONLY handle (WN_E_STATE
+ * otherwise), on rows of its own and with no limit on B; no device, and `in` is only tested against NULL.  n, restart, final: HOST int32 [P, B] (restart and final may be
+ * NULL).  Per push: status [P] is what the push would return (a refused push changes no row); per push and row, [P, B]: n_out, first_frame (the index of the row's first
+ * new frame), and after the push tail_len (carried samples; always below win_size), S and F. */
+int wn_test_mel_stream_plan(const wn_mel_stream* h, const float* in, int64_t in_pitch, const int32_t* n, const int32_t* restart, const int32_t* final, int32_t P, int32_t B,
+                            int64_t out_pitch, int32_t* status, int32_t* n_out, int64_t* first_frame, int32_t* tail_len, int64_t* S, int64_t* F);
 #endif /* WN_NO_TEST_HOOKS */
 
 #ifdef __cplusplus

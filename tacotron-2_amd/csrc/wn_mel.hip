@@ -10,21 +10,17 @@
 // accumulation, k ascending: a fixed order) and forms the power in registers; the powers of 32 frames x the chunk's 128 bins meet in an LDS patch,
 // from which wave w < ldm / 32 adds their product with the mel filters of mels 32 w ... 32 w + 31 to its [TF, 32] mel accumulator (bins ascending).
 // Then level, normalisation and the store in either layout.  No atomics, no split of the tap sum or the bin sum across workgroups, no scratch in HBM.
-#include "wn_common.h"
-#include <cmath>
-#include <vector>
+// Everything behind the staging is mel_core of wn_mel.h, which the streaming form (wn_mel_stream.hip) runs too: this file keeps the staging loop and the store.
+#include "wn_mel.h"
 
 struct wn_mel {
     wn_mel_config cfg;
     std::string err;
-    int NB = 0, G = 0, off = 0, win_pad = 0, MT = 0, FR = 0, ldb = 0, ldm = 0, n_cu = 256;      // FR: the largest frame tile / 32 this context runs
+    MelGeom g;
+    int FR = 0, n_cu = 256;                        // FR: the largest frame tile / 32 this context runs
     bool fixed_tile = false;                       // WN_MEL_TF: every call runs FR (the A/B of tools/mel_timing.py)
-    float min_lin = 0.f;
     DevBuf<float> basis, melT;                     // [win_pad][G][re 32 | im 32] window x cos / -sin;  [32 G][32 MT] mel filters transposed, zero padded
 };
-
-#define MEL_GROUP 64      // utterances per launch: their lengths travel as kernel arguments (no device copy of the host array, nothing to allocate)
-#define MEL_STAGE (32 * 129)      // power of 32 frames x the chunk's 128 bins, odd pitch
 
 struct MelArgs {
     const float* wav; int64_t ld; const float* gain; float* out; const float* basis; const float* melT;
@@ -35,27 +31,11 @@ struct MelArgs {
     int32_t n[MEL_GROUP];
 };
 
-// y[s] = gain * (x[s] - k_pre * x[s - 1]): three separately rounded operations (what numpy does on float32 arrays), the same in both kernels
-static __device__ __forceinline__ float mel_preem(const float* __restrict__ x, int64_t s, float kpre) {
-    return __fsub_rn(x[s], __fmul_rn(kpre, s > 0 ? x[s - 1] : 0.0f));
-}
-
-// audio.py:257-270: S = 20 log10(max(min_level, M)) - ref_level_db, then _normalize (without its assert)
-static __device__ __forceinline__ float mel_finish(const MelArgs& a, float M) {
-    const float S = 20.0f * log10f(fmaxf(a.min_lin, M)) - a.ref_db;
-    if (!a.norm) return S;
-    const float u = (S - a.lo) / (-a.lo);
-    float v = a.symmetric ? (2.0f * a.maxabs) * u - a.maxabs : a.maxabs * u;
-    if (a.clip) v = fminf(fmaxf(v, a.symmetric ? -a.maxabs : 0.0f), a.maxabs);
-    return v;
-}
-
 template <int FR>
 __global__ __launch_bounds__(256) void wn_mel_kernel(const MelArgs a) {
     extern __shared__ float lds[];
     constexpr int TF = FR * 32;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int l31 = lane & 31, lh = lane >> 5;
+    const int tid = threadIdx.x;
     const int b = blockIdx.y, n = a.n[b], Fb = 1 + n / a.hop;
     const int f0 = blockIdx.x * TF;
     const int64_t ub = a.b0 + b;
@@ -72,7 +52,6 @@ __global__ __launch_bounds__(256) void wn_mel_kernel(const MelArgs a) {
         return;
     }
     float* sig = lds;
-    float* stage = lds + a.sig_floats;
     {   // the contiguous span of this tile's frames: sig[i] = y[f0 hop + off - n_fft / 2 + i], zero outside the utterance
         const float* x = a.wav + ub * a.ld;
         const float g = a.gain ? a.gain[ub] : 1.0f;
@@ -83,74 +62,7 @@ __global__ __launch_bounds__(256) void wn_mel_kernel(const MelArgs a) {
         }
     }
     __syncthreads();
-    f32x16_t macc[FR];      // mel tile (frame subtile i, mels 32 wave ... 32 wave + 31): waves >= mt hold none
-#pragma unroll
-    for (int i = 0; i < FR; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) macc[i][r] = 0.0f;
-    const float* sp = sig + l31 * a.hop + lh;      // A operand of frame subtile i, taps k / k + 1: lane l holds frame 32 i + l % 32, tap k + l / 32
-    for (int c = 0; c < a.nchunks; ++c) {
-        const int g = c * 4 + wave;                // this wave's bin group (the basis is padded to 4 nchunks groups: no divergence)
-        f32x16_t re[FR], im[FR];
-#pragma unroll
-        for (int i = 0; i < FR; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { re[i][r] = 0.0f; im[i][r] = 0.0f; }
-        const float* bp = a.basis + (size_t)lh * a.ldb + g * 64 + l31;      // B operand: lane l holds basis[k + l / 32][column l % 32]
-        // taps in bodies of 8 (win_pad is a multiple of 8, zero rows beyond win_size): the basis loads of the next body are in flight while this one is multiplied
-        float nre[4], nim[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) { nre[u] = bp[(size_t)(2 * u) * a.ldb]; nim[u] = bp[(size_t)(2 * u) * a.ldb + 32]; }
-        for (int k0 = 0; k0 < a.win_pad; k0 += 8) {
-            float bre[4], bim[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) { bre[u] = nre[u]; bim[u] = nim[u]; }
-            if (k0 + 8 < a.win_pad) {
-#pragma unroll
-                for (int u = 0; u < 4; ++u) { nre[u] = bp[(size_t)(k0 + 8 + 2 * u) * a.ldb]; nim[u] = bp[(size_t)(k0 + 8 + 2 * u) * a.ldb + 32]; }
-            }
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-#pragma unroll
-                for (int i = 0; i < FR; ++i) {
-                    const float av = sp[i * 32 * a.hop + k0 + 2 * u];
-                    re[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bre[u], re[i], 0, 0, 0);
-                    im[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bim[u], im[i], 0, 0, 0);
-                }
-        }
-#pragma unroll
-        for (int i = 0; i < FR; ++i) {
-            // accumulator register r of lane l is (frame 8 (r / 4) + 4 (l / 32) + r % 4, bin l % 32): through the wave's LDS patch into the A layout
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                float p = re[i][r] * re[i][r] + im[i][r] * im[i][r];
-                if (a.pow_mode == 1) p = sqrtf(p); else if (a.pow_mode == 2) p = powf(p, a.pow_half);
-                stage[((r >> 2) * 8 + lh * 4 + (r & 3)) * 129 + wave * 32 + l31] = p;
-            }
-            __syncthreads();
-            if (wave < a.mt) {      // [32 frames, 128 bins of this chunk] x [128, 32 mels]: bins ascending, chunks ascending -- a fixed order
-                const float* mp = a.melT + (size_t)(c * 128 + lh) * a.ldm + wave * 32 + l31;
-#pragma unroll 8
-                for (int kk = 0; kk < 128; kk += 2)
-                    macc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(stage[l31 * 129 + kk + lh], mp[(size_t)kk * a.ldm], macc[i], 0, 0, 0);
-            }
-            __syncthreads();
-        }
-    }
-    // mel sums through LDS to the threads that finish and store them (red overlays the signal span, which is dead now)
-    float* red = lds;
-    if (wave < a.mt) {
-#pragma unroll
-        for (int i = 0; i < FR; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) red[(i * 32 + (r >> 2) * 8 + lh * 4 + (r & 3)) * a.ldm + wave * 32 + l31] = macc[i][r];
-    }
-    __syncthreads();
-    for (int e = tid; e < TF * a.num_mels; e += 256) {
-        int f, m;
-        if (a.channels_first) { f = e % TF; m = e / TF; } else { f = e / a.num_mels; m = e % a.num_mels; }
-        store(f, m, (f0 + f < Fb) ? mel_finish(a, red[f * a.ldm + m]) : pad);
-    }
+    mel_core<FR>(a, lds, Fb - f0, pad, store);
 }
 
 struct PeakArgs { const float* wav; int64_t ld; float* peak; int32_t b0; float kpre; int32_t n[MEL_GROUP]; };
@@ -174,14 +86,7 @@ __global__ __launch_bounds__(1024) void wn_mel_peak_kernel(const PeakArgs a) {
 typedef void (*mel_kernel_t)(const MelArgs);
 static mel_kernel_t mel_kernel(int FR) { return FR == 1 ? wn_mel_kernel<1> : FR == 2 ? wn_mel_kernel<2> : wn_mel_kernel<4>; }
 
-// LDS of a tile of FR x 32 frames: the signal span (or the mel buffer that overlays it) + the power patch
-static size_t mel_lds(const wn_mel* m, int FR, int* sig_floats) {
-    const int64_t span = (int64_t)(FR * 32 - 1) * m->cfg.hop_size + m->win_pad, red = (int64_t)FR * 32 * m->ldm;
-    const int64_t sf = span > red ? span : red;
-    if (sf > (1 << 22)) return (size_t)1 << 30;
-    if (sig_floats) *sig_floats = (int)sf;
-    return (size_t)(sf + MEL_STAGE) * 4;
-}
+static size_t mel_lds(const wn_mel* m, int FR, int* sig_floats) { return mel_lds(m->cfg, m->g, FR, sig_floats); }
 
 /* datasets/audio.py:70-77, 178-182, 243-270: the geometry and level hparams of melspectrogram; mel_basis = _build_mel_basis (librosa.filters.mel) */
 extern "C" int wn_mel_create(const wn_mel_config* cfg, const float* mel_basis, wn_mel** out) {
@@ -190,25 +95,13 @@ extern "C" int wn_mel_create(const wn_mel_config* cfg, const float* mel_basis, w
     *out = nullptr;
     if (cfg->abi_version != WN_ABI_VERSION) WN_FAIL(z, WN_E_ARG, "wn_mel_create: abi_version %d != %d", cfg->abi_version, WN_ABI_VERSION);
     if (!mel_basis) WN_FAIL(z, WN_E_ARG, "wn_mel_create: mel_basis is null");
-    if (cfg->n_fft < 2 || cfg->n_fft % 2) WN_FAIL(z, WN_E_SHAPE, "n_fft (%d) must be even and >= 2", cfg->n_fft);
-    if (cfg->win_size < 1 || cfg->win_size > cfg->n_fft) WN_FAIL(z, WN_E_SHAPE, "win_size (%d) must be in [1, n_fft = %d]", cfg->win_size, cfg->n_fft);
-    if (cfg->hop_size < 1) WN_FAIL(z, WN_E_SHAPE, "hop_size (%d) must be >= 1", cfg->hop_size);
-    if (cfg->num_mels < 1) WN_FAIL(z, WN_E_SHAPE, "num_mels (%d) must be >= 1", cfg->num_mels);
-    if (cfg->num_mels > 128) WN_FAIL(z, WN_E_UNSUPPORTED, "num_mels (%d) > 128: the mel accumulator tiles are built for up to 128", cfg->num_mels);
-    if (!(cfg->magnitude_power > 0.f)) WN_FAIL(z, WN_E_ARG, "magnitude_power (%g) must be > 0", (double)cfg->magnitude_power);
-    if (cfg->signal_normalization && !(cfg->min_level_db < 0.f)) WN_FAIL(z, WN_E_ARG, "min_level_db (%g) must be < 0 for signal_normalization", (double)cfg->min_level_db);
+    { char msg[256]; if (int rc = mel_check_geometry(cfg, msg, sizeof msg)) WN_FAIL(z, rc, "%s", msg); }
     if (cfg->max_batch < 0 || cfg->max_samples < 0 || cfg->max_samples > 0x7fffffffLL) WN_FAIL(z, WN_E_ARG, "max_batch / max_samples must be in [0, 2^31)");
     if (cfg->n_fft > (1 << 16)) WN_FAIL(z, WN_E_UNSUPPORTED, "n_fft (%d) > 65536", cfg->n_fft);
 
     wn_mel* m = new wn_mel();
     m->cfg = *cfg;
-    m->NB = 1 + cfg->n_fft / 2;
-    m->G = ((m->NB + 31) / 32 + 3) / 4 * 4;
-    m->off = (cfg->n_fft - cfg->win_size) / 2;
-    m->win_pad = (cfg->win_size + 7) / 8 * 8;
-    m->MT = (cfg->num_mels + 31) / 32;
-    m->ldb = m->G * 64; m->ldm = m->MT * 32;
-    m->min_lin = (float)std::pow(10.0, (double)cfg->min_level_db / 20.0);
+    m->g = mel_geom(*cfg);
     *out = m;
     if (cfg->max_batch == 0) return WN_OK;      // geometry-only context (wn_mel_num_frames): reserves nothing and never touches a device; wn_mel_run / wn_mel_peak refuse any B
 
@@ -224,23 +117,8 @@ extern "C" int wn_mel_create(const wn_mel_config* cfg, const float* mel_basis, w
         char bf[160]; snprintf(bf, sizeof bf, "hop_size %d / win_size %d: the signal span of a 32-frame tile does not fit the 160 KiB LDS", cfg->hop_size, cfg->win_size);
         g_create_err = bf; delete m; *out = nullptr; return WN_E_UNSUPPORTED;
     }
-    // DFT basis in double, argument reduced as integers; window = periodic Hann of win_size (scipy get_window('hann', win, fftbins=True))
-    const int n_fft = cfg->n_fft, win = cfg->win_size;
-    std::vector<double> ct(n_fft), st(n_fft);
-    const double two_pi = 6.283185307179586476925286766559;
-    for (int i = 0; i < n_fft; ++i) { ct[i] = std::cos(two_pi * i / n_fft); st[i] = std::sin(two_pi * i / n_fft); }
-    std::vector<float> hb((size_t)m->win_pad * m->ldb, 0.0f);
-    for (int k = 0; k < win; ++k) {
-        const double w = 0.5 - 0.5 * std::cos(two_pi * k / win);
-        for (int j = 0; j < m->NB; ++j) {
-            const int idx = (int)(((int64_t)(k + m->off) * j) % n_fft);
-            float* p = &hb[(size_t)k * m->ldb + (j / 32) * 64 + (j % 32)];
-            p[0] = (float)(w * ct[idx]); p[32] = (float)(-w * st[idx]);
-        }
-    }
-    std::vector<float> hm((size_t)m->G * 32 * m->ldm, 0.0f);
-    for (int q = 0; q < cfg->num_mels; ++q)
-        for (int j = 0; j < m->NB; ++j) hm[(size_t)j * m->ldm + q] = mel_basis[(size_t)q * m->NB + j];
+    std::vector<float> hb, hm;
+    mel_build_tables(*cfg, m->g, mel_basis, &hb, &hm);
     int rc = [&]() -> int {
         WN_HIP(m, m->basis.reserve(hb.size()));
         WN_HIP(m, m->melT.reserve(hm.size()));
@@ -329,18 +207,13 @@ extern "C" int wn_mel_run(wn_mel* m, const float* wav, int64_t ld, const int32_t
     const int hop = m->cfg.hop_size;
     for (int b = 0; b < B; ++b)
         if (F_max < 1 + lengths[b] / hop) WN_FAIL(m, WN_E_SHAPE, "wn_mel_run: F_max (%d) < the %d frames of lengths[%d] = %d", F_max, 1 + lengths[b] / hop, b, lengths[b]);
-    MelArgs a;
-    a.wav = wav; a.ld = ld; a.gain = gain; a.out = out; a.basis = m->basis; a.melT = m->melT;
-    a.F_max = F_max; a.channels_first = channels_first != 0;
-    a.hop = hop; a.win_pad = m->win_pad; a.off_lo = m->off - m->cfg.n_fft / 2; a.nchunks = m->G / 4; a.ldb = m->ldb;
     const int FR = mel_pick_tile(m, lengths, B);
     int sig_floats = 0;
     const size_t lds_bytes = mel_lds(m, FR, &sig_floats);
-    a.num_mels = m->cfg.num_mels; a.mt = m->MT; a.ldm = m->ldm; a.sig_floats = sig_floats;
-    a.kpre = m->cfg.preemphasis; a.pow_half = 0.5f * m->cfg.magnitude_power;
-    a.pow_mode = m->cfg.magnitude_power == 2.0f ? 0 : m->cfg.magnitude_power == 1.0f ? 1 : 2;
-    a.min_lin = m->min_lin; a.ref_db = m->cfg.ref_level_db; a.lo = m->cfg.min_level_db; a.maxabs = m->cfg.max_abs_value;
-    a.norm = m->cfg.signal_normalization != 0; a.clip = m->cfg.allow_clipping != 0; a.symmetric = m->cfg.symmetric_mels != 0;
+    MelArgs a;
+    mel_core_args(m->cfg, m->g, m->basis, m->melT, channels_first, sig_floats, &a);
+    a.wav = wav; a.ld = ld; a.gain = gain; a.out = out;
+    a.F_max = F_max; a.off_lo = m->g.off - m->cfg.n_fft / 2;
     const int TF = FR * 32;
     mel_kernel_t kern = mel_kernel(FR);
     for (int b0 = 0; b0 < B; b0 += MEL_GROUP) {

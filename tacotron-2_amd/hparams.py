@@ -148,6 +148,9 @@ MI355 = dict(
     mi355_output_sample_rate=0,     # N > 0: the wavs Synthesizer writes are converted to N Hz after the de-emphasis and before the peak normalisation and the int16
                                      # cast, on both mi355_output_stage settings and every route; the checks keep seeing the model-rate signal.  0: no handle is created,
                                      # nothing of it runs and every file is byte-identical to a run without the key
+    mi355_synthesis_live_chunk_ms=0,   # N > 0: synthesize.py --wavs_dir reads every recording in chunks of N ms and analyses and generates it push by push
+                                     # (wavenet_vocoder/live.py: csrc/wn_mel_stream.hip feeding a slot session; the rescale gain from a first chunked pass over the file, as
+                                     # --gain peak); the wavs grow as they are generated.  0: nothing of this runs and every file is byte-identical to a run without the key
 )
 
 

@@ -269,6 +269,12 @@ def load_library():
         'wn_resample_push': (ctypes.c_int, [vp, vp, i64, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32), i32, vp, i64, ctypes.POINTER(i32), vp]),
         'wn_test_resample_host': (ctypes.c_int, [ctypes.POINTER(WnResampleConfig), vp, i64, vp, vp, vp, i32, i32, vp, i64, vp]),
         'wn_test_resample_table': (ctypes.c_int, [ctypes.POINTER(WnResampleConfig), vp, i64]),
+        'wn_mel_stream_create': (ctypes.c_int, [ctypes.POINTER(WnMelConfig), vp, i32, i32, ctypes.POINTER(vp)]),
+        'wn_mel_stream_destroy': (None, [vp]),
+        'wn_mel_stream_last_error': (ctypes.c_char_p, [vp]),
+        'wn_mel_stream_ready': (i64, [vp, i64, i32]),
+        'wn_mel_stream_push': (ctypes.c_int, [vp, vp, i64, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(f32), i32, vp, i64, i32, ctypes.POINTER(i32), vp]),
+        'wn_test_mel_stream_plan': (ctypes.c_int, [vp, vp, i64, vp, vp, vp, i32, i32, i64, vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)            # AttributeError here == ABI symbol missing
@@ -990,6 +996,133 @@ class MelAnalyzer:
     def close(self):
         if getattr(self, 'h', None):
             self.lib.wn_mel_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---- streaming mel analysis (csrc/wn_mel_stream.hip)
+def mel_stream_geometry(n_fft, win_size, hop):
+    """(Hl, Hr) of the frames: frame f reads the samples [f hop - Hl, f hop + Hr)."""
+    off = (int(n_fft) - int(win_size)) // 2
+    Hl = int(n_fft) // 2 - off
+    return Hl, int(win_size) - Hl
+
+
+def mel_stream_ready(n_fft, win_size, hop, S, final=False):
+    """The rule of readiness in Python (what wn_mel_stream_ready computes): frames analysed of a row that was given S samples since its restart."""
+    S, hop = int(S), int(hop)
+    Hr = mel_stream_geometry(n_fft, win_size, hop)[1]
+    if final:
+        return 1 + S // hop
+    return (S - Hr) // hop + 1 if S >= Hr else 0
+
+
+def mel_stream_plan(stream, pushes, in_pitch=None, out_pitch=None, have_in=True):
+    """wn_test_mel_stream_plan on a geometry-only MelStream: pushes is a list of (n [B], restart [B] or None, final [B] or None).  Returns a dict of numpy arrays:
+    status [P], and [P, B] n_out, first_frame, tail_len, S, F (the counters after each push; a refused push changes none)."""
+    vp = ctypes.c_void_p
+    P, B = len(pushes), len(pushes[0][0])
+    n = np.zeros((P, B), np.int32); rs = np.zeros((P, B), np.int32); fin = np.zeros((P, B), np.int32)
+    for p, (nn, r, f) in enumerate(pushes):
+        n[p] = nn
+        if r is not None:
+            rs[p] = np.asarray(r, np.int32)
+        if f is not None:
+            fin[p] = np.asarray(f, np.int32)
+    ipitch = int(max(1, n.max())) if in_pitch is None else int(in_pitch)
+    opitch = int(n.max()) // stream.hop + 3 if out_pitch is None else int(out_pitch)
+    res = {'status': np.full(P, -99, np.int32), 'n_out': np.full((P, B), -1, np.int32), 'first_frame': np.full((P, B), -1, np.int64),
+           'tail_len': np.full((P, B), -1, np.int32), 'S': np.full((P, B), -1, np.int64), 'F': np.full((P, B), -1, np.int64)}
+    dummy = np.zeros(1, np.float32)
+    lib = load_library()
+    rc = lib.wn_test_mel_stream_plan(stream.h, dummy.ctypes.data_as(vp) if have_in else None, ipitch, n.ctypes.data_as(vp), rs.ctypes.data_as(vp), fin.ctypes.data_as(vp), P, B, opitch,
+                                     *[res[k].ctypes.data_as(vp) for k in ('status', 'n_out', 'first_frame', 'tail_len', 'S', 'F')])
+    if rc != 0:
+        raise WnError(rc, (lib.wn_mel_stream_last_error(None) or b'').decode())
+    return res
+
+
+class MelStream:
+    """One wn_mel_stream: MelAnalyzer.run on rows that arrive push by push on the current device (csrc/wn_mel_stream.hip), asynchronously.  A row's frames,
+    concatenated, are bit-identical to MelAnalyzer.run on the whole row with the same gain and pre-emphasis; they lag the samples given by lag_samples = Hr
+    (ready()).  rows = 0: a geometry-only handle that needs no GPU.  Use one handle from one stream at a time."""
+
+    def __init__(self, hparams, rows, max_push, preemphasis=0.0, mel_basis=None):
+        if getattr(hparams, 'use_lws', False):
+            raise NotImplementedError('use_lws: the lws package is not available')
+        self.lib = load_library()
+        self.cfg = mel_config_from_hparams(hparams, 0, 0, preemphasis)
+        if mel_basis is None:
+            from datasets.audio import _build_mel_basis
+            mel_basis = _build_mel_basis(hparams)
+        mb = np.ascontiguousarray(mel_basis, dtype=np.float32)
+        if mb.shape != (self.cfg.num_mels, 1 + self.cfg.n_fft // 2):
+            raise ValueError('mel_basis must be [num_mels, 1 + n_fft // 2] = %r (got %r)' % ((self.cfg.num_mels, 1 + self.cfg.n_fft // 2), mb.shape))
+        h = ctypes.c_void_p()
+        rc = self.lib.wn_mel_stream_create(ctypes.byref(self.cfg), mb.ctypes.data_as(ctypes.c_void_p), int(rows), int(max_push), ctypes.byref(h))
+        if rc != 0:
+            raise WnError(rc, (self.lib.wn_mel_stream_last_error(None) or b'').decode())
+        self.h = h
+        self.num_mels, self.hop = int(self.cfg.num_mels), int(self.cfg.hop_size)
+        self.rows, self.max_push = int(rows), int(max_push)
+        self.lead_samples, self.lag_samples = mel_stream_geometry(self.cfg.n_fft, self.cfg.win_size, self.hop)
+
+    def _ok(self, rc):
+        if rc != 0:
+            raise WnError(rc, (self.lib.wn_mel_stream_last_error(self.h) or b'').decode())
+
+    def ready(self, S, final=False):
+        r = int(self.lib.wn_mel_stream_ready(self.h, int(S), int(bool(final))))
+        if r < 0:
+            raise WnError(r, 'wn_mel_stream_ready(%d)' % S)
+        return r
+
+    def push(self, samples, n=None, restart=None, final=None, gain=None, channels_first=True, out=None):
+        """samples [B, pitch] float32 on the device, n: B ints (None: the whole pitch), restart / final: B flags (None: none; True: all), gain: B host floats read
+        where restart is set (None: 1).  Returns (mel float32 [B, num_mels, pitch'] -- channels_first False: [B, pitch', num_mels] -- on the device, n_out: B
+        ints): row b's next n_out[b] frames, zeros beyond (with out given: its bytes kept)."""
+        import torch
+        _check(samples, torch.float32, 'samples')
+        if samples.dim() == 1:
+            samples = samples.reshape(1, -1)
+        if samples.dim() != 2:
+            raise ValueError('samples must be [B, pitch]')
+        B, pitch = int(samples.shape[0]), int(samples.shape[1])
+        n = [pitch] * B if n is None else [int(v) for v in n]
+        if len(n) != B:
+            raise ValueError('one count per row of samples (%d for %d rows)' % (len(n), B))
+
+        def flags(v, name):
+            if v is None:
+                return None
+            f = [1] * B if v is True else [int(bool(x)) for x in v]
+            if len(f) != B:
+                raise ValueError('one %s flag per row' % name)
+            return (ctypes.c_int32 * B)(*f)
+        rs, fin = flags(restart, 'restart'), flags(final, 'final')
+        if gain is not None:
+            if len(gain) != B:
+                raise ValueError('one gain per row')
+            gain = (ctypes.c_float * B)(*[float(np.float32(g)) for g in gain])
+        if out is None:
+            frames = (max(max(n), 0) + self.lead_samples + self.lag_samples) // self.hop + 2      # a push adds at most the frames of n + win_size samples
+            out = torch.zeros((B, self.num_mels, frames) if channels_first else (B, frames, self.num_mels), dtype=torch.float32, device=samples.device)
+        _check(out, torch.float32, 'out')
+        if out.dim() != 3 or int(out.shape[0]) != B or int(out.shape[1 if channels_first else 2]) != self.num_mels:
+            raise ValueError('out must be [B, num_mels, pitch] (channels_first) or [B, pitch, num_mels]')
+        opitch = int(out.shape[2 if channels_first else 1])
+        n_out = (ctypes.c_int32 * B)()
+        self._ok(self.lib.wn_mel_stream_push(self.h, _ptr(samples), pitch, (ctypes.c_int32 * B)(*n), rs, fin, gain, B, _ptr(out), opitch, int(bool(channels_first)), n_out, _stream()))
+        return out, [int(v) for v in n_out]
+
+    def close(self):
+        if getattr(self, 'h', None):
+            self.lib.wn_mel_stream_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -1076,6 +1076,15 @@ class WaveNet(object):
         rs.tail = self.output_stage(rows, in_type='raw', deemphasis=0.0)
         return rs
 
+    def mel_stream(self, rows, max_push, preemphasis=None):
+        """An _ext.MelStream of `rows` rows for pushes of up to `max_push` samples per row (csrc/wn_mel_stream.hip): the analysis of preprocessing on
+        recordings that arrive chunk by chunk, the front end of wavenet_vocoder.live.LiveVocoder.  preemphasis None: hparams.preemphasis if
+        hparams.preemphasize else 0, as preprocessing analyses."""
+        hp = self._hparams
+        if preemphasis is None:
+            preemphasis = float(hp.preemphasis) if hp.preemphasize else 0.0
+        return _ext.MelStream(hp, rows, max_push, preemphasis=preemphasis)
+
     def train_stats(self):
         """The model's _ext.TrainStats (csrc/wn_stats.hip), built at the first call: histograms of up to max_batch rows of max_time samples and the
         per-tensor statistics of a flat buffer in the engine's layout (``grads``, ``params``, the Adam slots)."""

@@ -124,6 +124,9 @@ def run_wav_synthesis(args, checkpoint_path, output_dir, hparams):
     for d in (plot_dir, wav_dir):
         os.makedirs(d, exist_ok=True)
     step = int(hparams.wavenet_synthesis_batch_size)
+    live_ms = float(getattr(hparams, 'mi355_synthesis_live_chunk_ms', 0))
+    if live_ms > 0:
+        return run_live_wav_synthesis(synth, paths, wav_dir, hparams, live_ms)
     with open(os.path.join(wav_dir, 'map.txt'), 'w') as index:
         for start in tqdm(range(0, len(paths), step)):
             batch = paths[start:start + step]
@@ -137,6 +140,27 @@ def run_wav_synthesis(args, checkpoint_path, output_dir, hparams):
             wavs = synth.synthesize(mels, None, names, wav_dir, plot_dir)
             for p, mp, wav in zip(batch, mel_paths, wavs):
                 index.write('|'.join([p, mp, wav]) + '\n')
+    log('synthesized audio waveforms at {}'.format(wav_dir))
+
+
+def run_live_wav_synthesis(synth, paths, wav_dir, hparams, chunk_ms):
+    """mi355_synthesis_live_chunk_ms > 0: the recordings chunk by chunk through wavenet_vocoder.live.LiveVocoder -- never a whole recording on the device, the
+    analysis and the generation push by push, each wav growing as it is generated (int16 from the device output stage).  The rescale gain comes from a first
+    chunked pass over the file (live's --gain peak), so mel-<basename>.npy holds the bytes analyse_wavs gives.  Same file names and map.txt rows as the
+    whole-recording route; silence is not trimmed and no plots are made."""
+    from datasets.audio import get_hop_size
+    from wavenet_vocoder import live
+    hop = get_hop_size(hparams)
+    chunk = max(1, int(round(hparams.sample_rate * chunk_ms / 1000.0)))
+    rows = max(1, min(len(paths), int(hparams.wavenet_synthesis_batch_size), 32))
+    synth._ensure_capacity(rows, (chunk // hop + 12) * hop)      # a push generates the frames of one chunk, and at the end those the look-ahead held back
+    names = [os.path.basename(p)[:-len('.wav')] for p in paths]
+    outs = [os.path.join(wav_dir, 'wavenet-audio-{}.wav'.format(n)) for n in names]
+    mel_paths = [os.path.join(wav_dir, 'mel-{}.npy'.format(n)) for n in names]
+    live.vocode_files(synth.model, paths, outs, chunk, gain='peak', mel_paths=mel_paths, rows=rows)
+    with open(os.path.join(wav_dir, 'map.txt'), 'w') as index:
+        for p, mp, wav in zip(paths, mel_paths, outs):
+            index.write('|'.join([p, mp, wav]) + '\n')
     log('synthesized audio waveforms at {}'.format(wav_dir))
 
 
