@@ -891,6 +891,10 @@ int wn_test_fill_noise_tempered(wn_ctx* ctx, float* noise, int32_t B, int32_t T,
 /* which launches of this context take the 8-phase kernel (csrc/wn_tile8p.h; WN_GEMM8P in the environment of wn_create -- an A/B switch,
  * default 0): bit 0 = the gate GEMM, bit 1 = d x.  A model that does not fit the kernel reports 0 whatever the switch says. */
 int wn_test_gemm8p_mask(const wn_ctx* ctx);
+/* which launch kinds of this context issue v_mfma_f32_16x16x32_bf16 in the LDS-DMA ring kernel (csrc/wn_tile.h; WN_MFMA16 in the environment of
+ * wn_create, unset: the library's default): bit 0 = the gate GEMM, bit 1 = d x, bit 2 = the other 32-channel-chunk launches (skip sum and full-tile
+ * 1x1 convs, d z, the head's mask GEMMs).  Bits the library does not know are dropped. */
+int wn_test_mfma16_mask(const wn_ctx* ctx);
 /* The fragment-ordered bf16 operand packs that wn_pack_weights wrote.  kind: "w1", "wo", "ws", "w2T", "w1T" (one per layer) or "wskip", "wh1",
  * "wh2", "wh2T", "wh1T", "wcT" (`layer` ignored).  wn_test_pack_info: out = {M, K, kil, gate_interleave} (padded sizes; kil = 0 / 32 / 64 the
  * K interleave of the three taps).  wn_test_pack_copy: the M * K elements IN STORAGE ORDER, bf16 -> fp32, nothing un-shuffled, into the device

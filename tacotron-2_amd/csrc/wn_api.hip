@@ -250,6 +250,7 @@ extern "C" int wn_create(const wn_config* cfg, wn_ctx** out) {
         else { delete c; WN_FAIL(z, WN_E_ARG, "WN_PIPE_DTYPE='%s': expected fp16 (f16, half, float16) or bf16 (bfloat16)", ed); }
     }
     { const char* e8 = getenv("WN_GEMM8P"); c->gemm8p = e8 ? atoi(e8) : 0; }      // bit 0: gate, bit 1: d x on the 8-phase kernel (wn_tile8p.h; measured: not faster on any shipped workload)
+    { const char* e16 = getenv("WN_MFMA16"); c->mfma16 = (e16 ? atoi(e16) : WN_MFMA16_DEFAULT) & WN_MF16_ALL; }      // MFMA shape per launch kind of the ring kernel (wn_tile.h); unset: the kinds that won
     c->gin = cfg->gin_channels > 0 ? cfg->gin_channels : 0;
     c->OP = (int)align_up(c->O, 32); c->CP = (int)align_up(c->C, 32);
     const int per = c->L / cfg->stacks;
@@ -317,7 +318,9 @@ extern "C" int wn_tensor_info(const wn_ctx* c, int i, char* name, int32_t* shape
     return WN_OK;
 }
 extern "C" int64_t wn_workspace_bytes(const wn_ctx* c) { return c ? (int64_t)(c->ws.bytes() + c->wg_partial.bytes()) : (int64_t)WN_E_ARG; }
-extern "C" const char* wn_dominant_kernel_name(void) { return "wn_gemm_lds_kernel<2, 2, 4, 2, 32, 3, 0, 1, 3>"; }
+extern "C" const char* wn_dominant_kernel_name(void) {      // the gate launch of a context created without WN_MFMA16 (last template argument: the MFMA shape)
+    return (WN_MFMA16_DEFAULT & WN_MF16_GATE) ? "wn_gemm_lds_kernel<2, 2, 4, 2, 32, 3, 0, 1, 3, 1>" : "wn_gemm_lds_kernel<2, 2, 4, 2, 32, 3, 0, 1, 3, 0>";
+}
 
 // rocTX ranges around the host side of the drop-in entry points (tracing): `rocprofv3 --marker-trace --kernel-trace` then
 // shows which call enqueued which kernels.  The marker library is looked up at run time (dlopen of libroctx64.so / the SDK's
@@ -550,6 +553,7 @@ extern "C" int wn_test_gemm8p_mask(const wn_ctx* c) {
     if (c->packs.empty()) return 0;
     return (c->packs[0].w1.kil == 64 ? 1 : 0) | (c->packs[0].w1T.kil == 64 ? 2 : 0);
 }
+extern "C" int wn_test_mfma16_mask(const wn_ctx* c) { return c ? c->mfma16 : WN_E_ARG; }
 extern "C" int wn_synth_pipe_eligible(const wn_ctx* c, int32_t B) {
     if (!c || B <= 0) return WN_E_ARG;
     const char* m = getenv("WN_SYNTH_MODE");

@@ -164,6 +164,13 @@ struct wn_ctx {
     bf16_t* zero_page = nullptr;          // zeros: DMA source for out-of-range rows / k-steps (wn_gemm_lds_kernel: 16 B per lane from one address;
                                           // wn_gemm8p_kernel's SGPR-base form: base + 16 * lane, i.e. 1 KiB)
     int gemm8p = 0;                       // WN_GEMM8P at wn_create, bit 0: gate, bit 1: d x on the 8-phase kernel (wn_tile8p.h) where the model fits it; default 0: the 256 x 128 LDS-DMA ring kernel
+#define WN_MF16_GATE 1
+#define WN_MF16_DX 2
+#define WN_MF16_CHAIN 4
+#define WN_MF16_ALL 7
+#define WN_MFMA16_DEFAULT 7               // the launch kinds whose live step won with the 16x16x32 shape: all three (profiles/mfma16_ab_bits.json)
+    int mfma16 = WN_MFMA16_DEFAULT;       // WN_MFMA16 at wn_create: the launch kinds of the LDS-DMA ring kernel that issue v_mfma_f32_16x16x32_bf16 instead of 32x32x16 (wn_tile.h):
+                                          // bit 0 gate, bit 1 d x, bit 2 the other BK = 32 launches (skip sum / full-tile 1x1 convs, d z, the head's mask GEMMs); other bits are ignored
     float* scal;                          // device scalars: [0]=loss sum [1]=denominator [2]=1/denominator [3]=count
     double* score_part = nullptr;         // [max_batch][ceil(max_time / 256)][3] per-chunk partials of the validation scores (wn_loss.hip: wn_score_run); in the workspace
     // state of the last forward

@@ -17,6 +17,7 @@
 // 64-wide wavefronts, 4 waves per workgroup, 2 workgroups per CU (36 KiB LDS each).
 #pragma once
 #include "wn_common.h"
+#include "wn_frag.h"
 #include <type_traits>
 
 struct SrcSeg {
@@ -394,9 +395,19 @@ struct LdsGemmCfg {
 
 // The kernel BODY is a device function of (arguments, LDS arena, workgroup id): wn_gemm_lds_kernel is the one-launch wrapper, and a
 // grid that holds the workgroups of several launches (tools/: the fused-pair grid of round 3, the persistent chain prototype) can call it.
-template <int MT, int NT, int WM, int WN, int BK, int NBUF, int EPI, int PIPE_ = 1, int TAPS = 0>
+// MF picks the MFMA shape (wn_frag.h holds both lane maps): 0 = v_mfma_f32_32x32x16_bf16, acc[MT][NT] of 16 registers; 1 = v_mfma_f32_16x16x32_bf16,
+// acc[2 MT][2 NT] of 4 registers -- the same 64 x 64 wave tile, LDS reads, fragment and accumulator registers and MFMA cycles per chunk, the same packs, DMAs,
+// ring and epilogue items; the chip holds a higher clock on the smaller shape.  A chunk's K order is the same; inside a chunk one 32-wide step
+// replaces two 16-wide ones, so the two shapes may differ in the last fp32 bits of a sum (measured: the same bits, profiles/mfma16_harness.txt; nothing relies on it).
+// The MF = 0 arms below keep the text they had before MF existed where a rewrite through wn_frag.h, though equal in value, reordered the compiler's output:
+// every MF = 0 instantiation disassembles to the instructions it had (the header's MF = 0 maps are pinned to the same expressions by tests/host/frag_main.cpp).
+template <int MT, int NT, int WM, int WN, int BK, int NBUF, int EPI, int PIPE_ = 1, int TAPS = 0, int MF = 0>
 __device__ __forceinline__ void wn_gemm_lds_body(const GemmArgs& a, char* const lds, const int wg_id) {
     using Cfg = LdsGemmCfg<MT, NT, WM, WN, BK, NBUF>;
+    static_assert(MF == 0 || MF == 1, "MFMA shape");
+    static_assert(MF == 0 || (BK == 32 && EPI != EPI_STORE_F32_BOT), "16x16x32: the BK = 32 launches with an LDS-staged epilogue (the register epilogue and the BK = 64 tiles keep 32x32x16)");
+    using acc_t = std::conditional_t<MF == 0, f32x16_t, f32x4_t>;
+    constexpr int AI = MF == 0 ? MT : 2 * MT, AJ = MF == 0 ? NT : 2 * NT;      // accumulator fragments per wave
     // PIPE_ names the main-loop schedule; the library has schedule 1 only (every fragment of a chunk is requested from LDS right after the chunk's
     // barrier, the DMAs of chunk + 2 are issued while those reads fly, then the chunk's MFMAs go back to back).  The schedules that were measured against
     // it in rounds 2 - 4 and lost -- fragment reads one k-step ahead, half the waves issuing the DMAs, wave halves half a chunk apart, weight fragments
@@ -448,15 +459,16 @@ __device__ __forceinline__ void wn_gemm_lds_body(const GemmArgs& a, char* const 
     // The accumulators START at the bias of their output channel (gate: b_dil + b_cin + global-conditioning row of this utterance;
     // 1x1 convs: their bias), so the fused epilogues neither load nor add it: 4 x 16-B loads here, under the first DMAs, instead of
     // 16 bias values per 8-channel item in the epilogue.  acc[i][j][r] is output row (wm*MT + i)*32 + (r/4)*8 + (lane>>5)*4 + r%4.
-    f32x16_t acc[MT][NT];
+    // (MF = 1: acc[i16][j16][r] is output row wm*MT*32 + 16*i16 + 4*(lane>>4) + r, one bias quad per fragment row.)
+    acc_t acc[AI][AJ];
     if constexpr (EPI == EPI_GATE || EPI == EPI_STORE_BF16) {
         const float* bp = a.e.bias;
         if constexpr (EPI == EPI_GATE) bp += (int64_t)b * a.e.bias_bstride;
 #pragma unroll
-        for (int i = 0; i < MT; ++i)
+        for (int i = 0; i < AI; ++i)
 #pragma unroll
-            for (int qd = 0; qd < 4; ++qd) {
-                const int ml = (wm * MT + i) * 32 + qd * 8 + (lane >> 5) * 4;       // row inside the workgroup's M tile
+            for (int qd = 0; qd < (MF == 0 ? 4 : 1); ++qd) {
+                const int ml = MF == 0 ? (wm * MT + i) * 32 + qd * 8 + (lane >> 5) * 4 : wn_frag_acc_ml(MF, MT, wm, i, qd, lane);       // row inside the workgroup's M tile (MF = 0: == wn_frag_acc_ml)
                 float4 bv = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
                 if (bp) {
                     if constexpr (EPI == EPI_GATE) {
@@ -468,15 +480,15 @@ __device__ __forceinline__ void wn_gemm_lds_body(const GemmArgs& a, char* const 
                     }
                 }
 #pragma unroll
-                for (int j = 0; j < NT; ++j) { acc[i][j][qd * 4] = bv.x; acc[i][j][qd * 4 + 1] = bv.y; acc[i][j][qd * 4 + 2] = bv.z; acc[i][j][qd * 4 + 3] = bv.w; }
+                for (int j = 0; j < AJ; ++j) { acc[i][j][qd * 4] = bv.x; acc[i][j][qd * 4 + 1] = bv.y; acc[i][j][qd * 4 + 2] = bv.z; acc[i][j][qd * 4 + 3] = bv.w; }
             }
     } else {
 #pragma unroll
-    for (int i = 0; i < MT; ++i)
+    for (int i = 0; i < AI; ++i)
 #pragma unroll
-        for (int j = 0; j < NT; ++j)
+        for (int j = 0; j < AJ; ++j)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+            for (int r = 0; r < (MF == 0 ? 16 : 4); ++r) acc[i][j][r] = 0.0f;
     }
 
     const int mtile_wg = mblk * (WM * MT);           // first 32-row m-tile of this workgroup
@@ -507,9 +519,14 @@ __device__ __forceinline__ void wn_gemm_lds_body(const GemmArgs& a, char* const 
     };
 #pragma unroll
     for (int p = 0; p < BPW; ++p) {
-        const int row = (wave + p * NWD) * (1024 / Cfg::RB) + (lane * 16) / Cfg::RB;
-        b_c8[p] = ((lane % Cfg::SPR) ^ ((row / Cfg::RPL) % Cfg::SPR)) * 8;
-        b_t[p] = t0 + row;
+        if constexpr (MF == 0) {      // (== wn_frag_b_stage_row / _slot, tests/host/frag_main.cpp; the 32x32x16 arm keeps its text, and with it its code, instruction for instruction)
+            const int row = (wave + p * NWD) * (1024 / Cfg::RB) + (lane * 16) / Cfg::RB;
+            b_c8[p] = ((lane % Cfg::SPR) ^ ((row / Cfg::RPL) % Cfg::SPR)) * 8;
+            b_t[p] = t0 + row;
+        } else {
+            b_c8[p] = wn_frag_b_stage_slot(BK, MF, wave + p * NWD, lane) * 8;
+            b_t[p] = t0 + wn_frag_b_stage_row(BK, wave + p * NWD, lane);
+        }
     }
     int b_offt[TAPS ? TAPS : 1][BPW];          // TAPS: per-tap element offsets of this lane's rows (-1: zero page)
     if constexpr (TAPS > 0) {
@@ -602,16 +619,21 @@ __device__ __forceinline__ void wn_gemm_lds_body(const GemmArgs& a, char* const 
     };
 
     // fragment read offsets (loop invariant): A lane-linear, B swizzled
-    int b_rd[NT][Cfg::KS];
+    // (MF = 1: KR = KS/2 steps of 32; the blocks 16 rows apart share the swizzle term, so the compiler folds every second B offset into an immediate)
+    constexpr int KR = MF == 0 ? Cfg::KS : Cfg::KS / 2;
+    int b_rd[AJ][KR];
 #pragma unroll
-    for (int j = 0; j < NT; ++j)
+    for (int j = 0; j < AJ; ++j)
 #pragma unroll
-        for (int ks = 0; ks < Cfg::KS; ++ks) {
-            const int row = (wn * NT + j) * 32 + (lane & 31);
-            b_rd[j][ks] = row * Cfg::RB + (((ks * 2 + (lane >> 5)) ^ ((row / Cfg::RPL) % Cfg::SPR)) * 16);
+        for (int ks = 0; ks < KR; ++ks) {
+            if constexpr (MF == 0) {      // (== wn_frag_b_read(BK, 0, ...))
+                const int row = (wn * NT + j) * 32 + (lane & 31);
+                b_rd[j][ks] = row * Cfg::RB + (((ks * 2 + (lane >> 5)) ^ ((row / Cfg::RPL) % Cfg::SPR)) * 16);
+            } else b_rd[j][ks] = wn_frag_b_read(BK, MF, NT, wn, j, ks, lane);
         }
-    const int a_rd = (wm * MT * Cfg::KS * 64 + lane) * 16;
-
+    const int a_rd = MF == 0 ? (wm * MT * Cfg::KS * 64 + lane) * 16 : wn_frag_a_read(MF, MT, Cfg::KS, wm, 0, 0, lane);
+    // fragment (i, ks) of the wave's A panel: a_rd + a compile-time offset
+#define WN_A_FRAG_OFF(i, ks) (MF == 0 ? ((i) * Cfg::KS + (ks)) * 1024 : wn_frag_a_read(MF, MT, Cfg::KS, 0, (i), (ks), 0) - wn_frag_a_read(MF, MT, Cfg::KS, 0, 0, 0, 0))
     // one ring step: chunk `ch` lives in buffer BUF; chunk ch+NBUF-1 is DMA'd into the buffer freed by chunk ch-1.  Every fragment of
     // the chunk is requested from LDS straight after the barrier, the DMA issue + iterator bookkeeping of the next chunk runs while
     // those reads are in flight, then the chunk's MFMAs go back to back.  In a partial chunk (segment width % BK != 0) the tail
@@ -625,26 +647,28 @@ __device__ __forceinline__ void wn_gemm_lds_body(const GemmArgs& a, char* const 
         __builtin_amdgcn_s_barrier();
         if (ch == 0) WN_STAMP(2);
         const char* const buf = lds + Cfg::a_base(BUF); const char* const bufb = lds + Cfg::b_base(BUF);
-        bf16x8_t af[Cfg::KS][MT], bfr[Cfg::KS][NT];
+        bf16x8_t af[KR][AI], bfr[KR][AJ];
 #pragma unroll
-        for (int ks = 0; ks < Cfg::KS; ++ks) {
+        for (int ks = 0; ks < KR; ++ks) {
 #pragma unroll
-            for (int i = 0; i < MT; ++i)
-                af[ks][i] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(buf + a_rd + (i * Cfg::KS + ks) * 1024));
+            for (int i = 0; i < AI; ++i)
+                af[ks][i] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(buf + a_rd + WN_A_FRAG_OFF(i, ks)));
 #pragma unroll
-            for (int j = 0; j < NT; ++j)
+            for (int j = 0; j < AJ; ++j)
                 bfr[ks][j] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(bufb + b_rd[j][ks]));
         }
         __builtin_amdgcn_sched_barrier(0);
         if (ch + NBUF - 1 < nchunks) stage(std::integral_constant<int, (BUF + NBUF - 1) % NBUF>{});
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int ks = 0; ks < Cfg::KS; ++ks)
+        for (int ks = 0; ks < KR; ++ks)
 #pragma unroll
-            for (int i = 0; i < MT; ++i)
+            for (int i = 0; i < AI; ++i)
 #pragma unroll
-                for (int j = 0; j < NT; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[ks][i], bfr[ks][j], acc[i][j], 0, 0, 0);
+                for (int j = 0; j < AJ; ++j) {
+                    if constexpr (MF == 0) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[ks][i], bfr[ks][j], acc[i][j], 0, 0, 0);
+                    else acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[ks][i], bfr[ks][j], acc[i][j], 0, 0, 0);
+                }
     };
     static_assert(NBUF == 2 || NBUF == 3, "ring depth");
 
@@ -694,26 +718,28 @@ __device__ __forceinline__ void wn_gemm_lds_body(const GemmArgs& a, char* const 
                 asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(Cfg::LPC) : "memory");
                 __builtin_amdgcn_s_barrier();
                 const char* const buf = lds + Cfg::a_base(BUF); const char* const bufb = lds + Cfg::b_base(BUF);
-                bf16x8_t af[Cfg::KS][MT], bfr[Cfg::KS][NT];
+                bf16x8_t af[KR][AI], bfr[KR][AJ];
 #pragma unroll
-                for (int ks = 0; ks < Cfg::KS; ++ks) {
+                for (int ks = 0; ks < KR; ++ks) {
 #pragma unroll
-                    for (int i = 0; i < MT; ++i)
-                        af[ks][i] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(buf + a_rd + (i * Cfg::KS + ks) * 1024));
+                    for (int i = 0; i < AI; ++i)
+                        af[ks][i] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(buf + a_rd + WN_A_FRAG_OFF(i, ks)));
 #pragma unroll
-                    for (int j = 0; j < NT; ++j)
+                    for (int j = 0; j < AJ; ++j)
                         bfr[ks][j] = __builtin_bit_cast(bf16x8_t, *reinterpret_cast<const uint4*>(bufb + b_rd[j][ks]));
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 fast_stage(std::integral_constant<int, (BUF + NBUF - 1) % NBUF>{});
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int ks = 0; ks < Cfg::KS; ++ks)
+                for (int ks = 0; ks < KR; ++ks)
 #pragma unroll
-                    for (int i = 0; i < MT; ++i)
+                    for (int i = 0; i < AI; ++i)
 #pragma unroll
-                        for (int j = 0; j < NT; ++j)
-                            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[ks][i], bfr[ks][j], acc[i][j], 0, 0, 0);
+                        for (int j = 0; j < AJ; ++j) {
+                            if constexpr (MF == 0) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[ks][i], bfr[ks][j], acc[i][j], 0, 0, 0);
+                            else acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[ks][i], bfr[ks][j], acc[i][j], 0, 0, 0);
+                        }
             };
             for (int kb = 0; kb < nkb - 1; ++kb) {
                 fast_step(std::integral_constant<int, 0>{});
@@ -731,7 +757,7 @@ __device__ __forceinline__ void wn_gemm_lds_body(const GemmArgs& a, char* const 
     }
 
     WN_STAMP(3);
-    if constexpr (EPI == EPI_STORE_F32_BOT) {
+    if constexpr (EPI == EPI_STORE_F32_BOT && MF == 0) {
         // [B][M][T] fp32 output: lanes are consecutive time steps, already coalesced
         wn_tile_epilogue<MT, NT, EPI>(a, acc, mtile0, t0 + wn * NT * 32, b, T, rowbase, lane);
     } else {
@@ -741,6 +767,19 @@ __device__ __forceinline__ void wn_gemm_lds_body(const GemmArgs& a, char* const 
         constexpr int PROWS = Cfg::EPI_ROWS;                 // rows per pass (one 32-row tile of every wave column)
         const EpiArgs& e = a.e;
         const int h = lane >> 5;
+        // accumulators of pass j -> fp32 [time row of the pass][channel of the M tile] for the 16x16x32 shape (lane maps: wn_frag.h): one ds_write_b128 per fragment
+        auto stage_acc16 = [&](const int j) __attribute__((always_inline)) {
+            if constexpr (MF == 1) {
+#pragma unroll
+                for (int i = 0; i < AI; ++i)
+#pragma unroll
+                    for (int jh = 0; jh < 2; ++jh) {
+                        const int rl = wn_frag_acc_rl(1, wn, jh, lane), ml = wn_frag_acc_ml(1, MT, wm, i, 0, lane);
+                        const acc_t& v = acc[i][2 * j + jh];
+                        *reinterpret_cast<float4*>(lds + rl * PITCH + ml * 4) = make_float4(v[0], v[1], v[2], v[3]);
+                    }
+            }
+        };
         // The barriers of the epilogue order LDS traffic only (no LDS-DMA is in flight any more: the last ring step drained vmcnt), so
         // they must not drain the vector-memory counter: the global loads of a pass are issued BEFORE its two barriers and the stores
         // of the previous pass stay in flight across them.
@@ -759,6 +798,7 @@ __device__ __forceinline__ void wn_gemm_lds_body(const GemmArgs& a, char* const 
         for (int j = 0; j < NT; ++j) {
             if constexpr (EPI == EPI_GATE) {
                 epi_barrier();
+                if constexpr (MF == 0) {      // (rl, ml == wn_frag_acc_rl / _ml(0, ...))
 #pragma unroll
                 for (int i = 0; i < MT; ++i)
 #pragma unroll
@@ -767,6 +807,7 @@ __device__ __forceinline__ void wn_gemm_lds_body(const GemmArgs& a, char* const 
                         *reinterpret_cast<float4*>(lds + rl * PITCH + ml * 4) =
                             make_float4(acc[i][j][qd * 4], acc[i][j][qd * 4 + 1], acc[i][j][qd * 4 + 2], acc[i][j][qd * 4 + 3]);
                     }
+                } else stage_acc16(j);
                 epi_barrier();
                 constexpr int GT = Cfg::MTILE / 2, C8 = GT / 8, ITEMS = PROWS * C8;
                 static_assert(ITEMS % NTH == 0 && NTH % C8 == 0, "gate epilogue items");
@@ -824,6 +865,7 @@ __device__ __forceinline__ void wn_gemm_lds_body(const GemmArgs& a, char* const 
                     }
                 }
                 epi_barrier();
+                if constexpr (MF == 0) {      // (rl, ml == wn_frag_acc_rl / _ml(0, ...))
 #pragma unroll
                 for (int i = 0; i < MT; ++i)
 #pragma unroll
@@ -832,6 +874,7 @@ __device__ __forceinline__ void wn_gemm_lds_body(const GemmArgs& a, char* const 
                         *reinterpret_cast<float4*>(lds + rl * PITCH + ml * 4) =
                             make_float4(acc[i][j][qd * 4], acc[i][j][qd * 4 + 1], acc[i][j][qd * 4 + 2], acc[i][j][qd * 4 + 3]);
                     }
+                } else stage_acc16(j);
                 epi_barrier();
                 bf16_t* const o0 = (bf16_t*)e.out0 + tile_row0 * e.ld_out0 + mo;
 #pragma unroll
@@ -909,13 +952,21 @@ __device__ __forceinline__ void wn_gemm_lds_body(const GemmArgs& a, char* const 
     if (a.kclk && id == 0 && tid == 0) { a.kclk[0] = __builtin_amdgcn_s_memtime() - a.kclk[0]; a.kclk[1] = (unsigned long long)wall_clock64() - a.kclk[1]; }
 #endif
 #undef WN_STAMP
+#undef WN_A_FRAG_OFF
 }
 
-template <int MT, int NT, int WM, int WN, int BK, int NBUF, int EPI, int PIPE = 1, int TAPS = 0>
+template <int MT, int NT, int WM, int WN, int BK, int NBUF, int EPI, int PIPE = 1, int TAPS = 0, int MF = 0>
 __global__ __launch_bounds__(WM * WN * 64, (lds_gemm_min_waves(MT, NT, WM, WN, BK, NBUF)))
 void wn_gemm_lds_kernel(const GemmArgs a) {
     __shared__ __attribute__((aligned(1024))) char lds[LdsGemmCfg<MT, NT, WM, WN, BK, NBUF>::LDS_BYTES];
-    wn_gemm_lds_body<MT, NT, WM, WN, BK, NBUF, EPI, PIPE, TAPS>(a, lds, blockIdx.x);
+    wn_gemm_lds_body<MT, NT, WM, WN, BK, NBUF, EPI, PIPE, TAPS, MF>(a, lds, blockIdx.x);
+}
+
+// WN_MFMA16 bits (wn_ctx::mfma16): which launch kinds of wn_launch_gemm take the 16x16x32 shape.  A kind has ONE shape in a context -- every
+// batch part, stream, batch size and wn_eval_fwd -- so the bit-identity of parts, of evaluation against training and of two runs holds by construction.
+template <int EPI>
+static inline bool wn_gemm_mfma16(const wn_ctx* ctx) {
+    return (ctx->mfma16 & (EPI == EPI_GATE ? WN_MF16_GATE : EPI == EPI_DX ? WN_MF16_DX : WN_MF16_CHAIN)) != 0;
 }
 
 // grids of at least this many workgroups (more than two full rounds of 2 x 256 slots) de-phase their second-resident workgroups
@@ -958,13 +1009,18 @@ static inline int wn_launch_gemm(wn_ctx* ctx, GemmArgs& a, int M, hipStream_t st
             a.xcd_span = cdiv(a.ntiles, 8);
             const int grid = cdiv(a.ntiles, 8) * a.mblocks * 8;
             a.stagger = grid >= WN_STAGGER_MIN_GRID ? 8000 : 0;      // more than two full rounds: desynchronise the co-resident workgroups
+            const bool mf16 = wn_gemm_mfma16<EPI>(ctx);
             if constexpr (EPI == EPI_GATE || EPI == EPI_DX) {
                 if (a.taps == 3) {       // K-interleaved taps (packs built with kil = 32)
+                    if (mf16) hipLaunchKernelGGL((wn_gemm_lds_kernel<2, 2, 4, 2, 32, 3, EPI, 1, 3, 1>), dim3(grid), dim3(512), 0, st, a);
+                    else
                     hipLaunchKernelGGL((wn_gemm_lds_kernel<2, 2, 4, 2, 32, 3, EPI, 1, 3>), dim3(grid), dim3(512), 0, st, a);
                     WN_LAUNCH_CHECK(ctx);
                     return WN_OK;
                 }
             }
+            if (mf16) hipLaunchKernelGGL((wn_gemm_lds_kernel<2, 2, 4, 2, 32, 3, EPI, 1, 0, 1>), dim3(grid), dim3(512), 0, st, a);
+            else
             hipLaunchKernelGGL((wn_gemm_lds_kernel<2, 2, 4, 2, 32, 3, EPI, 1>), dim3(grid), dim3(512), 0, st, a);
             WN_LAUNCH_CHECK(ctx);
             return WN_OK;
@@ -979,13 +1035,18 @@ static inline int wn_launch_gemm(wn_ctx* ctx, GemmArgs& a, int M, hipStream_t st
             a.xcd_span = cdiv(a.ntiles, 8);
             const int grid = cdiv(a.ntiles, 8) * a.mblocks * 8;
             a.stagger = grid >= WN_STAGGER_MIN_GRID ? 8000 : 0;
+            const bool mf16 = wn_gemm_mfma16<EPI>(ctx);
             if constexpr (EPI == EPI_GATE || EPI == EPI_DX) {
                 if (a.taps == 3) {
+                    if (mf16) hipLaunchKernelGGL((wn_gemm_lds_kernel<1, 2, 4, 2, 32, 3, EPI, 1, 3, 1>), dim3(grid), dim3(512), 0, st, a);
+                    else
                     hipLaunchKernelGGL((wn_gemm_lds_kernel<1, 2, 4, 2, 32, 3, EPI, 1, 3>), dim3(grid), dim3(512), 0, st, a);
                     WN_LAUNCH_CHECK(ctx);
                     return WN_OK;
                 }
             }
+            if (mf16) hipLaunchKernelGGL((wn_gemm_lds_kernel<1, 2, 4, 2, 32, 3, EPI, 1, 0, 1>), dim3(grid), dim3(512), 0, st, a);
+            else
             hipLaunchKernelGGL((wn_gemm_lds_kernel<1, 2, 4, 2, 32, 3, EPI, 1>), dim3(grid), dim3(512), 0, st, a);
             WN_LAUNCH_CHECK(ctx);
             return WN_OK;

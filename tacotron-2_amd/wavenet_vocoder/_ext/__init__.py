@@ -158,6 +158,7 @@ def load_library():
         'wn_synth_check': (ctypes.c_int, [vp]),
         'wn_synth_last_path': (ctypes.c_int, [vp]),
         'wn_test_gemm8p_mask': (ctypes.c_int, [vp]),
+        'wn_test_mfma16_mask': (ctypes.c_int, [vp]),
         'wn_test_pack_info': (ctypes.c_int, [vp, ctypes.c_char_p, i32, ctypes.POINTER(i32)]),
         'wn_test_pack_copy': (ctypes.c_int, [vp, ctypes.c_char_p, i32, vp, i64]),
         'wn_test_pipe_layout': (ctypes.c_int, [i32, i32, i32, vp, i32, vp, i32, vp, vp]),

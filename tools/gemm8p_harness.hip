@@ -5,7 +5,10 @@
 // bf16 rounding of sums taken in a different order (<= 2 ulp); the 8-phase kernel is also run repeatedly and must reproduce its own
 // bits (race screen: a read that overtakes its DMA shows up as run-to-run differences).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++20 -I tacotron-2_amd/csrc tools/gemm8p_harness.hip -o tools/gemm8p_harness
-//   tools/gemm8p_harness [B=8] [T=11000] [d=64] [rounds=3]
+//   tools/gemm8p_harness [B=8] [T=11000] [d=64] [rounds=3] [mfma16]
+// With a fifth argument `mfma16` only the MFMA-shape sections run: the production ring kernel with v_mfma_f32_32x32x16_bf16 (MF 0) against the same kernel with
+// v_mfma_f32_16x16x32_bf16 (MF 1) on the same operands, alternating launch by launch: wall time per launch (median, p05 - p95), the shader clock inside the
+// kernel (workgroup 0's cycle counter over the 100 MHz wall clock), energy per launch, and MF 1's outputs within 2 bf16 ulp of MF 0's.
 #include "wn_tile8p.h"
 #include "power_sampler.h"
 #include <vector>
@@ -77,12 +80,44 @@ static float time_ms(const std::function<void()>& f, int iters = 10) {
 }
 
 // the production launch of the gate / dx GEMMs (wn_launch_gemm's TAPS branch)
-template <int EPI> static void launch_prod(GemmArgs a, int M, hipStream_t st) {
+template <int EPI, int MF = 0> static void launch_prod(GemmArgs a, int M, hipStream_t st) {
     a.mblocks = M / 256; a.tiles_per_utt = cdiv(a.T, 128); a.ntiles = a.tiles_per_utt * a.B;
     a.xcd_span = cdiv(a.ntiles, 8); a.taps = 3;
     const int grid = cdiv(a.ntiles, 8) * a.mblocks * 8;
     a.stagger = grid >= WN_STAGGER_MIN_GRID ? 8000 : 0;
-    hipLaunchKernelGGL((wn_gemm_lds_kernel<2, 2, 4, 2, 32, 3, EPI, 1, 3>), dim3(grid), dim3(512), 0, st, a);
+    hipLaunchKernelGGL((wn_gemm_lds_kernel<2, 2, 4, 2, 32, 3, EPI, 1, 3, MF>), dim3(grid), dim3(512), 0, st, a);
+}
+
+// ---- MFMA shape A/B of the production kernel.  a0 / a1: the same launch writing two sets of outputs (MF 0 / MF 1).
+static std::string arm_name(const char* what, int mf) { return std::string(what) + (mf ? ", ring kernel 16x16x32" : ", ring kernel 32x32x16"); }
+struct ArmStat { std::vector<float> us; double cyc = 0, ticks = 0; };
+static float pct(std::vector<float> v, double q) { std::sort(v.begin(), v.end()); return v[(size_t)std::min<double>(v.size() - 1, q * v.size())]; }
+template <int EPI> static void mfma16_ab(const char* what, GemmArgs a0, GemmArgs a1, int M, double fl, int samples) {
+    unsigned long long* kclk; CK(hipMalloc(&kclk, 16));
+    hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+    ArmStat st[2];
+    for (int w = 0; w < 4; ++w) { launch_prod<EPI, 0>(a0, M, 0); launch_prod<EPI, 1>(a1, M, 0); }
+    CK(hipDeviceSynchronize());
+    for (int i = 0; i < samples; ++i)
+        for (int arm = 0; arm < 2; ++arm) {
+            GemmArgs a = arm ? a1 : a0; a.kclk = kclk;
+            CK(hipEventRecord(e0, 0));
+            if (arm) launch_prod<EPI, 1>(a, M, 0); else launch_prod<EPI, 0>(a, M, 0);
+            CK(hipEventRecord(e1, 0)); CK(hipEventSynchronize(e1));
+            float ms; CK(hipEventElapsedTime(&ms, e0, e1));
+            unsigned long long h[2]; CK(hipMemcpy(h, kclk, 16, hipMemcpyDeviceToHost));
+            st[arm].us.push_back(ms * 1e3f); st[arm].cyc += (double)h[0]; st[arm].ticks += (double)h[1];
+        }
+    // back-to-back launches (no host gap): what a layer chain sees
+    float b2b[2];
+    for (int arm = 0; arm < 2; ++arm) b2b[arm] = arm ? time_ms([&] { launch_prod<EPI, 1>(a1, M, 0); }, 20) : time_ms([&] { launch_prod<EPI, 0>(a0, M, 0); }, 20);
+    for (int arm = 0; arm < 2; ++arm)
+        printf("%-4s B %d MF %d (%s): single launch median %7.1f us (p05 %7.1f, p95 %7.1f) | 20 back to back %7.1f us %6.1f TF | in-kernel clock %5.0f MHz\n", what, a0.B, arm,
+               arm ? "16x16x32" : "32x32x16", pct(st[arm].us, 0.5), pct(st[arm].us, 0.05), pct(st[arm].us, 0.95), b2b[arm] * 1e3, fl / b2b[arm] / 1e9, 100.0 * st[arm].cyc / st[arm].ticks);
+    printf("%-4s B %d MF 1 / MF 0: single launch %.4f, back to back %.4f\n", what, a0.B, pct(st[1].us, 0.5) / pct(st[0].us, 0.5), b2b[1] / b2b[0]);
+    report_power(arm_name(what, 0).c_str(), measure_power([&] { launch_prod<EPI, 0>(a0, M, 0); }), fl);
+    report_power(arm_name(what, 1).c_str(), measure_power([&] { launch_prod<EPI, 1>(a1, M, 0); }), fl);
+    CK(hipEventDestroy(e0)); CK(hipEventDestroy(e1)); CK(hipFree(kclk));
 }
 template <int EPI, int ABL = 0, int SCHED = 1> static void launch_8p(GemmArgs a, int M, hipStream_t st) {
     a.mblocks = M / 256; a.tiles_per_utt = cdiv(a.T, 256); a.ntiles = a.tiles_per_utt * a.B;
@@ -95,6 +130,7 @@ int main(int argc, char** argv) {
     const int B = argc > 1 ? atoi(argv[1]) : 8, T = argc > 2 ? atoi(argv[2]) : 11000, d = argc > 3 ? atoi(argv[3]) : 64, rounds = argc > 4 ? atoi(argv[4]) : 3;
     const int R = 256, G = 512, GH = 256, C = 80;
     const int64_t NT_ = (int64_t)B * T;
+    const bool mf_only = argc > 5 && std::string(argv[5]) == "mfma16";
     int fails = 0;
     printf("gemm8p harness: B %d T %d d %d (rows %lld)\n", B, T, d, (long long)NT_);
     bf16_t* zero; CK(hipMalloc(&zero, 4096)); CK(hipMemset(zero, 0, 4096));
@@ -131,6 +167,18 @@ int main(int argc, char** argv) {
         GemmArgs a3 = a2; a3.e.out0 = TS3; a3.e.out1 = U3;
         if (!wn_gemm8p_fits(a2, M, NT_)) { printf("gate: wn_gemm8p_fits says no\n"); return 1; }
         const double fl = 2.0 * M * K * (double)NT_;
+        {   // MFMA shape: MF 1 into TS3 / U3, within 2 ulp of MF 0 (same chunk order; one 32-wide step for two 16-wide ones inside a chunk)
+            GemmArgs a16 = a1; a16.e.out0 = TS3; a16.e.out1 = U3;
+            launch_prod<EPI_GATE, 0>(a1, M, 0); launch_prod<EPI_GATE, 1>(a16, M, 0); CK(hipDeviceSynchronize());
+            Cmp cs = compare_bf16(TS1, TS3, NT_ * GH), cu = compare_bf16(U1, U3, NT_ * GH);
+            printf("gate   16x16x32 vs 32x32x16: sigmoid %zu of %zu differ (max |d| %.4g, %zu beyond 2 ulp) | u %zu differ (max |d| %.4g, %zu beyond 2 ulp)  %s\n",
+                   cs.ndiff, cs.n, cs.maxabs, cs.nbad, cu.ndiff, cu.maxabs, cu.nbad, (cs.nbad + cu.nbad) ? "FAIL" : "ok");
+            fails += (cs.nbad + cu.nbad) != 0;
+            mfma16_ab<EPI_GATE>("gate", a1, a16, M, fl, 30);
+            if (B >= 2) { GemmArgs h0 = a1, h16 = a16; h0.B = h16.B = B / 2; mfma16_ab<EPI_GATE>("gate", h0, h16, M, fl / B * (B / 2), 30); }
+            CK(hipMemset(TS3, 0xff, NT_ * GH * 2)); CK(hipMemset(U3, 0xff, NT_ * GH * 2));
+        }
+        if (!mf_only) {
         launch_prod<EPI_GATE>(a1, M, 0); launch_8p<EPI_GATE>(a2, M, 0); CK(hipDeviceSynchronize());
         Cmp cs = compare_bf16(TS1, TS2, NT_ * GH), cu = compare_bf16(U1, U2, NT_ * GH);
         printf("gate   8p vs production: sigmoid %zu of %zu differ (max |d| %.4g, %zu beyond 2 ulp) | u %zu differ (max |d| %.4g, %zu beyond 2 ulp)  %s\n",
@@ -176,6 +224,7 @@ int main(int argc, char** argv) {
                 printf("gate   two half batches on two streams (host-synchronised): production %7.1f us | 8-phase %7.1f us\n", tp * 1e3, t8 * 1e3);
             }
         }
+        }
     }
     {   // ---------------- dx
         const int M = R, K = 3 * G;
@@ -189,6 +238,17 @@ int main(int argc, char** argv) {
         GemmArgs a1 = a; a1.e.out0 = O1; GemmArgs a2 = a; a2.Apk = A64; a2.e.out0 = O2; GemmArgs a3 = a2; a3.e.out0 = O3;
         if (!wn_gemm8p_fits(a2, M, NT_)) { printf("dx: wn_gemm8p_fits says no\n"); return 1; }
         const double fl = 2.0 * M * K * (double)NT_;
+        {
+            GemmArgs a16 = a1; a16.e.out0 = O3;
+            launch_prod<EPI_DX, 0>(a1, M, 0); launch_prod<EPI_DX, 1>(a16, M, 0); CK(hipDeviceSynchronize());
+            Cmp c = compare_bf16(O1, O3, NT_ * R);
+            printf("dx     16x16x32 vs 32x32x16: %zu of %zu differ (max |d| %.4g, %zu beyond 2 ulp)  %s\n", c.ndiff, c.n, c.maxabs, c.nbad, c.nbad ? "FAIL" : "ok");
+            fails += c.nbad != 0;
+            mfma16_ab<EPI_DX>("dx", a1, a16, M, fl, 30);
+            if (B >= 2) { GemmArgs h0 = a1, h16 = a16; h0.B = h16.B = B / 2; mfma16_ab<EPI_DX>("dx", h0, h16, M, fl / B * (B / 2), 30); }
+            CK(hipMemset(O3, 0xff, NT_ * R * 2));
+        }
+        if (!mf_only) {
         launch_prod<EPI_DX>(a1, M, 0); launch_8p<EPI_DX>(a2, M, 0); CK(hipDeviceSynchronize());
         Cmp c = compare_bf16(O1, O2, NT_ * R);
         printf("dx     8p vs production: %zu of %zu differ (max |d| %.4g, %zu beyond 2 ulp)  %s\n", c.ndiff, c.n, c.maxabs, c.nbad, c.nbad ? "FAIL" : "ok");
@@ -220,6 +280,7 @@ int main(int argc, char** argv) {
         }
         report_power("d x, ring kernel (production)", measure_power([&] { launch_prod<EPI_DX>(a1, M, 0); }), fl);
         report_power("d x, 8-phase kernel", measure_power([&] { launch_8p<EPI_DX, 0, 1>(a2, M, 0); }), fl);
+        }
     }
     printf("(energy of the d x launches: see above per kernel)\n");
     printf("gemm8p harness %s (%d failing checks)\n", fails ? "FAILED" : "passed", fails);

@@ -38,7 +38,8 @@ def read_counters(path):
     return acc
 
 
-def traffic_summary(fetch_path, write_path, gate_kernel='wn_gemm_lds_kernel<2, 2, 4, 2, 32, 3, 0, 1, 3>'):
+def traffic_summary(fetch_path, write_path, gate_kernel='wn_gemm_lds_kernel<2, 2, 4, 2, 32, 3, 0, 1, 3'):
+    # (no closing '>': profiles taken before the MFMA-shape argument end '..., 1, 3>', later ones '..., 1, 3, 0>' or '..., 1, 3, 1>')
     fe, wr = read_counters(fetch_path), read_counters(write_path)
 
     def steps_of(acc, counter):

@@ -12,7 +12,8 @@ def short(n):
     if m:
         a = [x.strip() for x in m.group(1).split(',')]
         epi = {'0': 'gate', '1': 'store(out/skip/head)', '2': 'f32(yhat/dc)', '3': 'dgate', '4': 'relumask', '5': 'dx'}.get(a[6], a[6])
-        return 'gemm<%sx%s,%s>' % (a[0], a[1], epi)
+        # (a 10th argument, absent in traces taken before it existed: the MFMA shape, 1 = 16x16x32)
+        return 'gemm<%sx%s,%s%s>' % (a[0], a[1], epi, ',mfma16' if len(a) > 9 and a[9] == '1' else '')
     m = re.match(r'void (wn_wgrad_lds_kernel<[^>]*>)', n)
     if m:
         return m.group(1)
