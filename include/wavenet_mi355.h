@@ -834,6 +834,52 @@ int64_t wn_mel_stream_ready(const wn_mel_stream* h, int64_t S, int32_t final);
 int  wn_mel_stream_push(wn_mel_stream* h, const float* in, int64_t in_pitch, const int32_t* n, const int32_t* restart, const int32_t* final, const float* gain, int32_t B,
                         float* out, int64_t out_pitch, int32_t channels_first, int32_t* n_out, void* stream);
 
+/* ---- Griffin-Lim: mel -> signal without a model (csrc/wn_griffin.hip) ----------------------------
+ * The reference's inv_mel_spectrogram / _griffin_lim (datasets/audio.py:97-112, 151-161) up to the de-emphasis: the baseline a trained vocoder has to beat
+ * on the same mels.  A handle of its own, independent of wn_ctx; additions only, WN_ABI_VERSION unchanged.  Geometry: n_fft, win_size <= n_fft, hop; the
+ * window is a periodic Hann of win_size centred in n_fft, frames as those of the mel analysis -- frame f centred on f hop, zeros outside the row --, the inverse is librosa's istft
+ * (windowed inverse DFT, overlap-add, division by the window-square sum of the covering frames, n_fft / 2 trimmed at both ends): a row of F frames is
+ * n = hop (F - 1) samples.  Magnitudes S [F, 1 + n_fft / 2] come from a normalised mel -- the inverse of the four _normalize variants of wn_mel,
+ * 10^((D + ref_level_db) / 20), ^(1 / magnitude_power), the product with pinv(mel_basis) (mels ascending), max(1e-10, .), ^power -- or are given.
+ * A run: the start y0 = ISTFT(S e^{2 pi i u}) from caller-given uniforms u (or zero phase, or a caller-given y0), then `iters` iterations
+ * y <- ISTFT(S phase(STFT(y))); an exactly zero bin takes the phase (1, 0).  Exact fp32 products (the fp32 matrix instruction) summed in orders that depend
+ * on the geometry and the sample's own row alone: two runs, and a row alone or inside any batch, are bit-identical; run(a) then a continuation of b equals
+ * run(a + b).  All device memory -- the two tables, pinv, the magnitudes, the spectrum and frame workspaces and y -- is reserved by wn_griffin_create; a run
+ * allocates nothing and never synchronises; frame counts travel as kernel arguments (the host array is free when the call returns).  max_batch = 0 makes a
+ * geometry-only handle.
+ * Validation before any device call.  WN_E_ARG: a null pointer, a foreign abi_version, a negative size or pitch, num_mels outside [0, 512], magnitude_power
+ * or power not finite or <= 0, B < 1, iters < 0, a src_kind outside 0 ... 2, a mel input on a handle created without pinv, unknown flags.  WN_E_STATE: a
+ * continuation before any run.  WN_E_SHAPE: n_fft odd or below 8, win_size outside [4, n_fft], hop outside [1, win_size / 4] (the range that keeps every
+ * trimmed sample's window-square sum positive), frames[b] < 2, B > max_batch, frames[b] above F_max or max_frames, a row longer than a pitch.
+ * WN_E_UNSUPPORTED: n_fft not a multiple of 32 or above 4096. */
+typedef struct wn_griffin_config {
+    int32_t abi_version;   /* = WN_ABI_VERSION */
+    int32_t n_fft, win_size, hop;
+    int32_t num_mels;      /* 0: magnitudes only */
+    float   magnitude_power, power;                               /* hparams.py magnitude_power, power (1.5) */
+    float   min_level_db, ref_level_db, max_abs_value;
+    int32_t signal_normalization, allow_clipping, symmetric_mels; /* as wn_mel_config */
+    int32_t max_batch;     /* rows per call; 0: geometry-only handle */
+    int32_t max_frames;    /* frames per row */
+} wn_griffin_config;
+typedef struct wn_griffin wn_griffin;
+#define WN_GRIFFIN_SRC_MEL 0        /* src: device float [B, F_max, num_mels] */
+#define WN_GRIFFIN_SRC_MEL_CF 1     /* [B, num_mels, F_max] */
+#define WN_GRIFFIN_SRC_MAG 2        /* [B, F_max, 1 + n_fft / 2], used as is */
+#define WN_GRIFFIN_CONTINUE 1       /* flags: carry on from the handle's y and magnitudes */
+/* pinv: HOST float [1 + n_fft / 2, num_mels] (np.linalg.pinv(mel_basis)), or NULL for a handle that takes magnitudes only */
+int  wn_griffin_create(const wn_griffin_config* cfg, const float* pinv, wn_griffin** out);
+void wn_griffin_destroy(wn_griffin* h);
+const char* wn_griffin_last_error(const wn_griffin* h);   /* NULL: text of the last failed create or host hook */
+/* hop (frames - 1); WN_E_ARG for a NULL handle or frames < 1 (host only) */
+int64_t wn_griffin_num_samples(const wn_griffin* h, int64_t frames);
+/* src: as src_kind says; frames: HOST int32 [B].  The start: y0 (device float [B, y0_pitch]) if given, else u (device float [B, F_max, 1 + n_fft / 2] in
+ * [0, 1)) if given, else zero phase.  Then `iters` iterations.  out: device float [B, out_pitch] or NULL (the result stays in the handle); row b receives
+ * hop (frames[b] - 1) samples, elements beyond keep the caller's bytes.  flags = WN_GRIFFIN_CONTINUE: src, src_kind, F_max, frames, B, u, y0 are ignored and
+ * `iters` further iterations run on the rows of the handle's last run. */
+int  wn_griffin_run(wn_griffin* h, const float* src, int32_t src_kind, int32_t F_max, const int32_t* frames, int32_t B, const float* u, const float* y0,
+                    int64_t y0_pitch, int32_t iters, int32_t flags, float* out, int64_t out_pitch, void* stream);
+
 /* ---- introspection ------------------------------------------------------------------------------ */
 int64_t wn_workspace_bytes(const wn_ctx* ctx);
 /* name of the kernel that dominates training time (bench.py's roofline line names it) */
@@ -963,6 +1009,17 @@ int wn_test_resample_table(const wn_resample_config* cfg, float* table, int64_t 
  * new frame), and after the push tail_len (carried samples; always below win_size), S and F. */
 int wn_test_mel_stream_plan(const wn_mel_stream* h, const float* in, int64_t in_pitch, const int32_t* n, const int32_t* restart, const int32_t* final, int32_t P, int32_t B,
                             int64_t out_pitch, int32_t* status, int32_t* n_out, int64_t* first_frame, int32_t* tail_len, int64_t* S, int64_t* F);
+/* Griffin-Lim test hooks.  wn_test_griffin_store_spectrum: with on != 0 the iterations of later runs take the variant of the tile kernel that also stores
+ * the spectrum BEFORE the projection (the last iteration's survives) to a workspace reserved by this call; the result of a run is the same bits either way.
+ * wn_test_griffin_copy (SYNCHRONISES the stream): what = 0 the magnitudes of the last run into dst HOST float [B, F_max, 1 + n_fft / 2], what = 1 that
+ * spectrum into dst HOST float [B, F_max, 1 + n_fft / 2, 2] (re, im); frames beyond a row's are left alone.
+ * wn_test_griffin_host: a run on the host (no handle, no GPU), every pointer in HOST memory, in plain C++ float32 with the device's tables, packed
+ * spectrum and orders of summation (csrc/wn_griffin.h); the two sides agree to float32 roundoff, not bit for bit.  mag_out [B, F_max, 1 + n_fft / 2] and
+ * pre_out [B, F_max, 1 + n_fft / 2, 2] (the spectrum before the last projection) are optional.  cfg->max_batch / max_frames are not limits here. */
+int wn_test_griffin_store_spectrum(wn_griffin* h, int32_t on);
+int wn_test_griffin_copy(wn_griffin* h, int32_t what, float* dst, int32_t F_max, void* stream);
+int wn_test_griffin_host(const wn_griffin_config* cfg, const float* pinv, const float* src, int32_t src_kind, int32_t F_max, const int32_t* frames, int32_t B,
+                         const float* u, const float* y0, int64_t y0_pitch, int32_t iters, float* out, int64_t out_pitch, float* mag_out, float* pre_out);
 #endif /* WN_NO_TEST_HOOKS */
 
 #ifdef __cplusplus

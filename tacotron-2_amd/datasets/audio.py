@@ -1,7 +1,9 @@
 """Audio helpers the WaveNet path needs (reference datasets/audio.py:9-59, 70-77, 178-270): loading, pre-emphasis, silence trimming,
 padding, and the mel analysis -- melspectrogram in numpy float64 (the pinned reference of the tests) and melspectrogram_device on the
-GPU (csrc/wn_mel.hip through _ext.MelAnalyzer; what wavenet_preprocess.py and synthesize.py --wavs_dir run).  The Griffin-Lim inversion
-and the linear spectrogram belong to the Tacotron model: out of scope."""
+GPU (csrc/wn_mel.hip through _ext.MelAnalyzer; what wavenet_preprocess.py and synthesize.py --wavs_dir run), and its model-free inverse
+(reference datasets/audio.py:97-112, 151-161, 184-185, 231-235, 252-253, 272-284): inv_mel_spectrogram in numpy and inv_mel_spectrogram_device on
+the GPU (csrc/wn_griffin.hip through _ext.GriffinLim) -- the Griffin-Lim baseline a trained vocoder has to beat on the same mels.  The linear
+spectrogram and the lws variant belong to the Tacotron model: out of scope."""
 import numpy as np
 from scipy import signal
 from scipy.io import wavfile
@@ -262,3 +264,149 @@ def melspectrogram_device(wavs, hparams, analyzer=None):
     finally:
         if own:
             analyzer.close()
+
+
+# ---- mel -> wav without a model (reference datasets/audio.py:97-112, 151-161): the pseudo-inverse of the mel filters, ** power, Griffin-Lim.  librosa's
+# istft is restated on numpy from its published algorithm: the inverse DFT of every frame under the same window, overlap-add, division by the
+# window-square sum of the covering frames (where it exceeds the smallest normal float32, as librosa does), n_fft / 2 trimmed at both ends.
+_inv_mel_basis_cache = {}
+
+
+def _inv_mel_basis(hparams):
+    key = (hparams.sample_rate, hparams.n_fft, hparams.num_mels, hparams.fmin, hparams.fmax)
+    if key not in _inv_mel_basis_cache:
+        _inv_mel_basis_cache[key] = np.linalg.pinv(np.asarray(_build_mel_basis(hparams), np.float64))
+    return _inv_mel_basis_cache[key]
+
+
+def _denormalize(D, hparams):
+    """Reference audio.py:272-284."""
+    m, lo = hparams.max_abs_value, hparams.min_level_db
+    if hparams.allow_clipping_in_normalization:
+        if hparams.symmetric_mels:
+            return ((np.clip(D, -m, m) + m) * -lo / (2 * m)) + lo
+        return (np.clip(D, 0, m) * -lo / m) + lo
+    if hparams.symmetric_mels:
+        return ((D + m) * -lo / (2 * m)) + lo
+    return (D * -lo / m) + lo
+
+
+def _db_to_amp(x):
+    return np.power(10.0, x * 0.05)
+
+
+def _mel_to_linear(mel_spectrogram, hparams):
+    return np.maximum(1e-10, np.dot(_inv_mel_basis(hparams), mel_spectrogram))
+
+
+def _window(hparams):
+    from scipy.signal import get_window
+    n_fft, win = hparams.n_fft, hparams.n_fft if hparams.win_size is None else hparams.win_size
+    lpad = (n_fft - win) // 2
+    return np.pad(get_window('hann', win, fftbins=True), (lpad, n_fft - win - lpad))
+
+
+def _istft(Y, hparams):
+    """== librosa.istft(Y, hop_length, win_length) for complex Y [1 + n_fft // 2, frames] -> hop (frames - 1) samples."""
+    if getattr(hparams, 'use_lws', False):
+        raise NotImplementedError('use_lws: the lws package is not available')
+    n_fft, hop = hparams.n_fft, get_hop_size(hparams)
+    w = _window(hparams)
+    F = Y.shape[1]
+    fr = np.fft.irfft(Y.T, n_fft, axis=1) * w[None, :]
+    y = np.zeros(n_fft + hop * (F - 1))
+    wss = np.zeros_like(y)
+    for f in range(F):
+        y[f * hop:f * hop + n_fft] += fr[f]
+        wss[f * hop:f * hop + n_fft] += w * w
+    ok = wss > np.finfo(np.float32).tiny
+    y[ok] /= wss[ok]
+    return y[n_fft // 2:n_fft // 2 + hop * (F - 1)]
+
+
+def _griffin_lim(S, hparams, rng=None):
+    """Reference audio.py:151-161; the random start comes from `rng` (a numpy Generator or RandomState; None: a fresh default_rng())."""
+    rng = np.random.default_rng() if rng is None else rng
+    u = rng.random(S.shape) if hasattr(rng, 'random') else rng.random_sample(S.shape)
+    S_complex = np.abs(S).astype(np.complex128)
+    y = _istft(S_complex * np.exp(2j * np.pi * u), hparams)
+    for _ in range(hparams.griffin_lim_iters):
+        angles = np.exp(1j * np.angle(_stft(y, hparams)))
+        y = _istft(S_complex * angles, hparams)
+    return y
+
+
+def mel_to_magnitude(mel_spectrogram, hparams):
+    """[num_mels, F] normalised mel -> the magnitudes Griffin-Lim aims at, [1 + n_fft // 2, F] (reference audio.py:99-104 and the ** power of :112)"""
+    D = _denormalize(mel_spectrogram, hparams) if hparams.signal_normalization else mel_spectrogram
+    return _mel_to_linear(_db_to_amp(D + hparams.ref_level_db) ** (1 / hparams.magnitude_power), hparams) ** hparams.power
+
+
+def inv_mel_spectrogram(mel_spectrogram, hparams, rng=None):
+    """Reference audio.py:97-112: [num_mels, F] -> the de-emphasised waveform of hop (F - 1) samples, in numpy float64 (no GPU)."""
+    if getattr(hparams, 'use_lws', False):
+        raise NotImplementedError('use_lws: the lws package is not available')
+    return inv_preemphasis(_griffin_lim(mel_to_magnitude(np.asarray(mel_spectrogram, np.float64), hparams), hparams, rng), hparams.preemphasis, hparams.preemphasize)
+
+
+def inv_mel_spectrogram_host(mels, hparams, seed=0, deemphasize=True):
+    """inv_mel_spectrogram over a list of [num_mels, F_b] mels in numpy (no GPU): float32 waveforms; mel b starts from default_rng(seed + b).
+    deemphasize False: the signals before the de-emphasis (the model domain of the checks)."""
+    if getattr(hparams, 'use_lws', False):
+        raise NotImplementedError('use_lws: the lws package is not available')
+    out = []
+    for b, mel in enumerate(mels):
+        y = _griffin_lim(mel_to_magnitude(np.asarray(mel, np.float64), hparams), hparams, np.random.default_rng(int(seed) + b))
+        out.append((inv_preemphasis(y, hparams.preemphasis, hparams.preemphasize) if deemphasize else y).astype(np.float32))
+    return out
+
+
+GRIFFIN_BATCH = 20
+
+
+def inv_mel_spectrogram_device(mels, frames, hparams, iters=None, seed=0, griffin=None, deemphasize=True, return_model_domain=False):
+    """inv_mel_spectrogram for a batch on the GPU (csrc/wn_griffin.hip): mels a list of [num_mels, F_b] arrays (frames None: their widths) or one array
+    [B, num_mels, F_max] with frames the B frame counts.  Returns a list of float32 waveforms of hop (F_b - 1) samples, de-emphasised through the device
+    output stage (_ext.OutputStage, in_type 'raw') when hparams.preemphasize and deemphasize; return_model_domain: (waveforms, the signals before the
+    de-emphasis).  iters None: hparams.griffin_lim_iters.  The start is drawn on the device from `seed` (row b of the call's k-th batch: seed + k).
+    griffin: an _ext.GriffinLim to reuse (its capacity bounds the batch and the longest mel); None builds one for this call."""
+    import torch
+    from wavenet_vocoder import _ext
+    if getattr(hparams, 'use_lws', False):
+        raise NotImplementedError('use_lws: the lws package is not available')
+    if frames is None:
+        mels = [np.ascontiguousarray(m, dtype=np.float32) for m in mels]
+        frames = [int(m.shape[1]) for m in mels]
+    else:
+        frames = [int(f) for f in frames]
+        mels = [np.ascontiguousarray(np.asarray(mels[b])[:, :frames[b]], dtype=np.float32) for b in range(len(frames))]
+    if not mels:
+        return ([], []) if return_model_domain else []
+    iters = int(hparams.griffin_lim_iters) if iters is None else int(iters)
+    hop = get_hop_size(hparams)
+    own = griffin is None
+    if own:
+        griffin = _ext.GriffinLim(hparams, min(len(mels), GRIFFIN_BATCH), max(frames))
+    k_de = float(hparams.preemphasis) if (hparams.preemphasize and deemphasize) else 0.0
+    post = _ext.OutputStage(hparams, griffin.rows, deemphasis=k_de, in_type='raw') if k_de != 0.0 else None
+    try:
+        out, raw = [None] * len(mels), [None] * len(mels)
+        order = sorted(range(len(mels)), key=lambda i: frames[i])      # neighbours in length share a batch: little padding
+        for k, lo in enumerate(range(0, len(order), griffin.rows)):
+            idx = order[lo:lo + griffin.rows]
+            fr = [frames[i] for i in idx]
+            host = np.zeros((len(idx), int(hparams.num_mels), max(fr)), np.float32)
+            for r, i in enumerate(idx):
+                host[r, :, :fr[r]] = mels[i]
+            y = griffin.run_mel(torch.from_numpy(host).cuda(), fr, iters=iters, channels_first=True, seed=None if seed is None else int(seed) + k)
+            n = [hop * (f - 1) for f in fr]
+            z = post.finish(y, n, pcm=False) if post is not None else y
+            y, z = y.cpu().numpy(), z.cpu().numpy()
+            for r, i in enumerate(idx):
+                raw[i], out[i] = y[r, :n[r]].copy(), z[r, :n[r]].copy()
+        return (out, raw) if return_model_domain else out
+    finally:
+        if post is not None:
+            post.close()
+        if own:
+            griffin.close()

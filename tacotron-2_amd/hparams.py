@@ -121,6 +121,11 @@ MI355 = dict(
                                        # recordings (all three routes) -- F0 and voicing of both are estimated on the device (YIN, csrc/wn_pitch.hip) and compared: three
                                        # scalars beside the eval loss, one row per utterance appended to wavs/pitch.tsv, one log line.  False: nothing of it runs and every
                                        # file is byte-identical to a run without the key
+    mi355_griffin_lim_baseline=False,  # True: beside every wav Synthesizer.synthesize writes (all three routes), wavs/griffin-lim-<basename>.wav: the model-free inversion of the
+                                       # same conditioning (pinv of the mel filters, ** power, griffin_lim_iters iterations on the device, csrc/wn_griffin.hip; GL_on_GPU=False:
+                                       # in numpy), and, with the two checks above on, its scores through the same check handles in wavs/reconstruction_griffin_lim.tsv /
+                                       # wavs/pitch_griffin_lim.tsv with one log line beside the model's.  False: no handle exists, nothing of it runs and every file is
+                                       # byte-identical to a run without the key
     mi355_pitch_fmin=60.0,             # lowest f0 searched, Hz: tau_max = ceil(sample_rate / fmin)
     mi355_pitch_fmax=500.0,            # highest f0 searched, Hz: tau_min = max(2, sample_rate // fmax)
     mi355_pitch_threshold=0.15,        # YIN's absolute threshold on the normalised difference: a frame with no lag below it is unvoiced

@@ -92,6 +92,13 @@ class WnDenoiseStreamConfig(ctypes.Structure):
                 ('in_type', ctypes.c_int32)]
 
 
+class WnGriffinConfig(ctypes.Structure):
+    _fields_ = [('abi_version', ctypes.c_int32), ('n_fft', ctypes.c_int32), ('win_size', ctypes.c_int32), ('hop', ctypes.c_int32), ('num_mels', ctypes.c_int32),
+                ('magnitude_power', ctypes.c_float), ('power', ctypes.c_float), ('min_level_db', ctypes.c_float), ('ref_level_db', ctypes.c_float),
+                ('max_abs_value', ctypes.c_float), ('signal_normalization', ctypes.c_int32), ('allow_clipping', ctypes.c_int32), ('symmetric_mels', ctypes.c_int32),
+                ('max_batch', ctypes.c_int32), ('max_frames', ctypes.c_int32)]
+
+
 class WnResampleConfig(ctypes.Structure):
     _fields_ = [('abi_version', ctypes.c_int32), ('max_rows', ctypes.c_int32), ('max_in', ctypes.c_int32), ('sr_in', ctypes.c_int32), ('sr_out', ctypes.c_int32),
                 ('zeros', ctypes.c_int32), ('beta', ctypes.c_double), ('rolloff', ctypes.c_double)]
@@ -276,6 +283,14 @@ def load_library():
         'wn_mel_stream_ready': (i64, [vp, i64, i32]),
         'wn_mel_stream_push': (ctypes.c_int, [vp, vp, i64, ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(i32), ctypes.POINTER(f32), i32, vp, i64, i32, ctypes.POINTER(i32), vp]),
         'wn_test_mel_stream_plan': (ctypes.c_int, [vp, vp, i64, vp, vp, vp, i32, i32, i64, vp, vp, vp, vp, vp, vp]),
+        'wn_griffin_create': (ctypes.c_int, [ctypes.POINTER(WnGriffinConfig), vp, ctypes.POINTER(vp)]),
+        'wn_griffin_destroy': (None, [vp]),
+        'wn_griffin_last_error': (ctypes.c_char_p, [vp]),
+        'wn_griffin_num_samples': (i64, [vp, i64]),
+        'wn_griffin_run': (ctypes.c_int, [vp, vp, i32, i32, ctypes.POINTER(i32), i32, vp, vp, i64, i32, i32, vp, i64, vp]),
+        'wn_test_griffin_store_spectrum': (ctypes.c_int, [vp, i32]),
+        'wn_test_griffin_copy': (ctypes.c_int, [vp, i32, vp, i32, vp]),
+        'wn_test_griffin_host': (ctypes.c_int, [ctypes.POINTER(WnGriffinConfig), vp, vp, i32, i32, ctypes.POINTER(i32), i32, vp, vp, i64, i32, vp, i64, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)            # AttributeError here == ABI symbol missing
@@ -1614,6 +1629,199 @@ class SpectralDenoiser:
     def close(self):
         if getattr(self, 'h', None):
             self.lib.wn_denoise_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---- Griffin-Lim baseline (csrc/wn_griffin.hip)
+GRIFFIN_SRC = {'mel': 0, 'mel_cf': 1, 'magnitude': 2}
+GRIFFIN_CONTINUE = 1
+
+
+def griffin_config(n_fft, win_size, hop, num_mels=0, magnitude_power=1.0, power=1.0, min_level_db=-100.0, ref_level_db=0.0, max_abs_value=1.0,
+                   signal_normalization=False, allow_clipping=False, symmetric_mels=False, max_batch=0, max_frames=0):
+    cfg = WnGriffinConfig()
+    cfg.abi_version = WN_ABI_VERSION
+    cfg.n_fft, cfg.win_size, cfg.hop, cfg.num_mels = int(n_fft), int(win_size), int(hop), int(num_mels)
+    cfg.magnitude_power, cfg.power = float(magnitude_power), float(power)
+    cfg.min_level_db, cfg.ref_level_db, cfg.max_abs_value = float(min_level_db), float(ref_level_db), float(max_abs_value)
+    cfg.signal_normalization, cfg.allow_clipping, cfg.symmetric_mels = int(bool(signal_normalization)), int(bool(allow_clipping)), int(bool(symmetric_mels))
+    cfg.max_batch, cfg.max_frames = int(max_batch), int(max_frames)
+    return cfg
+
+
+def griffin_config_from_hparams(hp, max_batch=0, max_frames=0):
+    """hparams (reference keys, hparams.py:102-133, 150-152) -> wn_griffin_config"""
+    from datasets.audio import get_hop_size
+    return griffin_config(hp.n_fft, hp.n_fft if hp.win_size is None else hp.win_size, get_hop_size(hp), hp.num_mels, hp.magnitude_power, hp.power,
+                          hp.min_level_db, hp.ref_level_db, hp.max_abs_value, hp.signal_normalization, hp.allow_clipping_in_normalization, hp.symmetric_mels,
+                          max_batch, max_frames)
+
+
+def griffin_pinv(hp):
+    """np.linalg.pinv(mel_basis) in float64, rounded to float32 once: [1 + n_fft / 2, num_mels] (reference audio.py:231-235)"""
+    from datasets.audio import _build_mel_basis
+    return np.ascontiguousarray(np.linalg.pinv(np.asarray(_build_mel_basis(hp), np.float64)).astype(np.float32))
+
+
+def _griffin_src(cfg, src, kind, frames):
+    """(kind code, B, F_max, frames array) of a source array [B, F_max, num_mels] ('mel'), [B, num_mels, F_max] ('mel_cf') or [B, F_max, bins] ('magnitude')"""
+    if kind not in GRIFFIN_SRC:
+        raise ValueError("kind must be 'mel', 'mel_cf' or 'magnitude' (got %r)" % (kind,))
+    if src.ndim != 3:
+        raise ValueError('the source must have three dimensions')
+    B = int(src.shape[0])
+    width = 1 + int(cfg.n_fft) // 2 if kind == 'magnitude' else int(cfg.num_mels)
+    F_max = int(src.shape[2] if kind == 'mel_cf' else src.shape[1])
+    if int(src.shape[1] if kind == 'mel_cf' else src.shape[2]) != width:
+        raise ValueError('the source of kind %r must have %d channels (got shape %r)' % (kind, width, tuple(src.shape)))
+    if len(frames) != B:
+        raise ValueError('one frame count per row (%d for %d rows)' % (len(frames), B))
+    return GRIFFIN_SRC[kind], B, F_max, (ctypes.c_int32 * max(B, 1))(*[int(f) for f in frames])
+
+
+def griffin_host(cfg, src, frames, kind='magnitude', pinv=None, u=None, y0=None, iters=0, return_all=False, fill=0.0):
+    """wn_test_griffin_host: a run in plain C++ float32 on numpy arrays (no handle, no GPU).  Returns out [B, hop (F_max - 1)] (`fill` beyond a row's samples),
+    with return_all also the magnitudes [B, F_max, bins] and the spectrum before the last projection, complex64 [B, F_max, bins]."""
+    vp = ctypes.c_void_p
+    src = np.ascontiguousarray(src, dtype=np.float32)
+    code, B, F_max, fr = _griffin_src(cfg, src, kind, frames)
+    nb = 1 + int(cfg.n_fft) // 2
+    pitch = max(1, int(cfg.hop) * max(F_max - 1, 0))
+    out = np.full((B, pitch), fill, np.float32)
+    p = None if pinv is None else np.ascontiguousarray(pinv, dtype=np.float32)
+    if p is not None and p.shape != (nb, int(cfg.num_mels)):
+        raise ValueError('pinv must be [%d, %d] (got %r)' % (nb, int(cfg.num_mels), p.shape))
+    uu = None if u is None else np.ascontiguousarray(u, dtype=np.float32)
+    if uu is not None and uu.shape != (B, F_max, nb):
+        raise ValueError('u must be [%d, %d, %d]' % (B, F_max, nb))
+    yy = None if y0 is None else np.ascontiguousarray(y0, dtype=np.float32)
+    mag = np.zeros((B, F_max, nb), np.float32)
+    pre = np.zeros((B, F_max, nb, 2), np.float32)
+    lib = load_library()
+    rc = lib.wn_test_griffin_host(ctypes.byref(cfg), None if p is None else p.ctypes.data_as(vp), src.ctypes.data_as(vp), code, F_max, fr, B,
+                                  None if uu is None else uu.ctypes.data_as(vp), None if yy is None else yy.ctypes.data_as(vp), 0 if yy is None else int(yy.shape[1]),
+                                  int(iters), out.ctypes.data_as(vp), pitch, mag.ctypes.data_as(vp), pre.ctypes.data_as(vp))
+    if rc != 0:
+        raise WnError(rc, (lib.wn_griffin_last_error(None) or b'').decode())
+    return (out, mag, pre[..., 0] + 1j * pre[..., 1]) if return_all else out
+
+
+class GriffinLim:
+    """One wn_griffin: normalised mels (or magnitudes) -> signals by Griffin-Lim on the current device (csrc/wn_griffin.hip), asynchronously: the reference's
+    inv_mel_spectrogram up to the de-emphasis.  Built from hparams with pinv(mel_basis) computed in float64; rows = 0: a geometry-only handle."""
+
+    def __init__(self, hparams, rows, max_frames, pinv=None, cfg=None):
+        """cfg: a wn_griffin_config to use instead of the one hparams gives (tests; hparams may then be None); pinv [1 + n_fft / 2, num_mels]: default
+        griffin_pinv(hparams), with cfg given: none (a handle that takes magnitudes only)."""
+        if hparams is not None and getattr(hparams, 'use_lws', False):
+            raise NotImplementedError('use_lws: the lws package is not available')
+        self.lib = load_library()
+        if cfg is None:
+            cfg = griffin_config_from_hparams(hparams, rows, max_frames)
+            if pinv is None and rows > 0:
+                pinv = griffin_pinv(hparams)
+        else:
+            cfg.max_batch, cfg.max_frames = int(rows), int(max_frames)
+        self.cfg = cfg
+        self.bins = 1 + int(cfg.n_fft) // 2
+        p = None
+        if pinv is not None:
+            p = np.ascontiguousarray(pinv, dtype=np.float32)
+            if p.shape != (self.bins, int(cfg.num_mels)):
+                raise ValueError('pinv must be [1 + n_fft // 2, num_mels] = %r (got %r)' % ((self.bins, int(cfg.num_mels)), p.shape))
+        h = ctypes.c_void_p()
+        rc = self.lib.wn_griffin_create(ctypes.byref(cfg), None if p is None else p.ctypes.data_as(ctypes.c_void_p), ctypes.byref(h))
+        if rc != 0:
+            raise WnError(rc, (self.lib.wn_griffin_last_error(None) or b'').decode())
+        self.h = h
+        self.hop, self.rows, self.max_frames = int(cfg.hop), int(rows), int(max_frames)
+        self._frames = None
+
+    def _ok(self, rc):
+        if rc != 0:
+            raise WnError(rc, (self.lib.wn_griffin_last_error(self.h) or b'').decode())
+
+    def num_samples(self, frames):
+        r = int(self.lib.wn_griffin_num_samples(self.h, int(frames)))
+        if r < 0:
+            raise WnError(r, 'wn_griffin_num_samples(%d)' % frames)
+        return r
+
+    def _out(self, out, B, frames, device):
+        import torch
+        if out is None:
+            out = torch.zeros((B, max(1, self.hop * (max(frames) - 1))), dtype=torch.float32, device=device)
+        _check(out, torch.float32, 'out')
+        if out.dim() != 2 or int(out.shape[0]) != B:
+            raise ValueError('out must be [B, pitch]')
+        return out
+
+    def _run(self, src, kind, frames, iters, u, y0, out, seed):
+        import torch
+        _check(src, torch.float32, 'src')
+        code, B, F_max, fr = _griffin_src(self.cfg, src, kind, frames)
+        if y0 is not None:
+            _check(y0, torch.float32, 'y0')
+            if y0.dim() != 2 or int(y0.shape[0]) != B:
+                raise ValueError('y0 must be [B, pitch]')
+        elif u is None and seed is not None:      # the reference's np.random.rand start, from a seeded torch generator on the device: no RNG of our own
+            gen = torch.Generator(device=src.device)
+            gen.manual_seed(int(seed))
+            u = torch.rand((B, F_max, self.bins), dtype=torch.float32, device=src.device, generator=gen)
+        if u is not None:
+            _check(u, torch.float32, 'u')
+            if tuple(u.shape) != (B, F_max, self.bins):
+                raise ValueError('u must be %r' % ((B, F_max, self.bins),))
+        out = self._out(out, B, [int(f) for f in frames], src.device)
+        self._ok(self.lib.wn_griffin_run(self.h, _ptr(src), code, F_max, fr, B, _ptr(u), _ptr(y0), 0 if y0 is None else int(y0.shape[1]), int(iters), 0, _ptr(out),
+                                         int(out.shape[1]), _stream()))
+        self._frames = [int(f) for f in frames]
+        return out
+
+    def run_mel(self, mel, frames, iters=60, channels_first=False, u=None, y0=None, seed=0, out=None):
+        """mel float32 [B, F_max, num_mels] (channels_first: [B, num_mels, F_max]) on the device, frames: B ints (host) -> out [B, pitch] on the device, row b
+        holding hop (frames[b] - 1) samples (pre-emphasised domain).  The start: y0 if given, else the uniforms u [B, F_max, bins] if given, else uniforms drawn
+        on the device from `seed` (seed None: zero phase); then `iters` iterations."""
+        return self._run(mel, 'mel_cf' if channels_first else 'mel', frames, iters, u, y0, out, seed)
+
+    def run_magnitude(self, S, frames, iters=60, u=None, y0=None, seed=0, out=None):
+        """S float32 [B, F_max, 1 + n_fft / 2] on the device, used as is; otherwise as run_mel"""
+        return self._run(S, 'magnitude', frames, iters, u, y0, out, seed)
+
+    def continue_(self, iters, out=None):
+        """`iters` further iterations on the rows of the last run -> out [B, pitch]: run(a) then continue_(b) has the bits of run(a + b)"""
+        import torch
+        if self._frames is None:
+            raise WnError(-5, 'GriffinLim.continue_: no run has been made on this handle')
+        out = self._out(out, len(self._frames), self._frames, torch.device('cuda', torch.cuda.current_device()))
+        self._ok(self.lib.wn_griffin_run(self.h, None, 0, 0, None, 0, None, None, 0, int(iters), GRIFFIN_CONTINUE, _ptr(out), int(out.shape[1]), _stream()))
+        return out
+
+    # test hooks
+    def store_spectrum(self, on=True):
+        self._ok(self.lib.wn_test_griffin_store_spectrum(self.h, int(bool(on))))
+
+    def magnitudes(self, F_max):
+        """the magnitudes of the last run as numpy [B, F_max, bins] (synchronises)"""
+        m = np.zeros((len(self._frames), int(F_max), self.bins), np.float32)
+        self._ok(self.lib.wn_test_griffin_copy(self.h, 0, m.ctypes.data_as(ctypes.c_void_p), int(F_max), _stream()))
+        return m
+
+    def spectrum(self, F_max):
+        """the spectrum before the last projection as numpy complex64 [B, F_max, bins] (store_spectrum must be on; synchronises)"""
+        p = np.zeros((len(self._frames), int(F_max), self.bins, 2), np.float32)
+        self._ok(self.lib.wn_test_griffin_copy(self.h, 1, p.ctypes.data_as(ctypes.c_void_p), int(F_max), _stream()))
+        return p[..., 0] + 1j * p[..., 1]
+
+    def close(self):
+        if getattr(self, 'h', None):
+            self.lib.wn_griffin_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -1050,6 +1050,11 @@ class WaveNet(object):
         from wavenet_vocoder.pitch import PitchCheck
         return PitchCheck(self._hparams, rows, max_samples)
 
+    def griffin_lim(self, rows, max_frames):
+        """An _ext.GriffinLim for up to `rows` mels of up to `max_frames` frames (csrc/wn_griffin.hip): the model-free inversion of this model's
+        conditioning, the baseline its output is compared with; geometry, levels, power and the pseudo-inverse of the mel filters from the hparams."""
+        return _ext.GriffinLim(self._hparams, rows, max_frames)
+
     def denoiser(self, rows, max_samples):
         """An OutputDenoiser for up to `rows` decoded utterances of up to `max_samples` samples of this model (csrc/wn_denoise.hip): the bias denoiser of
         sampled vocoders; geometry from the hparams (mi355_output_denoise_fft / _hop).  .fit(wav, lengths) / .fit_from_model(frames, seed, speaker) set the

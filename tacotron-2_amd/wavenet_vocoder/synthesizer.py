@@ -147,6 +147,7 @@ class Synthesizer(object):
         table = chk.score(decoded, n, torch.from_numpy(np.ascontiguousarray(cond, dtype=np.float32)).to(dev), frames=list(lengths), c_channels_first=False)
         reconstruction.append_tsv(os.path.join(out_dir, 'reconstruction.tsv'), basenames, lengths, table)
         log(reconstruction.log_line(basenames, table))
+        self._recon_table = table          # (the Griffin-Lim baseline's log line puts its own means beside these)
         return table
 
     def _pitch(self, decoded, generated_wavs, basenames, out_dir):
@@ -154,6 +155,7 @@ class Synthesizer(object):
         generated utterance against its recording (WaveNet.pitch_check), one row each appended to <out_dir>/pitch.tsv and one log line.  decoded /
         generated_wavs as _reconstruction takes them.  Reads results only; a failure logs one line and never fails the run."""
         refs, self.pitch_references = getattr(self, 'pitch_references', None), None
+        self._baseline_refs = refs          # (the Griffin-Lim baseline of the same call is scored against the same recordings)
         if refs is None or not bool(getattr(self._hparams, 'mi355_pitch_check', False)):
             return None
         try:
@@ -179,10 +181,92 @@ class Synthesizer(object):
             table = chk.score(decoded, torch.from_numpy(ref).to(dev), n)
             pitch.append_tsv(os.path.join(out_dir, 'pitch.tsv'), basenames, table)
             log(pitch.log_line(basenames, table))
+            self._pitch_table = table
             return table
         except Exception as e:
             log('pitch check skipped: {}'.format(e))
             return None
+
+    def _griffin_lim_baseline(self, mel_spectrograms, basenames, out_dir):
+        """mi355_griffin_lim_baseline: beside every generated wav, <out_dir>/griffin-lim-<basename>.wav -- the model-free inversion of the same conditioning
+        (datasets.audio.inv_mel_spectrogram_device, csrc/wn_griffin.hip; with GL_on_GPU off the numpy path), hop (frames - 1) samples, de-emphasised when
+        the generated wavs are (mi355_output_deemphasis).  With mi355_reconstruction_check / mi355_pitch_check on, the Griffin-Lim signal BEFORE the
+        de-emphasis (the checks' model domain) is scored through the same check handles into <out_dir>/reconstruction_griffin_lim.tsv /
+        pitch_griffin_lim.tsv, and one log line puts the batch means beside the model's.  Off: no handle exists and nothing runs.  A mel of one frame has
+        no Griffin-Lim signal and is left out.  Reads results only: nothing the call writes otherwise changes."""
+        hparams = self._hparams
+        recon_table, self._recon_table = getattr(self, '_recon_table', None), None
+        pitch_table, self._pitch_table = getattr(self, '_pitch_table', None), None
+        refs, self._baseline_refs = getattr(self, '_baseline_refs', None), None
+        if not bool(getattr(hparams, 'mi355_griffin_lim_baseline', False)):
+            return None
+        from datasets import audio
+        keep = [b for b, m in enumerate(mel_spectrograms) if len(m) >= 2]
+        if not keep:
+            return []
+        mels = [np.ascontiguousarray(np.asarray(mel_spectrograms[b], np.float32).T) for b in keep]
+        names, frames = [basenames[b] for b in keep], [int(m.shape[1]) for m in mels]
+        hop, seed = get_hop_size(hparams), int(getattr(hparams, 'wavenet_random_seed', 0))
+        k = self._output_mode()[1]
+        if bool(getattr(hparams, 'GL_on_GPU', True)):
+            gl = getattr(self, '_griffin', None)
+            if gl is None or gl.rows < min(len(mels), audio.GRIFFIN_BATCH) or gl.max_frames < max(frames):
+                if gl is not None:
+                    gl.close()
+                gl = self._griffin = self.model.griffin_lim(max(min(len(mels), audio.GRIFFIN_BATCH), gl.rows if gl else 0), max(max(frames), gl.max_frames if gl else 0))
+            _, raw = audio.inv_mel_spectrogram_device(mels, None, hparams, seed=seed, griffin=gl, deemphasize=False, return_model_domain=True)
+        else:
+            raw = audio.inv_mel_spectrogram_host(mels, hparams, seed=seed, deemphasize=False)
+        paths = []
+        for name, w in zip(names, raw):
+            paths.append(os.path.join(out_dir, 'griffin-lim-{}.wav'.format(name)))
+            save_wavenet_wav(inv_preemphasis(w, k).astype(np.float32) if k != 0.0 else w, paths[-1], sr=hparams.sample_rate)
+        n = [len(w) for w in raw]
+        parts = []
+        if bool(getattr(hparams, 'mi355_reconstruction_check', False)) or (bool(getattr(hparams, 'mi355_pitch_check', False)) and refs is not None):
+            dev = self.model.device
+            host = np.zeros((len(n), max(n)), np.float32)
+            for b, w in enumerate(raw):
+                host[b, :n[b]] = w
+            decoded = torch.from_numpy(host).to(dev)
+        if bool(getattr(hparams, 'mi355_reconstruction_check', False)):
+            from wavenet_vocoder import reconstruction
+            lo = -hparams.max_abs_value if hparams.symmetric_mels else 0
+            cond = np.stack([_pad_inputs(m.T, max(frames), _pad=lo) for m in mels]).astype(np.float32)
+            chk = getattr(self, '_recon', None)
+            if chk is None or chk.rows < len(n) or chk.max_samples < max(n):
+                if chk is not None:
+                    chk.close()
+                chk = self._recon = self.model.reconstruction_check(max(len(n), chk.rows if chk else 0), max(max(n), chk.max_samples if chk else 0))
+            table = chk.score(decoded, n, torch.from_numpy(cond).to(dev), frames=frames, c_channels_first=False)
+            reconstruction.append_tsv(os.path.join(out_dir, 'reconstruction_griffin_lim.tsv'), names, frames, table)
+            t = np.asarray(table, np.float64).reshape(len(n), -1)
+            parts.append('reconstruction l1c {:.2f} dB, lsdc {:.2f} dB, mcd {:.2f} dB'.format(t[:, 4].mean(), t[:, 5].mean(), t[:, 3].mean()) +
+                         (' (model {:.2f} / {:.2f} / {:.2f})'.format(*[np.asarray(recon_table, np.float64)[:, c].mean() for c in (4, 5, 3)]) if recon_table is not None else ''))
+        if bool(getattr(hparams, 'mi355_pitch_check', False)) and refs is not None:
+            try:
+                from wavenet_vocoder import pitch
+                if len(refs) != len(basenames):
+                    raise ValueError('{} recordings for {} utterances'.format(len(refs), len(basenames)))
+                refs = [refs[b] for b in keep]
+                m = [min(len(r), g) for r, g in zip(refs, n)]
+                ref = np.zeros((len(m), max(max(m), 1)), np.float32)
+                for b, r in enumerate(refs):
+                    ref[b, :m[b]] = np.asarray(r, np.float32)[:m[b]]
+                chk = getattr(self, '_pitch_chk', None)
+                if chk is None or chk.rows < len(m) or chk.max_samples < max(m):
+                    if chk is not None:
+                        chk.close()
+                    chk = self._pitch_chk = self.model.pitch_check(max(len(m), chk.rows if chk else 0), max(max(m), chk.max_samples if chk else 0))
+                table = chk.score(decoded, torch.from_numpy(ref).to(dev), m)
+                pitch.append_tsv(os.path.join(out_dir, 'pitch_griffin_lim.tsv'), names, table)
+                t = np.asarray(table, np.float64).reshape(len(m), -1)
+                parts.append('pitch V/UV error {:.3f}, gross pitch error {:.3f}, F0 RMSE {:.1f} cents'.format(t[:, 4].mean(), t[:, 5].mean(), t[:, 6].mean()) +
+                             (' (model {:.3f} / {:.3f} / {:.1f})'.format(*[np.asarray(pitch_table, np.float64)[:, c].mean() for c in (4, 5, 6)]) if pitch_table is not None else ''))
+            except Exception as e:
+                log('pitch check of the Griffin-Lim baseline skipped: {}'.format(e))
+        log('Griffin-Lim baseline: {} utterance(s), {} iterations'.format(len(names), int(hparams.griffin_lim_iters)) + ''.join('; ' + p for p in parts))
+        return paths
 
     def _ensure_capacity(self, batch, time_steps):
         if batch <= self._capacity[0] and time_steps <= self._capacity[1]:
@@ -486,6 +570,7 @@ class Synthesizer(object):
                                   title='WaveNet generated Waveform.')
                 except Exception as e:
                     log('plotting skipped: {}'.format(e))
+        self._griffin_lim_baseline(mel_spectrograms, basenames, out_dir)
         return audio_filenames
 
     def _check_conditions(self):
