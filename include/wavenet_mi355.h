@@ -893,7 +893,9 @@ const char* wn_dominant_kernel_name(void);
 /* copy an internal activation buffer of the last step to `out` as fp32 ("X","U","TS","DZ","R1","H2","DY","DSKIP","DPRE1","GX0",
  * "GX1","cbt" are bf16 [rows][channels]; "YHAT","DC","CUP" fp32).  "GX" with layer 0 ... L is d L / d h_layer as the backward chain
  * keeps it (layer L: the zero-filled top), "XD" with layer 0 ... L-1 the dropout-applied conv input (the same buffer as "X" when
- * dropout is 0); a layer outside these ranges is WN_E_ARG.
+ * dropout is 0); a layer outside these ranges is WN_E_ARG.  An fp32-mode context (compute_dtype = WN_COMPUTE_F32) keeps fp32 buffers instead: "X", "U" and
+ * "Z" (the gate pre-activations [rows][gate_channels]) per layer 0 ... L-1, "SK" (ReLU of the skip sum) and "H1" (ReLU of final_convolution_1), both
+ * [rows][skip_out_channels] with layer 0; they persist after the forward.
  * The weight path (fp32, `layer` ignored, n above the buffer's length is WN_E_ARG, WN_E_STATE before wn_pack_weights; all but "DEFF" also on
  * inference-only contexts): "PARAMS" the context's EFFECTIVE parameter copy (n_params floats in the effective layout: the raw tensors without
  * the gains, each 8-float aligned, in wn_tensor_info order); "DEFF" the gradients with respect to the effective parameters that the last
@@ -1020,6 +1022,24 @@ int wn_test_griffin_store_spectrum(wn_griffin* h, int32_t on);
 int wn_test_griffin_copy(wn_griffin* h, int32_t what, float* dst, int32_t F_max, void* stream);
 int wn_test_griffin_host(const wn_griffin_config* cfg, const float* pinv, const float* src, int32_t src_kind, int32_t F_max, const int32_t* frames, int32_t B,
                          const float* u, const float* y0, int64_t y0_pitch, int32_t iters, float* out, int64_t out_pitch, float* mag_out, float* pre_out);
+/* fp32 training mode (csrc/wn_f32.hip), ONE launch on operands the caller owns (device pointers; tests/test_hip_f32_kernels.py).  Each goes through the very
+ * function the chain calls, so the grid computation, the partial-sum capacity check and the slab reduction are under test.  Rows are b * T + t for B utterances
+ * of T samples; the context's forward shape and dropout seed are set for the call and restored after it.  WN_E_STATE: not an fp32-mode training context;
+ * WN_E_ARG: B > max_batch, T > max_time, a null operand.
+ * wn_test_f32_sgemm: Out[row][m] (out_bot: Out[b][m][t]) = mask(relu(((accumulate ? Out : 0) + drop_out(alpha * sum_k drop_a(In[row + shift][col0 + k]) *
+ *   W[k * wk + m * wm]) + bias[b * bias_bstride + m] + add[row][m]) * scale)); a row with t + shift outside [0, T) of ITS utterance contributes zero.  thresh16 > 0:
+ *   dropout from (key_lo, key_hi) on element row * drop_ld + column of the A operand, or of the output with drop_on_out.  mask, bias, add may be NULL.
+ * wn_test_f32_wgrad: out[k][m] (row pitch ldo) = alpha * sum_rows drop(A[row + shift][k]) * Bm[row][m]; bias_out / bias_out2 (either may be NULL) = alpha * column
+ *   sums of Bm.  A == NULL: only the column sums.  drop_layer >= 0: the context's dropout with the key of (seed, drop_layer) on element row * lda + k of A.
+ *   WN_E_STATE when B * ceil(T / 2048) * (K + 1) * M exceeds the context's partial-sum buffer.
+ * wn_test_f32_gate: U [rows][GH] = tanh(Z_a) * sigmoid(Z_b) of Z [rows][2 GH]; DZ [rows][2 GH] = the gate's derivative times GU [rows][GH]. */
+int wn_test_f32_sgemm(wn_ctx* ctx, int32_t B, int32_t T, const float* In, int32_t ld_in, int32_t col0, int32_t shift, const float* W, int32_t wk, int32_t wm,
+                      int32_t K, int32_t M, float* Out, int32_t ld_out, int32_t accumulate, const float* mask, int32_t ld_mask, int32_t drop_on_out,
+                      float alpha, float scale, const float* bias, int32_t bias_bstride, const float* add, int32_t ld_add, int32_t relu, int32_t out_bot,
+                      uint32_t key_lo, uint32_t key_hi, uint32_t thresh16, float keep_scale, int32_t drop_ld, void* stream);
+int wn_test_f32_wgrad(wn_ctx* ctx, int32_t B, int32_t T, const float* A, int32_t lda, int32_t shift, int32_t K, const float* Bm, int32_t ldb, int32_t M,
+                      float* out, int32_t ldo, float alpha, int32_t drop_layer, uint64_t seed, float* bias_out, float* bias_out2, void* stream);
+int wn_test_f32_gate(wn_ctx* ctx, const float* Z, const float* GU, float* U, float* DZ, int64_t rows, int32_t GH, void* stream);
 #endif /* WN_NO_TEST_HOOKS */
 
 #ifdef __cplusplus

@@ -612,7 +612,8 @@ extern "C" int wn_debug_copy(wn_ctx* c, const char* name, int32_t layer, float* 
     const int64_t NT = c->NT;
     const bf16_t* b = nullptr; const float* f = nullptr;
     std::string s = name;
-    if (c->cfg.compute_dtype == WN_COMPUTE_F32 && (s == "X" || s == "U")) {
+    if (c->cfg.compute_dtype == WN_COMPUTE_F32 && (s == "X" || s == "U" || s == "Z" || s == "SK" || s == "H1")) {
+        if (layer < 0 || layer >= c->L) WN_FAIL(c, WN_E_ARG, "wn_debug_copy('%s'): layer %d outside [0, %d)", name, layer, c->L);
         f = wn_f32_debug(c, name, layer);
         if (!f) WN_FAIL(c, WN_E_STATE, "wn_debug_copy('%s'): no fp32 forward has run yet", name);
     }

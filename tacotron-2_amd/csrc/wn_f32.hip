@@ -195,6 +195,9 @@ __global__ void wn_f32_gate(const float* __restrict__ Z, float* __restrict__ U, 
     const float za = Z[row * 2 * GH + g], zb = Z[row * 2 * GH + GH + g];
     U[i] = tanhf(za) * (1.0f / (1.0f + expf(-zb)));
 }
+static void gate32(const float* Z, float* U, int64_t rows, int GH, hipStream_t st) {
+    hipLaunchKernelGGL(wn_f32_gate, dim3(cdiv(rows * GH, 256)), dim3(256), 0, st, Z, U, rows, GH);
+}
 // [B][C][T] -> [B*T][C]
 __global__ void wn_f32_transpose_c(const float* __restrict__ cup, float* __restrict__ c32, int B, int C, int T) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -227,6 +230,9 @@ const float* wn_f32_debug(const wn_ctx* c, const char* name, int layer) {
     if (!s || !s->X || !s->U) return nullptr;
     if (!strcmp(name, "X")) return s->X + (size_t)layer * c->NT * c->R;
     if (!strcmp(name, "U")) return s->U + (size_t)layer * c->NT * c->GH;
+    if (!strcmp(name, "Z")) return s->Z ? s->Z + (size_t)layer * c->NT * c->G : nullptr;      // the gate pre-activations
+    if (!strcmp(name, "SK")) return s->SK;      // ReLU(skip sum + biases)
+    if (!strcmp(name, "H1")) return s->H1;      // ReLU(final_convolution_1)
     return nullptr;
 }
 
@@ -275,7 +281,7 @@ int wn_f32_forward(wn_ctx* c, hipStream_t st) {
             SgemmArgs a = mk(s->C32, C, 0, P + c->lay[l].cin_k, G, C, G, Zl, G); a.accumulate = 1;
             if ((rc = sgemm(c, a, st))) return rc;
         }
-        hipLaunchKernelGGL(wn_f32_gate, dim3(cdiv(rows * GH, 256)), dim3(256), 0, st, Zl, Ul, rows, GH);
+        gate32(Zl, Ul, rows, GH, st);
         {   // skip sum (wavenet.py:706-715 unrolled: the legacy factors are folded into skip_scale)
             SgemmArgs a = mk(Ul, GH, 0, P + c->lay[l].skip_k, S, GH, S, s->SK, S); a.accumulate = l > 0; a.alpha = c->skip_scale[l];
             if ((rc = sgemm(c, a, st))) return rc;
@@ -434,6 +440,9 @@ __global__ void wn_f32_gate_bwd(const float* __restrict__ GU, const float* __res
     DZ[row * 2 * GH + g] = gu * s * (1.0f - t * t);
     DZ[row * 2 * GH + GH + g] = gu * t * s * (1.0f - s);
 }
+static void gate_bwd32(const float* GU, const float* Z, float* DZ, int64_t rows, int GH, hipStream_t st) {
+    hipLaunchKernelGGL(wn_f32_gate_bwd, dim3(cdiv(rows * GH, 256)), dim3(256), 0, st, GU, Z, DZ, rows, GH);
+}
 // [B*T][C] -> [B][C][T]
 __global__ void wn_f32_transpose_back(const float* __restrict__ c32, float* __restrict__ cbt, int B, int C, int T) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -549,7 +558,7 @@ int wn_f32_backward(wn_ctx* c, float* grads, hipStream_t st) {
                 if ((rc = sgemm(c, o, st))) return rc;
             }
         }
-        hipLaunchKernelGGL(wn_f32_gate_bwd, dim3(cdiv(rows * GH, 256)), dim3(256), 0, st, s->GU, Zl, s->DZ, rows, GH);
+        gate_bwd32(s->GU, Zl, s->DZ, rows, GH, st);
         // ---- weight gradients of this layer (bias gradients ride along as a ones column of the A operand)
         if ((rc = wgrad32(c, Ul, GH, 0, GH, s->DSK, S, S, grads + c->lay[l].skip_k, S, c->skip_scale[l], -1, c->lbias ? grads + c->lay[l].skip_b : nullptr, nullptr, st))) return rc;
         if (!top && (rc = wgrad32(c, Ul, GH, 0, GH, gx_up, R, R, grads + c->lay[l].out_k, R, 1.0f, -1, c->lbias ? grads + c->lay[l].out_b : nullptr, nullptr, st))) return rc;
@@ -587,6 +596,55 @@ int wn_f32_backward(wn_ctx* c, float* grads, hipStream_t st) {
         hipLaunchKernelGGL(wn_f32_transpose_back, dim3(cdiv(rows * C, 256)), dim3(256), 0, st, s->DC, s->DCT, B, C, T);
         if ((rc = wn_upsample_bwd(c, s->DCT, grads, st))) return rc;
     }
+    WN_LAUNCH_CHECK(c);
+    return WN_OK;
+}
+
+// =============================================================================================== test hooks (include/wavenet_mi355.h, WN_TEST_HOOKS)
+// One launch of sgemm() / wgrad32() / the gate kernels on operands the caller owns, at a (B, T) of the caller's choice: the context's
+// forward shape and dropout seed are set for the call and put back after it, nothing else of the context changes.
+static int f32_hook_enter(wn_ctx* c, const char* who, int32_t B, int32_t T) {
+    if (c->cfg.compute_dtype != WN_COMPUTE_F32) WN_FAIL(c, WN_E_STATE, "%s: the context is not in the fp32 mode (compute_dtype = WN_COMPUTE_F32)", who);
+    if (c->inference) WN_FAIL(c, WN_E_STATE, "%s: no training workspace on an inference-only context", who);
+    if (B <= 0 || T <= 0 || B > c->maxB || T > c->maxT) WN_FAIL(c, WN_E_ARG, "%s: B = %d, T = %d outside (0, %d] x (0, %d]", who, B, T, c->maxB, c->maxT);
+    return WN_OK;
+}
+struct F32HookShape {      // fB / fT / fseed of the context for the life of one hook call
+    wn_ctx* c; int fB, fT; uint64_t fseed;
+    F32HookShape(wn_ctx* ctx, int B, int T, uint64_t seed) : c(ctx), fB(ctx->fB), fT(ctx->fT), fseed(ctx->fseed) { c->fB = B; c->fT = T; c->fseed = seed; }
+    ~F32HookShape() { c->fB = fB; c->fT = fT; c->fseed = fseed; }
+};
+extern "C" int wn_test_f32_sgemm(wn_ctx* c, int32_t B, int32_t T, const float* In, int32_t ld_in, int32_t col0, int32_t shift, const float* W, int32_t wk, int32_t wm,
+                                 int32_t K, int32_t M, float* Out, int32_t ld_out, int32_t accumulate, const float* mask, int32_t ld_mask, int32_t drop_on_out,
+                                 float alpha, float scale, const float* bias, int32_t bias_bstride, const float* add, int32_t ld_add, int32_t relu, int32_t out_bot,
+                                 uint32_t key_lo, uint32_t key_hi, uint32_t thresh16, float keep_scale, int32_t drop_ld, void* stream) {
+    if (!c) return WN_E_ARG;
+    int rc = f32_hook_enter(c, "wn_test_f32_sgemm", B, T);
+    if (rc) return rc;
+    if (!In || !W || !Out || K <= 0 || M <= 0) WN_FAIL(c, WN_E_ARG, "wn_test_f32_sgemm: null operand or K = %d, M = %d not positive", K, M);
+    SgemmArgs a = mk(In, ld_in, shift, W, wk, K, M, Out, ld_out);
+    a.col0 = col0; a.wk = wk; a.wm = wm; a.accumulate = accumulate; a.mask = mask; a.ld_mask = ld_mask; a.drop_on_out = drop_on_out; a.alpha = alpha; a.scale = scale;
+    a.bias = bias; a.bias_bstride = bias_bstride; a.add = add; a.ld_add = ld_add; a.relu = relu; a.out_bot = out_bot;
+    a.key_lo = key_lo; a.key_hi = key_hi; a.thresh16 = thresh16; a.keep_scale = keep_scale; a.drop_ld = drop_ld;
+    F32HookShape shape(c, B, T, c->fseed);
+    return sgemm(c, a, (hipStream_t)stream);
+}
+extern "C" int wn_test_f32_wgrad(wn_ctx* c, int32_t B, int32_t T, const float* A, int32_t lda, int32_t shift, int32_t K, const float* Bm, int32_t ldb, int32_t M,
+                                 float* out, int32_t ldo, float alpha, int32_t drop_layer, uint64_t seed, float* bias_out, float* bias_out2, void* stream) {
+    if (!c) return WN_E_ARG;
+    int rc = f32_hook_enter(c, "wn_test_f32_wgrad", B, T);
+    if (rc) return rc;
+    if (!Bm || M <= 0 || (A && (K <= 0 || !out)) || (!A && !bias_out && !bias_out2)) WN_FAIL(c, WN_E_ARG, "wn_test_f32_wgrad: null operand or K = %d, M = %d not positive", K, M);
+    if ((rc = f32_reserve(c)) || (rc = f32_reserve_bwd(c))) return rc;
+    F32HookShape shape(c, B, T, seed);
+    return wgrad32(c, A, lda, shift, K, Bm, ldb, M, out, ldo, alpha, drop_layer, bias_out, bias_out2, (hipStream_t)stream);
+}
+extern "C" int wn_test_f32_gate(wn_ctx* c, const float* Z, const float* GU, float* U, float* DZ, int64_t rows, int32_t GH, void* stream) {
+    if (!c) return WN_E_ARG;
+    if (c->cfg.compute_dtype != WN_COMPUTE_F32) WN_FAIL(c, WN_E_STATE, "wn_test_f32_gate: the context is not in the fp32 mode (compute_dtype = WN_COMPUTE_F32)");
+    if (!Z || !GU || !U || !DZ || rows <= 0 || GH <= 0) WN_FAIL(c, WN_E_ARG, "wn_test_f32_gate: null operand or rows = %lld, GH = %d not positive", (long long)rows, GH);
+    gate32(Z, U, rows, GH, (hipStream_t)stream);
+    gate_bwd32(GU, Z, DZ, rows, GH, (hipStream_t)stream);
     WN_LAUNCH_CHECK(c);
     return WN_OK;
 }

@@ -168,6 +168,10 @@ def load_library():
         'wn_test_mfma16_mask': (ctypes.c_int, [vp]),
         'wn_test_pack_info': (ctypes.c_int, [vp, ctypes.c_char_p, i32, ctypes.POINTER(i32)]),
         'wn_test_pack_copy': (ctypes.c_int, [vp, ctypes.c_char_p, i32, vp, i64]),
+        'wn_test_f32_sgemm': (ctypes.c_int, [vp, i32, i32, vp, i32, i32, i32, vp, i32, i32, i32, i32, vp, i32, i32, vp, i32, i32, f32, f32, vp, i32, vp, i32, i32, i32,
+                                             ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, f32, i32, vp]),
+        'wn_test_f32_wgrad': (ctypes.c_int, [vp, i32, i32, vp, i32, i32, i32, vp, i32, i32, vp, i32, f32, i32, u64, vp, vp, vp]),
+        'wn_test_f32_gate': (ctypes.c_int, [vp, vp, vp, vp, vp, i64, i32, vp]),
         'wn_test_pipe_layout': (ctypes.c_int, [i32, i32, i32, vp, i32, vp, i32, vp, vp]),
         'wn_test_device_resources': (ctypes.c_int, [ctypes.POINTER(i64)]),
         'wn_synth_pipe_dtype': (ctypes.c_int, [vp, i32]),
@@ -781,6 +785,40 @@ class Engine:
         out = torch.empty(rows, cols, dtype=torch.float32, device='cuda')
         self._ok(self.lib.wn_debug_copy(self.h, name.encode(), int(layer), _ptr(out), ctypes.c_int64(rows * cols), _stream()))
         return out
+
+    def f32_sgemm(self, B, T, In, ld_in, W, wk, wm, K, M, Out, ld_out, shift=0, col0=0, accumulate=0, mask=None, ld_mask=0, drop_on_out=0, alpha=1.0, scale=1.0,
+                  bias=None, bias_bstride=0, add=None, ld_add=0, relu=0, out_bot=0, key=(0, 0), thresh16=0, keep_scale=1.0, drop_ld=0):
+        """Test hook: ONE launch of the fp32 mode's SGEMM on float32 device tensors of the caller's (wn_test_f32_sgemm; tensors may be views that
+        start at any float of a buffer, the pitches are the caller's to state)."""
+        import torch
+        for name, t in (('In', In), ('W', W), ('Out', Out), ('mask', mask), ('bias', bias), ('add', add)):
+            if t is not None:
+                _check(t, torch.float32, name)
+        self._ok(self.lib.wn_test_f32_sgemm(self.h, int(B), int(T), _ptr(In), int(ld_in), int(col0), int(shift), _ptr(W), int(wk), int(wm), int(K), int(M), _ptr(Out),
+                                            int(ld_out), int(accumulate), _ptr(mask), int(ld_mask), int(drop_on_out), float(alpha), float(scale), _ptr(bias),
+                                            int(bias_bstride), _ptr(add), int(ld_add), int(relu), int(out_bot), int(key[0]), int(key[1]), int(thresh16),
+                                            float(keep_scale), int(drop_ld), _stream()))
+
+    def f32_wgrad(self, B, T, A, lda, K, Bm, ldb, M, out, ldo, shift=0, alpha=1.0, drop_layer=-1, seed=0, bias_out=None, bias_out2=None):
+        """Test hook: ONE weight gradient of the fp32 mode (launch + slab reduction) on float32 device tensors of the caller's (wn_test_f32_wgrad).
+        A None: only the column sums of Bm into bias_out / bias_out2.  drop_layer >= 0: the engine's wavenet_dropout keyed by (seed, drop_layer) on A."""
+        import torch
+        for name, t in (('A', A), ('Bm', Bm), ('out', out), ('bias_out', bias_out), ('bias_out2', bias_out2)):
+            if t is not None:
+                _check(t, torch.float32, name)
+        self._ok(self.lib.wn_test_f32_wgrad(self.h, int(B), int(T), _ptr(A), int(lda), int(shift), int(K), _ptr(Bm), int(ldb), int(M), _ptr(out), int(ldo), float(alpha),
+                                            int(drop_layer), ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), _ptr(bias_out), _ptr(bias_out2), _stream()))
+
+    def f32_gate(self, Z, GU):
+        """Test hook: the fp32 mode's gate and its derivative on Z [rows, 2 GH] and GU [rows, GH] -> (U [rows, GH], DZ [rows, 2 GH])  (wn_test_f32_gate)."""
+        import torch
+        _check(Z, torch.float32, 'Z'); _check(GU, torch.float32, 'GU')
+        rows, GH = int(GU.shape[0]), int(GU.shape[1])
+        if tuple(Z.shape) != (rows, 2 * GH):
+            raise ValueError('f32_gate: Z must be [rows=%d, 2 * GH=%d] (got %s)' % (rows, 2 * GH, tuple(Z.shape)))
+        U = torch.empty_like(GU); DZ = torch.empty_like(Z)
+        self._ok(self.lib.wn_test_f32_gate(self.h, _ptr(Z), _ptr(GU), _ptr(U), _ptr(DZ), ctypes.c_int64(rows), GH, _stream()))
+        return U, DZ
 
     def pack_info(self, kind, layer=0):
         """(M, K, kil, gate_interleave) of one fragment-ordered operand pack (wn_test_pack_info; tests only)."""

@@ -48,7 +48,9 @@ def test_library_loads_and_exports_every_declared_symbol():
     assert set(_ext.exported_symbols()) <= declared | {'wn_debug_copy'}
     for sym in ('wn_test_pack_info', 'wn_test_pack_copy'):      # the read hooks of the operand packs: declared, exported and bound
         assert sym in declared and sym in _ext.exported_symbols() and hasattr(lib, sym), sym
-    for name in ('PARAMS', 'DEFF', 'B1SUM', 'SKIPB'):           # ... and the weight-path names of wn_debug_copy are documented where it is declared
+    for sym in ('wn_test_f32_sgemm', 'wn_test_f32_wgrad', 'wn_test_f32_gate'):      # the single-launch hooks of the fp32 training mode
+        assert sym in declared and sym in _ext.exported_symbols() and hasattr(lib, sym), sym
+    for name in ('PARAMS', 'DEFF', 'B1SUM', 'SKIPB', 'Z', 'SK', 'H1'):      # ... and the weight-path / fp32-mode names of wn_debug_copy are documented where it is declared
         assert '"%s"' % name in header, name
     # host-only entry points work without a GPU
     assert abs(_ext.learning_rate('exponential', 1e-3, 200000) - 5e-4) < 1e-9
