@@ -880,6 +880,56 @@ int64_t wn_griffin_num_samples(const wn_griffin* h, int64_t frames);
 int  wn_griffin_run(wn_griffin* h, const float* src, int32_t src_kind, int32_t F_max, const int32_t* frames, int32_t B, const float* u, const float* y0,
                     int64_t y0_pitch, int32_t iters, int32_t flags, float* out, int64_t out_pitch, void* stream);
 
+/* ---- alignment check (csrc/wn_align.hip): MCD along a dynamic-time-warping path, and the path itself -------------------------------------------
+ * The reconstruction and pitch checks need frame-aligned signals.  A generated utterance whose mels were PREDICTED (synthesize.py --mels_dir) has another
+ * length and timing than any recording; this module aligns the two mel-spectrograms by dynamic time warping over their cepstral distance and reports the
+ * mel-cepstral distortion along the path (MCD-DTW) with the path and the two frame maps, so that F0 can be compared along the same path.  A handle of its
+ * own, independent of wn_ctx; additions only, WN_ABI_VERSION unchanged.  a, b: device float32, each channels-first [B, num_mels, pitch] or channels-last
+ * [B, pitch, num_mels] as wn_melcmp_run takes them; row r has frames_a[r] resp. frames_b[r] frames (Fa, Fb), each >= 1; elements beyond are never read
+ * into a result.  Arithmetic, all float32, every step rounded on its own (csrc/wn_align.h):
+ *   cepstra     u[m] = unit_db * x[m];  c[k] = sum_m D[k][m] u[m], k = 1 ... n_cep, fused multiply-adds in channel order, D the table of wn_melcmp
+ *   cell cost   cost(i, j) = sqrt(0.5 * sum_k (ca[i][k] - cb[j][k])^2): e = ca - cb, acc = fma(e, e, acc), k ascending -- the MCD of the frame pair in dB
+ *   band        (i, j) is admissible iff band == 0 or |i Fb - j Fa| <= band * max(Fa, Fb) (int64); inadmissible cells count as +inf.  For band >= 1
+ *               the staircase j = floor(i Fb / Fa) (or its transpose) lies inside the band, so (0, 0) and (Fa-1, Fb-1) are always connected
+ *   recurrence  Dm(0, 0) = cost(0, 0);  Dm(i, j) = cost(i, j) + min(Dm(i-1, j-1), Dm(i-1, j), Dm(i, j-1)), one rounded add; the predecessor is the smallest
+ *               candidate, ties to the first of diagonal, (i-1, j), (i, j-1); cells outside the matrix or the band are never chosen
+ *   path        back-trace from (Fa-1, Fb-1) to (0, 0), at most Fa + Fb - 2 steps whose indices cannot leave the matrix whatever the values (non-finite
+ *               inputs give an unspecified but valid path), delivered in FORWARD order
+ * Outputs (device; elements beyond a row's extent keep the caller's bytes): path int32 [B, 2, path_pitch] (i then j of the n_path cells), map_ab int32
+ * [B, map_a_pitch] the largest j paired with i, map_ba int32 [B, map_b_pitch] the largest i paired with j -- each may be NULL -- and summary float
+ * [B, 7]: Fa, Fb, n_path, total = Dm(Fa-1, Fb-1), mcd_dtw = (the sum of the path's costs as doubles in path order) / n_path, the share of
+ * non-diagonal steps, max_p |i_p Fb - j_p Fa| / max(Fa, Fb).  A row's results depend on that row alone -- not on B, its index, the pitches, the
+ * layouts, which outputs are asked for, or the run -- bit for bit.  Four launches per group of 32 rows on the caller's stream (cepstra, cost matrix,
+ * recurrence with one workgroup per row walking 64 x 64 blocks along block anti-diagonals, back-trace); nothing waits across workgroups.  The cepstra,
+ * the cost matrix [max_batch, max_frames_a, max_frames_b] and the 2-bit directions are reserved at creation; no run allocates or synchronises, and the
+ * frame counts travel as kernel arguments (the host arrays are free when the call returns).  max_batch = 0 makes a validation-only handle that
+ * touches no device and refuses every run.
+ * Validation before any device call: WN_E_ARG for a null pointer (a, b, frames_a, frames_b, summary), a foreign abi_version, num_mels outside 1 ... 128,
+ * n_cep outside [1, num_mels - 1], unit_db not finite or <= 0, band outside [0, 2^20], a negative max_batch / max_frames_a / max_frames_b (or below 1 with
+ * max_batch > 0), B < 1, a frame count < 1; WN_E_UNSUPPORTED from wn_align_create for max_frames_a or max_frames_b above 4096 or
+ * max_batch x max_frames_a x max_frames_b above 2^27 cells (the reserve limit); WN_E_SHAPE for B > max_batch, frames above the maxima, path_pitch below
+ * the longest possible path max_r (Fa + Fb - 1), a map pitch or an input pitch below the longest row. */
+typedef struct wn_align_config {
+    int32_t abi_version;   /* = WN_ABI_VERSION */
+    int32_t num_mels;      /* 1 ... 128 */
+    int32_t n_cep;         /* cepstral coefficients 1 ... n_cep of the cost, 1 <= n_cep <= num_mels - 1 */
+    float   unit_db;       /* as wn_melcmp_config */
+    int32_t band;          /* 0: every cell admissible; r >= 1: |i Fb - j Fa| <= r max(Fa, Fb) */
+    int32_t max_batch;     /* rows per call; 0: a validation-only handle that touches no device and refuses every run */
+    int32_t max_frames_a;  /* frames per row of a and of b: size the handle's scratch */
+    int32_t max_frames_b;
+} wn_align_config;
+typedef struct wn_align wn_align;
+int  wn_align_create(const wn_align_config* cfg, wn_align** out);
+void wn_align_destroy(wn_align* h);
+const char* wn_align_last_error(const wn_align* h);   /* NULL: text of the last failed create or host hook */
+/* rows and columns of one block of the recurrence (64): tests place frame counts around its multiples */
+int  wn_align_tile(const wn_align* h);
+/* a, b: device float; frames_a, frames_b: HOST int32 [B]; path, map_ab, map_ba: device int32 or NULL; summary: device float [B, 7] */
+int  wn_align_run(wn_align* h, const float* a, int32_t a_channels_first, int64_t a_pitch, const float* b, int32_t b_channels_first, int64_t b_pitch,
+                  const int32_t* frames_a, const int32_t* frames_b, int32_t B, int32_t* path, int64_t path_pitch, int32_t* map_ab, int64_t map_a_pitch,
+                  int32_t* map_ba, int64_t map_b_pitch, float* summary, void* stream);
+
 /* ---- introspection ------------------------------------------------------------------------------ */
 int64_t wn_workspace_bytes(const wn_ctx* ctx);
 /* name of the kernel that dominates training time (bench.py's roofline line names it) */
@@ -1040,6 +1090,25 @@ int wn_test_f32_sgemm(wn_ctx* ctx, int32_t B, int32_t T, const float* In, int32_
 int wn_test_f32_wgrad(wn_ctx* ctx, int32_t B, int32_t T, const float* A, int32_t lda, int32_t shift, int32_t K, const float* Bm, int32_t ldb, int32_t M,
                       float* out, int32_t ldo, float alpha, int32_t drop_layer, uint64_t seed, float* bias_out, float* bias_out2, void* stream);
 int wn_test_f32_gate(wn_ctx* ctx, const float* Z, const float* GU, float* U, float* DZ, int64_t rows, int32_t GH, void* stream);
+/* Alignment check test hooks.  wn_test_align_host: a run on the host (no handle, no GPU), every pointer in HOST memory, evaluated by the very functions
+ * the kernels inline (csrc/wn_align.h): the same bits.  cfg->max_batch / max_frames_* are not limits here; otherwise validated as a create followed by a
+ * run.  The stages are optional outputs with Fa_max / Fb_max the longest rows of the call: cep_a [B, Fa_max, n_cep], cep_b [B, Fb_max, n_cep], cost and dm
+ * [B, Fa_max, Fb_max]; cells beyond a row's extent are left alone.
+ * wn_test_align_dp_host: recurrence, back-trace and outputs on a caller's HOST cost matrix [B, Fa_max, Fb_max] instead of mels, band as given; dm optional.
+ * wn_test_align_dp: the same on the device through the kernels of wn_align_run, cost a DEVICE float [B, Fa_max, Fb_max]; validated as a run.
+ * wn_test_align_store_matrix: with on != 0 later runs also keep Dm in a buffer [max_batch, max_frames_a, max_frames_b] reserved by this call; the results
+ * of a run are the same bits either way.  wn_test_align_copy (SYNCHRONISES the stream): the handle's own scratch of the last run into dst HOST float [cap],
+ * what = 0 the cepstra of a [max_batch, max_frames_a, n_cep], 1 of b [max_batch, max_frames_b, n_cep], 2 the cost matrix and 3 Dm [max_batch, max_frames_a,
+ * max_frames_b]; WN_E_ARG when cap is below that size, WN_E_STATE for Dm before wn_test_align_store_matrix. */
+int wn_test_align_host(const wn_align_config* cfg, const float* a, int32_t a_channels_first, int64_t a_pitch, const float* b, int32_t b_channels_first, int64_t b_pitch,
+                       const int32_t* frames_a, const int32_t* frames_b, int32_t B, int32_t* path, int64_t path_pitch, int32_t* map_ab, int64_t map_a_pitch,
+                       int32_t* map_ba, int64_t map_b_pitch, float* summary, float* cep_a, float* cep_b, float* cost, float* dm);
+int wn_test_align_dp_host(int32_t band, const float* cost, int32_t Fa_max, int32_t Fb_max, const int32_t* frames_a, const int32_t* frames_b, int32_t B, int32_t* path,
+                          int64_t path_pitch, int32_t* map_ab, int64_t map_a_pitch, int32_t* map_ba, int64_t map_b_pitch, float* summary, float* dm);
+int wn_test_align_dp(wn_align* h, const float* cost, int32_t Fa_max, int32_t Fb_max, const int32_t* frames_a, const int32_t* frames_b, int32_t B, int32_t* path,
+                     int64_t path_pitch, int32_t* map_ab, int64_t map_a_pitch, int32_t* map_ba, int64_t map_b_pitch, float* summary, void* stream);
+int wn_test_align_store_matrix(wn_align* h, int32_t on);
+int wn_test_align_copy(wn_align* h, int32_t what, float* dst, int64_t cap, void* stream);
 #endif /* WN_NO_TEST_HOOKS */
 
 #ifdef __cplusplus

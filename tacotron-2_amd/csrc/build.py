@@ -12,8 +12,8 @@ import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCES = ['wn_api.hip', 'wn_pack.hip', 'wn_frontend.hip', 'wn_loss.hip', 'wn_optim.hip', 'wn_train.hip', 'wn_synth.hip', 'wn_synth_pipe.hip', 'wn_f32.hip', 'wn_synth_f32.hip', 'wn_mel.hip', 'wn_fold.hip', 'wn_post.hip', 'wn_melcmp.hip', 'wn_stats.hip', 'wn_pitch.hip', 'wn_denoise.hip', 'wn_denoise_stream.hip', 'wn_resample.hip', 'wn_mel_stream.hip', 'wn_griffin.hip']
-HEADERS = ['wn_common.h', 'wn_dev.h', 'wn_post.h', 'wn_melcmp.h', 'wn_stats.h', 'wn_pitch.h', 'wn_denoise.h', 'wn_denoise_dev.h', 'wn_denoise_stream.h', 'wn_resample.h', 'wn_mel.h', 'wn_mel_stream.h', 'wn_griffin.h', 'wn_steps.h', 'wn_temper.h', 'wn_tile.h', 'wn_tile8p.h', 'wn_wgrad.h', 'wn_mulaw_tables.h', os.path.join('..', '..', 'include', 'wavenet_mi355.h')]
+SOURCES = ['wn_api.hip', 'wn_pack.hip', 'wn_frontend.hip', 'wn_loss.hip', 'wn_optim.hip', 'wn_train.hip', 'wn_synth.hip', 'wn_synth_pipe.hip', 'wn_f32.hip', 'wn_synth_f32.hip', 'wn_mel.hip', 'wn_fold.hip', 'wn_post.hip', 'wn_melcmp.hip', 'wn_stats.hip', 'wn_pitch.hip', 'wn_denoise.hip', 'wn_denoise_stream.hip', 'wn_resample.hip', 'wn_mel_stream.hip', 'wn_griffin.hip', 'wn_align.hip']
+HEADERS = ['wn_common.h', 'wn_dev.h', 'wn_post.h', 'wn_melcmp.h', 'wn_stats.h', 'wn_pitch.h', 'wn_denoise.h', 'wn_denoise_dev.h', 'wn_denoise_stream.h', 'wn_resample.h', 'wn_mel.h', 'wn_mel_stream.h', 'wn_griffin.h', 'wn_align.h', 'wn_steps.h', 'wn_temper.h', 'wn_tile.h', 'wn_tile8p.h', 'wn_wgrad.h', 'wn_mulaw_tables.h', os.path.join('..', '..', 'include', 'wavenet_mi355.h')]
 LIB = os.path.join(HERE, 'libwavenet_mi355.so')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++20', '-fPIC', '-munsafe-fp-atomics', '-Wall', '-Wno-unused-function', '-Wno-unused-value', '-Wno-inline-asm']
 

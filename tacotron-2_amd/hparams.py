@@ -126,6 +126,12 @@ MI355 = dict(
                                        # in numpy), and, with the two checks above on, its scores through the same check handles in wavs/reconstruction_griffin_lim.tsv /
                                        # wavs/pitch_griffin_lim.tsv with one log line beside the model's.  False: no handle exists, nothing of it runs and every file is
                                        # byte-identical to a run without the key
+    mi355_alignment_reference_dir='',  # a directory of recordings: every utterance Synthesizer.synthesize generates (all three routes; the point is --mels_dir with PREDICTED
+                                       # mels, whose output has another length and timing than any recording) whose basename -- as it is, or without a leading mel- --
+                                       # has a <name>.wav there is aligned with it by dynamic time warping over the mel cepstra on the device (csrc/wn_align.hip) and scored
+                                       # along the path: MCD-DTW, F0 RMSE, voicing and gross pitch error, one row appended to wavs/alignment.tsv, one log line.  '': no
+                                       # handle exists, nothing of it runs and every file is byte-identical to a run without the key
+    mi355_alignment_band=0,            # 0: every frame pair is admissible; r >= 1: only pairs with |i Fb - j Fa| <= r max(Fa, Fb)
     mi355_pitch_fmin=60.0,             # lowest f0 searched, Hz: tau_max = ceil(sample_rate / fmin)
     mi355_pitch_fmax=500.0,            # highest f0 searched, Hz: tau_min = max(2, sample_rate // fmax)
     mi355_pitch_threshold=0.15,        # YIN's absolute threshold on the normalised difference: a frame with no lag below it is unvoiced

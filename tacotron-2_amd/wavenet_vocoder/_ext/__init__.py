@@ -74,6 +74,11 @@ class WnMelcmpConfig(ctypes.Structure):
                 ('max_batch', ctypes.c_int32), ('max_frames', ctypes.c_int32)]
 
 
+class WnAlignConfig(ctypes.Structure):
+    _fields_ = [('abi_version', ctypes.c_int32), ('num_mels', ctypes.c_int32), ('n_cep', ctypes.c_int32), ('unit_db', ctypes.c_float), ('band', ctypes.c_int32),
+                ('max_batch', ctypes.c_int32), ('max_frames_a', ctypes.c_int32), ('max_frames_b', ctypes.c_int32)]
+
+
 class WnStatsConfig(ctypes.Structure):
     _fields_ = [('abi_version', ctypes.c_int32), ('max_rows', ctypes.c_int32), ('max_time', ctypes.c_int32), ('max_tensors', ctypes.c_int32)]
 
@@ -295,6 +300,17 @@ def load_library():
         'wn_test_griffin_store_spectrum': (ctypes.c_int, [vp, i32]),
         'wn_test_griffin_copy': (ctypes.c_int, [vp, i32, vp, i32, vp]),
         'wn_test_griffin_host': (ctypes.c_int, [ctypes.POINTER(WnGriffinConfig), vp, vp, i32, i32, ctypes.POINTER(i32), i32, vp, vp, i64, i32, vp, i64, vp, vp]),
+        'wn_align_create': (ctypes.c_int, [ctypes.POINTER(WnAlignConfig), ctypes.POINTER(vp)]),
+        'wn_align_destroy': (None, [vp]),
+        'wn_align_last_error': (ctypes.c_char_p, [vp]),
+        'wn_align_tile': (ctypes.c_int, [vp]),
+        'wn_align_run': (ctypes.c_int, [vp, vp, i32, i64, vp, i32, i64, ctypes.POINTER(i32), ctypes.POINTER(i32), i32, vp, i64, vp, i64, vp, i64, vp, vp]),
+        'wn_test_align_host': (ctypes.c_int, [ctypes.POINTER(WnAlignConfig), vp, i32, i64, vp, i32, i64, ctypes.POINTER(i32), ctypes.POINTER(i32), i32, vp, i64, vp, i64, vp, i64,
+                                              vp, vp, vp, vp, vp]),
+        'wn_test_align_dp_host': (ctypes.c_int, [i32, vp, i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), i32, vp, i64, vp, i64, vp, i64, vp, vp]),
+        'wn_test_align_dp': (ctypes.c_int, [vp, vp, i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), i32, vp, i64, vp, i64, vp, i64, vp, vp]),
+        'wn_test_align_store_matrix': (ctypes.c_int, [vp, i32]),
+        'wn_test_align_copy': (ctypes.c_int, [vp, i32, vp, i64, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(lib, name)            # AttributeError here == ABI symbol missing
@@ -1389,6 +1405,196 @@ class MelCompare:
     def close(self):
         if getattr(self, 'h', None):
             self.lib.wn_melcmp_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# ---- alignment check (csrc/wn_align.hip)
+ALIGN_COLUMNS = ('frames_a', 'frames_b', 'n_path', 'total', 'mcd_dtw', 'stretch', 'deviation')      # summary[b][j]
+ALIGN_STAGES = ('cep_a', 'cep_b', 'cost', 'dm')                                                       # wn_test_align_copy's `what`
+
+
+def align_config(num_mels, n_cep=13, unit_db=1.0, band=0, max_batch=0, max_frames_a=0, max_frames_b=0):
+    cfg = WnAlignConfig()
+    cfg.abi_version = WN_ABI_VERSION
+    cfg.num_mels, cfg.n_cep, cfg.unit_db, cfg.band = int(num_mels), int(n_cep), float(unit_db), int(band)
+    cfg.max_batch, cfg.max_frames_a, cfg.max_frames_b = int(max_batch), int(max_frames_a), int(max_frames_b)
+    return cfg
+
+
+def _align_rows(frames_a, frames_b, B):
+    fa, fb = [int(f) for f in frames_a], [int(f) for f in frames_b]
+    if len(fa) != B or len(fb) != B:
+        raise ValueError('frames_a and frames_b must have one entry per row')
+    return fa, fb
+
+
+def _align_outputs(B, fa, fb, xp_full, path_pitch=None, map_a_pitch=None, map_b_pitch=None):
+    """The four outputs of a call, filled with -7 / NaN (cells beyond a row's extent keep that); xp_full(shape, value, kind) makes one."""
+    pp = max([a + b - 1 for a, b in zip(fa, fb)] + [1]) if path_pitch is None else int(path_pitch)
+    pa = max(fa + [1]) if map_a_pitch is None else int(map_a_pitch)
+    pb = max(fb + [1]) if map_b_pitch is None else int(map_b_pitch)
+    return xp_full((B, 2, pp), -7, 'i'), xp_full((B, pa), -7, 'i'), xp_full((B, pb), -7, 'i'), xp_full((B, len(ALIGN_COLUMNS)), float('nan'), 'f'), pp, pa, pb
+
+
+def _np_full(shape, value, kind):
+    return np.full(shape, value, np.int32 if kind == 'i' else np.float32)
+
+
+def align_host(a, b, frames_a, frames_b, num_mels=None, n_cep=13, unit_db=1.0, band=0, a_channels_first=True, b_channels_first=True, stages=False,
+               path_pitch=None, map_a_pitch=None, map_b_pitch=None):
+    """wn_test_align_host: the alignment check on the host (no handle, no GPU), in the device's order.  a, b: numpy float32, each [B, num_mels, pitch]
+    (channels_first) or [B, pitch, num_mels].  Returns a dict: path int32 [B, 2, path_pitch], map_ab int32 [B, map_a_pitch], map_ba int32 [B, map_b_pitch],
+    summary float32 [B, 7] (ALIGN_COLUMNS) and, with stages, cep_a [B, Fa_max, n_cep], cep_b [B, Fb_max, n_cep], cost and dm [B, Fa_max, Fb_max]; cells
+    beyond a row's extent keep the -7 / NaN they are created with."""
+    a, b = np.ascontiguousarray(a, dtype=np.float32), np.ascontiguousarray(b, dtype=np.float32)
+    M = int(a.shape[1 if a_channels_first else 2]) if num_mels is None else int(num_mels)
+    B, ap = _melcmp_geometry(a, a_channels_first, M, 'a')
+    B2, bp = _melcmp_geometry(b, b_channels_first, M, 'b')
+    if B2 != B:
+        raise ValueError('a and b must have one entry per row')
+    fa, fb = _align_rows(frames_a, frames_b, B)
+    cfg = align_config(M, n_cep, unit_db, band)
+    path, mab, mba, sm, pp, pa, pb = _align_outputs(B, fa, fb, _np_full, path_pitch, map_a_pitch, map_b_pitch)
+    res = {'path': path, 'map_ab': mab, 'map_ba': mba, 'summary': sm}
+    vp = ctypes.c_void_p
+    st = [None] * 4
+    if stages:
+        na, nb = max(fa + [1]), max(fb + [1])
+        for k, shape in enumerate(((B, na, int(n_cep)), (B, nb, int(n_cep)), (B, na, nb), (B, na, nb))):
+            res[ALIGN_STAGES[k]] = np.full(shape, np.nan, np.float32)
+            st[k] = res[ALIGN_STAGES[k]].ctypes.data_as(vp)
+    rc = load_library().wn_test_align_host(ctypes.byref(cfg), a.ctypes.data_as(vp), int(bool(a_channels_first)), ap, b.ctypes.data_as(vp), int(bool(b_channels_first)), bp,
+                                           (ctypes.c_int32 * max(B, 1))(*fa), (ctypes.c_int32 * max(B, 1))(*fb), B, path.ctypes.data_as(vp), pp, mab.ctypes.data_as(vp), pa,
+                                           mba.ctypes.data_as(vp), pb, sm.ctypes.data_as(vp), *st)
+    if rc != 0:
+        raise WnError(rc, (load_library().wn_align_last_error(None) or b'').decode())
+    return res
+
+
+def align_dp_host(cost, frames_a, frames_b, band=0, return_dm=True):
+    """wn_test_align_dp_host: recurrence, back-trace and outputs on a caller's cost matrix, numpy float32 [B, Fa_max, Fb_max].  Returns the dict of
+    align_host, with dm float32 [B, Fa_max, Fb_max] when return_dm."""
+    cost = np.ascontiguousarray(cost, dtype=np.float32)
+    if cost.ndim != 3:
+        raise ValueError('cost must be [B, Fa_max, Fb_max]')
+    B = int(cost.shape[0])
+    fa, fb = _align_rows(frames_a, frames_b, B)
+    path, mab, mba, sm, pp, pa, pb = _align_outputs(B, fa, fb, _np_full)
+    dm = np.full(cost.shape, np.nan, np.float32) if return_dm else None
+    vp = ctypes.c_void_p
+    rc = load_library().wn_test_align_dp_host(int(band), cost.ctypes.data_as(vp), int(cost.shape[1]), int(cost.shape[2]), (ctypes.c_int32 * max(B, 1))(*fa),
+                                              (ctypes.c_int32 * max(B, 1))(*fb), B, path.ctypes.data_as(vp), pp, mab.ctypes.data_as(vp), pa, mba.ctypes.data_as(vp), pb,
+                                              sm.ctypes.data_as(vp), dm.ctypes.data_as(vp) if return_dm else None)
+    if rc != 0:
+        raise WnError(rc, (load_library().wn_align_last_error(None) or b'').decode())
+    res = {'path': path, 'map_ab': mab, 'map_ba': mba, 'summary': sm}
+    if return_dm:
+        res['dm'] = dm
+    return res
+
+
+class Aligner:
+    """One wn_align: dynamic time warping of two mel-spectrograms over their cepstral distance on the current device (csrc/wn_align.hip), asynchronously.
+    max_batch = 0 gives a validation-only handle (no device; every run is refused)."""
+
+    def __init__(self, num_mels, max_batch, max_frames_a, max_frames_b, n_cep=13, unit_db=1.0, band=0):
+        self.lib = load_library()
+        self.cfg = align_config(num_mels, n_cep, unit_db, band, max_batch, max_frames_a, max_frames_b)
+        h = ctypes.c_void_p()
+        rc = self.lib.wn_align_create(ctypes.byref(self.cfg), ctypes.byref(h))
+        if rc != 0:
+            raise WnError(rc, (self.lib.wn_align_last_error(None) or b'').decode())
+        self.h = h
+        self.num_mels, self.n_cep, self.band = int(num_mels), int(n_cep), int(band)
+        self.max_batch, self.max_frames_a, self.max_frames_b = int(max_batch), int(max_frames_a), int(max_frames_b)
+
+    def _ok(self, rc):
+        if rc != 0:
+            raise WnError(rc, (self.lib.wn_align_last_error(self.h) or b'').decode())
+
+    @property
+    def tile(self):
+        return int(self.lib.wn_align_tile(self.h))
+
+    def _outputs(self, B, fa, fb, device, want, out, pitches):
+        import torch
+
+        def full(shape, value, kind):
+            return torch.full(shape, value, dtype=torch.int32 if kind == 'i' else torch.float32, device=device)
+        if out is None:
+            path, mab, mba, sm, _, _, _ = _align_outputs(B, fa, fb, full, *pitches)
+            out = {'path': path, 'map_ab': mab, 'map_ba': mba, 'summary': sm}
+            for k in ('path', 'map_ab', 'map_ba'):
+                if k not in want:
+                    out[k] = None
+        for k in ('path', 'map_ab', 'map_ba'):
+            if out.get(k) is not None:
+                _check(out[k], torch.int32, k)
+        _check(out['summary'], torch.float32, 'summary')
+        if tuple(out['summary'].shape) != (B, len(ALIGN_COLUMNS)):
+            raise ValueError('summary must be %r' % ((B, len(ALIGN_COLUMNS)),))
+
+        def pitch(t, dim):
+            if t is None:
+                return 0
+            if t.dim() != dim or int(t.shape[0]) != B or (dim == 3 and int(t.shape[1]) != 2):
+                raise ValueError('an output of the wrong shape: %r' % (tuple(t.shape),))
+            return int(t.shape[-1])
+        return out, pitch(out.get('path'), 3), pitch(out.get('map_ab'), 2), pitch(out.get('map_ba'), 2)
+
+    def run(self, a, b, frames_a, frames_b, a_channels_first=True, b_channels_first=True, want=('path', 'map_ab', 'map_ba'), out=None, pitches=(None, None, None)):
+        """a, b float32 on the device, each [B, num_mels, pitch] (channels_first) or [B, pitch, num_mels]; frames_a, frames_b: B ints each (host).  Returns a
+        dict of device tensors: 'summary' float32 [B, 7] (ALIGN_COLUMNS) and, as `want` lists them (None otherwise), 'path' int32 [B, 2, path_pitch],
+        'map_ab' int32 [B, map_a_pitch], 'map_ba' int32 [B, map_b_pitch]; cells beyond a row's extent keep the -7 / NaN fresh tensors are created with.
+        out: such a dict of ready tensors to write into instead; pitches: (path, map_a, map_b) pitches of fresh tensors."""
+        import torch
+        _check(a, torch.float32, 'a'); _check(b, torch.float32, 'b')
+        B, ap = _melcmp_geometry(a, a_channels_first, self.num_mels, 'a')
+        B2, bp = _melcmp_geometry(b, b_channels_first, self.num_mels, 'b')
+        if B2 != B:
+            raise ValueError('a and b must have one entry per row')
+        fa, fb = _align_rows(frames_a, frames_b, B)
+        out, pp, pa, pb = self._outputs(B, fa, fb, a.device, want, out, pitches)
+        self._ok(self.lib.wn_align_run(self.h, _ptr(a), int(bool(a_channels_first)), ap, _ptr(b), int(bool(b_channels_first)), bp, (ctypes.c_int32 * B)(*fa),
+                                       (ctypes.c_int32 * B)(*fb), B, _ptr(out.get('path')), pp, _ptr(out.get('map_ab')), pa, _ptr(out.get('map_ba')), pb, _ptr(out['summary']),
+                                       _stream()))
+        return out
+
+    def run_dp(self, cost, frames_a, frames_b, want=('path', 'map_ab', 'map_ba'), out=None):
+        """wn_test_align_dp: recurrence and back-trace on a caller's cost matrix, float32 [B, Fa_max, Fb_max] on the device; returns as run."""
+        import torch
+        _check(cost, torch.float32, 'cost')
+        if cost.dim() != 3:
+            raise ValueError('cost must be [B, Fa_max, Fb_max]')
+        B = int(cost.shape[0])
+        fa, fb = _align_rows(frames_a, frames_b, B)
+        out, pp, pa, pb = self._outputs(B, fa, fb, cost.device, want, out, (None, None, None))
+        self._ok(self.lib.wn_test_align_dp(self.h, _ptr(cost), int(cost.shape[1]), int(cost.shape[2]), (ctypes.c_int32 * B)(*fa), (ctypes.c_int32 * B)(*fb), B,
+                                           _ptr(out.get('path')), pp, _ptr(out.get('map_ab')), pa, _ptr(out.get('map_ba')), pb, _ptr(out['summary']), _stream()))
+        return out
+
+    def store_matrix(self, on=True):
+        self._ok(self.lib.wn_test_align_store_matrix(self.h, int(bool(on))))
+
+    def copy_stage(self, what):
+        """wn_test_align_copy (synchronises): the handle's own scratch of the last run as numpy float32 -- 'cep_a' [max_batch, max_frames_a, n_cep], 'cep_b'
+        [max_batch, max_frames_b, n_cep], 'cost' or 'dm' [max_batch, max_frames_a, max_frames_b]."""
+        k = ALIGN_STAGES.index(what)
+        shape = ((self.max_batch, self.max_frames_a, self.n_cep), (self.max_batch, self.max_frames_b, self.n_cep), (self.max_batch, self.max_frames_a, self.max_frames_b),
+                 (self.max_batch, self.max_frames_a, self.max_frames_b))[k]
+        dst = np.empty(shape, np.float32)
+        self._ok(self.lib.wn_test_align_copy(self.h, k, dst.ctypes.data_as(ctypes.c_void_p), int(dst.size), _stream()))
+        return dst
+
+    def close(self):
+        if getattr(self, 'h', None):
+            self.lib.wn_align_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -1044,6 +1044,13 @@ class WaveNet(object):
         from wavenet_vocoder.reconstruction import ReconstructionCheck
         return ReconstructionCheck(self._hparams, rows, max_samples, preemphasis=preemphasis, alarm_db=alarm_db)
 
+    def alignment_check(self, rows, max_samples, band=None):
+        """An AlignmentCheck (wavenet_vocoder/alignment.py) for up to `rows` pairs of signals of up to `max_samples` samples each: a generated utterance
+        against a recording of another length and timing, aligned by dynamic time warping over the mel cepstra and scored along the path, on the device;
+        band None: mi355_alignment_band."""
+        from wavenet_vocoder.alignment import AlignmentCheck
+        return AlignmentCheck(self._hparams, rows, max_samples, band=band)
+
     def pitch_check(self, rows, max_samples):
         """A PitchCheck (wavenet_vocoder/pitch.py) for up to `rows` utterances of up to `max_samples` samples: F0 and voicing of generated audio against
         a recording in the same domain, per utterance, on the device; the geometry comes from the hparams (mi355_pitch_*)."""

@@ -41,6 +41,7 @@ class Synthesizer(object):
         self._post_stages = {}
         self._recon = None
         self._pitch_chk = None
+        self._align_chk = None            # mi355_alignment_reference_dir: the AlignmentCheck; with the key empty no handle exists and nothing of it runs
         self.pitch_references = None      # mi355_pitch_check: the recordings of the next synthesize() call (run_wav_synthesis sets them)
         self._denoiser = None             # mi355_output_denoise > 0: the fitted OutputDenoiser; at 0 no handle exists and nothing of it runs
         if self._denoise_strength() > 0.0:
@@ -187,6 +188,53 @@ class Synthesizer(object):
             log('pitch check skipped: {}'.format(e))
             return None
 
+    def _alignment(self, decoded, generated_wavs, lengths, basenames, out_dir):
+        """mi355_alignment_reference_dir: every generated utterance whose basename has a recording there (alignment.reference_for: <basename>.wav, else the
+        same without a leading mel-) aligned with it by dynamic time warping and scored along the path (WaveNet.alignment_check), one row each appended to
+        <out_dir>/alignment.tsv and one log line.  The recordings are pre-emphasised as preprocessing does, so that they stand beside the model-domain
+        output.  decoded / generated_wavs as _reconstruction takes them; lengths: mel frames per utterance.  Reads results only; a failure logs one line
+        and never fails the run."""
+        ref_dir = str(getattr(self._hparams, 'mi355_alignment_reference_dir', '') or '')
+        if not ref_dir:
+            return None
+        try:
+            from wavenet_vocoder import alignment
+            from wavenet_vocoder.synthesize import pitch_references
+            hop = get_hop_size(self._hparams)
+            found = [(b, alignment.reference_for(ref_dir, name)) for b, name in enumerate(basenames)]
+            found = [(b, p) for b, p in found if p is not None]
+            if not found:
+                log('Alignment check: none of the {} utterance(s) has a recording in {}'.format(len(basenames), ref_dir))
+                return None
+            refs = pitch_references([p for _, p in found], self._hparams)
+            names = [basenames[b] for b, _ in found]
+            gl, rl = [int(lengths[b]) * hop for b, _ in found], [len(r) for r in refs]
+            dev = self.model.device
+            ref = np.zeros((len(refs), max(max(rl), 1)), np.float32)
+            for k, r in enumerate(refs):
+                ref[k, :rl[k]] = r
+            if decoded is None:
+                gen = np.zeros((len(found), max(gl)), np.float32)
+                for k, (b, _) in enumerate(found):
+                    gen[k, :gl[k]] = np.asarray(generated_wavs[b], np.float32)[:gl[k]]
+                gen = torch.from_numpy(gen).to(dev)
+            else:
+                gen = decoded.float()[[b for b, _ in found]].contiguous()
+            chk = self._align_chk
+            need = max(max(gl), max(rl))
+            if chk is None or chk.rows < len(found) or chk.max_samples < need:
+                rows, cap = max(len(found), chk.rows if chk else 0), max(need, chk.max_samples if chk else 0)
+                if chk is not None:
+                    chk.close()
+                chk = self._align_chk = self.model.alignment_check(rows, cap)
+            table = chk.score(gen, gl, torch.from_numpy(ref).to(dev), rl)
+            alignment.append_tsv(os.path.join(out_dir, 'alignment.tsv'), names, table)
+            log(alignment.log_line(names, table))
+            return table
+        except Exception as e:
+            log('alignment check skipped: {}'.format(e))
+            return None
+
     def _griffin_lim_baseline(self, mel_spectrograms, basenames, out_dir):
         """mi355_griffin_lim_baseline: beside every generated wav, <out_dir>/griffin-lim-<basename>.wav -- the model-free inversion of the same conditioning
         (datasets.audio.inv_mel_spectrogram_device, csrc/wn_griffin.hip; with GL_on_GPU off the numpy path), hop (frames - 1) samples, de-emphasised when
@@ -322,11 +370,13 @@ class Synthesizer(object):
             generated_wavs, upsampled_features, pcm, decoded = self._synthesize_wide(c_batch, frames, speaker_ids, nwide)
             self._reconstruction(decoded, generated_wavs, cond, frames, basenames, out_dir)
             self._pitch(decoded, generated_wavs, basenames, out_dir)
+            self._alignment(decoded, generated_wavs, frames, basenames, out_dir)
             return self._write(generated_wavs, upsampled_features, mel_spectrograms, basenames, out_dir, log_dir, pcm)
         if nfold > 0 and not self.synth_debug:
             generated_wavs, upsampled_features, pcm, decoded = self._synthesize_folded(c_batch, frames, speaker_ids, min(nfold, 32), log_dir is not None)
             self._reconstruction(decoded, generated_wavs, cond, frames, basenames, out_dir)
             self._pitch(decoded, generated_wavs, basenames, out_dir)
+            self._alignment(decoded, generated_wavs, frames, basenames, out_dir)
             return self._write(generated_wavs, upsampled_features, mel_spectrograms, basenames, out_dir, log_dir, pcm)
         nslots, nwslots = int(getattr(hparams, 'mi355_synthesis_slots', 0)), int(getattr(hparams, 'mi355_synthesis_wide_slots', 0))
         if (nslots > 0 or nwslots > 0) and not self.synth_debug:
@@ -334,6 +384,7 @@ class Synthesizer(object):
                                                                                       log_dir is not None, wide=nwslots > 0)
             self._reconstruction(decoded, generated_wavs, cond, frames, basenames, out_dir)
             self._pitch(decoded, generated_wavs, basenames, out_dir)
+            self._alignment(decoded, generated_wavs, frames, basenames, out_dir)
             return self._write(generated_wavs, upsampled_features, mel_spectrograms, basenames, out_dir, log_dir, pcm)
         self._ensure_capacity(len(c_batch), maxlen * hop)
         dev = self.model.device
@@ -361,6 +412,7 @@ class Synthesizer(object):
         if not self.synth_debug:
             self._reconstruction(y_hat if device else None, generated_wavs, cond, frames, basenames, out_dir)
             self._pitch(y_hat if device else None, generated_wavs, basenames, out_dir)
+            self._alignment(y_hat if device else None, generated_wavs, frames, basenames, out_dir)
         return self._write(generated_wavs, upsampled_features, mel_spectrograms, basenames, out_dir, log_dir, pcm)
 
     def _synthesize_folded(self, c_batch, lengths, speaker_ids, nrows, want_features):
@@ -382,7 +434,8 @@ class Synthesizer(object):
         staged = device and not dn          # the fold's own stage finishes every group; with the denoiser on, the rows are denoised and finished after the loop, as a whole
         pcm = [] if staged else None
         check = device and (bool(getattr(hparams, 'mi355_reconstruction_check', False)) or
-                            (bool(getattr(hparams, 'mi355_pitch_check', False)) and getattr(self, 'pitch_references', None) is not None))
+                            (bool(getattr(hparams, 'mi355_pitch_check', False)) and getattr(self, 'pitch_references', None) is not None) or
+                            bool(getattr(hparams, 'mi355_alignment_reference_dir', '')))
         keep = check or dn
         decoded = torch.zeros(len(lengths), max(lengths) * hop, device=self.model.device) if keep else None      # out_wav of every group, kept on the device
         ids = None if not self.global_conditions else np.asarray(speaker_ids).reshape(-1)
