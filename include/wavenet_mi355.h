@@ -993,6 +993,19 @@ int wn_test_gemm8p_mask(const wn_ctx* ctx);
  * wn_create, unset: the library's default): bit 0 = the gate GEMM, bit 1 = d x, bit 2 = the other 32-channel-chunk launches (skip sum and full-tile
  * 1x1 convs, d z, the head's mask GEMMs).  Bits the library does not know are dropped. */
 int wn_test_mfma16_mask(const wn_ctx* ctx);
+/* The reuse contract of the training workspace: a step may assume NOTHING about bytes it did not write itself.  This hook fills every
+ * buffer that only training steps write with 0xFF bytes -- a NaN in bf16 and in fp32 -- over its WHOLE allocation, not just the rows of the last step, by
+ * hipMemsetAsync on `stream` (no kernel, no allocation), so that a launch which reads a row, a partial block or a tile it did not write this step shows in
+ * its output (tests/test_hip_reuse.py).  Covered: the activation slabs X, XD, TS, U, R1, H2; the gradient slabs YHAT, DY, DPRE1, DSKIP, DZ, GX of every layer
+ * (GX0 and GX1 are its first two), DC; the upsample levels CUP[], DCUP[] and cbt; the kept input copies XIN, CIN; the partial sums UPPART, the column-sum
+ * partials and the split-K partials of the grouped weight gradients; the effective-gradient buffer ("DEFF"); the per-step global-conditioning tables (gate
+ * bias per utterance, per-utterance column sums); every buffer the fp32 mode's state holds so far.  NOT touched: parameters, operand packs, the zero page,
+ * "B1SUM", "SKIPB", the global-conditioning inputs of wn_set_global_condition, the device scalars and score partials, integer tables, profiling and trace
+ * state, and all synthesis, stream and slot state.  The last forward is forgotten: wn_train_bwd is WN_E_STATE until the next wn_train_fwd.
+ * The memsets are ordered on `stream` alone: pass the stream the last step was enqueued on (wn_train_fwd / wn_train_bwd join their own streams back into
+ * it before they return), or synchronise the device first; work of that step which `stream` is not ordered after would race with the fill.
+ * WN_E_ARG: ctx == NULL; WN_E_STATE: an inference-only context (it has no training workspace). */
+int wn_test_poison_workspace(wn_ctx* ctx, void* stream);
 /* The fragment-ordered bf16 operand packs that wn_pack_weights wrote.  kind: "w1", "wo", "ws", "w2T", "w1T" (one per layer) or "wskip", "wh1",
  * "wh2", "wh2T", "wh1T", "wcT" (`layer` ignored).  wn_test_pack_info: out = {M, K, kil, gate_interleave} (padded sizes; kil = 0 / 32 / 64 the
  * K interleave of the three taps).  wn_test_pack_copy: the M * K elements IN STORAGE ORDER, bf16 -> fp32, nothing un-shuffled, into the device

@@ -192,6 +192,7 @@ static int alloc_workspace(wn_ctx* c) {
     c->UPPART = (float*)bump(p, (size_t)c->uppart_floats * 4);
     c->XIN = (void*)bump(p, NT * 4); c->CIN = (float*)bump(p, NT * c->C * 4);
     c->cs_part = (float*)bump(p, (size_t)WN_CS_SLOTS * WN_CS_MAXBLK * 2 * 1024 * 4);      // exactly what wn_colsum2 addresses (was twice that: ADVICE round 3)
+    c->ws_step_bytes = (size_t)(p - (char*)c->ws);      // everything carved so far is written by training steps only (wn_test_poison_workspace fills it); what follows is not
     c->scal = (float*)bump(p, 256);
     c->zero_page = (bf16_t*)bump(p, WN_ZERO_PAGE_BYTES);
     c->score_part = (double*)bump(p, (size_t)wn_score_part_doubles(c->maxB, c->maxT) * 8);
@@ -554,6 +555,23 @@ extern "C" int wn_test_gemm8p_mask(const wn_ctx* c) {
     return (c->packs[0].w1.kil == 64 ? 1 : 0) | (c->packs[0].w1T.kil == 64 ? 2 : 0);
 }
 extern "C" int wn_test_mfma16_mask(const wn_ctx* c) { return c ? c->mfma16 : WN_E_ARG; }
+// Every byte a training step may find from an earlier one becomes 0xFF (a NaN in bf16 and in fp32), over the whole allocations: the step-owned front of
+// the workspace (cbt, X, XD, TS, U, R1, H2, DY, DPRE1, DSKIP, DZ, GXall, YHAT, DC, CUP[], DCUP[], UPPART, XIN, CIN, cs_part), the split-K partials of the
+// grouped weight gradients, the effective-gradient buffer, the per-step global-conditioning tables (gbias, colsum) and the fp32 mode's state.  Memsets in
+// stream order only.  Not touched: scal, zero_page and score_part behind that front, parameters, packs, b1sum, the skip-bias total, gvec / gids, every
+// integer table, profiling and trace state, and all synthesis / stream / slot state.
+extern "C" int wn_test_poison_workspace(wn_ctx* c, void* stream) {
+    if (!c) return WN_E_ARG;
+    if (c->inference) WN_FAIL(c, WN_E_STATE, "wn_test_poison_workspace: no training workspace on an inference-only context");
+    hipStream_t st = (hipStream_t)stream;
+    c->have_fwd = false; c->have_bwd = false; c->have_loss = false;      // nothing of the last step is left to run a backward on
+    WN_HIP(c, hipMemsetAsync(c->ws.get(), 0xFF, c->ws_step_bytes, st));
+    if (c->wg_partial) WN_HIP(c, hipMemsetAsync(c->wg_partial.get(), 0xFF, c->wg_partial.bytes(), st));
+    if (c->deff) WN_HIP(c, hipMemsetAsync(c->deff.get(), 0xFF, c->deff.bytes(), st));
+    if (c->gbias) WN_HIP(c, hipMemsetAsync(c->gbias.get(), 0xFF, c->gbias.bytes(), st));
+    if (c->colsum) WN_HIP(c, hipMemsetAsync(c->colsum.get(), 0xFF, c->colsum.bytes(), st));
+    return wn_f32_poison(c, st);
+}
 extern "C" int wn_synth_pipe_eligible(const wn_ctx* c, int32_t B) {
     if (!c || B <= 0) return WN_E_ARG;
     const char* m = getenv("WN_SYNTH_MODE");

@@ -148,6 +148,7 @@ struct wn_ctx {
     DevBuf<int32_t> norm_spans_dev, norm_first_dev; DevBuf<float> norm_part_dev; int norm_nspans = 0;   // atomic-free clip norms
     // workspace: ONE allocation; every pointer below down to score_part is carved from it by alloc_workspace (wn_api.hip) and owns nothing
     DevBuf<char> ws;
+    size_t ws_step_bytes = 0;             // the leading part of ws that only training steps write (cbt ... cs_part: all of it in front of scal); 0 on inference-only contexts
     int maxB, maxT; int64_t NT;
     bf16_t* XD;                           // [L][NT][R] dropout-applied layer inputs (aliases X when dropout == 0)
     bf16_t *cbt, *X, *TS, *U, *R1, *H2, *DY, *DPRE1, *DSKIP, *DZ, *GX0, *GX1;
@@ -365,6 +366,7 @@ void wn_plan_buckets(wn_ctx* ctx);
 int wn_f32_forward(wn_ctx* ctx, hipStream_t st);                  // fp32-accurate forward into YHAT (wn_f32.hip)
 int wn_f32_backward(wn_ctx* ctx, float* grads, hipStream_t st);       // fp32 backward of the last fp32 forward (wn_f32.hip)
 int wn_f32_dy(wn_ctx* ctx, float** dy);                               // fp32 d y_hat buffer of the fp32 state (allocates it)
+int wn_f32_poison(wn_ctx* ctx, hipStream_t st);                       // 0xFF bytes over every buffer the fp32 state holds so far (wn_test_poison_workspace)
 int wn_upsample_bwd(wn_ctx* c, const float* dc_final, float* grads, hipStream_t st);
 int wn_loss_fwd_bwd(wn_ctx* c, float* loss_out, hipStream_t st);
 int wn_score_last_fwd(wn_ctx* c, float* stats_out, float* nll_out, hipStream_t st);      // per-utterance / per-sample scores of the last forward's y_hat

@@ -225,6 +225,15 @@ static int f32_reserve(wn_ctx* c) {
     s->bytes = (size_t)NT * 4 * ((size_t)c->L * (c->R + c->GH + c->G) + 2 * c->S + c->C);
     return WN_OK;
 }
+// wn_test_poison_workspace: 0xFF over every buffer of the state that exists so far, whole allocations (they are all rewritten by a step; nothing is allocated here)
+int wn_f32_poison(wn_ctx* c, hipStream_t st) {
+    F32State* s = c->f32.get();
+    if (!s) return WN_OK;
+    DevBuf<float>* all[] = {&s->X, &s->U, &s->Z, &s->SK, &s->H1, &s->C32, &s->DY, &s->DH1, &s->DSK, &s->GU, &s->DZ, &s->GX[0], &s->GX[1], &s->DC, &s->DCT, &s->PART};
+    for (DevBuf<float>* b : all)
+        if (*b) WN_HIP(c, hipMemsetAsync(b->get(), 0xFF, b->bytes(), st));
+    return WN_OK;
+}
 const float* wn_f32_debug(const wn_ctx* c, const char* name, int layer) {
     const F32State* s = c->f32.get();
     if (!s || !s->X || !s->U) return nullptr;

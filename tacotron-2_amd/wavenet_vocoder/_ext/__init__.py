@@ -171,6 +171,7 @@ def load_library():
         'wn_synth_last_path': (ctypes.c_int, [vp]),
         'wn_test_gemm8p_mask': (ctypes.c_int, [vp]),
         'wn_test_mfma16_mask': (ctypes.c_int, [vp]),
+        'wn_test_poison_workspace': (ctypes.c_int, [vp, vp]),
         'wn_test_pack_info': (ctypes.c_int, [vp, ctypes.c_char_p, i32, ctypes.POINTER(i32)]),
         'wn_test_pack_copy': (ctypes.c_int, [vp, ctypes.c_char_p, i32, vp, i64]),
         'wn_test_f32_sgemm': (ctypes.c_int, [vp, i32, i32, vp, i32, i32, i32, vp, i32, i32, i32, i32, vp, i32, i32, vp, i32, i32, f32, f32, vp, i32, vp, i32, i32, i32,
@@ -795,6 +796,11 @@ class Engine:
         if n < 0:
             self._ok(n)
         return [(int(k[i]), int(st[i]), int(t0[i]), int(t1[i])) for i in range(n)]
+
+    def poison_workspace(self):
+        """Test hook: 0xFF bytes (NaN in bf16 and fp32) over every buffer that only training steps write, whole allocations; the last forward is forgotten
+        (wn_test_poison_workspace)."""
+        self._ok(self.lib.wn_test_poison_workspace(self.h, _stream()))
 
     def debug_copy(self, name, layer, rows, cols):
         import torch

@@ -50,6 +50,7 @@ def test_library_loads_and_exports_every_declared_symbol():
         assert sym in declared and sym in _ext.exported_symbols() and hasattr(lib, sym), sym
     for sym in ('wn_test_f32_sgemm', 'wn_test_f32_wgrad', 'wn_test_f32_gate'):      # the single-launch hooks of the fp32 training mode
         assert sym in declared and sym in _ext.exported_symbols() and hasattr(lib, sym), sym
+    assert 'wn_test_poison_workspace' in declared and 'wn_test_poison_workspace' in _ext.exported_symbols()      # the reuse tests' hook
     for name in ('PARAMS', 'DEFF', 'B1SUM', 'SKIPB', 'Z', 'SK', 'H1'):      # ... and the weight-path / fp32-mode names of wn_debug_copy are documented where it is declared
         assert '"%s"' % name in header, name
     # host-only entry points work without a GPU
@@ -657,6 +658,15 @@ def test_c_abi_rejects_bad_configurations_before_touching_the_gpu():
     assert lib.wn_receptive_field(None) == ARG and lib.wn_param_count(None) == ARG and lib.wn_num_tensors(None) == ARG
     assert lib.wn_noise_per_step(None) == ARG and lib.wn_set_batch_parts(None, 1) == ARG and lib.wn_profile(None, 1) == ARG
     assert lib.wn_train_bwd(None, None, None) == ARG and lib.wn_pack_weights(None, None, None) == ARG
+    assert lib.wn_test_poison_workspace(None, None) == ARG
+    # ... and the workspace poison hook refuses a context without a training workspace (a context exists only on a GPU box: WN_E_HIP here otherwise)
+    cfg = _ext.config_from_hparams(H._build(), 1, 275, inference_only=True)
+    h = ctypes.c_void_p()
+    rc = lib.wn_create(ctypes.byref(cfg), ctypes.byref(h))
+    assert rc in (0, -3)
+    if rc == 0:
+        assert lib.wn_test_poison_workspace(h, None) == -5 and b'inference-only' in lib.wn_last_error(h)      # WN_E_STATE
+        lib.wn_destroy(h)
     lib.wn_destroy(None)
     # Python-side wrapper turns the status into an exception that carries it
     hp = H._build(); hp.layers = 7; hp.stacks = 2

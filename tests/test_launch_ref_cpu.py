@@ -409,3 +409,122 @@ def test_gate_bound_covers_saturated_and_tiny_preactivations():
     assert bool((es <= Es).all()), float((es / Es).max())
     assert float(Et.max()) < 8 * LR.U24 * 1.01 and float(Es.max()) < 40 * LR.U24      # (absolute errors of a few fp32 ulps of 1: far below the bf16 store)
     print('\nfast_tanh err / bound %.3f, fast_sigmoid err / bound %.3f' % (float((et / Et).max()), float((es / Es).max())))
+
+
+# ------------------------------------------------------------------------------------------------------------------ the report itself
+# launch_report.Report decides every launch-local GPU test.  A NaN compares false with everything, so `ratio > 1` and `rel > tol` alone
+# would pass a device buffer full of them: the cases below hold the report to "a device value that is not finite is a failure, with its
+# coordinates" on a synthetic [B, T, ch] triple, and to "a reference or bound that is not finite raises".
+def _triple(B=2, T=160, ch=8, bound_scale=2.0 ** -8):
+    g = torch.Generator().manual_seed(5)
+    ref = torch.randn(B, T, ch, generator=g, dtype=torch.float64)
+    bound = bound_scale * ref.abs() + 1e-6
+    dev = ref + 0.25 * bound * (2 * torch.rand(B, T, ch, generator=g, dtype=torch.float64) - 1)
+    return dev, ref, bound
+
+
+def _report(B=2, T=160):
+    from launch_report import Report
+    return Report('synthetic', B, T, False)
+
+
+def _expect_one_failure(rep, *words):
+    assert len(rep.fail) == 1, rep.fail
+    for w in words:
+        assert w in rep.fail[0], (w, rep.fail[0])
+    with pytest.raises(AssertionError):
+        rep.finish()
+
+
+def test_report_passes_a_clean_triple():
+    dev, ref, bound = _triple()
+    rep = _report()
+    rep.elementwise('GX', 3, dev, ref, bound, d=4)
+    rep.elementwise('GX edge', 3, dev, ref, bound, d=4, group=torch.ones(2, 160, 1, dtype=torch.float64))
+    rep.elementwise('DY', 0, ref.clone(), ref, torch.zeros_like(bound))      # bound 0: exact
+    rep.exact('XD', 3, ref.clone(), ref)
+    rep.tensor('ResidualConv1DGLU_3/residual_block_causal_conv/kernel', 3, (ref * (1 + 1e-7)).float(), ref, 1e-7)
+    rep.tensor('ResidualConv1DGLU_3/residual_block_out_conv/kernel', 3, torch.zeros(4, 4), torch.zeros(4, 4, dtype=torch.float64), 0.0)
+    assert rep.fail == []
+    rep.finish()
+
+
+@pytest.mark.parametrize('value', [float('nan'), float('inf'), -float('inf')])
+def test_report_fails_a_non_finite_element_under_a_positive_bound(value):
+    """(The NaN case passes the Report of the commit before this one: NaN / bound > 1 is false.)"""
+    dev, ref, bound = _triple()
+    dev[1, 131, 5] = value
+    rep = _report()
+    rep.elementwise('GX', 3, dev, ref, bound, d=4)
+    _expect_one_failure(rep, 'GX layer 3', 'utterance 1 t 131 channel 5', 'row 291, tile 2', '1 of 2560 elements', 'not finite')
+
+
+def test_report_fails_a_nan_where_the_bound_is_zero():
+    dev, ref, _ = _triple()
+    dev = ref.clone()
+    dev[0, 159, 0] = float('nan')
+    rep = _report()
+    rep.elementwise('DY', 0, dev, ref, torch.zeros_like(ref), d=4)
+    _expect_one_failure(rep, 'DY layer 0', 'utterance 0 t 159 channel 0', 'within 2d of an utterance end')
+
+
+def test_report_group_sees_a_nan_inside_it_and_not_one_outside():
+    dev, ref, bound = _triple()
+    grp = torch.zeros(2, 160, 1, dtype=torch.float64)
+    grp[1:, :8] = 1.0
+    inside, outside = dev.clone(), dev.clone()
+    inside[1, 7, 2] = float('nan')
+    outside[1, 8, 2] = float('nan')
+    rep = _report()
+    rep.elementwise('U start', 2, outside, ref, bound, d=4, group=grp)
+    assert rep.fail == []                                    # not this call's rows ...
+    rep.elementwise('U', 2, outside, ref, bound, d=4)        # ... the ungrouped call of the same buffer covers them
+    _expect_one_failure(rep, '] U layer 2', 'utterance 1 t 8 channel 2')
+    rep = _report()
+    rep.elementwise('U start', 2, inside, ref, bound, d=4, group=grp)
+    _expect_one_failure(rep, 'U start layer 2', 'utterance 1 t 7 channel 2')
+
+
+def test_report_exact_fails_a_nan():
+    _, ref, _ = _triple()
+    dev = ref.clone()
+    dev[1, 3, 1] = float('nan')
+    rep = _report()
+    rep.exact('cbt', 0, dev, ref)
+    _expect_one_failure(rep, 'cbt layer 0', '1 elements differ', 'utterance 1 t 3 channel 1')
+
+
+def test_report_fails_a_nan_in_a_weight_gradient_tensor():
+    """(Passes the Report of the commit before this one: the rel-L2 is NaN and NaN > tol is false.)"""
+    ref = torch.randn(3, 8, 16, generator=torch.Generator().manual_seed(1), dtype=torch.float64)
+    dev = ref.float()
+    dev[2, 1, 4] = float('nan')
+    rep = _report()
+    rep.tensor('ResidualConv1DGLU_3/residual_block_causal_conv/kernel', 3, dev, ref, 1e-7)
+    _expect_one_failure(rep, 'wgrad ResidualConv1DGLU_3/residual_block_causal_conv/kernel', 'layer 3', '1 of 384 elements are not finite', 'flat index %d' % (2 * 128 + 16 + 4))
+
+
+def test_report_fails_a_nan_in_a_zero_reference_tensor():
+    dev = torch.zeros(4, 4)
+    dev[3, 3] = float('nan')
+    rep = _report()
+    rep.tensor('ResidualConv1DGLU_3/residual_block_out_conv/kernel', 3, dev, torch.zeros(4, 4, dtype=torch.float64), 0.0)
+    _expect_one_failure(rep, 'residual_block_out_conv/kernel', 'not finite', 'flat index 15')
+
+
+def test_report_raises_on_a_non_finite_reference_or_bound():
+    dev, ref, bound = _triple()
+    for bad_ref, bad_bound in ((True, False), (False, True)):
+        r, b = ref.clone(), bound.clone()
+        (r if bad_ref else b)[0, 0, 0] = float('nan')
+        rep = _report()
+        with pytest.raises(AssertionError, match='mistake of the test'):
+            rep.elementwise('GX', 0, dev, r, b)
+        assert rep.fail == []
+    r = ref.clone(); r[0, 0, 0] = float('inf')
+    with pytest.raises(AssertionError, match='mistake of the test'):
+        _report().exact('XD', 0, dev, r)
+    with pytest.raises(AssertionError, match='mistake of the test'):
+        _report().tensor('x/kernel', 0, dev, r, 1e-7)
+    with pytest.raises(AssertionError, match='mistake of the test'):
+        _report().tensor('x/kernel', 0, dev, ref, float('nan'))
